@@ -9,11 +9,11 @@ envs whose episode ends (200 steps, drone_env.py:30) reset + re-observed inside 
 (train_problem.py:132).  Actions are synthetic U(-1,1)^2 (RandomAgent, SAC_agents.py:22),
 pre-generated and resident in HBM before the timed region.
 
-Timing: the K requested steps are captured as ONE hipGraph (whatever K is; a short request several times
-over, ~4000 launches per graph, because a replay costs 0.1-0.3 ms of GPU idle time whatever it holds) and the
-timed region replays that graph `repeats` times -- enough for >= 0.5 s -- between the two barriers, so a
-short `--steps 20` run measures the same thing as a long one: value = N * E * timed_steps / elapsed and
-ms_per_step = elapsed / timed_steps, timed_steps = K * graph_copies * repeats.
+Timing: the timed region is exactly the K = --steps requested steps, launched from hipGraphs: one graph of
+min(K, ~4000) launches (a replay costs 0.1-0.3 ms of GPU idle time whatever it holds, so long requests are cut into
+replays of a ~4000-launch graph, a whole number of episodes) replayed as often as it fits into K, and one more graph for
+the rest.  Each graph is replayed once, untimed, after W = --warmup eager warm-up steps; then the timed replays run
+between two barriers: value = N * E * K / elapsed and ms_per_step = elapsed / K.
 
 The path's only exchange (train_problem.py:118-121: the per-episode log) runs inside the timed region at the
 reference's cadence: every 200 steps (one episode, drone_env.py:30) the capture holds one fixed-order reduction of
@@ -24,14 +24,19 @@ collectives the timed region held and whether a real collective ran.
 Default workload = BASELINE.json configs[2] (N=64 x E=4096 per GPU, Delta=1.0, G=28): the
 configuration the headline target (>= 1e7 agent-steps/s on 1 GPU) is quoted on.  --scaling weak (default):
 every extra GPU adds another 4096 envs (configs[3] at 8 GPUs); --scaling strong: configs[3]'s 32768 envs are ONE
-job split over the ranks.  --workload c2|c5 select the other single-GPU-sized configs; the default run also times
-them (c2, the c5 shard, the c5 shard with the float32 Gaussian policy in the loop) after the graded region and
-appends them as `other_workloads`.
+job split over the ranks.  --workload c2|c5 select the other single-GPU-sized configs.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given and
+prints the line.  --full adds every secondary measurement, each after the graded region or outside it: the eager
+loop, the step kernel's own duration and its roofline (device clock, write ceiling), the fused rollouts, the CPU
+baseline, the other workloads (c2, the c5 shard, the c5 shard with the float32 Gaussian policy in the loop, ...) as
+`other_workloads`, the RCCL probe and, with several ranks, the N = 1 comparison and the collective's latency.
 
 The JSON line is kept under 8 KB (the driver keeps an 8 KB tail of stdout): numbers with 5-6 significant digits and short
 keys, no prose -- what every key means, and the workload behind every side line, is in DESIGN.md section 7.
 
     python bench.py --gpus 1 --steps 2000 --warmup 200
+    python bench.py --gpus 1 --steps 2000 --warmup 200 --full --dump-outputs out/
     python bench.py --gpus 8 --steps 2000 --warmup 200        # starts its own 8 ranks (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 2000 --warmup 200
@@ -427,6 +432,29 @@ def compact(o, sig=5):
     return o
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, env, ring):
+    """What the timed path handed its caller after its last step, as float32 / float64 `.npy` files: the StepResult
+    buffers (state, z_states, rewards, n_collisions, finished, true_rewards), the neighbour indices of the new
+    observation and the last replay's ring of episode reductions (the exchange's input).  Over DUMP_LIMIT_BYTES in
+    all, a fixed seeded sample of envs is written, with its indices as `env_index.npy`."""
+    arrays = {"state_pos": env.pos, "state_vel": env.vel, "z_states": env.z, "rewards": env.reward,
+              "true_rewards": env.true_reward, "n_collisions": env.n_coll, "finished": env.done, "nbr_idx": env.nbr_idx}
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in arrays.items()}   # int32 / uint8 values: exact in float32
+    E = env.n_envs
+    per_env = sum(a.nbytes for a in arrays.values()) / E
+    if per_env * E > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(E, int(DUMP_LIMIT_BYTES // per_env), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["env_index"] = keep.astype(np.float64)
+    arrays["episode_ring"] = ring.cpu().numpy().astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a))
+
+
 def c1_compat(torch, dev, episodes=3):
     """BASELINE configs[0]'s shape (n = 5, ONE env, 200-step episodes) through the E = 1 drop-in face: the loop of
     train_problem.py:82-107 -- list-of-ndarray actions in, the reference's 6-tuple of host objects out, env.reset() between
@@ -466,7 +494,8 @@ def main():
                          "(32768 envs = BASELINE configs[3]) is ONE job split over however many ranks run")
     ap.add_argument("--envs-per-gpu", type=int, default=None)
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of hipGraph replay")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="minimum length of the timed region (graph replays)")
+    ap.add_argument("--min-seconds", type=float, default=0.5,
+                    help="--full with several ranks: the N = 1 comparison replays the graph for 0.6 x this many seconds")
     ap.add_argument("--no-episode-layer", action="store_true",
                     help="plain dronesim_step launches (no per-step statistic, explicit reset kernel every 200 steps)")
     ap.add_argument("--policy", default="random", choices=["random", "softmax16", "gaussian"],
@@ -480,7 +509,14 @@ def main():
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the c2 / c5 side measurements appended to the default single-GPU run")
     ap.add_argument("--no-rccl-probe", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements (eager loop, roofline, fused rollouts, CPU baseline, other "
+                         "workloads, RCCL probe; with several ranks the N = 1 comparison and the collective's latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank r of several: DIR/rank<r>/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it (how the driver's scaling run may call it): start the N
@@ -561,65 +597,74 @@ def main():
         one_step(step_no); step_no += 1
     torch.cuda.synchronize()
 
-    # secondary figure: the same K steps launched eagerly from Python (host launch latency included)
-    eager_steps = max(args.steps, EAGER_MIN_STEPS) if policy is None else args.steps     # (a 20-step loop would mostly time its two syncs)
-    barrier()
-    t0 = time.perf_counter()
-    for s in range(eager_steps):
-        one_step(step_no); step_no += 1
-    barrier()
-    eager_elapsed = time.perf_counter() - t0
+    # secondary figure (--full): the same K steps launched eagerly from Python (host launch latency included)
+    eager_steps, eager_elapsed = 0, 0.0
+    if args.full:
+        eager_steps = max(args.steps, EAGER_MIN_STEPS) if policy is None else args.steps     # (a 20-step loop would mostly time its two syncs)
+        barrier()
+        t0 = time.perf_counter()
+        for s in range(eager_steps):
+            one_step(step_no); step_no += 1
+        barrier()
+        eager_elapsed = time.perf_counter() - t0
 
-    # the K steps as ONE hipGraph.  All episode state (t, episode counters, records, RNG stream position) lives on
-    # the device, so every replay continues the rollout: episodes end, are logged and restart inside the replays.
-    graph = None
+    # the K steps from hipGraphs.  All episode state (t, episode counters, records, RNG stream position) lives on the
+    # device, so every replay continues the rollout: episodes end, are logged and restart inside the replays.
     K = args.steps
-    ring = None                                          # [slots, 8] float64: one in-graph reduction per episode length
+    schedule = []                                        # the timed replays, in order: (graph, ring, slots, launches)
     if not args.no_graph:
         if not layer:
             while step_no % T_ep:                   # plain path resets by step index: align the capture to an episode
                 one_step(step_no); step_no += 1
         torch.cuda.synchronize()
         # a replay costs ~0.1-0.3 ms of GPU idle time whatever the graph holds (tools/replay_probe.py: 6.01 us per step
-        # with 250 launches per graph, 5.73 with 1000, 5.62 with 4000): the request is captured several times over into
-        # ONE graph of ~4000 launches (the episode layer keeps every counter on the device, so the copies simply
-        # continue the rollout), and the per-step figure of `--steps 20` is that of `--steps 2000`
-        copies = max(1, -(-GRAPH_LAUNCHES // K)) if layer else 1
-        L = K * copies
-        # the exchange's local half at the reference's cadence, INSIDE the capture: after every T_ep-th launch one
-        # fixed-order reduction of the episode records (train_problem.py:118-121 logs once per episode) into its own
-        # ring slot; a capture shorter than an episode gets one at its end
-        slots = max(1, L // T_ep)
-        ring = torch.zeros(slots, 8, dtype=torch.float64, device=dev)
+        # with 250 launches per graph, 5.73 with 1000, 5.62 with 4000): a long request is cut into replays of ONE graph
+        # of ~4000 launches, a whole number of episodes (so that launch i of the request steps with pool[i % T_ep] and the
+        # plain path's resets stay aligned), and a second graph holds the rest
+        chunk = K if K <= GRAPH_LAUNCHES else max(T_ep, GRAPH_LAUNCHES // T_ep * T_ep)
+        n_chunks, rest = divmod(K, chunk)
+
+        def capture(L):
+            # the exchange's local half at the reference's cadence, INSIDE the capture: after every T_ep-th launch one
+            # fixed-order reduction of the episode records (train_problem.py:118-121 logs once per episode) into its own
+            # ring slot; a capture shorter than an episode gets one at its end
+            slots = max(1, L // T_ep)
+            ring = torch.zeros(slots, 8, dtype=torch.float64, device=dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for s in range(L):
+                    one_step(s)
+                    if (s + 1) % T_ep == 0 and L >= T_ep:
+                        env.episode_totals(out=ring[(s + 1) // T_ep - 1])
+                if L < T_ep:
+                    env.episode_totals(out=ring[0])
+            return graph, ring, slots, L
+
         launches_before = launches
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for s in range(L):
-                one_step(s)
-                if (s + 1) % T_ep == 0 and (s + 1) // T_ep <= slots and L >= T_ep:
-                    env.episode_totals(out=ring[(s + 1) // T_ep - 1])
-            if L < T_ep:
-                env.episode_totals(out=ring[0])
+        captured = [capture(chunk)] + ([capture(rest)] if rest else [])
         launches = launches_before                       # capturing enqueues nothing
-        for _ in range(2):                          # untimed replays: instantiate + clocks
+        schedule = [captured[0]] * n_chunks + captured[1:]
+        for graph, _, _, L in captured:             # one untimed replay per graph: instantiate + clocks
             graph.replay(); launches += L
         torch.cuda.synchronize()
-        t0 = time.perf_counter(); graph.replay(); torch.cuda.synchronize(); launches += L
-        one = max(time.perf_counter() - t0, 1e-6)
-        if world > 1:                               # every rank must replay (and exchange) the same number of times
-            o = torch.tensor([one], dtype=torch.float64, device=cdev)
-            dist.all_reduce(o, op=dist.ReduceOp.MIN)
-            one = float(o.item())
-        repeats = max(1, int(np.ceil(1.2 * args.min_seconds / one)))
+        launch_desc = f"hipGraph {chunk} launches x {n_chunks} replays" + (f" + hipGraph {rest} launches" if rest else "")
     else:
-        repeats, copies, L, slots = 1, 1, K, 1
+        chunk, launch_desc = K, "eager"
         ring = torch.zeros(1, 8, dtype=torch.float64, device=dev)
 
-    # world > 1: the figure the N-rank value is to be compared with -- the SAME graph replayed by rank 0 ALONE (the other
-    # ranks wait at the barrier below), i.e. this workload on one GPU with nothing else running on the node.  Computed by
-    # the script so that no reader has to pair lines of different runs.  (Untimed for the N-rank figure: it precedes it.)
+    # world > 1 (--full): the figure the N-rank value is to be compared with -- the SAME graph replayed by rank 0 ALONE
+    # (the other ranks wait at the barrier below), i.e. this workload on one GPU with nothing else running on the node.
+    # Computed by the script so that no reader has to pair lines of different runs.  (Untimed for the N-rank figure: it
+    # precedes it.)
     n1 = None
-    if world > 1 and graph is not None and args.scaling == "weak":     # (strong: a rank's shard is not the N = 1 job)
+    if args.full and world > 1 and schedule and args.scaling == "weak":     # (strong: a rank's shard is not the N = 1 job)
+        graph, _, _, L = schedule[0]
+        barrier()
+        t0 = time.perf_counter(); graph.replay(); torch.cuda.synchronize(); launches += L
+        one = max(time.perf_counter() - t0, 1e-6)
+        o = torch.tensor([one], dtype=torch.float64, device=cdev)
+        dist.all_reduce(o, op=dist.ReduceOp.MIN)
+        one = float(o.item())
         barrier()
         if rank == 0:
             r1 = max(1, int(np.ceil(0.6 * args.min_seconds / one)))
@@ -635,31 +680,33 @@ def main():
     # async on RCCL's own stream behind the replay that filled them; the rollout's next replay is not held up
     exchanges = []
 
-    def exchange():
-        exchanges.append(all_gather_stats(ring.view(-1), async_op=True))
+    def exchange(ring, slots):
+        exchanges.append(all_gather_stats(ring.view(-1), async_op=True) + (slots,))
 
     barrier()
     t0 = time.perf_counter()
-    if graph is not None:
-        for r in range(repeats):
+    if schedule:
+        for graph, ring, slots, L in schedule:
             graph.replay(); launches += L
-            exchange()
+            exchange(ring, slots)
     else:
         for s in range(K):
             one_step(step_no); step_no += 1
             if (s + 1) % T_ep == 0 or s == K - 1:
-                env.episode_totals(out=ring[0]); exchange()
-    for _, work in exchanges:                       # every exchange of the timed region has completed
+                env.episode_totals(out=ring[0]); exchange(ring, 1)
+    for _, work, _ in exchanges:                    # every exchange of the timed region has completed
         if work is not None:
             work.wait()
     barrier()
     elapsed = time.perf_counter() - t0
-    total_steps = L * repeats
-    reductions = (slots * repeats) if graph is not None else len(exchanges)
+    total_steps = K
+    reductions = sum(slots for _, _, slots, _ in schedule) if schedule else len(exchanges)
+    if args.dump_outputs:                           # the last timed step's outputs, before anything else launches
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), env, ring)
     # final exchange: global per-episode figures from one more reduction + all-gather of the same kind
     final = all_gather_stats(env.episode_totals())
     summary = summarize_episodes(final, N)
-    last = exchanges[-1][0].to(dev).view(-1, slots, 8) if exchanges else None      # [world, slots, 8]
+    last = exchanges[-1][0].to(dev).view(-1, exchanges[-1][2], 8) if exchanges else None      # [world, slots, 8]
     summary["last_timed_exchange_episodes"] = None if last is None else float(last[:, -1, 4].double().sum())
     # the device-side records must account for every launch this process issued: env_steps = launches x envs
     if layer:
@@ -675,123 +722,113 @@ def main():
                     "env_steps_recorded_all_ranks": summary["env_steps"],
                     "ok": (not layer) or summary["env_steps"] == float(issued.item())}
 
-    # measured latency of the exchange's collective on this job's process group (world > 1), outside the timed region
-    allgather_us = None
-    if world > 1:
-        src = ring.view(-1)
-        for _ in range(5):
-            all_gather_stats(src)
-        barrier(); t1 = time.perf_counter()
-        for _ in range(50):
-            all_gather_stats(src)
-        torch.cuda.synchronize()
-        allgather_us = (time.perf_counter() - t1) / 50 * 1e6
+    # --full: the secondary measurements, each outside the timed region
+    allgather_us = kern_ms = ro_us = rp_us = rr_us = None
+    if args.full:
+        # measured latency of the exchange's collective on this job's process group (world > 1), outside the timed region
+        if world > 1:
+            src = ring.view(-1)
+            for _ in range(5):
+                all_gather_stats(src)
+            barrier(); t1 = time.perf_counter()
+            for _ in range(50):
+                all_gather_stats(src)
+            torch.cuda.synchronize()
+            allgather_us = (time.perf_counter() - t1) / 50 * 1e6
 
-    # Duration of the dominant kernel (drone_kernel<step>) per launch, by HIP events on the launch stream: events
-    # bracket a hipGraph holding ONLY `n_samp` back-to-back step launches, so (t1 - t0) / n_samp is the kernel's
-    # duration including the dependent-launch boundary and excluding host launch latency.  rocprofv3 --kernel-trace
-    # --stats of this command reports the same kernel's average duration (profiles/).  With the episode layer the graph
-    # holds twenty episodes (the in-kernel resets fire inside it, as in the timed region).
-    kern_ms = step_kernel_ms(torch, env, pool, KERNEL_SAMPLE_EPISODES * T_ep if layer else T_ep)
+        # Duration of the dominant kernel (drone_kernel<step>) per launch, by HIP events on the launch stream: events
+        # bracket a hipGraph holding ONLY `n_samp` back-to-back step launches, so (t1 - t0) / n_samp is the kernel's
+        # duration including the dependent-launch boundary and excluding host launch latency.  rocprofv3 --kernel-trace
+        # --stats of this command reports the same kernel's average duration (profiles/).  With the episode layer the graph
+        # holds twenty episodes (the in-kernel resets fire inside it, as in the timed region).
+        kern_ms = step_kernel_ms(torch, env, pool, KERNEL_SAMPLE_EPISODES * T_ep if layer else T_ep)
 
-    # secondary figure: the same workload through dronesim_rollout (200 steps fused in ONE launch, actions
-    # known up front -- RandomAgent rollouts); every per-step output except the per-step state is written
-    ro_us = None
-    try:
-        env.reset(renew_obstacles=False)
-        out = env.rollout(pool); torch.cuda.synchronize(); del out
-        # (four launches per bracket: the host-side cost of a call -- output allocation, argument marshalling, ~50 us --
-        # is hidden behind the previous launch instead of being charged to a 0.6 ms kernel)
-        rs = []
-        for _ in range(3):
-            env.reset(renew_obstacles=False)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _r in range(4):
-                out = env.rollout(pool); del out
-            e1.record(); torch.cuda.synchronize()
-            rs.append(e0.elapsed_time(e1) * 1e3 / (4 * T_ep))
-        ro_us = float(np.median(rs))
-    except RuntimeError:                               # e.g. not enough memory for the [T, ...] outputs
-        ro_us = None
-    # the plain entry point (dronesim_rollout: no episode records, no in-kernel reset) on an env of the same shape
-    rp_us = None
-    if ro_us is not None and args.scaling != "strong":
+        # secondary figure: the same workload through dronesim_rollout (200 steps fused in ONE launch, actions
+        # known up front -- RandomAgent rollouts); every per-step output except the per-step state is written
         try:
-            penv = drones(N, 0, [G, G], "O", k_closest=2, deltas=np.ones(N) * delta, simplify_zstate=True,
-                          n_envs=E_global, device=dev, seed=1234, rank=rank, world_size=world, batched=True)
-            out = penv.rollout(pool); torch.cuda.synchronize(); del out
+            env.reset(renew_obstacles=False)
+            out = env.rollout(pool); torch.cuda.synchronize(); del out
+            # (four launches per bracket: the host-side cost of a call -- output allocation, argument marshalling, ~50 us --
+            # is hidden behind the previous launch instead of being charged to a 0.6 ms kernel)
             rs = []
             for _ in range(3):
-                penv.reset(renew_obstacles=False)
+                env.reset(renew_obstacles=False)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 for _r in range(4):
-                    out = penv.rollout(pool); del out
+                    out = env.rollout(pool); del out
                 e1.record(); torch.cuda.synchronize()
                 rs.append(e0.elapsed_time(e1) * 1e3 / (4 * T_ep))
-            rp_us = float(np.median(rs))
-            del penv
+            ro_us = float(np.median(rs))
+        except RuntimeError:                               # e.g. not enough memory for the [T, ...] outputs
+            ro_us = None
+        # the plain entry point (dronesim_rollout: no episode records, no in-kernel reset) on an env of the same shape
+        if ro_us is not None and args.scaling != "strong":
+            try:
+                penv = drones(N, 0, [G, G], "O", k_closest=2, deltas=np.ones(N) * delta, simplify_zstate=True,
+                              n_envs=E_global, device=dev, seed=1234, rank=rank, world_size=world, batched=True)
+                out = penv.rollout(pool); torch.cuda.synchronize(); del out
+                rs = []
+                for _ in range(3):
+                    penv.reset(renew_obstacles=False)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _r in range(4):
+                        out = penv.rollout(pool); del out
+                    e1.record(); torch.cuda.synchronize()
+                    rs.append(e0.elapsed_time(e1) * 1e3 / (4 * T_ep))
+                rp_us = float(np.median(rs))
+                del penv
+            except RuntimeError:
+                rp_us = None
+        # and with the actions drawn inside the kernel (dronesim_rollout_random: RandomAgent.forward, SAC_agents.py:22,
+        # from a counter-based stream; no action pool, 44 B/agent-step), episode layer on: runs across episode ends
+        try:
+            env.reset(renew_obstacles=False)
+            out = env.rollout_random(T_ep); torch.cuda.synchronize(); del out
+            rs = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _r in range(4):
+                    out = env.rollout_random(T_ep); del out
+                e1.record(); torch.cuda.synchronize()
+                rs.append(e0.elapsed_time(e1) * 1e3 / (4 * T_ep))
+            rr_us = float(np.median(rs))
         except RuntimeError:
-            rp_us = None
-    # and with the actions drawn inside the kernel (dronesim_rollout_random: RandomAgent.forward, SAC_agents.py:22,
-    # from a counter-based stream; no action pool, 44 B/agent-step), episode layer on: runs across episode ends
-    rr_us = None
-    try:
-        env.reset(renew_obstacles=False)
-        out = env.rollout_random(T_ep); torch.cuda.synchronize(); del out
-        rs = []
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _r in range(4):
-                out = env.rollout_random(T_ep); del out
-            e1.record(); torch.cuda.synchronize()
-            rs.append(e0.elapsed_time(e1) * 1e3 / (4 * T_ep))
-        rr_us = float(np.median(rs))
-    except RuntimeError:
-        rr_us = None
+            rr_us = None
 
     el = torch.tensor([elapsed, eager_elapsed], dtype=torch.float64, device=cdev)
     per_rank = None
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
-        mine = torch.tensor([kern_ms, elapsed, float(E)], dtype=torch.float64, device=cdev)
+        mine = torch.tensor([kern_ms or 0.0, elapsed, float(E)], dtype=torch.float64, device=cdev)
         allr = torch.empty(world, 3, dtype=torch.float64, device=cdev)
         dist.all_gather_into_tensor(allr, mine.view(1, 3))
-        per_rank = [{"rank": r, "step_kernel_ms": float(allr[r, 0]), "timed_seconds": float(allr[r, 1]), "envs": int(allr[r, 2])}
-                    for r in range(world)]
+        per_rank = [{"rank": r, "timed_seconds": float(allr[r, 1]), "envs": int(allr[r, 2])} for r in range(world)]
+        if args.full:
+            for r, q in enumerate(per_rank):
+                q["step_kernel_ms"] = float(allr[r, 0])
     elapsed, eager_elapsed = float(el[0].item()), float(el[1].item())
 
     if rank == 0:
         agent_steps = N * E_global * total_steps
         value = agent_steps / elapsed
-        bytes_launch = algorithmic_bytes(N, E, layer)
-        achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(args.workload) if (e_gpu == WORKLOADS[args.workload][1] and E == e_gpu) else (None, None)
-        fr52 = lambda us: 52.0 * N * E / (us * 1e-6) / 1e9 / HBM_PEAK_GBS
         out = {
             "metric": "env agent-steps/sec (n_agents x n_envs x steps)",
             "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "repeats": repeats, "graph_copies": copies, "timed_steps": total_steps, "timed_seconds": elapsed,
+            "repeats": len(schedule) if schedule else 1, "graph_launches": chunk if schedule else None,
+            "timed_steps": total_steps, "timed_seconds": elapsed,
             "ms_per_step": elapsed / total_steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": label, "n_agents": N, "envs_per_gpu": E, "n_envs_total": E_global,
                        "grid": G, "delta": delta, "k_closest": 2, "simplify_zstate": True,
-                       "launch": (f"hipGraph {K}x{copies} launches, {repeats} replays" if graph is not None else "eager"),
+                       "launch": launch_desc,
                        "episode_layer": bool(layer),
                        "actions": "pool U(-1,1)^2 in HBM" if policy is None else f"{args.policy} policy {args.policy_precision}",
                        "parallelism": f"env-shard x{world}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         # SURVEY.md 8(d) bytes only (76 B per agent-step + 13 B per env-step, no episode-record bytes)
-                         "frac_survey_bytes": algorithmic_bytes(N, E, False) / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "survey_bytes_per_launch": algorithmic_bytes(N, E, False),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "drone_kernel<K=2,FAR=0,step,%s>" % ("epi" if layer else "plain"), "kernel_ms": kern_ms,
-                         "algorithmic_bytes_per_launch": bytes_launch},
             # the path's only exchange (train_problem.py:118-121): in-capture fixed-order reductions + one all-gather per replay
-            "exchange": {"reduce_every_steps": T_ep if L >= T_ep else L,
+            "exchange": {"reduce_every_steps": min(T_ep, chunk),
                          "reductions_in_timed_region": reductions,
                          "collectives_in_timed_region": len(exchanges),
                          "doubles_per_collective_and_rank": int(ring.numel()),
@@ -801,64 +838,77 @@ def main():
                          "collective_latency_us": allgather_us},
             "launch_check": launch_check,
             "episode_end_stats": summary,
-            "eager": {"ms_per_step": eager_elapsed / eager_steps * 1e3, "steps": eager_steps},
-            # dronesim_rollout_ex (episode layer) / dronesim_rollout (plain) / dronesim_rollout_random: us per step, 52 B per agent-step
-            "fused_rollout": None if ro_us is None else {
-                "epi_us": ro_us, "epi_frac52": fr52(ro_us),
-                "plain_us": rp_us, "plain_frac52": None if rp_us is None else fr52(rp_us),
-                "rand_us": rr_us},
         }
         if n1 is not None:          # the N = 1 figure of the SAME workload / episode layer, timed on rank 0 alone ahead of the N-rank region
             out["n1"] = {"value": n1["value"], "ms_per_step": n1["ms"], "ratio": value / n1["value"],
                          "efficiency": value / n1["value"] / world}
         if per_rank is not None:
             out["per_rank"] = per_rank
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(N, G, delta, args.cpu_budget)
-            out["cpu_baseline"]["reference"] = reference_record(args.workload)
-        else:
-            out["cpu_baseline"] = None
-        # the other BASELINE configs, timed by THIS process after the graded region (single-GPU default run only)
-        if (world == 1 and not args.no_other_workloads and args.workload == "c3" and policy is None and layer
-                and args.scaling == "weak" and not args.envs_per_gpu):
-            del pool
-            torch.cuda.empty_cache()
-            other = {}
-            for key, wl, pk, pr in (("c2", "c2", None, "f32"), ("c5_env", "c5", None, "f32"),
-                                    ("c3_8192", "c3_8192", None, "f32"), ("c4_one_gpu", "c4_one_gpu", None, "f32"),
-                                    ("c5_full", "c5_full", None, "f32"),
-                                    ("default_construction", "c3", None, "f32"),
-                                    ("c5_gaussian_f32", "c5", "gaussian", "f32"), ("c5_gaussian_bf16x3", "c5", "gaussian", "bf16x3"),
-                                    ("c5_gaussian_f16x2", "c5", "gaussian", "f16x2"),
-                                    ("c5_full_gaussian_f16x2", "c5_full", "gaussian", "f16x2"),   # configs[4]'s whole env axis WITH its policy, one rank
-                                    ("c3_softmax16_f32", "c3", "softmax16", "f32"), ("c3_softmax16_f16x2", "c3", "softmax16", "f16x2")):
-                try:
-                    other[key] = side_workload(torch, dev, wl, pk, precision=pr, default_construction=(key == "default_construction"))
-                except Exception as ex:                 # a side measurement must never cost the headline line
-                    other[key] = {"error": f"{type(ex).__name__}: {ex}"}
-            try:                                        # learner-side scans, reset, controllers
-                other["aux_kernels"] = aux_kernels(torch, dev)
-            except Exception as ex:
-                other["aux_kernels"] = {"error": f"{type(ex).__name__}: {ex}"}
-            try:                                        # BASELINE configs[0] shape through the E = 1 drop-in face
-                other["c1_compat"] = c1_compat(torch, dev)
-            except Exception as ex:
-                other["c1_compat"] = {"error": f"{type(ex).__name__}: {ex}"}
-            out["other_workloads"] = other
-        if world == 1 and not args.no_other_workloads and args.workload in ("c2", "c3", "c5") and policy is None and layer and not args.envs_per_gpu:
-            torch.cuda.empty_cache()
-            ds = device_span(args.workload)
-            if ds is not None:                           # bytes moved inside the launch's own execution window
-                ds["frac_inside_span"] = bytes_launch / (ds["span_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS
-            out["roofline"]["device_clock"] = ds
-            wc = write_ceiling()
-            if wc is not None and "write_GBps" in wc:    # bytes WRITTEN per launch (60 B per agent-step + per-env words) against the measured write rate
-                written = 60 * N * E + (9 + (32 if layer else 0)) * E
-                wc["written_bytes_per_launch"] = written
-                wc["frac"] = written / (kern_ms * 1e-3) / 1e9 / wc["write_GBps"]
-            out["roofline"]["write_ceiling"] = wc
-        if world == 1 and not args.no_rccl_probe:
-            out["exchange"]["rccl_probe"] = rccl_probe()
+        if args.full:
+            bytes_launch = algorithmic_bytes(N, E, layer)
+            achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+            traffic, traffic_src = pmc_traffic(args.workload) if (e_gpu == WORKLOADS[args.workload][1] and E == e_gpu) else (None, None)
+            fr52 = lambda us: 52.0 * N * E / (us * 1e-6) / 1e9 / HBM_PEAK_GBS
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               # SURVEY.md 8(d) bytes only (76 B per agent-step + 13 B per env-step, no episode-record bytes)
+                               "frac_survey_bytes": algorithmic_bytes(N, E, False) / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "survey_bytes_per_launch": algorithmic_bytes(N, E, False),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": "drone_kernel<K=2,FAR=0,step,%s>" % ("epi" if layer else "plain"), "kernel_ms": kern_ms,
+                               "algorithmic_bytes_per_launch": bytes_launch}
+            out["eager"] = {"ms_per_step": eager_elapsed / eager_steps * 1e3, "steps": eager_steps}
+            # dronesim_rollout_ex (episode layer) / dronesim_rollout (plain) / dronesim_rollout_random: us per step, 52 B per agent-step
+            out["fused_rollout"] = None if ro_us is None else {
+                "epi_us": ro_us, "epi_frac52": fr52(ro_us),
+                "plain_us": rp_us, "plain_frac52": None if rp_us is None else fr52(rp_us),
+                "rand_us": rr_us}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(N, G, delta, args.cpu_budget)
+                out["cpu_baseline"]["reference"] = reference_record(args.workload)
+            else:
+                out["cpu_baseline"] = None
+            # the other BASELINE configs, timed by THIS process after the graded region (single-GPU default run only)
+            if (world == 1 and not args.no_other_workloads and args.workload == "c3" and policy is None and layer
+                    and args.scaling == "weak" and not args.envs_per_gpu):
+                del pool
+                torch.cuda.empty_cache()
+                other = {}
+                for key, wl, pk, pr in (("c2", "c2", None, "f32"), ("c5_env", "c5", None, "f32"),
+                                        ("c3_8192", "c3_8192", None, "f32"), ("c4_one_gpu", "c4_one_gpu", None, "f32"),
+                                        ("c5_full", "c5_full", None, "f32"),
+                                        ("default_construction", "c3", None, "f32"),
+                                        ("c5_gaussian_f32", "c5", "gaussian", "f32"), ("c5_gaussian_bf16x3", "c5", "gaussian", "bf16x3"),
+                                        ("c5_gaussian_f16x2", "c5", "gaussian", "f16x2"),
+                                        ("c5_full_gaussian_f16x2", "c5_full", "gaussian", "f16x2"),   # configs[4]'s whole env axis WITH its policy, one rank
+                                        ("c3_softmax16_f32", "c3", "softmax16", "f32"), ("c3_softmax16_f16x2", "c3", "softmax16", "f16x2")):
+                    try:
+                        other[key] = side_workload(torch, dev, wl, pk, precision=pr, default_construction=(key == "default_construction"))
+                    except Exception as ex:                 # a side measurement must never cost the headline line
+                        other[key] = {"error": f"{type(ex).__name__}: {ex}"}
+                try:                                        # learner-side scans, reset, controllers
+                    other["aux_kernels"] = aux_kernels(torch, dev)
+                except Exception as ex:
+                    other["aux_kernels"] = {"error": f"{type(ex).__name__}: {ex}"}
+                try:                                        # BASELINE configs[0] shape through the E = 1 drop-in face
+                    other["c1_compat"] = c1_compat(torch, dev)
+                except Exception as ex:
+                    other["c1_compat"] = {"error": f"{type(ex).__name__}: {ex}"}
+                out["other_workloads"] = other
+            if world == 1 and not args.no_other_workloads and args.workload in ("c2", "c3", "c5") and policy is None and layer and not args.envs_per_gpu:
+                torch.cuda.empty_cache()
+                ds = device_span(args.workload)
+                if ds is not None:                           # bytes moved inside the launch's own execution window
+                    ds["frac_inside_span"] = bytes_launch / (ds["span_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS
+                out["roofline"]["device_clock"] = ds
+                wc = write_ceiling()
+                if wc is not None and "write_GBps" in wc:    # bytes WRITTEN per launch (60 B per agent-step + per-env words) against the measured write rate
+                    written = 60 * N * E + (9 + (32 if layer else 0)) * E
+                    wc["written_bytes_per_launch"] = written
+                    wc["frac"] = written / (kern_ms * 1e-3) / 1e9 / wc["write_GBps"]
+                out["roofline"]["write_ceiling"] = wc
+            if world == 1 and not args.no_rccl_probe:
+                out["exchange"]["rccl_probe"] = rccl_probe()
         line = json.dumps(compact(out), separators=(",", ":"))
         if len(line) > 7900:                            # the driver keeps 8 KB of stdout: never let the head fall off
             print(f"bench.py: JSON line is {len(line)} bytes (> 7900): dropping episode_end_stats / per-rank detail", file=sys.stderr)

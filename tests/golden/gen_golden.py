@@ -14,6 +14,8 @@ Fixtures hold DATA only (inputs and the reference's outputs):
   init_states.npz        seeded ctor/reset states + z/Ni       drone_env.py:171-212
   episode_n5.npz         config C1: one full episode, N=5, seeded softmax-16 policy
                          (rollout loop of train_problem.py:82-107)
+  discrete-A2C{critics,actors}_zeroed.pth
+                         the reference's saved module lists, weights zeroed   SAC_agents.py:404-406
 """
 import os
 import platform
@@ -294,9 +296,29 @@ def gen_policies():
     print("policies:", {k: v.shape for k, v in data.items() if k.endswith("_out")})
 
 
+def gen_saved_networks():
+    """The reference's saved module lists (models/discrete-A2C{critics,actors}.pth, torch.save of a list of
+    per-agent networks, SAC_agents.py:404-406) for the loader test: the pickle stream (archive/data.pkl) is copied
+    byte for byte, every tensor storage is zeroed and the archive members are deflated, so that the files keep
+    their structure and shapes but fit far under the size limit of a committed file."""
+    import zipfile
+    for name in ("discrete-A2Ccritics", "discrete-A2Cactors"):
+        src = zipfile.ZipFile(os.path.join(os.path.dirname(drone_env.__file__), "models", name + ".pth"))
+        dst = os.path.join(OUT, f"{name}_zeroed.pth")
+        with zipfile.ZipFile(dst, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as zo:
+            for info in src.infolist():                  # (the members keep their names and time stamps)
+                b = src.read(info.filename)
+                zo.writestr(zipfile.ZipInfo(info.filename, info.date_time), bytes(len(b)) if "/data/" in info.filename else b,
+                           compress_type=zipfile.ZIP_DEFLATED, compresslevel=9)
+        print("saved networks:", dst, os.path.getsize(dst), "bytes")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "policies":
         gen_policies()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "saved_networks":
+        gen_saved_networks()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "controllers":
         gen_controllers()
@@ -332,6 +354,7 @@ def main():
     gen_episode()
     gen_controllers()
     gen_policies()
+    gen_saved_networks()
 
 
 if __name__ == "__main__":

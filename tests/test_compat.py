@@ -72,14 +72,14 @@ def test_saved_module_lists_load_without_the_reference_code(tmp_path, kind, name
     assert (ok, sk) == {"critic": (0, 0), "discrete_softmax": (1, 1), "normal_actor": (2, 2)}[name]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/models/discrete-A2Ccritics.pth"), reason="reference artefacts absent")
-def test_real_reference_artefacts_load():
-    """The reference's own files (5 agents): critics 6 -> 200 -> 200 -> 1, discrete actors 6 -> 200 -> 200 -> 4."""
+def test_real_reference_artefacts_load(golden_dir):
+    """The reference's own files (5 agents): critics 6 -> 200 -> 200 -> 1, discrete actors 6 -> 200 -> 200 -> 4.
+    Fixtures: the files' pickle streams byte for byte, tensor storages zeroed (tests/golden/gen_golden.py)."""
     from scalable_collision_avoidance_rl_amd.compat import load_reference_modules
     from scalable_collision_avoidance_rl_amd.policies import stack_reference_modules
-    crit = stack_reference_modules(load_reference_modules("/root/reference/models/discrete-A2Ccritics.pth"))
+    crit = stack_reference_modules(load_reference_modules(os.path.join(golden_dir, "discrete-A2Ccritics_zeroed.pth")))
     assert tuple(crit[0].shape) == (5, 6, 200) and tuple(crit[4].shape) == (5, 200, 1) and crit[6:] == (0, 0)
-    act = stack_reference_modules(load_reference_modules("/root/reference/models/discrete-A2Cactors.pth"))
+    act = stack_reference_modules(load_reference_modules(os.path.join(golden_dir, "discrete-A2Cactors_zeroed.pth")))
     assert tuple(act[2].shape) == (5, 200, 200) and tuple(act[4].shape) == (5, 200, 4) and act[6:] == (1, 1)
 
 

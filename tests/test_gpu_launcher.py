@@ -61,14 +61,14 @@ def test_ranks_own_their_shards_of_the_gpu_outputs(tmp_path, N, G, E, T, W):
 def test_bench_py_runs_with_two_ranks_on_one_device():
     """bench.py through the driver's launcher (2 ranks, gloo, one device): barrier, max-over-ranks timing, the
     exchange inside the timed region, one JSON line from rank 0 with whole-job figures."""
-    r = _launch(2, "bench.py", ["--gpus", 2, "--steps", 30, "--warmup", 5, "--envs-per-gpu", 512, "--min-seconds", 0.05,
-                                "--no-cpu-baseline"], extra_env=dict(BENCH_BACKEND="gloo", BENCH_ONE_DEVICE="1"))
+    r = _launch(2, "bench.py", ["--gpus", 2, "--steps", 400, "--warmup", 5, "--envs-per-gpu", 512, "--min-seconds", 0.05,
+                                "--no-cpu-baseline", "--full"], extra_env=dict(BENCH_BACKEND="gloo", BENCH_ONE_DEVICE="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                      # rank 0 only
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["n_envs_total"] == 1024 and out["config"]["parallelism"] == "env-shard x2"
-    assert out["steps"] == 30 and out["repeats"] >= 1 and out["timed_steps"] == 30 * out["graph_copies"] * out["repeats"]
+    assert out["steps"] == 400 and out["repeats"] == 1 and out["timed_steps"] == 400 and out["graph_launches"] == 400
     assert out["value"] == pytest.approx(64 * 1024 * out["timed_steps"] / out["timed_seconds"], rel=1e-5)
     st = out["episode_end_stats"]
     assert st["world_size"] == 2 and st["agent_steps"] > 0
@@ -94,7 +94,7 @@ def test_bench_py_runs_with_eight_ranks_on_one_device():
     inside the timed region with its `rccl_ranks` / `backend` fields, every launch accounted for by the device records.
     (Ragged shards over 8 ranks: the next test.)"""
     r = _launch(8, "bench.py", ["--gpus", 8, "--steps", 20, "--warmup", 2, "--envs-per-gpu", 100, "--min-seconds", 0.03,
-                                "--no-cpu-baseline"],
+                                "--no-cpu-baseline", "--full"],
                 # (eight processes time-slice one GPU: the secondary measurements are shrunk, the graded region is not)
                 extra_env=dict(BENCH_BACKEND="gloo", BENCH_ONE_DEVICE="1", BENCH_EAGER_MIN_STEPS="40", BENCH_KERNEL_SAMPLE_EPISODES="1",
                                BENCH_GRAPH_LAUNCHES="400"), timeout=900)
@@ -120,7 +120,7 @@ def test_bench_py_c5_with_its_policy_runs_with_two_ranks_on_one_device():
     the observation every step) as 2 ranks on one device: one line, `per_rank`, every launch accounted for, the N = 1
     figure of the same loop next to `value`."""
     r = _launch(2, "bench.py", ["--gpus", 2, "--workload", "c5", "--policy", "gaussian", "--policy-precision", "f16x2",
-                                "--steps", 20, "--warmup", 2, "--min-seconds", 0.05, "--no-cpu-baseline"],
+                                "--steps", 20, "--warmup", 2, "--min-seconds", 0.05, "--no-cpu-baseline", "--full"],
                 extra_env=dict(BENCH_BACKEND="gloo", BENCH_ONE_DEVICE="1", BENCH_EAGER_MIN_STEPS="20", BENCH_KERNEL_SAMPLE_EPISODES="1",
                                BENCH_GRAPH_LAUNCHES="200"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -165,7 +165,7 @@ def test_bench_py_starts_its_own_ranks_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_BACKEND="gloo", BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--envs-per-gpu", "512",
-                        "--min-seconds", "0.05", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--min-seconds", "0.05", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -199,6 +199,37 @@ def test_bench_py_strong_scaling_splits_one_job():
     assert out["scaling"] == "strong" and out["config"]["n_envs_total"] == 512 and out["config"]["envs_per_gpu"] == 256
     assert out["value"] == pytest.approx(64 * 512 * out["timed_steps"] / out["timed_seconds"], rel=1e-5)
     assert out["launch_check"]["ok"] is True
+
+
+def test_bench_py_plain_run_times_exactly_the_requested_steps_and_dumps_its_outputs(tmp_path):
+    """A plain one-GPU run: the timed region is exactly --steps launches (here cut into two replays of a 200-launch graph
+    and one of the 50 left), no secondary measurement runs, and --dump-outputs writes the last step's outputs -- the same
+    files, bit for bit, from two runs with the same arguments."""
+    lines = []
+    for run in ("a", "b"):
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_ONE_DEVICE")}
+        env.update(BENCH_GRAPH_LAUNCHES="200")
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "450", "--warmup", "3", "--envs-per-gpu", "256",
+                            "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    out = lines[0]
+    assert out["steps"] == out["timed_steps"] == 450 and out["repeats"] == 3 and out["graph_launches"] == 200
+    assert out["ms_per_step"] == pytest.approx(out["timed_seconds"] / 450 * 1e3, rel=1e-4)
+    assert out["value"] == pytest.approx(64 * 256 * 450 / out["timed_seconds"], rel=1e-5)
+    assert out["exchange"]["reductions_in_timed_region"] == 3 and out["exchange"]["collectives_in_timed_region"] == 3
+    assert out["launch_check"]["ok"] is True and out["full"] is False
+    for key in ("roofline", "eager", "fused_rollout", "cpu_baseline", "other_workloads", "n1"):
+        assert key not in out, key
+    shapes = {"state_pos": (256, 64, 2), "state_vel": (256, 64, 2), "z_states": (256, 64, 6), "rewards": (256, 64),
+              "true_rewards": (256, 64), "n_collisions": (256,), "finished": (256,), "nbr_idx": (256, 64, 3), "episode_ring": (1, 8)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.shape == shape and a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
+        assert np.array_equal(a, b), k
+    # the ring of the last replay (50 launches, one reduction at its end) holds the env-steps of the whole rollout
+    assert np.load(tmp_path / "a" / "episode_ring.npy")[0, [3, 7]].sum() == out["launch_check"]["env_steps_recorded_all_ranks"]
 
 
 def test_rccl_all_gather_in_a_world_of_one():

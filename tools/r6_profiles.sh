@@ -26,7 +26,7 @@ rm -rf $OUT/prof_calib
 (cd /tmp && $T rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_calib -- python $ROOT/tools/prof_overhead.py run > $OUT/${TAG}_calib_prof.log 2>/dev/null)
 python tools/prof_overhead.py combine $OUT/${TAG}_calib_plain.log $OUT/prof_calib $OUT/${TAG}_calib_prof.log $OUT/${TAG}_c3_period_raw.json $OUT/${TAG}_c3_bench.json > $OUT/${TAG}_c3_period.json
 grep -E "period_corrected|per_dispatch_overhead|us_per_step" $OUT/${TAG}_c3_period.json
-prof c5_bench python $ROOT/bench.py --workload c5 --steps 1000 --warmup 100 $Q
+prof c5_bench python $ROOT/bench.py --full --workload c5 --steps 1000 --warmup 100 $Q
 python tools/trace_period.py $OUT/prof_c5_bench --kernel "drone_kernel<2, false, 0, 2, true>" --bench-log $OUT/prof_c5_bench.log --bytes 9968128 > $OUT/${TAG}_c5_period.json
 # (c) one CSV per policy shape (exact f32) at the C5 shard and at C3
 for kind in gaussian softmax16 critic; do
@@ -39,7 +39,7 @@ done
 PB_PREC=f16x2 PB_KINDS=gaussian prof c5_policy_f16x2_gaussian python $ROOT/tools/pbench.py c5
 (for sp in 1 "" 1 ""; do echo "# PB_SPLIT=$sp (1 = split kernel of rounds 2-5, empty = row-tile kernel)"; PB_SPLIT=$sp PB_PREC=f16x2 PB_KINDS=gaussian,critic,softmax16 $T python tools/pbench.py c5 c3 2>&1 | grep -v amdgpu.ids; done) > $OUT/${TAG}_pbench_f16x2_rowtile.log
 [ -f abl/libdronesim_trace.so ] && (for k in gaussian critic; do DRONESIM_LIB=abl/libdronesim_trace.so $T python tools/trace_rt16.py $k c5 2>&1 | grep -v amdgpu.ids; done) > $OUT/${TAG}_trace_rt16.log
-$T python bench.py --workload c5 --policy gaussian --policy-precision f16x2 > $OUT/${TAG}_c5_gaussian_f16x2_bench.json 2>/dev/null
+$T python bench.py --full --workload c5 --policy gaussian --policy-precision f16x2 > $OUT/${TAG}_c5_gaussian_f16x2_bench.json 2>/dev/null
 # SQ counters of the C5-shard step kernel
 bash tools/sq_counters.sh $TAG c5 > $OUT/${TAG}_sq_c5.log 2>&1
 # raw traces stay on the box (the merge back is capped at 64 MiB)

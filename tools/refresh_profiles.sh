@@ -10,16 +10,16 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 T="timeout 280"
 [ -f tools/libcalib.so ] || make -C tools libcalib.so   # PMC calibration copies (pmc_run.py)
-$T python bench.py --steps 2000 --warmup 200 > $OUT/${TAG}_c3_bench.json 2> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --steps 2000 --warmup 200 > $OUT/${TAG}_c3_bench.json 2> $OUT/${TAG}_c3_bench.err
 tail -1 $OUT/${TAG}_c3_bench.json | cut -c1-400
 Q="--no-cpu-baseline --no-other-workloads --no-rccl-probe"
-$T python bench.py --steps 20 --warmup 5 $Q > $OUT/${TAG}_c3_bench_steps20.json 2>> $OUT/${TAG}_c3_bench.err
-$T python bench.py --steps 2000 --warmup 200 $Q --no-episode-layer > $OUT/${TAG}_c3_bench_plain.json 2>> $OUT/${TAG}_c3_bench.err
-$T python bench.py --steps 200 --warmup 20 $Q --scaling strong > $OUT/${TAG}_c4_one_gpu_bench.json 2>> $OUT/${TAG}_c3_bench.err
-$T python bench.py --workload c5 --steps 1000 --warmup 100 $Q > $OUT/${TAG}_c5_bench.json 2>> $OUT/${TAG}_c3_bench.err
-$T python bench.py --workload c5 --policy gaussian --steps 400 --warmup 20 $Q > $OUT/${TAG}_c5_gaussian_f32_bench.json 2>> $OUT/${TAG}_c3_bench.err
-$T python bench.py --workload c5 --policy gaussian --policy-precision bf16x3 --steps 400 --warmup 20 $Q > $OUT/${TAG}_c5_gaussian_bf16x3_bench.json 2>> $OUT/${TAG}_c3_bench.err
-$T python bench.py --workload c2 --steps 2000 --warmup 200 $Q > $OUT/${TAG}_c2_bench.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --steps 20 --warmup 5 $Q > $OUT/${TAG}_c3_bench_steps20.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --steps 2000 --warmup 200 $Q --no-episode-layer > $OUT/${TAG}_c3_bench_plain.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --steps 200 --warmup 20 $Q --scaling strong > $OUT/${TAG}_c4_one_gpu_bench.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --workload c5 --steps 1000 --warmup 100 $Q > $OUT/${TAG}_c5_bench.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --workload c5 --policy gaussian --steps 400 --warmup 20 $Q > $OUT/${TAG}_c5_gaussian_f32_bench.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --workload c5 --policy gaussian --policy-precision bf16x3 --steps 400 --warmup 20 $Q > $OUT/${TAG}_c5_gaussian_bf16x3_bench.json 2>> $OUT/${TAG}_c3_bench.err
+$T python bench.py --full --workload c2 --steps 2000 --warmup 200 $Q > $OUT/${TAG}_c2_bench.json 2>> $OUT/${TAG}_c3_bench.err
 cd /tmp
 prof() {   # name, command...
     local name=$1; shift
@@ -27,7 +27,7 @@ prof() {   # name, command...
     $T rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- "$@" > $OUT/prof_$name.log 2>&1
     cp $(find $OUT/prof_$name -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_${name}_kernel_stats.csv
 }
-(cd $ROOT && prof c3_bench python bench.py --steps 1000 --warmup 100 $Q)
+(cd $ROOT && prof c3_bench python bench.py --full --steps 1000 --warmup 100 $Q)
 cp $(find $OUT/prof_c3_bench -name '*domain_stats.csv' | head -1) $OUT/${TAG}_c3_bench_domain_stats.csv 2>/dev/null
 (cd $ROOT && prof c3_kbench python tools/kbench.py c3)
 (cd $ROOT && prof rollout python tools/rbench.py c3 c5)
