@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""The reference's training loop (train_problem.py:82-115) on the device: per episode, a rollout window of T steps into an
+on-device `RolloutStorage` (batched softmax-16 policy, one env launch per step), then ONE `SA2CLearner.train` -- the
+batched `SA2CAgents.train_NN` (SAC_agents.py:280-357): critic MSE + clip + Adam, baseline from the post-update critic,
+actor loss + clip + Adam, for all N agents' networks at once in HIP.
+
+    python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from scalable_collision_avoidance_rl_amd import drones
+from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
+from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
+
+
+def linear_init(gen, n, fan_in, fan_out):
+    """torch.nn.Linear's default initialisation, stacked over agents, in the kernels' [in, out] layout."""
+    b = 1 / np.sqrt(fan_in)
+    return ((torch.rand(n, fan_in, fan_out, generator=gen) * 2 - 1) * b, (torch.rand(n, fan_out, generator=gen) * 2 - 1) * b)
+
+
+def network(gen, n, sizes):
+    out = []
+    for fi, fo in zip(sizes[:-1], sizes[1:]):
+        out += linear_init(gen, n, fi, fo)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--agents", type=int, default=5)
+    ap.add_argument("--episodes", type=int, default=5)
+    args = ap.parse_args()
+    N, E, T, dev = args.agents, args.envs, 200, "cuda:0"
+    env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
+                 device=dev, seed=1, auto_reset=True)
+    d_in = env.local_state_space
+    gen = torch.Generator().manual_seed(0)
+    actor = BatchedMLP(*network(gen, N, [d_in, 300, 300, 16]), 1, 1, device=dev, seed=3)     # DiscreteSoftmaxNN x N
+    critic = BatchedMLP(*network(gen, N, [d_in, 200, 200, 1]), 0, 0, device=dev)            # CriticNN x N
+    storage = RolloutStorage(env, T, actions=True)
+    # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
+    learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0)
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for ep in range(args.episodes):
+        storage.begin()
+        for t in range(T):
+            actor.sample_action(env.z, env=env, act_out=storage.actions[t])
+            env.step(storage.actions[t], into=(storage, t))
+        start.record()
+        out = learner.train(storage)
+        stop.record()
+        torch.cuda.synchronize()
+        print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
+              f"actor loss {float(out['actor_loss'].mean()):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
+              f"{float(out['actor_grad_norm'].mean()):.1f}  update {start.elapsed_time(stop):.2f} ms")
+
+
+if __name__ == "__main__":
+    main()

@@ -34,6 +34,7 @@
 #ifndef DRONESIM_H
 #define DRONESIM_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -406,6 +407,38 @@ int dronesim_mlp_rt16_blocks(int h1, int h2, int nout);
 int dronesim_mlp_forward_f16x2_rt(const DroneMlpBf16 *m, const float *x, float *out, float *act, int32_t *act_idx,
                                   uint64_t seed, uint64_t counter, int64_t env_base,
                                   const int32_t *t, const int32_t *episode, int E, void *stream);
+
+/* Per-agent learner step of the batched MLPs (SAC_agents.py:280-357, SA2CAgents.train_NN), exact float32.  The DroneMlp must
+ * describe the PLAIN weight arrays (w2_layout = 0, EINVAL otherwise): w1 [N][d_in][h1], b1 [N][h1], w2 [N][h1][h2], b2 [N][h2],
+ * w3 [N][h2][nout], b3 [N][nout]; 1 <= d_in <= 64, h1, h2 <= 4096, nout <= 32; out_kind 0 with nout = 1, 1 with nout >= 2,
+ * 2 with nout = 4 and an even h2 (the block-diagonal output layer of DroneMlp's NormalActorNN: w3[k][j] with
+ * (k < h2/2) != (j < 2) is a structural zero -- its gradient is defined as 0, so it stays 0 under dronesim_adam_step).
+ *
+ * Flat gradient layout (grad, and Adam's m1 / m2): ONE buffer per network holding the six tensors in the order
+ *   w1 | b1 | w2 | b2 | w3 | b3, each [N][...] like the weights: N * (d_in h1 + h1 + h1 h2 + h2 + h2 nout + nout) floats.
+ *
+ * dronesim_mlp_grad: gradients of the loss  sum_i L_i,  L_i = row_scale * sum_r l(r, i)  over R rows:
+ *   x      float32 [R][N][d_in]   (a RolloutStorage window z_pre [T][E][N][d_in] is R = T E rows)
+ *   out_kind 0 (critic):   l = (V_i(x_r) - target[r][i])^2                      target float32 [R][N]; row_scale = 1 / R is MSE
+ *   out_kind 1 (softmax):  l = -weight[r][i] log softmax(o)[a]                   act float32 [R][N][2]: a = the index of the action list
+ *                          entry (angle 2 pi a / nout) nearest to the stored unit action; weight float32 [R][N]
+ *   out_kind 2 (Gaussian): l = -weight[r][i] sum_d [-0.5 log(2 pi var_d) - (act_d - mu_d)^2 / (2 var_d)],  mu = tanh, var = sigmoid
+ * grad (flat, above) is OVERWRITTEN with dL_i / dparams_i, loss float32 [N] with L_i.  Rows go in chunks of rows_per_chunk (a
+ * positive multiple of 64); ws is a device workspace of at least dronesim_mlp_grad_workspace(m, rows_per_chunk) bytes.  No float
+ * atomics: the result is bit-identical run to run.
+ *
+ * dronesim_adam_step: per agent i, clip_grad_norm_ then torch.optim.Adam (no weight decay, no amsgrad), IN PLACE on the weight
+ * arrays of m (the const pointers are written):
+ *   grad_norm[i] = || grad_i ||_2 over the six tensors (pre-clip, float32 [N]);  grad_i *= min(1, max_norm / (grad_norm[i] + 1e-6))
+ *   (the clipped gradient is written back);  step[i] += 1 (int32 [N], device memory: a captured graph advances it on every replay);
+ *   m1 = m1 + (1 - beta1) (g - m1);  m2 = beta2 m2 + (1 - beta2) g^2;
+ *   p -= lr / (1 - beta1^step) * m1 / (sqrt(m2) / sqrt(1 - beta2^step) + eps).
+ * m1, m2: flat layout, zero before the first step.                                                                       */
+int dronesim_mlp_grad_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
+int dronesim_mlp_grad(const DroneMlp *m, const float *x, int R, float row_scale, const float *target, const float *act,
+                      const float *weight, float *grad, float *loss, int rows_per_chunk, void *ws, size_t ws_bytes, void *stream);
+int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1, float beta2,
+                       float eps, float max_norm, float *grad_norm, void *stream);
 
 const char *dronesim_last_error(void);
 const char *dronesim_error_string(int code);

@@ -30,6 +30,7 @@ EPISODE_REDUCE_DOUBLES = 8           # DRONESIM_EPISODE_REDUCE_DOUBLES
 SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_rollout", "dronesim_control", "dronesim_returns", "dronesim_advantage", "dronesim_episode_stats", "dronesim_mlp_forward", "dronesim_mlp_forward_bf16",
            "dronesim_step_ex", "dronesim_step_call", "dronesim_rollout_ex", "dronesim_rollout_random", "dronesim_reset_ex", "dronesim_reset_observe", "dronesim_episode_reduce",
            "dronesim_mlp_forward_bf16x3", "dronesim_mlp_forward_f16x2", "dronesim_mlp_bf16x3_stages", "dronesim_mlp_rt_blocks", "dronesim_mlp_rt16_blocks", "dronesim_mlp_forward_f16x2_rt",
+           "dronesim_mlp_grad_workspace", "dronesim_mlp_grad", "dronesim_adam_step",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -140,6 +141,11 @@ def lib():
     L.dronesim_mlp_forward_f16x2_rt.argtypes = L.dronesim_mlp_forward_bf16.argtypes
     L.dronesim_mlp_forward_f16x2_rt.restype = C.c_int
     L.dronesim_mlp_bf16x3_stages.restype = C.c_int
+    PM = C.POINTER(DroneMlp)
+    L.dronesim_mlp_grad_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
+    L.dronesim_mlp_grad.argtypes = [PM, vp, i32, f32, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    L.dronesim_adam_step.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp]
+    L.dronesim_mlp_grad_workspace.restype = L.dronesim_mlp_grad.restype = L.dronesim_adam_step.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

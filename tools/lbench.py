@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Learner micro-benchmark (developer tool; bench.py stays the project's yardstick): one `SA2CLearner.train` per shape,
+timed with device events after warm-up.
+
+    python tools/lbench.py [--configs c1,c3,c5] [--reps 3] [--warmup 1]
+
+Shapes (N x E x T, actor + critic of the reference's widths):
+    c1   5 x 1 x 200       softmax-16 actor (6 -> 300 -> 300 -> 16) + critic (6 -> 200 -> 200 -> 1)
+    c3   64 x 4096 x 200   the same networks
+    c5   256 x 512 x 200   Gaussian actor (6 -> 400 -> 200|200 -> 4) + critic          (the C5 shard)
+Prints one JSON line per shape: ms per update, FLOP from shapes (2 per multiply-add: forward, the two backward products of
+each layer, and the critic's post-update forward for the baseline) and the share of the 157.3 TF float32 matrix peak.
+Per-kernel times come from a separate run under `rocprofv3 --kernel-trace --stats -d DIR -o lbench -- python tools/lbench.py
+--configs c3 --reps 1 --warmup 0` (one update, nothing else on the GPU but the setup's small kernels):
+`python tools/lbench.py --stats DIR/.../lbench_kernel_stats.csv` prints each kernel's total ms and share of the update's."""
+import argparse
+import json
+import math
+import os
+import sys
+from types import SimpleNamespace
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PEAK_TF = 157.3
+CONFIGS = {"c1": (5, 1, 200, "softmax"), "c3": (64, 4096, 200, "softmax"), "c5": (256, 512, 200, "gaussian")}
+
+
+def mlp_flop(rows, d_in, h1, h2, nout, backward=True):
+    fwd = 2 * rows * (d_in * h1 + h1 * h2 + h2 * nout)
+    if not backward:
+        return fwd
+    # dW3, dH2, dW2, dH1, dW1 (the bias rows are noise)
+    return fwd + 2 * rows * (2 * h2 * nout + 2 * h1 * h2 + d_in * h1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="c1,c3,c5")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--stats", help="a rocprofv3 kernel_stats.csv to summarise instead of running")
+    args = ap.parse_args()
+    if args.stats:
+        import csv
+        rows = list(csv.DictReader(open(args.stats)))
+        tot = sum(float(r["TotalDurationNs"]) for r in rows)
+        for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):
+            print(json.dumps(dict(kernel=r["Name"][:60], calls=int(r["Calls"]), total_ms=round(float(r["TotalDurationNs"]) / 1e6, 3),
+                                  share=round(float(r["TotalDurationNs"]) / tot, 4))))
+        return
+    import torch
+    from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
+    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+    dev = "cuda:0"
+    for name in args.configs.split(","):
+        N, E, T, kind = CONFIGS[name]
+        d_in = 6
+        g = torch.Generator(device=dev).manual_seed(0)
+        u = lambda *s, fan: (torch.rand(*s, device=dev, generator=g) * 2 - 1) / math.sqrt(fan)
+        net = lambda h1, h2, no: [u(N, d_in, h1, fan=d_in), u(N, h1, fan=d_in), u(N, h1, h2, fan=h1), u(N, h2, fan=h1),
+                                  u(N, h2, no, fan=h2), u(N, no, fan=h2)]
+        if kind == "softmax":
+            aw, ak, (h1a, h2a, noa) = net(300, 300, 16), 1, (300, 300, 16)
+        else:
+            aw, ak, (h1a, h2a, noa) = net(400, 400, 4), 2, (400, 400, 4)
+            aw[4][:, :200, 2:] = 0; aw[4][:, 200:, :2] = 0
+        actor, critic = BatchedMLP(*aw, ak, ak, device=dev), BatchedMLP(*net(200, 200, 1), 0, 0, device=dev)
+        x = (torch.rand(T, E, N, d_in, device=dev, generator=g) * 2 - 1) * 3
+        a = torch.randint(0, 16, (T, E, N), device=dev, generator=g).float() * (2 * math.pi / 16)
+        st = SimpleNamespace(z_pre=x, reward=torch.randn(T, E, N, device=dev, generator=g),
+                             done=torch.zeros(T, E, dtype=torch.uint8, device=dev), actions=torch.stack([a.cos(), a.sin()], -1),
+                             nbr_pre=torch.stack([torch.arange(N, device=dev).expand(T, E, N)] * 3, -1).int().contiguous())
+        st.done[-1] = 1
+        learner = SA2CLearner(actor, critic, 0.99)
+        for _ in range(args.warmup):
+            learner.train(st)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        times = []
+        for _ in range(args.reps):
+            ev[0].record(); learner.train(st); ev[1].record()
+            torch.cuda.synchronize()
+            times.append(ev[0].elapsed_time(ev[1]))
+        rows = T * E * N
+        flop = mlp_flop(rows, d_in, 200, 200, 1) + mlp_flop(rows, d_in, h1a, h2a, noa) + mlp_flop(rows, d_in, 200, 200, 1, False)
+        ms = min(times)
+        print(json.dumps(dict(config=name, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3), ms_all=[round(t, 3) for t in times],
+                              flop=flop, tflops=round(flop / ms / 1e9, 2), peak_share=round(flop / ms / 1e9 / PEAK_TF, 4))))
+
+
+if __name__ == "__main__":
+    main()
