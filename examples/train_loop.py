@@ -4,7 +4,10 @@ on-device `RolloutStorage` (batched softmax-16 policy, one env launch per step),
 batched `SA2CAgents.train_NN` (SAC_agents.py:280-357): critic MSE + clip + Adam, baseline from the post-update critic,
 actor loss + clip + Adam, for all N agents' networks at once in HIP.
 
-    python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5]
+    python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
+
+``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
+used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
 """
 import argparse
 import os
@@ -16,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from scalable_collision_avoidance_rl_amd import drones
-from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
+from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
 from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
 from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
 
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--agents", type=int, default=5)
     ap.add_argument("--episodes", type=int, default=5)
+    ap.add_argument("--learner", choices=("sa2c", "ppo"), default="sa2c")
+    ap.add_argument("--epochs", type=int, default=10, help="epochs per window (--learner ppo)")
     args = ap.parse_args()
     N, E, T, dev = args.agents, args.envs, 200, "cuda:0"
     env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
@@ -49,7 +54,10 @@ def main():
     critic = BatchedMLP(*network(gen, N, [d_in, 200, 200, 1]), 0, 0, device=dev)            # CriticNN x N
     storage = RolloutStorage(env, T, actions=True)
     # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
-    learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0)
+    if args.learner == "ppo":
+        learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0)
+    else:
+        learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0)
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for ep in range(args.episodes):
         storage.begin()
@@ -60,9 +68,13 @@ def main():
         out = learner.train(storage)
         stop.record()
         torch.cuda.synchronize()
+        ppo = ""
+        if args.learner == "ppo":       # the last epoch's diagnostics (the first epoch's ratio is exactly 1)
+            ppo = (f"  clipped {float(out['clip_fraction'][-1].mean()):.3f}  kl {float(out['approx_kl'][-1].mean()):+.2e}  "
+                   f"ratio [{float(out['ratio_min'][-1].min()):.3f}, {float(out['ratio_max'][-1].max()):.3f}]")
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(out['actor_loss'].mean()):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
-              f"{float(out['actor_grad_norm'].mean()):.1f}  update {start.elapsed_time(stop):.2f} ms")
+              f"{float(out['actor_grad_norm'].mean()):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")
 
 
 if __name__ == "__main__":

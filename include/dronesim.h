@@ -277,11 +277,17 @@ int dronesim_episode_stats(const float *reward, const float *true_reward, const 
  *   dronesim_advantage  weight of the actor loss  w[t,i] = gamma^t / N * sum_{j in Ni[t]} (G[t,j] - V[t,i])
  *                       (SAC_agents.py:333-351); nbr_idx [T][E][N][K1] is the neighbour list the action was
  *                       based on (slot 0 = i, -1 = empty); with `done` the exponent restarts after every
- *                       episode end.                                                            */
+ *                       episode end.
+ *   dronesim_neighbour_advantage   the PPO learner's advantage (SAC_agents.py:498-501, :512-513), no gamma^t, no 1 / N:
+ *                       adv[t,i] = sum_{j in Ni[t]} G[t,j] - c V[t,i],  c = 1 (per_neighbour = 0: ONE baseline against the
+ *                       neighbour sum, the reference's form) or c = |Ni[t]| (per_neighbour = 1).  G, V, adv [T][E][N],
+ *                       nbr_idx as for dronesim_advantage; independent of `done` (nothing runs along t).  */
 int dronesim_returns(const float *reward, const uint8_t *done, float gamma, float *G,
                      int T, int E, int N, void *stream);
 int dronesim_advantage(const float *G, const float *V, const int32_t *nbr_idx, const uint8_t *done,
                        float gamma, float *w, int T, int E, int N, int K1, void *stream);
+int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *nbr_idx, int per_neighbour, float *adv,
+                                 int T, int E, int N, int K1, void *stream);
 
 /* Batched per-agent policy / critic forward: N independent 3-layer MLPs, one per agent,
  * evaluated on x[E][N][d_in] in one launch on the matrix cores in exact float32.
@@ -433,10 +439,32 @@ int dronesim_mlp_forward_f16x2_rt(const DroneMlpBf16 *m, const float *x, float *
  *   (the clipped gradient is written back);  step[i] += 1 (int32 [N], device memory: a captured graph advances it on every replay);
  *   m1 = m1 + (1 - beta1) (g - m1);  m2 = beta2 m2 + (1 - beta2) g^2;
  *   p -= lr / (1 - beta1^step) * m1 / (sqrt(m2) / sqrt(1 - beta2^step) + eps).
- * m1, m2: flat layout, zero before the first step.                                                                       */
+ * m1, m2: flat layout, zero before the first step.
+ *
+ * PPO with the clipped probability ratio (SAC_agents.py:410-573, SPPOAgents.train), actors only (out_kind 1 or 2; a critic is
+ * EINVAL); same chunked chain, the same GEMM launches and the same log-probability expressions as dronesim_mlp_grad:
+ * dronesim_mlp_logp: forward only.  logp[r][i] = log pi_i(act[r][i] | x_r)  (float32 [R][N], OVERWRITTEN): out_kind 1 the log
+ *   softmax at the stored action's index, out_kind 2 the Gaussian log density with VARIANCE sigmoid (:558-573).  ws as for
+ *   dronesim_mlp_grad (dronesim_mlp_grad_workspace bytes).  grad-free: no weight or gradient buffer is written.
+ * dronesim_mlp_grad_ppo: gradients of  sum_i L_i,  L_i = -row_scale * sum_r min(r Adv, clamp(r, 1 - clip_eps, 1 + clip_eps) Adv)
+ *   with  r = exp(logp - logp_old[r][i]),  Adv = adv[r][i]  (both float32 [R][N], constants of the loss; row_scale = 1 / R is
+ *   the reference's mean).  As autograd gives it, a row contributes  -row_scale Adv r dlogp/dparams  unless the clipped branch
+ *   is the strict minimum (Adv > 0 and r > 1 + clip_eps, or Adv < 0 and r < 1 - clip_eps), where it contributes 0.
+ *   0 < clip_eps < 1.  grad (flat) and loss [N] are OVERWRITTEN as by dronesim_mlp_grad; so is stats, float32 [4][N]:
+ *     stats[0][i] share of agent i's rows on the clipped branch, stats[1][i] mean of logp_old - logp (approximate KL),
+ *     stats[2][i] / stats[3][i] min / max of r   -- per-row values reduced in a fixed order (no float atomics).
+ *   ws: at least dronesim_mlp_grad_ppo_workspace(m, rows_per_chunk) bytes (the gradient workspace + 12 N rows_per_chunk).
+ *   With the logp_old of dronesim_mlp_logp at the same weights and rows_per_chunk, logp == logp_old bit for bit: r is
+ *   exactly 1, nothing is clipped and stats[1] is 0.                                                                     */
 int dronesim_mlp_grad_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
 int dronesim_mlp_grad(const DroneMlp *m, const float *x, int R, float row_scale, const float *target, const float *act,
                       const float *weight, float *grad, float *loss, int rows_per_chunk, void *ws, size_t ws_bytes, void *stream);
+int dronesim_mlp_grad_ppo_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
+int dronesim_mlp_logp(const DroneMlp *m, const float *x, int R, const float *act, float *logp, int rows_per_chunk, void *ws,
+                      size_t ws_bytes, void *stream);
+int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, float row_scale, const float *act, const float *logp_old,
+                          const float *adv, float clip_eps, float *grad, float *loss, float *stats, int rows_per_chunk, void *ws,
+                          size_t ws_bytes, void *stream);
 int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1, float beta2,
                        float eps, float max_norm, float *grad_norm, void *stream);
 

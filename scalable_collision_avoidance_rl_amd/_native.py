@@ -31,6 +31,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_step_ex", "dronesim_step_call", "dronesim_rollout_ex", "dronesim_rollout_random", "dronesim_reset_ex", "dronesim_reset_observe", "dronesim_episode_reduce",
            "dronesim_mlp_forward_bf16x3", "dronesim_mlp_forward_f16x2", "dronesim_mlp_bf16x3_stages", "dronesim_mlp_rt_blocks", "dronesim_mlp_rt16_blocks", "dronesim_mlp_forward_f16x2_rt",
            "dronesim_mlp_grad_workspace", "dronesim_mlp_grad", "dronesim_adam_step",
+           "dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -146,6 +147,12 @@ def lib():
     L.dronesim_mlp_grad.argtypes = [PM, vp, i32, f32, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
     L.dronesim_adam_step.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp]
     L.dronesim_mlp_grad_workspace.restype = L.dronesim_mlp_grad.restype = L.dronesim_adam_step.restype = C.c_int
+    L.dronesim_neighbour_advantage.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]
+    L.dronesim_mlp_grad_ppo_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
+    L.dronesim_mlp_logp.argtypes = [PM, vp, i32, vp, vp, i32, vp, C.c_size_t, vp]
+    L.dronesim_mlp_grad_ppo.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    for name in ("dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo"):
+        getattr(L, name).restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

@@ -407,6 +407,43 @@ __global__ void __launch_bounds__(256) advantage_kernel(const float *__restrict_
     }
 }
 
+// advantage_kernel's sibling for the PPO learner (SAC_agents.py:498-501, :512-513): the neighbour sum of the returns less the
+// agent's own baseline, with no gamma^t and no 1 / N, so nothing runs along t and a thread owns one (t, e, i):
+//   adv = sum_{j in Ni[t]} G[t, e, j] - c V[t, e, i],   c = 1 (the reference's form) or |Ni[t]| (per_neighbour).
+// Coalesced reads of V and the neighbour rows and a coalesced store; the gathers of G fall into the env's own 4 N-byte row.
+template <int K1C>
+__global__ void __launch_bounds__(256) neighbour_advantage_kernel(const float *__restrict__ G, const float *__restrict__ V,
+                                                                  const int *__restrict__ nbr, int per_neighbour,
+                                                                  float *__restrict__ adv, size_t rows, int N, int K1)
+{
+    const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= rows * N) return;
+    const float *Grow = G + (o / N) * N;
+    const int k1 = K1C > 0 ? K1C : K1;
+    float q = 0.0f;
+    int cnt = 0;
+    if (K1C > 0) {
+        int j[K1C > 0 ? K1C : 1];
+        float g[K1C > 0 ? K1C : 1];
+#pragma unroll
+        for (int s = 0; s < K1C; ++s) j[s] = __builtin_nontemporal_load(nbr + o * K1C + s);
+#pragma unroll
+        for (int s = 0; s < K1C; ++s) g[s] = Grow[max(j[s], 0)];
+#pragma unroll
+        for (int s = 0; s < K1C; ++s) {
+            q += j[s] >= 0 ? g[s] : 0.0f;
+            cnt += j[s] >= 0;
+        }
+    } else {
+        for (int s = 0; s < k1; ++s) {
+            const int js = nbr[o * k1 + s];
+            if (js >= 0) { q += Grow[js]; ++cnt; }
+        }
+    }
+    const float c = per_neighbour ? (float)cnt : 1.0f;
+    adv[o] = q - c * V[o];
+}
+
 // ---------------------------------------------------------------------------------------
 // The logged statistic of one step (train_problem.py:98-100: sums of rewards, true rewards and collisions),
 // accumulated in float64 into acc[5] = (sum r, sum true r, sum collisions, agent-steps, env-steps).
@@ -961,6 +998,25 @@ int dronesim_advantage(const float *G, const float *V, const int32_t *nbr_idx, c
     else
         hipLaunchKernelGGL(advantage_kernel<0>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                            G, V, nbr_idx, done, gamma, w, T, E, N, K1);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *nbr_idx, int per_neighbour, float *adv,
+                                 int T, int E, int N, int K1, void *stream)
+{
+    if (!G || !V || !nbr_idx || !adv || T < 0 || E < 0 || N < 1 || K1 < 1 || per_neighbour < 0 || per_neighbour > 1)
+        return fail(DRONESIM_EINVAL, "dronesim_neighbour_advantage: bad argument");
+    if (T == 0 || E == 0) return DRONESIM_OK;
+    const size_t rows = (size_t)T * E, items = rows * N;
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (K1 == 3)
+        hipLaunchKernelGGL(neighbour_advantage_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+                           G, V, nbr_idx, per_neighbour, adv, rows, N, K1);
+    else
+        hipLaunchKernelGGL(neighbour_advantage_kernel<0>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+                           G, V, nbr_idx, per_neighbour, adv, rows, N, K1);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
     return DRONESIM_OK;

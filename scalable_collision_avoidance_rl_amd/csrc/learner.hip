@@ -15,6 +15,11 @@
 // adding to a cleared buffer: the entry point enqueues kernels only (no memset node), which keeps a captured graph's
 // replays identical to eager calls.  Bias gradients are one more output row of the same GEMM, fed by a virtual
 // row of ones.
+//
+// PPO (SAC_agents.py:410-573, SPPOAgents.train; include/dronesim.h: dronesim_mlp_logp, dronesim_mlp_grad_ppo) is the same chain
+// around another head: ppo_head_kernel computes log pi(a | x) with the expressions of the actor kinds above and either stops there
+// (the forward-only pass: the old policy's log-probabilities) or forms the ratio to a stored logp_old, the clipped surrogate's
+// per-row loss and dLoss/dO, plus three per-row diagnostics that ppo_stats_kernel reduces per agent in a fixed order.
 #include "common.hpp"
 #include "../../include/dronesim.h"
 
@@ -190,6 +195,113 @@ __global__ __launch_bounds__(kThreads) void loss_sum_kernel(const float *L, long
     if (threadIdx.x == 0) loss[i] = first ? part[0] : loss[i] + part[0];
 }
 
+// The PPO head of one (row, agent) of an actor (kinds 1 and 2; SAC_agents.py:494, :541-549): logp = log pi_i(a | x) with the
+// expressions of head_kernel's kinds; with `logp_out` set that is all it writes (the forward-only pass).  Otherwise
+//   r = exp(logp - logp_old),  l = -min(r Adv, clamp(r, lo, hi) Adv)  (times `scale`) into L,
+//   dLoss/dO = -scale Adv r dlogp/dO in place of O -- 0 where the clipped branch is the strict minimum (Adv > 0 and r > hi, or
+//   Adv < 0 and r < lo) --, and the row's diagnostics into S: [0] clipped (0 / 1), [1] logp_old - logp, [2] r, each [N][Rc].
+// Both modes are ONE kernel and share the instructions up to `lp`: on the same O they give the same bits, so r is exactly 1
+// until the actor moves.
+__global__ __launch_bounds__(kThreads) void ppo_head_kernel(float *O, float *L, float *S, long long Rc, int rc, long long r0, int N,
+                                                            int nout, int kind, float scale, const float *act,
+                                                            const float *logp_old, const float *adv, float lo, float hi,
+                                                            float *logp_out)
+{
+    const long long id = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (id >= (long long)rc * N) return;
+    const int i = (int)(id / rc), m = (int)(id % rc);
+    float *o = O + ((long long)i * Rc + m) * nout;
+    const long long src = (r0 + m) * N + i;
+    float lp, lse = 0.f;
+    int a = 0;
+    float mu[2], var[2], omv[2], diff[2];
+    if (kind == 1) {
+        const float ax = act[2 * src], ay = act[2 * src + 1];
+        a = (int)rintf(atan2f(ay, ax) * (float)nout * 0.15915494309189535f);
+        a = ((a % nout) + nout) % nout;
+        float mx = o[0];
+        for (int j = 1; j < nout; ++j) mx = fmaxf(mx, o[j]);
+        float s = 0.f;
+        for (int j = 0; j < nout; ++j) s += expf(o[j] - mx);
+        lse = mx + logf(s);
+        lp = o[a] - lse;
+    } else {
+        lp = 0.f;
+        for (int d = 0; d < 2; ++d) {
+            mu[d] = tanhf(o[d]);
+            const float e = expf(-o[2 + d]);
+            var[d] = 1.f / (1.f + e);
+            omv[d] = e / (1.f + e);
+            diff[d] = act[2 * src + d] - mu[d];
+            lp += -0.5f * logf(6.283185307179586f * var[d]) - diff[d] * diff[d] / (2.f * var[d]);
+        }
+    }
+    if (logp_out) {
+        logp_out[src] = lp;
+        return;
+    }
+    const float dl = lp - logp_old[src];
+    const float r = expf(dl);
+    const float A = adv[src];
+    const bool clipped = (A > 0.f && r > hi) || (A < 0.f && r < lo);
+    const float c = clipped ? 0.f : -scale * A * r;
+    if (kind == 1) {
+        for (int j = 0; j < nout; ++j) {
+            const float p = expf(o[j] - lse);
+            o[j] = c * ((j == a ? 1.f : 0.f) - p);
+        }
+    } else {
+        for (int d = 0; d < 2; ++d) {
+            o[d] = c * (diff[d] / var[d]) * (1.f - mu[d] * mu[d]);
+            o[2 + d] = c * (-0.5f + diff[d] * diff[d] / (2.f * var[d])) * omv[d];
+        }
+    }
+    const long long dst = (long long)i * Rc + m, plane = (long long)N * Rc;
+    L[dst] = -scale * fminf(r * A, fminf(fmaxf(r, lo), hi) * A);
+    S[dst] = clipped ? 1.f : 0.f;
+    S[plane + dst] = -dl;
+    S[2 * plane + dst] = r;
+}
+
+// stats [4][N] of agent i over the chunks, in loss_sum_kernel's fixed order (strided partials, then a fixed tree): the clipped
+// rows' count, the sum of logp_old - logp, min r, max r; the first chunk writes, the last divides the two sums by R
+__global__ __launch_bounds__(kThreads) void ppo_stats_kernel(const float *S, long long Rc, int rc, int N, int first, int last,
+                                                             float rows, float *stats)
+{
+    __shared__ float part[4][kThreads];
+    const int i = blockIdx.x;
+    const long long plane = (long long)N * Rc;
+    const float inf = __builtin_inff();
+    float nc = 0.f, kl = 0.f, lo = inf, hi = -inf;
+    for (int m = threadIdx.x; m < rc; m += kThreads) {
+        const long long at = (long long)i * Rc + m;
+        nc += S[at];
+        kl += S[plane + at];
+        const float r = S[2 * plane + at];
+        lo = fminf(lo, r);
+        hi = fmaxf(hi, r);
+    }
+    part[0][threadIdx.x] = nc; part[1][threadIdx.x] = kl; part[2][threadIdx.x] = lo; part[3][threadIdx.x] = hi;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            part[0][threadIdx.x] += part[0][threadIdx.x + w];
+            part[1][threadIdx.x] += part[1][threadIdx.x + w];
+            part[2][threadIdx.x] = fminf(part[2][threadIdx.x], part[2][threadIdx.x + w]);
+            part[3][threadIdx.x] = fmaxf(part[3][threadIdx.x], part[3][threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        nc = first ? part[0][0] : stats[i] + part[0][0];
+        kl = first ? part[1][0] : stats[N + i] + part[1][0];
+        stats[i] = last ? nc / rows : nc;
+        stats[N + i] = last ? kl / rows : kl;
+        stats[2 * N + i] = first ? part[2][0] : fminf(stats[2 * N + i], part[2][0]);
+        stats[3 * N + i] = first ? part[3][0] : fmaxf(stats[3 * N + i], part[3][0]);
+    }
+}
+
 struct Tensors {
     long long size[6];      // per agent: w1, b1, w2, b2, w3, b3
     long long off[6];       // of the [N, ...] tensor in the flat buffer
@@ -310,6 +422,101 @@ size_t workspace_bytes(const DroneMlp *m, int rc)
     return sizeof(float) * (size_t)m->N * (size_t)rc * (size_t)(m->h1 + m->h2 + m->nout + 1);
 }
 
+// what the PPO entry points add to the chain (all NULL / 0 for dronesim_mlp_grad)
+struct PpoArgs {
+    const float *logp_old, *adv;
+    float lo, hi;
+    float *stats;          // [4][N]
+    float *logp_out;       // set: forward + log-probabilities only
+};
+
+// The chunked chain of the header comment over all R rows; arguments validated by the entry points.
+int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const float *target, const float *act, const float *weight,
+              const PpoArgs *ppo, float *grad, float *loss, int rows_per_chunk, void *ws, hipStream_t st)
+{
+    const int N = m->N, din = m->d_in, h1 = m->h1, h2 = m->h2, no = m->nout;
+    const long long Rc = rows_per_chunk;
+    const Tensors t = tensors_of(m);
+    float *gw1 = grad + t.off[0], *gb1 = grad + t.off[1], *gw2 = grad + t.off[2];
+    float *gb2 = grad + t.off[3], *gw3 = grad + t.off[4], *gb3 = grad + t.off[5];
+    float *H1 = (float *)ws, *H2 = H1 + N * Rc * h1, *O = H2 + N * Rc * h2, *L = O + N * Rc * no, *S = L + N * Rc;
+
+    const long long xs = (long long)N * din;      // row stride of x
+    for (long long r0 = 0; r0 < R; r0 += Rc) {
+        const int rc = (int)((R - r0) < Rc ? (R - r0) : Rc);
+        const float *X = x + r0 * xs;
+        GemmArgs g;
+        // forward
+        g = gemm(X, xs, 1, din, m->w1, h1, 1, (long long)din * h1, H1, h1, Rc * h1, rc, h1, din, kReluBias);
+        g.bias = m->b1; g.bBias = h1;
+        launch_gemm(g, N, st);
+        g = gemm(H1, h1, 1, Rc * h1, m->w2, h2, 1, (long long)h1 * h2, H2, h2, Rc * h2, rc, h2, h1, kReluBias);
+        g.bias = m->b2; g.bBias = h2;
+        launch_gemm(g, N, st);
+        g = gemm(H2, h2, 1, Rc * h2, m->w3, no, 1, (long long)h2 * no, O, no, Rc * no, rc, no, h2, kBias);
+        g.bias = m->b3; g.bBias = no;
+        launch_gemm(g, N, st);
+        // head
+        const long long items = (long long)rc * N;
+        const dim3 hgrid((unsigned)((items + kThreads - 1) / kThreads));
+        if (ppo)
+            hipLaunchKernelGGL(ppo_head_kernel, hgrid, dim3(kThreads), 0, st, O, L, S, Rc, rc, r0, N, no, m->out_kind, row_scale, act,
+                               ppo->logp_old, ppo->adv, ppo->lo, ppo->hi, ppo->logp_out);
+        else
+            hipLaunchKernelGGL(head_kernel, hgrid, dim3(kThreads), 0, st, O, L, Rc, rc, r0, N, no, m->out_kind, row_scale, target, act,
+                               weight);
+        if (ppo && ppo->logp_out) continue;
+        // layer 3: dW3 += H2^T dO (+ db3), then dH2 = (dO W3^T) . [H2 > 0] in place of H2
+        g = gemm(H2, 1, h2, Rc * h2, O, no, 1, Rc * no, gw3, no, (long long)h2 * no, h2 + 1, no, rc, kAccumulate);
+        g.ones_row = h2; g.Cb = gb3; g.bCb = no; g.first = r0 == 0;
+        if (m->out_kind == 2) { g.half_m = h2 / 2; g.half_n = no / 2; }
+        launch_gemm(g, N, st);
+        g = gemm(O, no, 1, Rc * no, m->w3, 1, no, (long long)h2 * no, H2, h2, Rc * h2, rc, h2, no, kMask);
+        launch_gemm(g, N, st);
+        // layer 2: dW2 += H1^T dH2 (+ db2), then dH1 = (dH2 W2^T) . [H1 > 0] in place of H1
+        g = gemm(H1, 1, h1, Rc * h1, H2, h2, 1, Rc * h2, gw2, h2, (long long)h1 * h2, h1 + 1, h2, rc, kAccumulate);
+        g.ones_row = h1; g.Cb = gb2; g.bCb = h2; g.first = r0 == 0;
+        launch_gemm(g, N, st);
+        g = gemm(H2, h2, 1, Rc * h2, m->w2, 1, h2, (long long)h1 * h2, H1, h1, Rc * h1, rc, h1, h2, kMask);
+        launch_gemm(g, N, st);
+        // layer 1: dW1 += X^T dH1 (+ db1)
+        g = gemm(X, 1, xs, din, H1, h1, 1, Rc * h1, gw1, h1, (long long)din * h1, din + 1, h1, rc, kAccumulate);
+        g.ones_row = din; g.Cb = gb1; g.bCb = h1; g.first = r0 == 0;
+        launch_gemm(g, N, st);
+        hipLaunchKernelGGL(loss_sum_kernel, dim3(N), dim3(kThreads), 0, st, L, Rc, rc, (int)(r0 == 0), loss);
+        if (ppo)
+            hipLaunchKernelGGL(ppo_stats_kernel, dim3(N), dim3(kThreads), 0, st, S, Rc, rc, N, (int)(r0 == 0), (int)(r0 + Rc >= R),
+                               (float)R, ppo->stats);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+int fail_at(const char *where, const char *what)
+{
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", where, what);
+    return dronesim_fail(DRONESIM_EINVAL, msg);
+}
+
+// the checks the actor-only entry points share: an actor, R, the chunk size
+int check_actor_call(const DroneMlp *m, int R, int rows_per_chunk, const char *where)
+{
+    const int rc = check_mlp(m, where);
+    if (rc != DRONESIM_OK) return rc;
+    if (m->out_kind == 0) return fail_at(where, "needs an actor (out_kind 1 or 2), not a critic");
+    if (R < 1) return fail_at(where, "R < 1");
+    if (rows_per_chunk < 64 || rows_per_chunk % 64 != 0) return fail_at(where, "rows_per_chunk must be a positive multiple of 64");
+    return DRONESIM_OK;
+}
+
+// the PPO head's three per-row diagnostics behind the gradient workspace
+size_t ppo_workspace_bytes(const DroneMlp *m, int rc)
+{
+    return workspace_bytes(m, rc) + sizeof(float) * (size_t)m->N * (size_t)rc * 3;
+}
+
 }  // namespace
 
 extern "C" int dronesim_mlp_grad_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
@@ -338,56 +545,46 @@ extern "C" int dronesim_mlp_grad(const DroneMlp *m, const float *x, int R, float
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad: rows_per_chunk must be a positive multiple of 64");
     if (ws_bytes < workspace_bytes(m, rows_per_chunk))
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad: workspace smaller than dronesim_mlp_grad_workspace()");
+    return run_chain(m, x, R, row_scale, target, act, weight, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+}
 
-    hipStream_t st = (hipStream_t)stream;
-    const int N = m->N, din = m->d_in, h1 = m->h1, h2 = m->h2, no = m->nout;
-    const long long Rc = rows_per_chunk;
-    const Tensors t = tensors_of(m);
-    float *gw1 = grad + t.off[0], *gb1 = grad + t.off[1], *gw2 = grad + t.off[2];
-    float *gb2 = grad + t.off[3], *gw3 = grad + t.off[4], *gb3 = grad + t.off[5];
-    float *H1 = (float *)ws, *H2 = H1 + N * Rc * h1, *O = H2 + N * Rc * h2, *L = O + N * Rc * no;
-
-    const long long xs = (long long)N * din;      // row stride of x
-    for (long long r0 = 0; r0 < R; r0 += Rc) {
-        const int rc = (int)((R - r0) < Rc ? (R - r0) : Rc);
-        const float *X = x + r0 * xs;
-        GemmArgs g;
-        // forward
-        g = gemm(X, xs, 1, din, m->w1, h1, 1, (long long)din * h1, H1, h1, Rc * h1, rc, h1, din, kReluBias);
-        g.bias = m->b1; g.bBias = h1;
-        launch_gemm(g, N, st);
-        g = gemm(H1, h1, 1, Rc * h1, m->w2, h2, 1, (long long)h1 * h2, H2, h2, Rc * h2, rc, h2, h1, kReluBias);
-        g.bias = m->b2; g.bBias = h2;
-        launch_gemm(g, N, st);
-        g = gemm(H2, h2, 1, Rc * h2, m->w3, no, 1, (long long)h2 * no, O, no, Rc * no, rc, no, h2, kBias);
-        g.bias = m->b3; g.bBias = no;
-        launch_gemm(g, N, st);
-        // head
-        const long long items = (long long)rc * N;
-        hipLaunchKernelGGL(head_kernel, dim3((unsigned)((items + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                           O, L, Rc, rc, r0, N, no, m->out_kind, row_scale, target, act, weight);
-        // layer 3: dW3 += H2^T dO (+ db3), then dH2 = (dO W3^T) . [H2 > 0] in place of H2
-        g = gemm(H2, 1, h2, Rc * h2, O, no, 1, Rc * no, gw3, no, (long long)h2 * no, h2 + 1, no, rc, kAccumulate);
-        g.ones_row = h2; g.Cb = gb3; g.bCb = no; g.first = r0 == 0;
-        if (m->out_kind == 2) { g.half_m = h2 / 2; g.half_n = no / 2; }
-        launch_gemm(g, N, st);
-        g = gemm(O, no, 1, Rc * no, m->w3, 1, no, (long long)h2 * no, H2, h2, Rc * h2, rc, h2, no, kMask);
-        launch_gemm(g, N, st);
-        // layer 2: dW2 += H1^T dH2 (+ db2), then dH1 = (dH2 W2^T) . [H1 > 0] in place of H1
-        g = gemm(H1, 1, h1, Rc * h1, H2, h2, 1, Rc * h2, gw2, h2, (long long)h1 * h2, h1 + 1, h2, rc, kAccumulate);
-        g.ones_row = h1; g.Cb = gb2; g.bCb = h2; g.first = r0 == 0;
-        launch_gemm(g, N, st);
-        g = gemm(H2, h2, 1, Rc * h2, m->w2, 1, h2, (long long)h1 * h2, H1, h1, Rc * h1, rc, h1, h2, kMask);
-        launch_gemm(g, N, st);
-        // layer 1: dW1 += X^T dH1 (+ db1)
-        g = gemm(X, 1, xs, din, H1, h1, 1, Rc * h1, gw1, h1, (long long)din * h1, din + 1, h1, rc, kAccumulate);
-        g.ones_row = din; g.Cb = gb1; g.bCb = h1; g.first = r0 == 0;
-        launch_gemm(g, N, st);
-        hipLaunchKernelGGL(loss_sum_kernel, dim3(N), dim3(kThreads), 0, st, L, Rc, rc, (int)(r0 == 0), loss);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+extern "C" int dronesim_mlp_grad_ppo_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
+{
+    const int rc = check_actor_call(m, 1, rows_per_chunk, "dronesim_mlp_grad_ppo_workspace");
+    if (rc != DRONESIM_OK) return rc;
+    if (!bytes) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_workspace: NULL bytes");
+    *bytes = ppo_workspace_bytes(m, rows_per_chunk);
     return DRONESIM_OK;
+}
+
+extern "C" int dronesim_mlp_logp(const DroneMlp *m, const float *x, int R, const float *act, float *logp, int rows_per_chunk,
+                                 void *ws, size_t ws_bytes, void *stream)
+{
+    const int rc = check_actor_call(m, R, rows_per_chunk, "dronesim_mlp_logp");
+    if (rc != DRONESIM_OK) return rc;
+    if (!x || !act || !logp || !ws) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_logp: NULL x / act / logp / workspace");
+    if (ws_bytes < workspace_bytes(m, rows_per_chunk))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_logp: workspace smaller than dronesim_mlp_grad_workspace()");
+    PpoArgs p = {};
+    p.logp_out = logp;
+    // (grad and loss are not touched by the forward-only chain; the workspace stands in for their base address)
+    return run_chain(m, x, R, 1.f, nullptr, act, nullptr, &p, (float *)ws, nullptr, rows_per_chunk, ws, (hipStream_t)stream);
+}
+
+extern "C" int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, float row_scale, const float *act,
+                                     const float *logp_old, const float *adv, float clip_eps, float *grad, float *loss, float *stats,
+                                     int rows_per_chunk, void *ws, size_t ws_bytes, void *stream)
+{
+    const int rc = check_actor_call(m, R, rows_per_chunk, "dronesim_mlp_grad_ppo");
+    if (rc != DRONESIM_OK) return rc;
+    if (!x || !act || !logp_old || !adv || !grad || !loss || !stats || !ws)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo: NULL x / act / logp_old / adv / grad / loss / stats / workspace");
+    if (!(clip_eps > 0.f && clip_eps < 1.f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo: clip_eps must be in (0, 1)");
+    if (ws_bytes < ppo_workspace_bytes(m, rows_per_chunk))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo: workspace smaller than dronesim_mlp_grad_ppo_workspace()");
+    PpoArgs p = {};
+    p.logp_old = logp_old; p.adv = adv; p.lo = 1.f - clip_eps; p.hi = 1.f + clip_eps; p.stats = stats;
+    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,

@@ -6,6 +6,9 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
   mlp_gradients   dronesim_mlp_grad    per-agent loss gradients over all rows of a window, in one flat buffer
   BatchedAdam     dronesim_adam_step   clip_grad_norm_(max_norm) + torch.optim.Adam, per agent, in place on the weights
   SA2CLearner                          critic update, baseline from the post-update critic, actor update (train_NN)
+  PPOLearner      dronesim_mlp_logp, dronesim_neighbour_advantage, dronesim_mlp_grad_ppo
+                                       `SPPOAgents.train` (SAC_agents.py:410-573): clipped probability ratio, `epochs`
+                                       critic-and-actor steps per window
 
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
@@ -103,24 +106,76 @@ class GradientRunner:
         self.ws_bytes = grad_workspace_bytes(mlp, self.rc)
         self.ws = torch.empty(self.ws_bytes // 4, device=mlp.device)
 
-    def run(self, x, row_scale, target=None, act=None, weight=None):
+    def _check(self, x, **per_row):
         import torch
-        from . import _native
         mlp = self.mlp
         if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != self.rows * mlp.n_agents * mlp.d_in:
             raise ValueError(f"x must be a contiguous float32 tensor of {self.rows} rows x {mlp.n_agents} agents x {mlp.d_in}")
-        per_row = {"target": (target, 1), "act": (act, 2), "weight": (weight, 1)}
         for name, (t, k) in per_row.items():
             if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.rows * mlp.n_agents * k):
                 raise ValueError(f"{name} must be a contiguous float32 tensor of {self.rows} x {mlp.n_agents} x {k}")
+
+    def run(self, x, row_scale, target=None, act=None, weight=None, loss_out=None):
+        """``loss_out``: a float32 ``[N]`` device tensor that receives the losses instead of ``self.loss``."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, target=(target, 1), act=(act, 2), weight=(weight, 1))
+        loss = self.loss if loss_out is None else loss_out
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(mlp.device):
             rc = _native.lib().dronesim_mlp_grad(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), ptr(target),
-                                                 ptr(act), ptr(weight), self.grad.data_ptr(), self.loss.data_ptr(), self.rc,
+                                                 ptr(act), ptr(weight), self.grad.data_ptr(), loss.data_ptr(), self.rc,
                                                  self.ws.data_ptr(), self.ws_bytes,
                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _native.check(rc, "dronesim_mlp_grad")
-        return self.grad, self.loss
+        return self.grad, loss
+
+    # the PPO path (actors only): same chunks, same workspace (grown once by the head's three per-row diagnostics)
+    def _ppo_workspace(self):
+        import torch
+        from . import _native
+        n = C.c_size_t(0)
+        _native.check(_native.lib().dronesim_mlp_grad_ppo_workspace(C.byref(self._m), self.rc, C.byref(n)),
+                      "dronesim_mlp_grad_ppo_workspace")
+        if int(n.value) > self.ws.numel() * 4:
+            self.ws = torch.empty(int(n.value) // 4, device=self.mlp.device)
+        self.ppo_ws_bytes = int(n.value)
+        self.stats = torch.zeros(4, self.mlp.n_agents, device=self.mlp.device)
+
+    def logp(self, x, act, out):
+        """`dronesim_mlp_logp`: ``out [rows, N]`` (float32, overwritten) = log pi_i(act | x) under the current weights."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, act=(act, 2), logp=(out, 1))
+        with torch.cuda.device(mlp.device):
+            rc = _native.lib().dronesim_mlp_logp(C.byref(self._m), x.data_ptr(), self.rows, act.data_ptr(), out.data_ptr(), self.rc,
+                                                 self.ws.data_ptr(), self.ws_bytes,
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_mlp_logp")
+        return out
+
+    def run_ppo(self, x, row_scale, act, logp_old, adv, clip_eps, loss_out=None, stats_out=None):
+        """`dronesim_mlp_grad_ppo`: returns ``(grad, loss [N], stats [4, N])`` -- stats rows: clipped share, mean
+        ``logp_old - logp``, min and max ratio."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, act=(act, 2), logp_old=(logp_old, 1), adv=(adv, 1))
+        if not hasattr(self, "stats"):
+            self._ppo_workspace()
+        loss = self.loss if loss_out is None else loss_out
+        stats = self.stats if stats_out is None else stats_out
+        if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != 4 * mlp.n_agents:
+            raise ValueError(f"stats must be a contiguous float32 tensor [4, {mlp.n_agents}]")
+        with torch.cuda.device(mlp.device):
+            rc = _native.lib().dronesim_mlp_grad_ppo(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), act.data_ptr(),
+                                                     logp_old.data_ptr(), adv.data_ptr(), float(clip_eps), self.grad.data_ptr(),
+                                                     loss.data_ptr(), stats.data_ptr(), self.rc, self.ws.data_ptr(),
+                                                     self.ppo_ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_mlp_grad_ppo")
+        return self.grad, loss, stats
 
 
 def mlp_gradients(mlp, x, target=None, act=None, weight=None, row_scale=None, rows_per_chunk=None):
@@ -161,19 +216,23 @@ class BatchedAdam:
         self.grad_norm = torch.zeros(mlp.n_agents, device=mlp.device)
         self._m = plain_struct(mlp)
 
-    def step(self, grad):
+    def step(self, grad, norm_out=None, refresh=True):
+        """``norm_out``: a float32 ``[N]`` device tensor that receives the norms instead of ``self.grad_norm``;
+        ``refresh=False`` leaves the network's forward images stale (the caller refreshes them before the next forward)."""
         import torch
         from . import _native
+        norm = self.grad_norm if norm_out is None else norm_out
         if grad.dtype != torch.float32 or not grad.is_contiguous() or grad.numel() != self.numel or grad.device != self.m1.device:
             raise ValueError(f"grad must be the flat float32 gradient buffer ({self.numel} elements) on {self.m1.device}")
         with torch.cuda.device(self.mlp.device):
             rc = _native.lib().dronesim_adam_step(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
                                                   self.steps.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                  self.max_norm, self.grad_norm.data_ptr(),
+                                                  self.max_norm, norm.data_ptr(),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _native.check(rc, "dronesim_adam_step")
-        self.mlp.refresh_weights()
-        return self.grad_norm
+        if refresh:
+            self.mlp.refresh_weights()
+        return norm
 
 
 class SA2CLearner:
@@ -249,3 +308,112 @@ class SA2CLearner:
         ag, aloss = self._actor_grad.run(x, 1.0 / E, act=storage.actions, weight=self.w)
         anorm = self.actor_opt.step(ag)
         return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm)
+
+
+class PPOLearner:
+    """`SPPOAgents.train` (SAC_agents.py:410-573) -- PPO with the clipped probability ratio -- over a `RolloutStorage` window
+    of E envs, T steps, for all N agents' networks at once:
+
+      1. G = storage.returns(gamma)                                                          (:476-481, restarts at ``done``)
+      2. once per window, before any update, per row (t, e) and agent i:
+           logp_old = log pi_i(a | x) under the current actor           (:494; Gaussian density with VARIANCE sigma, :558-573;
+                                                                         for a softmax actor the stored action's index)
+           Q = sum_{j in N_i(t)} G[t, e, j]   (:498-501),   V = V_i(x) from the PRE-update critic (:512)
+           Adv = Q - V            ``baseline="once"``: ONE V_i against the neighbour SUM, the reference's form (:513);
+           Adv = Q - |N_i| V      ``baseline="per_neighbour"`` (as `train_NN` subtracts it, SAC_agents.py:346)
+         no gamma^t and no 1 / N factor
+      3. ``epochs`` times (:522-555), critic first, then actor, both over all T E rows:
+           critic: mean (V_i(x) - G)^2, clip to ``max_norm``, Adam (lr ``lr_critic``)         -- `SA2CLearner`'s critic step
+           actor:  r = exp(logp - logp_old),  L_i = -(1 / (T E)) sum_rows min(r Adv, clamp(r, 1 - clip_eps, 1 + clip_eps) Adv),
+                   clip to ``max_norm``, Adam (lr ``lr_actor``)
+
+    The reference class is NOT runnable as written; this is the algorithm its lines state with exactly three repairs:
+    the two lines :513-514 swapped (``Qjsum`` is read one line before it is assigned); ``Adv`` a constant (the reference keeps
+    the critic's autograd graph in it and reuses it in every epoch, a second ``backward`` through it raises); the actors
+    built with an ``lr`` (:423 omits `NormalActorNN`'s required argument, utils.py:59).  Its ``probability_of_ai`` does run
+    and is what tests/golden/ppo_n5.npz records.
+
+    ``train(storage)`` returns a dict of device tensors ``[epochs, N]``: critic_loss, actor_loss, critic_grad_norm,
+    actor_grad_norm (pre-clip), clip_fraction (share of rows on the clipped branch), approx_kl (mean logp_old - logp),
+    ratio_min, ratio_max.  In the first epoch logp is computed by the same kernels on the same weights as logp_old, so the
+    ratio is exactly 1 there (clip_fraction 0, approx_kl 0).  Same properties as `SA2CLearner`: softmax or Gaussian actors;
+    buffers allocated on the first call per storage shape (the returned tensors are among them: a later call overwrites
+    them); no host synchronisation; the HIP entry points enqueue kernels only (no memset nodes); step counters in device
+    memory -- a rollout window and the update can be captured in one ``torch.cuda.graph`` whose replays equal the eager
+    sequence.  The forward images are re-packed (`BatchedMLP.refresh_weights`, with the temporaries noted at `SA2CLearner`)
+    once per network per call, after the last epoch: the epochs themselves read the plain weight arrays."""
+
+    BASELINES = ("once", "per_neighbour")
+
+    def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
+                 baseline="once", rows_per_chunk=None):
+        if critic.out_kind != 0 or critic.nout != 1:
+            raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
+        if actor.out_kind not in (1, 2):
+            raise ValueError("the actor must be a softmax (out_kind 1) or Gaussian (out_kind 2) BatchedMLP")
+        if (actor.n_agents, actor.d_in) != (critic.n_agents, critic.d_in):
+            raise ValueError("actor and critic must have the same agents and inputs")
+        if int(epochs) != epochs or epochs < 1:
+            raise ValueError("epochs must be an integer >= 1")
+        if not 0.0 < float(clip_eps) < 1.0:
+            raise ValueError("clip_eps must be in (0, 1)")
+        if baseline not in self.BASELINES:
+            raise ValueError(f"baseline must be one of {self.BASELINES}")
+        self.actor, self.critic, self.gamma = actor, critic, float(gamma)
+        self.epochs, self.clip_eps, self.baseline = int(epochs), float(clip_eps), baseline
+        self.rows_per_chunk = rows_per_chunk
+        self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
+        self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
+        self._shape = None
+
+    def _prepare(self, storage):
+        import torch
+        if getattr(storage, "actions", None) is None:
+            raise ValueError("the learner needs a storage with actions")
+        T, E, N = storage.reward.shape
+        if self._shape == (T, E, N):
+            return
+        if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
+            raise ValueError("the storage's agents / observation width do not match the networks")
+        dev = self.critic.device
+        self.G = torch.empty(T, E, N, device=dev)
+        self.V = torch.empty(T * E, N, 1, device=dev)
+        self.adv = torch.empty(T, E, N, device=dev)
+        self.logp_old = torch.empty(T, E, N, device=dev)
+        self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
+        self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
+        self._actor_grad._ppo_workspace()
+        self._scalars = torch.zeros(4, self.epochs, N, device=dev)       # critic_loss, actor_loss, critic / actor grad norm
+        self._stats = torch.zeros(self.epochs, 4, N, device=dev)
+        self._shape = (T, E, N)
+
+    def train(self, storage):
+        import torch
+        from . import _native
+        self._prepare(storage)
+        T, E, N = self._shape
+        lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        x, act, nbr = storage.z_pre, storage.actions, storage.nbr_pre
+        with torch.cuda.device(self.critic.device):
+            rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
+                                      T, E, N, stream)
+        _native.check(rc, "dronesim_returns")
+        # the old policy's log-probabilities and the advantage from the pre-update critic, once per window (:484-501, :512-513)
+        self._actor_grad.logp(x, act, self.logp_old)
+        self.critic.forward(x.view(T * E, N, -1), out=self.V)
+        with torch.cuda.device(self.critic.device):
+            rc = lib.dronesim_neighbour_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(),
+                                                  int(self.baseline == "per_neighbour"), self.adv.data_ptr(), T, E, N,
+                                                  int(nbr.shape[3]), stream)
+        _native.check(rc, "dronesim_neighbour_advantage")
+        closs, aloss, cnorm, anorm = self._scalars
+        for ep in range(self.epochs):
+            last = ep == self.epochs - 1
+            cg, _ = self._critic_grad.run(x, 1.0 / (T * E), target=self.G, loss_out=closs[ep])
+            self.critic_opt.step(cg, norm_out=cnorm[ep], refresh=last)
+            ag, _, _ = self._actor_grad.run_ppo(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps, loss_out=aloss[ep],
+                                                stats_out=self._stats[ep])
+            self.actor_opt.step(ag, norm_out=anorm[ep], refresh=last)
+        st = self._stats
+        return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
+                    clip_fraction=st[:, 0], approx_kl=st[:, 1], ratio_min=st[:, 2], ratio_max=st[:, 3])

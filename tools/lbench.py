@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Learner micro-benchmark (developer tool; bench.py stays the project's yardstick): one `SA2CLearner.train` per shape,
-timed with device events after warm-up.
+"""Learner micro-benchmark (developer tool; bench.py stays the project's yardstick): one `SA2CLearner.train` per shape --
+or, with ``--learner ppo``, one `PPOLearner.train` of ``--epochs M`` epochs --, timed with device events after warm-up.
 
-    python tools/lbench.py [--configs c1,c3,c5] [--reps 3] [--warmup 1]
+    python tools/lbench.py [--configs c1,c3,c5] [--reps 3] [--warmup 1] [--learner {sa2c,ppo}] [--epochs M]
+
+A PPO epoch's cost is the marginal one, (t_3 - t_1) / 2 from runs at ``--epochs 1`` and ``--epochs 3``; the once-per-window
+part (returns, old log-probabilities, baseline, advantage) is t_1 less one epoch.
 
 Shapes (N x E x T, actor + critic of the reference's widths):
     c1   5 x 1 x 200       softmax-16 actor (6 -> 300 -> 300 -> 16) + critic (6 -> 200 -> 200 -> 1)
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("--configs", default="c1,c3,c5")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--learner", choices=("sa2c", "ppo"), default="sa2c")
+    ap.add_argument("--epochs", type=int, default=1, help="epochs per PPOLearner.train (--learner ppo)")
     ap.add_argument("--stats", help="a rocprofv3 kernel_stats.csv to summarise instead of running")
     args = ap.parse_args()
     if args.stats:
@@ -50,7 +55,7 @@ def main():
                                   share=round(float(r["TotalDurationNs"]) / tot, 4))))
         return
     import torch
-    from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
+    from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
     from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
     dev = "cuda:0"
     for name in args.configs.split(","):
@@ -72,7 +77,8 @@ def main():
                              done=torch.zeros(T, E, dtype=torch.uint8, device=dev), actions=torch.stack([a.cos(), a.sin()], -1),
                              nbr_pre=torch.stack([torch.arange(N, device=dev).expand(T, E, N)] * 3, -1).int().contiguous())
         st.done[-1] = 1
-        learner = SA2CLearner(actor, critic, 0.99)
+        ppo = args.learner == "ppo"
+        learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs) if ppo else SA2CLearner(actor, critic, 0.99)
         for _ in range(args.warmup):
             learner.train(st)
         torch.cuda.synchronize()
@@ -83,10 +89,16 @@ def main():
             torch.cuda.synchronize()
             times.append(ev[0].elapsed_time(ev[1]))
         rows = T * E * N
-        flop = mlp_flop(rows, d_in, 200, 200, 1) + mlp_flop(rows, d_in, h1a, h2a, noa) + mlp_flop(rows, d_in, 200, 200, 1, False)
+        step = mlp_flop(rows, d_in, 200, 200, 1) + mlp_flop(rows, d_in, h1a, h2a, noa)
+        if ppo:     # per window: the old policy's and the critic's forward; per epoch: both gradient chains
+            flop = args.epochs * step + mlp_flop(rows, d_in, h1a, h2a, noa, False) + mlp_flop(rows, d_in, 200, 200, 1, False)
+        else:
+            flop = step + mlp_flop(rows, d_in, 200, 200, 1, False)
         ms = min(times)
-        print(json.dumps(dict(config=name, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3), ms_all=[round(t, 3) for t in times],
-                              flop=flop, tflops=round(flop / ms / 1e9, 2), peak_share=round(flop / ms / 1e9 / PEAK_TF, 4))))
+        tag = dict(learner="ppo", epochs=args.epochs) if ppo else {}
+        print(json.dumps(dict(config=name, **tag, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3),
+                              ms_all=[round(t, 3) for t in times], flop=flop, tflops=round(flop / ms / 1e9, 2),
+                              peak_share=round(flop / ms / 1e9 / PEAK_TF, 4))), flush=True)
 
 
 if __name__ == "__main__":
