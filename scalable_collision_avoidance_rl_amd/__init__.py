@@ -2,7 +2,7 @@
 
 Drop-in for `/root/reference/drone_env.py` class `drones`; see drone_env.py in this
 package, include/dronesim.h (C ABI), csrc/drone_kernel.hpp (the gfx950 step / observe / rollout kernel),
-csrc/dronesim.hip (the ABI's entry points + the small kernels) and csrc/policy.hip (batched policies).
+csrc/dronesim.hip (the ABI's entry points + the small kernels) and csrc/policy_{rowtile,f32,split,bf16}.hip (batched policies, one kernel family each).
 Importing the package needs neither a GPU nor the built library; constructing an
 environment needs both (no CPU fallback)."""
 from .drone_env import (DroneState, StepResult, clip_deltas, dim, drones, dt, formation_O, gradient_control,

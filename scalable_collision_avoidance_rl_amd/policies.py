@@ -3,7 +3,7 @@
 The reference keeps one small torch module per agent and evaluates them one by one in Python every step
 (SAC_agents.py:170-180: ``actors[i].sample_action(z_states[i].flatten(), N[i])``).  `BatchedMLP` stacks the
 N networks' weights and evaluates all of them on the batched observation ``z [E,N,d_in]`` in ONE launch
-of the HIP kernel in csrc/policy.hip (exact float32 on the matrix cores), including the sampling of
+of the HIP kernels in csrc/policy_*.hip (by default csrc/policy_rowtile.hip: exact float32 on the matrix cores), including the sampling of
 ``sample_action``.  Architectures mirrored:
 
   DiscreteSoftmaxNN  utils.py:255-309   BatchedMLP.from_discrete_softmax(modules)
@@ -181,12 +181,12 @@ def pack_f32_fragments(w):
     return frag.reshape(n, nc, ns, 2, 64, 4).contiguous()
 
 
-RT_CHUNKS, RT_PAD = 7, 4          # csrc/policy.hip: kRtChunks (output chunks a wave keeps per pass), kRtPad (zero blocks behind a stream)
+RT_CHUNKS, RT_PAD = 7, 4          # csrc/policy_rowtile.hip: kRtChunks (output chunks a wave keeps per pass), kRtPad (zero blocks behind a stream)
 
 
 def pack_f32_rowtile_stream(w1, b1, w2, w3):
     """[N, d_in, h1], [N, h1], [N, h1, h2], [N, h2, nout] float32 -> the weight stream of the row-tile exact-f32 kernel
-    (`DroneMlp.w2_layout = 2`, csrc/policy.hip: mlp3_rt_kernel): ``[N, blocks, 4, 64, 4]`` float32, blocks of four 1-KiB pieces
+    (`DroneMlp.w2_layout = 2`, csrc/policy_rowtile.hip: mlp3_rt_kernel): ``[N, blocks, 4, 64, 4]`` float32, blocks of four 1-KiB pieces
     ``[64 lanes][4 floats]`` (lane = 32 half + i) in the kernel's consumption order:
 
         per pass p (output chunks S_p):  for c1: L1(c1), L2(c1, c2) for c2 in S_p;  then (nout > 4 only) L3(c2) for c2 in S_p;  RT_PAD zero blocks
@@ -232,7 +232,7 @@ def pack_f32_rowtile_stream(w1, b1, w2, w3):
 
 def pack_f16_rowtile_stream(w1, w2, blocks, w3=None):
     """[N, d_in, h1], [N, h1, h2] (and, for nout > 4, [N, h2, nout]) float32 weights ALREADY multiplied by their power-of-two factors
-    -> the weight stream of the float16 row-tile kernel (`dronesim_mlp_forward_f16x2_rt`, csrc/policy.hip: mlp3_rt16_kernel):
+    -> the weight stream of the float16 row-tile kernel (`dronesim_mlp_forward_f16x2_rt`, csrc/policy_rowtile.hip: mlp3_rt16_kernel):
     ``[N, blocks, 4, 64, 8]`` float16, blocks of four 1-KiB pieces in the kernel's consumption order -- per pass (output chunks S_p),
     for every in-chunk c1: L1(c1) = (W1 hi, W1 lo, 0, 0), then L2(c1, c2) = (hi, lo of k-step 2 c1; hi, lo of k-step 2 c1 + 1) for c2 in
     S_p; with `w3` the pass ends with L3(c2) = (hi, lo of k-step 2 c2; hi, lo of k-step 2 c2 + 1) of W3 for c2 in S_p -- zero blocks up
@@ -295,101 +295,75 @@ class BatchedMLP:
         assert self.w2.shape == (self.n_agents, self.h1, self.h2) and self.b3.shape == (self.n_agents, self.nout)
         self.out_kind, self.sample_kind = int(out_kind), int(sample_kind)
         self.seed, self.counter = int(seed), 0
-        m = _native.DroneMlp()
-        m.N, m.d_in, m.h1, m.h2, m.nout = self.n_agents, self.d_in, self.h1, self.h2, self.nout
-        m.out_kind, m.sample_kind = self.out_kind, self.sample_kind
-        m.w1, m.b1, m.w2 = self.w1.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr()
-        m.b2, m.w3, m.b3 = self.b2.data_ptr(), self.w3.data_ptr(), self.b3.data_ptr()
-        self._m = m
+        if precision not in ("f32", "f16x2", "bf16x3", "bf16"):
+            raise ValueError("precision must be 'f32', 'f16x2', 'bf16x3' or 'bf16'")
+        if precision != "f32" and self.d_in > 16:
+            raise ValueError(f"the {precision} path supports d_in <= 16")
         self.precision = precision
-        self._rowtile = False
-        if precision == "f32" and pack_w2 == "fragments":
-            # round 3-5 fast path: layer 2 reads its weights as matrix-core fragments (`DroneMlp.w2_layout = 1`)
-            self._w2p = pack_f32_fragments(self.w2)
-            m.w2, m.w2_layout = self._w2p.data_ptr(), 1
-        elif precision == "f32" and pack_w2 and self.d_in <= 14:
-            # round 6: ONE stream holding all three layers in the row-tile kernel's consumption order (`DroneMlp.w2_layout = 2`)
-            self._w2p = pack_f32_rowtile_stream(self.w1, self.b1, self.w2, self.w3)
-            assert self._w2p.shape[1] == int(self._lib.dronesim_mlp_rt_blocks(self.h1, self.h2, self.nout))
-            m.w2, m.w2_layout = self._w2p.data_ptr(), 2
-            self._rowtile = True
-        elif precision == "f32" and pack_w2:
-            self._w2p = pack_f32_fragments(self.w2)
-            m.w2, m.w2_layout = self._w2p.data_ptr(), 1
-        if precision == "bf16":
-            if self.d_in > 16:
-                raise ValueError("the bf16 path supports d_in <= 16")
-            nc1, nc2 = (self.h1 + 31) // 32, (self.h2 + 31) // 32
-            self._w1p = pack_bf16_fragments(self.w1, 1, nc1)
-            self._w2p = pack_bf16_fragments(self.w2, 2 * nc1, nc2)
-            self._w3p = pack_bf16_fragments(self.w3, 2 * nc2, 1, k_order="accumulator")
-            mb = _native.DroneMlpBf16()
-            mb.N, mb.d_in, mb.h1, mb.h2, mb.nout = self.n_agents, self.d_in, self.h1, self.h2, self.nout
-            mb.out_kind, mb.sample_kind = self.out_kind, self.sample_kind
-            mb.w1p, mb.w2p, mb.w3p = self._w1p.data_ptr(), self._w2p.data_ptr(), self._w3p.data_ptr()
-            mb.b1, mb.b2, mb.b3 = self.b1.data_ptr(), self.b2.data_ptr(), self.b3.data_ptr()
-            self._m = mb
-        elif precision in ("bf16x3", "f16x2"):
-            if self.d_in > 16:
-                raise ValueError(f"the {precision} path supports d_in <= 16")
-            stages = int(self._lib.dronesim_mlp_bf16x3_stages(self.h1, self.h2))
-            self._wscale = None
-            if precision == "f16x2":                               # power-of-two factors: the low parts stay normal float16
-                self._wscale = f16_weight_scales(self.w1, self.w2, self.w3)
+        lib, dims = self._lib, (self.h1, self.h2)
+        # the mode: which kernel runs and which packed image it reads (`_pack`); `_stages`: the length `DroneMlpBf16.reserved` carries
+        if precision == "f32":
+            # True: the row-tile kernel of round 6 (d_in <= 14); "fragments" (and True with a wider input): the kernel of rounds 3-5
+            self._mode = "f32" if not pack_w2 else "f32_rowtile" if pack_w2 != "fragments" and self.d_in <= 14 else "f32_fragments"
+        elif precision == "f16x2":
             # round 6: f16x2 takes the ROW-TILE kernel (one stream per agent, a ring per workgroup; layer 3 in exact float32 on the
             # vector ALU for nout <= 4, on the matrix cores otherwise); `split_kernel=True` keeps the split kernel of rounds 2-5
-            self._rt16 = precision == "f16x2" and not split_kernel
-            if self._rt16:
-                stages = int(self._lib.dronesim_mlp_rt16_blocks(self.h1, self.h2, self.nout))
-            self._w1p = self._split_image(stages)
-            mb = _native.DroneMlpBf16()
-            mb.N, mb.d_in, mb.h1, mb.h2, mb.nout = self.n_agents, self.d_in, self.h1, self.h2, self.nout
-            mb.out_kind, mb.sample_kind, mb.reserved = self.out_kind, self.sample_kind, stages
-            mb.w1p, mb.w2p, mb.w3p = self._w1p.data_ptr(), None, (self.w3.data_ptr() if self._rt16 and self.nout <= 4 else None)
-            mb.b1, mb.b2, mb.b3 = self.b1.data_ptr(), self.b2.data_ptr(), self.b3.data_ptr()
-            mb.wscale = None if self._wscale is None else self._wscale.data_ptr()
-            self._m = mb
-        elif precision != "f32":
-            raise ValueError("precision must be 'f32', 'f16x2', 'bf16x3' or 'bf16'")
+            self._mode = "f16x2_split" if split_kernel else "f16x2_rowtile"
+        else:
+            self._mode = precision
+        self._stages = (int(lib.dronesim_mlp_rt16_blocks(*dims, self.nout)) if self._mode == "f16x2_rowtile" else
+                        int(lib.dronesim_mlp_bf16x3_stages(*dims)) if self._mode in ("bf16x3", "f16x2_split") else 0)
+        self._packed = img = self._pack()
+        ptr = lambda name: img[name].data_ptr() if name in img else None
+        m = (_native.DroneMlp if precision == "f32" else _native.DroneMlpBf16)()
+        m.N, m.d_in, m.h1, m.h2, m.nout = self.n_agents, self.d_in, self.h1, self.h2, self.nout
+        m.out_kind, m.sample_kind = self.out_kind, self.sample_kind
+        m.b1, m.b2, m.b3 = self.b1.data_ptr(), self.b2.data_ptr(), self.b3.data_ptr()
+        if precision == "f32":
+            m.w1, m.w2, m.w3 = self.w1.data_ptr(), ptr("w2p") or self.w2.data_ptr(), self.w3.data_ptr()
+            m.w2_layout = {"f32": 0, "f32_fragments": 1, "f32_rowtile": 2}[self._mode]
+            assert self._mode != "f32_rowtile" or img["w2p"].shape[1] == int(lib.dronesim_mlp_rt_blocks(*dims, self.nout))
+        else:
+            m.reserved, m.w1p, m.w2p, m.wscale = self._stages, ptr("w1p"), ptr("w2p"), ptr("wscale")
+            # (the row-tile f16x2 kernel runs layer 3 of nout <= 4 from the plain float32 array)
+            m.w3p = self.w3.data_ptr() if self._mode == "f16x2_rowtile" and self.nout <= 4 else ptr("w3p")
+        self._m = m
+
+    def _pack(self):
+        """THE place that maps a mode to its packing functions: name -> packed tensor, made from the live ``w1 .. b3``."""
+        mode, w1, w2, w3 = self._mode, self.w1, self.w2, self.w3
+        if mode == "f32":
+            return {}
+        if mode == "f32_fragments":
+            return {"w2p": pack_f32_fragments(w2)}
+        if mode == "f32_rowtile":
+            return {"w2p": pack_f32_rowtile_stream(w1, self.b1, w2, w3)}
+        if mode == "bf16":
+            nc1, nc2 = (self.h1 + 31) // 32, (self.h2 + 31) // 32
+            return {"w1p": pack_bf16_fragments(w1, 1, nc1), "w2p": pack_bf16_fragments(w2, 2 * nc1, nc2),
+                    "w3p": pack_bf16_fragments(w3, 2 * nc2, 1, k_order="accumulator")}
+        if mode == "bf16x3":
+            return {"w1p": pack_split_streams(w1, w2, w3, self._stages, "bf16x3")}
+        # f16x2: the streams hold the weights times their power-of-two factors (the low parts stay normal float16)
+        sc = f16_weight_scales(w1, w2, w3)
+        w1, w2, w3 = (w * sc[:, i, None, None] for i, w in enumerate((w1, w2, w3)))
+        if mode == "f16x2_split":
+            return {"wscale": sc, "w1p": pack_split_streams(w1, w2, w3, self._stages, "f16x2")}
+        return {"wscale": sc, "w1p": pack_f16_rowtile_stream(w1, w2, self._stages, w3 if self.nout > 4 else None)}
 
     def refresh_weights(self, w1=None, b1=None, w2=None, b2=None, w3=None, b3=None):
-        """Call after every weight update.  The kernels read PACKED images of the weights (`_w2p` for f32 layer 2;
-        `_w1p/_w2p/_w3p` for the 16-bit paths) that are snapshots taken when the object was built: an in-place update
+        """Call after every weight update.  The kernels read PACKED images of the weights (`_pack`) that are snapshots
+        taken when the object was built: an in-place update
         of ``self.w2`` alone (optimizer step) would otherwise leave the kernel on a mix of new and stale weights.
         Optional arguments are copied into the live tensors first; every packed image is then re-made IN PLACE (same
         device addresses), so a captured hipGraph that holds them stays valid."""
         for name, val in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("w3", w3), ("b3", b3)):
             if val is not None:
                 getattr(self, name).copy_(self._torch.as_tensor(val, dtype=self._torch.float32))
-        if self.precision == "f32":
-            if getattr(self, "_w2p", None) is not None:
-                self._w2p.copy_(pack_f32_rowtile_stream(self.w1, self.b1, self.w2, self.w3) if self._rowtile
-                                else pack_f32_fragments(self.w2))
-        elif self.precision == "bf16":
-            nc1, nc2 = (self.h1 + 31) // 32, (self.h2 + 31) // 32
-            self._w1p.copy_(pack_bf16_fragments(self.w1, 1, nc1))
-            self._w2p.copy_(pack_bf16_fragments(self.w2, 2 * nc1, nc2))
-            self._w3p.copy_(pack_bf16_fragments(self.w3, 2 * nc2, 1, k_order="accumulator"))
-        else:
-            stages = int(self._lib.dronesim_mlp_rt16_blocks(self.h1, self.h2, self.nout) if getattr(self, "_rt16", False)
-                         else self._lib.dronesim_mlp_bf16x3_stages(self.h1, self.h2))
-            if self._wscale is not None:
-                self._wscale.copy_(f16_weight_scales(self.w1, self.w2, self.w3))
-            self._w1p.copy_(self._split_image(stages))
+        for name, image in self._pack().items():
+            self._packed[name].copy_(image)
 
     load_weights = refresh_weights
-
-    def _split_image(self, stages):
-        """The packed weight streams of the split precisions; f16x2: of the weights times their power-of-two factors."""
-        if getattr(self, "_rt16", False):
-            sc = self._wscale
-            return pack_f16_rowtile_stream(self.w1 * sc[:, 0, None, None], self.w2 * sc[:, 1, None, None], stages,
-                                           self.w3 * sc[:, 2, None, None] if self.nout > 4 else None)
-        if self._wscale is None:
-            return pack_split_streams(self.w1, self.w2, self.w3, stages, self.precision)
-        sc = self._wscale
-        return pack_split_streams(self.w1 * sc[:, 0, None, None], self.w2 * sc[:, 1, None, None], self.w3 * sc[:, 2, None, None],
-                                  stages, self.precision)
 
     # ------------------------------------------------------------------ constructors
     @classmethod
@@ -445,9 +419,9 @@ class BatchedMLP:
             if self.sample_kind == SAMPLE_CATEGORICAL:
                 idx = (torch.empty(E, self.n_agents, dtype=torch.int32, device=self.device) if idx_out is None
                        else self._given(idx_out, (E, self.n_agents), torch.int32, "idx_out"))
-        entry = {"bf16": self._lib.dronesim_mlp_forward_bf16, "bf16x3": self._lib.dronesim_mlp_forward_bf16x3,
-                 "f16x2": (self._lib.dronesim_mlp_forward_f16x2_rt if getattr(self, "_rt16", False) else self._lib.dronesim_mlp_forward_f16x2),
-                 "f32": self._lib.dronesim_mlp_forward}[self.precision]
+        entry = getattr(self._lib, {"bf16": "dronesim_mlp_forward_bf16", "bf16x3": "dronesim_mlp_forward_bf16x3",
+                                    "f16x2_split": "dronesim_mlp_forward_f16x2", "f16x2_rowtile": "dronesim_mlp_forward_f16x2_rt"}
+                        .get(self._mode, "dronesim_mlp_forward"))
         with torch.cuda.device(self.device):
             rc = entry(C.byref(m), z.data_ptr(), None if out is None else out.data_ptr(),
                                                 None if act is None else act.data_ptr(),

@@ -1084,7 +1084,7 @@ def test_policy_shape_fuzz_all_precisions(torch):
     for it in range(int(os.environ.get("FUZZ_ITERS", 48))):
         d = int(rng.integers(1, 17)); N = int(rng.integers(1, 7)); E = int(rng.choice([1, 2, 31, 63, 64, 65, 130, 257]))
         h1 = int(rng.choice([1, 5, 31, 32, 33, 64, 96, 100, 128, 200, 257, 400, 512]))
-        h2 = int(rng.choice([1, 7, 32, 33, 64, 65, 96, 127, 128, 129, 200, 232, 300, 400, 416, 480, 512]))   # (every dealing of csrc/policy.hip: tr_plan)
+        h2 = int(rng.choice([1, 7, 32, 33, 64, 65, 96, 127, 128, 129, 200, 232, 300, 400, 416, 480, 512]))   # (every dealing of csrc/policy_f32.hip: mlp3_kernel's leftover chunks)
         kind = int(rng.integers(0, 3))
         nout = 4 if kind == 2 else int(rng.integers(1, 33))
         sc1, sc2, sc3 = 0.8 / np.sqrt(d), 1.2 / np.sqrt(h1), 1.2 / np.sqrt(h2)

@@ -29,8 +29,8 @@ def kernels(path):
             elif name and line.strip():
                 ins = re.sub(r"^\s*[0-9a-f]+:\s*", "", line.split("//")[0]).strip()
                 ins = re.sub(r"<[^>]*\+0x[0-9a-f]+>", "<L>", ins)
-                if ins:
-                    out[name].append(ins)
+                if ins and ins != "...":       # "...": objdump's mark for the zero padding up to the NEXT kernel's alignment --
+                    out[name].append(ins)      # no instruction, and absent behind the last kernel of a code object
     return out
 
 

@@ -2,7 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -o build/mfma_valu_coissue tools/micro/mfma_valu_coissue.hip && ./build/mfma_valu_coissue
 // Both pipes have the same float32 peak on gfx950 (v_mfma_f32_32x32x2_f32: 4096 flop per 64 cycles per SIMD;
 // v_pk_fma_f32 on a wave64: 256 flop per 4 cycles per SIMD = 157 TFLOP/s each at 2.4 GHz x 1024 SIMDs).  The exact-float32
-// policy kernel (csrc/policy.hip, mlp3_kernel) uses the matrix pipe only; if a second wave of the SIMD could run a
+// policy kernel (csrc/policy_f32.hip, mlp3_kernel) uses the matrix pipe only; if a second wave of the SIMD could run a
 // k-ordered v_pk_fma_f32 GEMM on other output columns meanwhile, the float32-exact ceiling of a CU would double.
 // Workgroups of 8 waves (2 per SIMD): mode 0 = all waves matrix, 1 = all waves vector, 2 = waves 0-3 matrix + waves 4-7
 // vector (one of each per SIMD), 3 = every wave alternates 1 matrix instruction with 16 vector ones.

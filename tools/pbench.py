@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer benchmark: batched policy forward (csrc/policy.hip) alone and inside the rollout loop
+"""Developer benchmark: batched policy forward (csrc/policy_*.hip; default: policy_rowtile.hip) alone and inside the rollout loop
 obs -> sample_action -> env.step (hipGraph replay)."""
 import os
 import sys
