@@ -9,7 +9,10 @@ Part 2 -- the same loop batched: E envs x N agents stay on the device; a per-age
           (the batched `ExperienceBuffers`, utils.py:232-253), and the episode's Monte-Carlo returns /
           neighbour-summed advantage weights (SAC_agents.py:304-307, 333-351) are reduced on the device.
 
-    python examples/rollout_loop.py [--envs 4096] [--agents 64]
+Part 3 -- (--controller proportional|gradient) the classical baseline in closed loop as ONE launch per 200 steps
+          (`rollout_control`), next to the same loop as two launches per step.
+
+    python examples/rollout_loop.py [--envs 4096] [--agents 64] [--controller {proportional,gradient}]
 """
 import argparse
 import os
@@ -116,10 +119,40 @@ def part2(E, N):
           f"{bool((nz != st.z).any()) if int(st.done.sum()) else 'n/a'}")
 
 
+def part3(E, N, kind):
+    """control_test.py:30-45 batched: the controller's action computed inside the fused rollout launch."""
+    G = 28.0 if N == 64 else max(6.0, 0.45 * N)
+    T = drone_env.max_time_steps
+    mk = lambda: drone_env.drones(N, 0, [G, G], "O", deltas=np.ones(N), simplify_zstate=True, n_envs=E, seed=0, auto_reset=True)
+    env = mk()
+    env.rollout_control(kind, T); env.reset(renew_obstacles=False); torch.cuda.synchronize()
+    t0 = time.perf_counter(); out = env.rollout_control(kind, T); torch.cuda.synchronize()
+    dt_f = time.perf_counter() - t0
+    loop = mk()
+    for _ in range(T):
+        loop.step(loop.control(kind))
+    loop.reset(renew_obstacles=False); torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(T):
+        loop.step(loop.control(kind))
+    torch.cuda.synchronize()
+    dt_l = time.perf_counter() - t0
+    st = env.episode_stats()
+    print(f"[closed loop, {kind}] {E} envs x {N} agents x {T} steps:\n"
+          f"   rollout_control (one launch)   {dt_f*1e3:7.1f} ms = {E*N*T/dt_f:.3e} agent-steps/s\n"
+          f"   control() + step() per step    {dt_l*1e3:7.1f} ms = {E*N*T/dt_l:.3e} agent-steps/s\n"
+          f"   mean reward of the last step {float(out['reward'][-1].mean()):.3f}, collisions in the window "
+          f"{int(out['n_coll'].sum())}, episodes ended {int(out['done'].sum())} (completed per env: {float(st['episodes'].float().mean()):.2f})")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--agents", type=int, default=64)
+    ap.add_argument("--controller", choices=["proportional", "gradient"], default=None)
     a = ap.parse_args()
     part1()
-    part2(a.envs, a.agents)
+    if a.controller:
+        part3(a.envs, a.agents, a.controller)
+    else:
+        part2(a.envs, a.agents)

@@ -229,6 +229,22 @@ int dronesim_rollout_random(const DroneParams *p, const DroneEpisodeCtl *ctl, fl
                             float *act_out, float *reward, float *true_reward, float *z, int32_t *nbr_idx,
                             int32_t *n_coll, uint8_t *done, int E, int T, void *stream);
 
+/* T fused steps in CLOSED LOOP with a classical controller (control_test.py:30-45: proportional_control /
+ * gradient_control feeding env.step): the action of step s is computed inside the launch from the positions the
+ * env holds before step s -- exactly what dronesim_control(kind, u_max) returns on them -- so a step costs neither a
+ * second launch nor a round trip of the actions through memory.
+ *   kind    DRONESIM_CONTROL_PROPORTIONAL or DRONESIM_CONTROL_GRADIENT (anything else: DRONESIM_EINVAL)
+ *   u_max   the controller's clip, > 0 (<= 0 or NaN: DRONESIM_EINVAL)
+ * ctl may be NULL: a plain rollout without the episode layer.  With ctl->auto_reset an env that finishes at step s
+ * is re-sampled inside the launch and its action at step s + 1 is the controller's on the NEW episode's positions.
+ * act_out ([T][E][N][2], may be NULL) records the actions applied; replayed through dronesim_rollout_ex they give the
+ * same outputs bit for bit, and results do not depend on how T is split into calls.  Other buffers as
+ * dronesim_rollout_random; any of reward / true_reward / n_coll may be NULL.  c = 5 observations of envs whose rows
+ * do not fit the LDS tile (n_agents x k_closest near the size limit) return DRONESIM_EUNSUPPORTED.             */
+int dronesim_rollout_control(const DroneParams *p, const DroneEpisodeCtl *ctl, int kind, float u_max,
+                             float *pos, float *vel, int32_t *t, float *act_out, float *reward, float *true_reward,
+                             float *z, int32_t *nbr_idx, int32_t *n_coll, uint8_t *done, int E, int T, void *stream);
+
 /* dronesim_reset that also retires the episode records of the envs it resets (those with ep_len > 0).        */
 int dronesim_reset_ex(const DroneParams *p, const DroneEpisodeCtl *ctl, const uint8_t *mask,
                       float *pos, float *vel, int32_t *t, int32_t *node_out, int E, void *stream);

@@ -82,8 +82,46 @@ constexpr float kLn2 = 0.693147180559945309f;
 // actions / actions drawn in the kernel) -- the one-env-per-wave and N = 256 geometries (every BASELINE shape's rollout):
 // no run-time `rand_act` branches in the per-step loop and none of the other source's registers live across it (round 5).
 // kRollout itself keeps the run-time flag (the other geometries, and every plain rollout).
-enum Mode { kStep = 0, kObserve = 1, kRollout = 2, kRolloutPool = 3, kRolloutRand = 4 };
+// kRolloutCtrl (closed-loop rollouts, dronesim_rollout_control): the third compile-time action source -- the action of step s
+// is a classical controller's (drone_env.py:609-679), computed inside the launch from the positions the env holds before step
+// s.  With and without the episode layer, every geometry; which controller (KArgs.ctrl) is a launch-uniform run-time value of
+// these instances only.
+enum Mode { kStep = 0, kObserve = 1, kRollout = 2, kRolloutPool = 3, kRolloutRand = 4, kRolloutCtrl = 5 };
 constexpr bool is_rollout(int mode) { return mode >= kRollout; }
+
+// @phase h_control
+// Classical controllers (drone_env.py:609-679): shared by control_kernel (dronesim.hip: one launch per evaluation) and the
+// closed-loop rollout (kRolloutCtrl), so that both form the same float32 expressions.
+// proportional_control (:652-679, k_gain = 1); the goal in two float32 parts, the first difference exact near the goal
+__device__ __forceinline__ float2 control_proportional(float xi, float yi, float xFx, float xFy, float xLx, float xLy, float u_max)
+{
+    float ux = (xFx - xi) + xLx, uy = (xFy - yi) + xLy;                      // :667-668
+    const float nrm = sqrtf(fmaf(uy, uy, ux * ux));
+    if (nrm > u_max) { ux = ux / nrm * u_max; uy = uy / nrm * u_max; }       // :670-673
+    return make_float2(ux, uy);
+}
+// one ordered pair of gradient_control's repulsion sum (:639-644); the first test is the conservative reach test of the far filter
+__device__ __forceinline__ void gradient_pair(float xi, float yi, float ri, float dhat, float2 pj, float rj, float &t2x, float &t2y)
+{
+    const float dx = xi - pj.x, dy = yi - pj.y;
+    const float d2 = fmaf(dy, dy, dx * dx);
+    const float reach = dhat + ri + rj;
+    if (d2 <= reach * reach * 1.000001f) {
+        const float nrm = sqrtf(d2);
+        const float dij = nrm - ri - rj;                                     // :641
+        if (dij <= dhat) {                                                   // :643
+            const float w = 1.0f / (dij * nrm);
+            t2x = fmaf(dx, w, t2x); t2y = fmaf(dy, w, t2y);                  // :644
+        }
+    }
+}
+// gradient_control's action from the finished repulsion sum (:633, :646-647)
+__device__ __forceinline__ float2 control_gradient(float xi, float yi, float xFx, float xFy, float xLx, float xLy,
+                                                   float t2x, float t2y, float u_max)
+{
+    const float gx = 2.0f * ((xi - xFx) - xLx) - 0.1f * t2x, gy = 2.0f * ((yi - xFy) - xLy) - 0.1f * t2y;   // :633, :646
+    return make_float2(fminf(fmaxf(-gx, -u_max), u_max), fminf(fmaxf(-gy, -u_max), u_max));               // :647
+}
 
 // Developer trace builds (-DDRONESIM_TRACE / -DDRONESIM_TRACE_FINE: kTrace / kTraceFine of common.hpp) stamp per-wave
 // phase times into KArgs.trace; in the product build the stamps are dead code.  TRACE_FINE moves stamps 1 and 2 into the
@@ -113,6 +151,9 @@ struct KArgs {
     int lds_vel;                    //        agents sit in LDS at this byte offset (both sized by the host when they fit)
     int uniform;                    // all agents share d_hat, Delta and radius (host-known): constants come
     float dhat_u, delta_u, radius_u;   //   from the kernel arguments, no per-agent table is read
+    float u_max;                    // closed-loop rollout (kRolloutCtrl): the controller's clip.  (In the 4 bytes of padding ahead of
+                                    // `acc`: the size of the kernel-argument segment and every other field's offset stay what they
+                                    // were, and with them the code of every other instance.)
     // episode bookkeeping / in-kernel reset / in-kernel random actions (DroneEpisodeCtl; all off when zero)
     double *acc;                    // DroneEpisodeAcc[E] as 8 x 8 bytes per env, or nullptr
     int auto_reset, rand_act;
@@ -128,6 +169,8 @@ struct KArgs {
     int do_reset;                   // observe mode only (dronesim_reset_observe): draw the state instead of loading it
     int *node_out;                  //   optional record of the lattice nodes drawn, [E][N]
 };
+
+static_assert(sizeof(KArgs) == 336, "the kernel-argument segment keeps its size: the implicit arguments behind it (blockDim) keep their offsets");
 
 // @phase h_nbr_list
 // (d, j) as ONE unsigned key whose integer order is the lexicographic order of the pair:
@@ -495,8 +538,10 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // EPI: which parts of DroneEpisodeCtl are in use travels in the high half of the preloaded `epb` argument
     // (bit 16 records, bit 17 auto-reset, bit 18 random actions), so that the branches that depend on it never wait
     // for the kernel-argument fetch ahead of the first pos / act loads
-    const int epi_flags = EPI ? (epb >> 16) : 0;
-    if (EPI) epb &= 0xffff;
+    // (bit 19: the closed-loop rollout's controller is gradient_control -- kRolloutCtrl, with or without the episode layer)
+    constexpr bool CTRL = MODE == kRolloutCtrl;              // the action source is a controller evaluated in this launch
+    const int epi_flags = (EPI || CTRL) ? (epb >> 16) : 0;
+    if (EPI || CTRL) epb &= 0xffff;
     const unsigned xcd_blocks = (unsigned)P & ~255u;         // workgroups in whole groups of 256 (XCD map below)
     a.pos = pos; a.P = P & 255; a.epb = epb; a.E = E; a.N = n_agents;
     if (MODE == kObserve) a.vel = const_cast<float *>(vel_or_act); else a.act = vel_or_act;
@@ -584,7 +629,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     if (!kTrace && SYM && EPI && !is_rollout(MODE)) asm volatile("" : "+s"(epi_word));
 #define has_acc (EPI && (epi_word & 1) != 0)
 #define auto_reset (EPI && (epi_word & 2) != 0)
-    const bool rand_act = MODE == kRolloutRand ? true : MODE == kRolloutPool ? false : (EPI && is_rollout(MODE) && (epi_flags & 4) != 0);
+    const bool rand_act = MODE == kRolloutRand ? true : (MODE == kRolloutPool || CTRL) ? false : (EPI && is_rollout(MODE) && (epi_flags & 4) != 0);
     // the 32 hot bytes of the env's record live in registers for the whole launch, split over two lanes so that one
     // load and one store instruction move them: agent 0 holds (ep_return, ep_true_return) as two doubles, agent 1
     // holds (ep_collisions, ep_len, episodes, reserved) as four ints
@@ -620,8 +665,8 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
                 epi = (uint32_t)a.episode[env];               // resets this env has seen so far: the stream id of the draw
             }
         } else {
-            if (rand_act) {
-                // no action pool: the first action is drawn below, once t and the episode counter have arrived
+            if (rand_act || CTRL) {
+                // no action pool: the first action is drawn (computed) below, once t and the episode counter (the position) have arrived
             } else if (BLOCKGEO) {
                 u0 = vel_in[lane];
             } else {
@@ -976,13 +1021,56 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
         // (the packed geometry keeps the round-2 form, prefetch under `valid` straight into u0: at its 128-register cap
         // the separate pair is itself copied and waited for at once -- C2 +5 %)
         constexpr bool PREFETCH_SEP = is_rollout(MODE) && GEO != kPacked;
-        if (PREFETCH_SEP && !rand_act && step > 0) u0 = unext;
+        if (CTRL) {
+            // @phase control
+            // ---- closed loop: the controller's action on the positions the env holds BEFORE this step.  They sit in LDS by
+            // agent index: the previous step wrote them (its integrated positions, or the new episode's where the in-kernel
+            // reset ran) and ended on a barrier; the first step of a launch writes them here.
+            const bool gradient = (epi_flags & 8) != 0;       // launch-uniform
+            if (!gradient) {
+                u0 = control_proportional(xi, yi, xFx, xFy, xLx, xLy, a.u_max);
+            } else {
+                if (step == 0) {
+                    if (valid) spos_env[agent] = make_float2(xi, yi);
+                    group_sync<WL>();                         // (also orders the (Delta_j, l_j) table written above)
+                }
+                // the repulsion sum over the partners in ascending order (control_kernel's order; a partner beyond
+                // dhat_i + l_i + l_j adds no term, so any superset of those inside gives the same sum).  Geometries that keep
+                // a candidate list between steps walk it: the previous step took or confirmed it on exactly these positions
+                // (every pair inside reach_i is listed), unless that step re-sampled the env (no list: NaN reference point).
+                // Everything else -- and the first step of a launch -- visits all partners, every lane of the wave reading
+                // the same address per trip.
+                float t2x = 0.f, t2y = 0.f;
+                if (CACHED && valid && refx == refx) {
+#pragma unroll
+                    for (int w = 0; w < (CACHED_B ? WMAX : 1); ++w) {
+                        unsigned long long m = CACHED_B ? candw[w] : cand;
+                        while (m) {
+                            const int j = 64 * w + __builtin_ctzll(m);
+                            m &= m - 1ull;
+                            gradient_pair(xi, yi, li, dhat, spos_env[j], uni_args ? a.radius_u : sconst[j].y, t2x, t2y);
+                        }
+                    }
+                } else if (valid) {
+#pragma nounroll
+                    for (int j = 0; j < N; ++j) {
+                        const float rj = uni_args ? a.radius_u : sconst[j].y;
+                        if (j != agent) gradient_pair(xi, yi, li, dhat, spos_env[j], rj, t2x, t2y);
+                    }
+                }
+                u0 = control_gradient(xi, yi, xFx, xFy, xLx, xLy, t2x, t2y, a.u_max);
+                group_sync<WL>();                             // every read of the old positions before the integrator's write
+            }
+            if (valid && a.act_out != nullptr)
+                st_out2(a.act_out + 2 * (so + wga0 + lane), u0.x, u0.y);
+        }
+        if (PREFETCH_SEP && !rand_act && !CTRL && step > 0) u0 = unext;
         const float2 u = u0;
-        if (PREFETCH_SEP && !rand_act && step + 1 < nsteps) {
+        if (PREFETCH_SEP && !rand_act && !CTRL && step + 1 < nsteps) {
             const float2 *nxt = reinterpret_cast<const float2 *>(a.act) + (nval > 0 ? so + step_agents + wga0 : 0);
             unext = nxt[valid ? lane : 0u];
         }
-        if (is_rollout(MODE) && !PREFETCH_SEP && !rand_act && valid && step + 1 < nsteps)
+        if (is_rollout(MODE) && !PREFETCH_SEP && !rand_act && !CTRL && valid && step + 1 < nsteps)
             u0 = (reinterpret_cast<const float2 *>(a.act) + so + step_agents + wga0)[lane];
         if (valid) {
             if (MODE != kObserve) {
@@ -2048,6 +2136,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
 struct Geometry {
     int P, epb, threads, blocks, geo;
     size_t lds;
+    int ctrl;                       // closed-loop rollout: 1 + DRONESIM_CONTROL_* (0: the actions come from a pool / the Philox stream)
 };
 
 // more than 48 KiB of dynamic LDS (envs of several hundred agents) has to be opted into once per kernel
@@ -2077,7 +2166,8 @@ hipError_t launch_one(const KArgs &a, const Geometry &g, hipStream_t s)
     hipLaunchKernelGGL((drone_kernel<K, FAR, MODE, GEO, EPI>), dim3(g.blocks), dim3(g.threads), g.lds, s,
                        a.pos, MODE == kObserve ? static_cast<const float *>(a.vel) : a.act,
                        (int)((unsigned)a.P | ((unsigned)g.blocks & ~255u)),   // P <= 64; whole groups of 256 workgroups (XCD map)
-                       EPI ? (a.epb | ((a.acc != nullptr ? 1 : 0) | (a.auto_reset ? 2 : 0) | (a.rand_act ? 4 : 0)) << 16) : a.epb,
+                       (EPI || MODE == kRolloutCtrl) ? (a.epb | ((a.acc != nullptr ? 1 : 0) | (a.auto_reset ? 2 : 0) | (a.rand_act ? 4 : 0) |
+                                                                  (g.ctrl == 1 + DRONESIM_CONTROL_GRADIENT ? 8 : 0)) << 16) : a.epb,
                        a.E, a.N, a);
     return hipSuccess;
 }
@@ -2090,6 +2180,8 @@ hipError_t launch_mode(int mode, const KArgs &a, const Geometry &g, hipStream_t 
     case kStep: return epi ? launch_one<K, FAR, kStep, GEO, true>(a, g, s) : launch_one<K, FAR, kStep, GEO, false>(a, g, s);
     case kObserve: return launch_one<K, FAR, kObserve, GEO, false>(a, g, s);
     default:
+        if (g.ctrl != 0)               // closed-loop rollout: the controller is the action source, with or without the episode layer
+            return epi ? launch_one<K, FAR, kRolloutCtrl, GEO, true>(a, g, s) : launch_one<K, FAR, kRolloutCtrl, GEO, false>(a, g, s);
         if (!epi) return launch_one<K, FAR, kRollout, GEO, false>(a, g, s);
         if constexpr (GEO == kSym64)   // the action source at compile time (see Mode)
             return a.rand_act ? launch_one<K, FAR, kRolloutRand, GEO, true>(a, g, s) : launch_one<K, FAR, kRolloutPool, GEO, true>(a, g, s);
@@ -2109,6 +2201,8 @@ hipError_t launch_k(int mode, bool far, const KArgs &a, const Geometry &g, hipSt
         return far ? launch_mode<K, true, kBlock256>(mode, a, g, s) : launch_mode<K, false, kBlock256>(mode, a, g, s);
     case kBlockU256: {                              // rollouts only (launch() picks it for mode == kRollout)
         const bool epi = a.acc != nullptr || a.auto_reset != 0 || a.rand_act != 0;
+        if (g.ctrl != 0)
+            return epi ? launch_one<K, false, kRolloutCtrl, kBlockU256, true>(a, g, s) : launch_one<K, false, kRolloutCtrl, kBlockU256, false>(a, g, s);
         if (epi) return a.rand_act ? launch_one<K, false, kRolloutRand, kBlockU256, true>(a, g, s) : launch_one<K, false, kRolloutPool, kBlockU256, true>(a, g, s);
         return launch_one<K, false, kRollout, kBlockU256, false>(a, g, s);
     }

@@ -117,21 +117,8 @@ struct CArgs {
     float inv_cell;                 // 1 / cell width
 };
 
-// one ordered pair of the repulsion sum (:639-644); `cand` = the conservative reach test of the far filter
-__device__ __forceinline__ void gradient_pair(float xi, float yi, float ri, float dhat, float2 pj, float rj, float &t2x, float &t2y)
-{
-    const float dx = xi - pj.x, dy = yi - pj.y;
-    const float d2 = fmaf(dy, dy, dx * dx);
-    const float reach = dhat + ri + rj;
-    if (d2 <= reach * reach * 1.000001f) {
-        const float nrm = sqrtf(d2);
-        const float dij = nrm - ri - rj;                                     // :641
-        if (dij <= dhat) {                                                   // :643
-            const float w = 1.0f / (dij * nrm);
-            t2x = fmaf(dx, w, t2x); t2y = fmaf(dy, w, t2y);                  // :644
-        }
-    }
-}
+// (the controllers' arithmetic -- control_proportional, gradient_pair, control_gradient -- lives in drone_kernel.hpp: the
+// closed-loop rollout evaluates the same expressions inside its launch)
 
 template <bool WL>
 __global__ void __launch_bounds__(1024) control_kernel(const CArgs a)
@@ -181,11 +168,9 @@ __global__ void __launch_bounds__(1024) control_kernel(const CArgs a)
         }
         group_sync<WL>();
     }
-    float ux, uy;
+    float2 u;
     if (!gradient) {
-        ux = (xFx - xi) + xLx; uy = (xFy - yi) + xLy;                        // :667-668, k_gain = 1
-        const float nrm = sqrtf(fmaf(uy, uy, ux * ux));
-        if (nrm > a.u_max) { ux = ux / nrm * a.u_max; uy = uy / nrm * a.u_max; }   // :670-673
+        u = control_proportional(xi, yi, xFx, xFy, xLx, xLy, a.u_max);       // :652-679
     } else {
         const float2 *pe = spos + (size_t)slot * N;
         float t2x = 0.f, t2y = 0.f;
@@ -214,11 +199,9 @@ __global__ void __launch_bounds__(1024) control_kernel(const CArgs a)
             for (int j = 0; j < N; ++j)
                 if (j != agent) gradient_pair(xi, yi, ri, dhat, pe[j], srad_w[j], t2x, t2y);
         }
-        const float gx = 2.0f * ((xi - xFx) - xLx) - 0.1f * t2x, gy = 2.0f * ((yi - xFy) - xLy) - 0.1f * t2y;   // :633, :646
-        ux = fminf(fmaxf(-gx, -a.u_max), a.u_max);                           // :647
-        uy = fminf(fmaxf(-gy, -a.u_max), a.u_max);
+        u = control_gradient(xi, yi, xFx, xFy, xLx, xLy, t2x, t2y, a.u_max);   // :633, :646-647
     }
-    if (valid) (reinterpret_cast<float2 *>(a.act) + wga0)[lane] = make_float2(ux, uy);
+    if (valid) (reinterpret_cast<float2 *>(a.act) + wga0)[lane] = u;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -566,6 +549,7 @@ Geometry geometry(int N, int E)
     }
     g.blocks = (E + g.epb - 1) / g.epb;
     g.lds = 0;
+    g.ctrl = 0;
     return g;
 }
 
@@ -669,10 +653,12 @@ int apply_ctl(const DroneParams *p, const DroneEpisodeCtl *ctl, bool rand_act, K
     return DRONESIM_OK;
 }
 
-int launch(int mode, const DroneParams *p, KArgs &a, int E, void *stream)
+// ctrl: closed-loop rollout (mode kRollout), 1 + DRONESIM_CONTROL_* -- the kRolloutCtrl instances
+int launch(int mode, const DroneParams *p, KArgs &a, int E, void *stream, int ctrl = 0)
 {
     if (E == 0) return DRONESIM_OK;
     Geometry g = geometry(p->N, E);
+    g.ctrl = ctrl;
     // far agents matter when a z row carries (v, l) of a tie-ordered agent (c = 5) or
     // when a clipped distance can pass a Delta mask (Delta_j >= dhat_i possible)
     const bool far = (p->c == 5) || !(p->delta_max < p->d_hat_min);
@@ -709,6 +695,9 @@ int launch(int mode, const DroneParams *p, KArgs &a, int E, void *stream)
             a.stage5 = 1; a.lds_vel = (int)lds5; g.lds = lds5 + vel16;
         }
     }
+    // closed-loop rollout: the c = 5 rows of the k nearest carry the partners' velocities = their actions, which exist in LDS only
+    if (ctrl != 0 && p->c == 5 && !a.stage5)
+        return fail(DRONESIM_EUNSUPPORTED, "dronesim_rollout_control: c = 5 rows of this n_agents x k_closest do not fit the LDS tile");
     g.lds = (g.lds + 15) & ~(size_t)15;                 // the tail's float4 reads (per-wave partial sums) need 16 bytes
     a.lds_tail = (int)g.lds;
     if (epi_regions) {
@@ -864,6 +853,29 @@ int dronesim_rollout_random(const DroneParams *p, const DroneEpisodeCtl *ctl, fl
     a.act_out = act_out;
     if ((rc = apply_ctl(p, ctl, true, a)) != 0) return rc;
     return launch(kRollout, p, a, E, stream);
+}
+
+int dronesim_rollout_control(const DroneParams *p, const DroneEpisodeCtl *ctl, int kind, float u_max,
+                             float *pos, float *vel, int32_t *t, float *act_out, float *reward, float *true_reward,
+                             float *z, int32_t *nbr_idx, int32_t *n_coll, uint8_t *done, int E, int T, void *stream)
+{
+    int rc = check_params(p, E);
+    if (rc) return rc;
+    if (T < 0) return fail(DRONESIM_EINVAL, "T < 0");
+    if (kind != DRONESIM_CONTROL_PROPORTIONAL && kind != DRONESIM_CONTROL_GRADIENT)
+        return fail(DRONESIM_EINVAL, "unknown controller kind");
+    if (!(u_max > 0.0f)) return fail(DRONESIM_EINVAL, "dronesim_rollout_control: u_max must be > 0 (and not NaN)");
+    if (!pos || !vel || !t || !z || !nbr_idx || !done)
+        return fail(DRONESIM_EINVAL, "dronesim_rollout_control: required buffer is NULL");
+    if (T == 0) return DRONESIM_OK;
+    KArgs a{};
+    a.pos = pos; a.vel = vel; a.t = t; a.act = nullptr; a.reward = reward; a.true_reward = true_reward;
+    a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll; a.done = done; a.T = T;
+    a.skin = kSkin * (p->d_hat_max + 2.0f * p->radius_max);
+    a.act_out = act_out;
+    a.u_max = u_max;
+    if ((rc = apply_ctl(p, ctl, false, a)) != 0) return rc;
+    return launch(kRollout, p, a, E, stream, 1 + kind);
 }
 
 int dronesim_reset(const DroneParams *p, int div_x, int div_y, float pitch,

@@ -497,7 +497,26 @@ class drones:
         not depend on the sharding or on how T is split into calls.  ``record_actions`` adds ``actions [T,E,N,2]``."""
         return self.rollout(None, with_pre=with_pre, _random=(int(T), bool(record_actions)))
 
-    def rollout(self, actions, with_pre=False, _random=None):
+    def rollout_control(self, kind: str, T, u_max: float = 1.0, record_actions=False, with_pre=False):
+        """T fused steps in CLOSED LOOP with a classical controller (the reference's control_test.py:30-45 loop,
+        ``proportional_control`` / ``gradient_control`` feeding ``step``): the action of step s is computed inside the
+        launch from the positions the env holds before step s -- what ``control(kind, u_max)`` returns on them -- so a
+        step costs one launch share instead of two launches.  ``kind`` = "proportional" or "gradient".  Returns the
+        dict of `rollout()`; ``record_actions`` adds ``actions [T,E,N,2]`` (replayed through ``rollout(actions)`` they
+        reproduce every output bit for bit).  With ``auto_reset`` an env that finishes at step s acts at step s + 1 on
+        its new episode's positions.  Results do not depend on how T is split into calls."""
+        codes = {"proportional": self._native.CONTROL_PROPORTIONAL, "gradient": self._native.CONTROL_GRADIENT}
+        if kind not in codes:
+            raise ValueError(f"kind must be 'proportional' or 'gradient', got {kind!r}")
+        u_max = float(u_max)
+        if not u_max > 0.0:
+            raise ValueError(f"u_max must be > 0, got {u_max}")
+        T = int(T)
+        if T < 0:
+            raise ValueError("T < 0")
+        return self.rollout(None, with_pre=with_pre, _control=(T, bool(record_actions), codes[kind], u_max))
+
+    def rollout(self, actions, with_pre=False, _random=None, _control=None):
         """T fused steps in one launch with the actions known up front (RandomAgent-style rollouts,
         SAC_agents.py:9-22 + train_problem.py:82-107).  ``actions``: ``[T,E,N,2]`` float32 device tensor.
         Returns a dict of ``[T, ...]`` tensors with every per-step output of step(); ``with_pre=True`` adds
@@ -508,9 +527,10 @@ class drones:
         torch = self._torch
         E, N, K1, c = self.n_envs, self.n_agents, self.k_closest + 1, self.c
         random_actions = _random is not None
-        if random_actions:
-            T = _random[0]
-            act = torch.empty(T, E, N, 2, dtype=torch.float32, device=self.device) if _random[1] else None
+        in_kernel = _random if random_actions else _control          # (T, record the actions, ...): no action pool
+        if in_kernel is not None:
+            T = in_kernel[0]
+            act = torch.empty(T, E, N, 2, dtype=torch.float32, device=self.device) if in_kernel[1] else None
         else:
             act = actions.to(device=self.device, dtype=torch.float32).contiguous()
             T = act.shape[0]
@@ -541,6 +561,13 @@ class drones:
                     None if act is None else act.data_ptr(), out["reward"].data_ptr(), out["true_reward"].data_ptr(),
                     out["z"].data_ptr(), out["nbr_idx"].data_ptr(), out["n_coll"].data_ptr(),
                     out["done"].data_ptr(), E, T, self._stream())
+            elif _control is not None:
+                rc = self._lib.dronesim_rollout_control(
+                    C.byref(p), C.byref(ctl) if self._use_ctl else None, _control[2], _control[3],
+                    self.pos.data_ptr(), self.vel.data_ptr(), self.t.data_ptr(),
+                    None if act is None else act.data_ptr(), out["reward"].data_ptr(), out["true_reward"].data_ptr(),
+                    out["z"].data_ptr(), out["nbr_idx"].data_ptr(), out["n_coll"].data_ptr(),
+                    out["done"].data_ptr(), E, T, self._stream())
             else:
                 rc = self._lib.dronesim_rollout_ex(
                     C.byref(p), C.byref(ctl) if self._use_ctl else None, self.pos.data_ptr(),
@@ -548,7 +575,7 @@ class drones:
                     out["true_reward"].data_ptr(), out["z"].data_ptr(), out["nbr_idx"].data_ptr(),
                     out["n_coll"].data_ptr(), out["done"].data_ptr(), E, T, self._stream())
         self._native.check(rc, "dronesim_rollout")
-        if random_actions and act is not None:
+        if in_kernel is not None and act is not None:
             out["actions"] = act
         if with_pre and T > 0:
             out["z_pre"] = torch.cat([z0.unsqueeze(0), out["z"][:-1]], dim=0)

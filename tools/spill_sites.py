@@ -16,11 +16,26 @@ from kernel_resources import code_objects
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
+_LISTINGS = {}          # (path, mtime, size) -> objdump listing of every code object: a caller that asks about several kernels
+                        # of one library (tests/test_host_logic.py) pays for the disassembly once
+
+
+def listings(path):
+    st = os.stat(path)
+    key = (os.path.abspath(path), st.st_mtime_ns, st.st_size)
+    if key not in _LISTINGS:
+        out = []
+        for _, co in code_objects(open(path, "rb").read()):
+            with tempfile.NamedTemporaryFile(suffix=".co") as f:
+                f.write(co); f.flush()
+                out.append(subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", f.name], capture_output=True, text=True).stdout)
+        _LISTINGS.clear()
+        _LISTINGS[key] = out
+    return _LISTINGS[key]
+
+
 def disasm(path, pat):
-    for _, co in code_objects(open(path, "rb").read()):
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(co); f.flush()
-            txt = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", f.name], capture_output=True, text=True).stdout
+    for txt in listings(path):
         name, cur = None, {}
         for line in txt.split("\n"):
             m = re.match(r"^([0-9a-f]+) <(.+)>:$", line)
