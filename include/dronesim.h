@@ -316,9 +316,14 @@ int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *
  * Weights are stacked per agent, "in x out" row-major: w1 [N][d_in][h1], b1 [N][h1], w2 [N][h1][h2],
  * b2 [N][h2], w3 [N][h2][nout], b3 [N][nout] (torch Linear stores [out][in]: transpose when importing).
  * out [E][N][nout] (post-activation, may be NULL), act [E][N][2] and act_idx [E][N] (may be NULL).
- * Random stream: Philox4x32-10 keyed by (seed, env_base + e, agent, counter.lo + t[e],
- * counter.hi + episode[e]); t / episode (int32 [E], device, may be NULL) are the env's own step and
- * episode counters, so a captured hipGraph draws fresh numbers on every replay.                      */
+ * Random stream: row e, agent i draw the four words of
+ *   philox4x32-10(ctr = (i, env_base + e, counter.lo + t[e], counter.hi + episode[e]); key = (seed.lo, seed.hi)),
+ * every counter word modulo 2^32 on its own (no carry from counter.lo + t[e] into the high word); t / episode
+ * (int32 [E], device, may be NULL = 0) are the env's own step and episode counters, so a captured hipGraph draws
+ * fresh numbers on every replay.  Categorical: u = (word 0 >> 8) / 2^24, the pick is the first j with u < cdf_j
+ * (nout - 1 if there is none).  Gaussian: component d takes words (2 d, 2 d + 1): u1 = ((w >> 8) + 1) / 2^24,
+ * u2 = (w' >> 8) / 2^24, act_d = mu_d + sqrt(var_d) sqrt(-2 ln u1) cos(2 pi u2).  Pinned draw by draw by
+ * tests/test_gpu_sampling.py against tests/sampling_ref.py.                                            */
 typedef struct DroneMlp {
     int32_t N, d_in, h1, h2, nout;
     int32_t out_kind;       /* 0 identity, 1 softmax, 2 tanh(first half) + sigmoid(second half).  Accuracy contract of kinds 1 / 2

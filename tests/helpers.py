@@ -26,6 +26,27 @@ def atol_coord(G):
 MARGIN = 1e-4
 
 
+# every policy kernel configuration by the label the tests give it: the exact-f32 row-tile stream ("f32"; the fragment kernel when
+# d_in > 14), layer 2 on fragment-packed weights, on the plain [N, h1, h2] array of the C ABI, the two splits, the superseded
+# f16x2 split kernel and plain bf16
+POLICY_CONFIGS = ("f32", "f32-fragments", "f32-w2-unpacked", "bf16x3", "f16x2", "f16x2-split", "bf16")
+
+
+def prec_kw(prec):
+    """BatchedMLP keywords of a test's precision label: "f16x2" runs the row-tile float16 kernel of round 6 (mlp3_rt16_kernel: layer 3 on the
+    vector ALU for nout <= 4, on the matrix cores otherwise), "f16x2-split" the split kernel of rounds 2-5."""
+    return dict(precision="f16x2", split_kernel=True) if prec == "f16x2-split" else dict(precision=prec)
+
+
+def policy_kw(config):
+    """BatchedMLP keywords (the constructor switches) of one of POLICY_CONFIGS."""
+    if config == "f32-w2-unpacked":
+        return dict(precision="f32", pack_w2=False)
+    if config == "f32-fragments":
+        return dict(precision="f32", pack_w2="fragments")
+    return prec_kw(config)
+
+
 def single_step_files():
     return sorted(glob.glob(os.path.join(GOLDEN, "single_step_*.npz")))
 

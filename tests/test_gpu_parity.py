@@ -34,10 +34,7 @@ def env_for(fx, E):
     return env
 
 
-def _prec_kw(prec):
-    """BatchedMLP keywords of a test's precision label: "f16x2" runs the row-tile float16 kernel of round 6 (mlp3_rt16_kernel: layer 3 on the
-    vector ALU for nout <= 4, on the matrix cores otherwise), "f16x2-split" the split kernel of rounds 2-5."""
-    return dict(precision="f16x2", split_kernel=True) if prec == "f16x2-split" else dict(precision=prec)
+_prec_kw = H.prec_kw            # (shared with tests/test_gpu_sampling.py)
 
 
 def host(t):
@@ -1098,10 +1095,8 @@ def test_policy_shape_fuzz_all_precisions(torch):
                else torch.cat([torch.tanh(y[..., :2]), torch.sigmoid(y[..., 2:])], -1)).numpy()
         tag = f"policy fuzz#{it} d={d} h1={h1} h2={h2} nout={nout} kind={kind} N={N} E={E}"
         # ("f32" = the row-tile stream of round 6 for d_in <= 14, else the fragment-packed layer 2; the other two layouts by name)
-        for prec in ("f32", "f32-fragments", "f32-w2-unpacked", "bf16x3", "f16x2", "f16x2-split", "bf16"):
-            pol = (BatchedMLP(*w, out_kind=kind, sample_kind=0, precision="f32", pack_w2=False) if prec == "f32-w2-unpacked"
-                   else BatchedMLP(*w, out_kind=kind, sample_kind=0, precision="f32", pack_w2="fragments") if prec == "f32-fragments"
-                   else BatchedMLP(*w, out_kind=kind, sample_kind=0, **_prec_kw(prec)))
+        for prec in H.POLICY_CONFIGS:
+            pol = BatchedMLP(*w, out_kind=kind, sample_kind=0, **H.policy_kw(prec))
             out = host(pol.forward(x.cuda()))
             if prec == "bf16":
                 H.assert_close(out, ref, f"{tag} {prec}", rtol=3e-2, atol=3e-2 * max(1.0, float(np.abs(ref).max())))
