@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""The reference's `benchmark_agent.py` on the MI355X-native stack: roll a trained actor out without learning and report the
+per-episode figures, the critic against the simulated return and the collision histogram.
+
+The reference runs 1500 episodes one after the other (benchmark_agent.py:53-118); here E envs run `rounds` fresh episodes
+each (E x rounds >= --episodes), every step of every env in one launch, and the tables are reduced on the device.
+
+    python examples/benchmark_agent.py --critics discrete-A2Ccritics.pth --actors discrete-A2Cactors.pth [--models models]
+    python examples/benchmark_agent.py --controller proportional            # the commented alternatives of :76-77
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import scalable_collision_avoidance_rl_amd.drone_env as drone_env          # was: import drone_env
+from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, TrainedAgent    # was: from SAC_agents import *
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--critics", default="discrete-A2Ccritics.pth")
+    ap.add_argument("--actors", default="discrete-A2Cactors.pth")
+    ap.add_argument("--models", default="models")
+    ap.add_argument("--controller", choices=["proportional", "gradient"], default=None)
+    ap.add_argument("--agents", type=int, default=None, help="default: the number of saved critics (8 with a controller)")
+    ap.add_argument("--episodes", type=int, default=1500)
+    ap.add_argument("--envs", type=int, default=512)
+    ap.add_argument("--precision", default="f32")
+    a = ap.parse_args()
+
+    if a.controller:
+        n_agents, actor, critic = a.agents or 8, a.controller, None
+    else:
+        agents = TrainedAgent(critics_name=a.critics, actors_name=a.actors, n_agents=a.agents or "auto", models_dir=a.models,
+                              precision=a.precision)                                                # benchmark_agent.py:47
+        n_agents, actor, critic = agents.n_agents, agents.actor, agents.critic
+    deltas = np.ones(n_agents) * 1                                                                  # :29
+    env = drone_env.drones(n_agents=n_agents, n_obstacles=0, grid=[5, 5], end_formation="O", deltas=deltas, simplify_zstate=True,
+                           n_envs=a.envs, auto_reset=True)                                          # :30
+    env.collision_weight = 0.2                                                                      # :31
+    rounds = -(-a.episodes // a.envs)
+    print("### Running Trained agent (no learning)")                                               # :48-50
+    print(f"Episodes = {rounds * a.envs} ({a.envs} envs x {rounds} rounds), max Time iterations = {drone_env.max_time_steps} "
+          f"(T = {drone_env.max_time_steps * drone_env.dt}s, dt = {drone_env.dt}s)")
+    print(f"N of agents = {env.n_agents}, collision weight b = {env.collision_weight}")
+
+    ev = Evaluator(env, actor, critic, gamma=0.99)
+    ev.run(rounds)
+    s = ev.summary()
+    print(f"Episodes {s['episodes']} - Average Reward/Collisions/Steps: {s['mean_return']:.1f}/{s['mean_collisions']:.2f}/"
+          f"{s['mean_length']:.1f}. True r={s['mean_true_return']:.1f}.")                          # :119-120
+    if s["mean_advantage"] is not None:
+        print("mean_T [G_t - V(z_t)] per agent: " + " ".join(f"{x:.3f}" for x in s["mean_advantage"]))   # :105, :143
+    # the reference's histogram has bins of two collisions starting at the smallest count seen (:150): counts[0], counts[1]
+    hist = np.asarray(s["collision_hist"], np.float64)
+    lo = int(np.flatnonzero(hist)[0]) if hist.any() else 0
+    pair = lambda j: hist[lo + 2 * j:lo + 2 * j + 2].sum() / max(hist.sum(), 1.0)
+    print(f"Runs with 0 coll. = {pair(0) * 100:.2f}%. 2 coll. = {pair(1) * 100:.2f}%")             # :151
+    print(f"(episodes without any collision: {s['zero_collision_share'] * 100:.2f}%)")
+
+
+if __name__ == "__main__":
+    main()

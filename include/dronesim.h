@@ -305,6 +305,30 @@ int dronesim_advantage(const float *G, const float *V, const int32_t *nbr_idx, c
 int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *nbr_idx, int per_neighbour, float *adv,
                                  int T, int E, int N, int K1, void *stream);
 
+/* Policy evaluation over a stored window (benchmark_agent.py:59-106, :148-156): the table of the FIRST episode of every
+ * env.  reward, true_reward, V, G [T][E][N] float32, n_coll [T][E] int32, done [T][E] uint8 as the step launches write
+ * them.  L_e = 1 + min{t : done[t][e] != 0}, 0 when no step of the window ended an episode.
+ *   ep_len [E] int32                      L_e  (required)
+ *   ep_collisions [E] int32               sum_{t < L} n_coll[t][e]  (needs n_coll)
+ *   agent_return, agent_true_return [E][N] float64   sum_{t < L} of the float32 rewards, each widened to double first
+ *   ep_return, ep_true_return [E] float64 (1 / N) sum_i agent_return[e][i], agents in ascending order (:85-86, :98-99: the
+ *                                         sum over steps of mean(rewards)); each needs its agent_* array
+ *   G [T][E][N] float32                   the WHOLE window's Monte-Carlo returns, bit-identical to dronesim_returns
+ *   mean_adv [E][N] float64               (1 / L) sum_{t < L} ((double)G[t][e][i] - (double)V[t][e][i])  (:105; needs V)
+ * Every output but ep_len may be NULL; V may be NULL (and is not read without mean_adv); n_coll may be NULL without
+ * ep_collisions.  Envs with L_e = 0 get zeros everywhere except G.  Two launches on `stream` (the column scan, then one
+ * thread per env); no float atomics: results are bit-identical run to run.                                            */
+int dronesim_episode_eval(const float *reward, const float *true_reward, const int32_t *n_coll, const uint8_t *done,
+                          const float *V, float gamma, int32_t *ep_len, int32_t *ep_collisions,
+                          double *agent_return, double *agent_true_return, double *ep_return, double *ep_true_return,
+                          float *G, double *mean_adv, int T, int E, int N, void *stream);
+
+/* counts[min(v, n_bins)] += 1 for every e < E with values[e] = v >= 0 and (valid == NULL or valid[e] != 0): counts
+ * [n_bins + 1] int64, the last bin takes the overflow (the collision histogram of benchmark_agent.py:148-156).
+ * accumulate == 0: the kernel writes the counts itself (no memset); != 0: it adds to what is there.  One launch.    */
+int dronesim_histogram_i32(const int32_t *values, const uint8_t *valid, int E, int n_bins, int64_t *counts,
+                           int accumulate, void *stream);
+
 /* Batched per-agent policy / critic forward: N independent 3-layer MLPs, one per agent,
  * evaluated on x[E][N][d_in] in one launch on the matrix cores in exact float32.
  *   DiscreteSoftmaxNN  utils.py:255-309   d_in -> 300 relu -> 300 relu -> n_actions softmax; sample_kind 1

@@ -7,8 +7,9 @@ Importing the package needs neither a GPU nor the built library; constructing an
 environment needs both (no CPU fallback)."""
 from .drone_env import (DroneState, StepResult, clip_deltas, dim, drones, dt, formation_O, gradient_control,
                         lattice_divisions, max_time_steps, proportional_control, shard_range)
+from .evaluate import Evaluator, TrainedAgent
 from .learner import PPOLearner, SA2CLearner
 
 __all__ = ["drones", "DroneState", "StepResult", "dim", "dt", "max_time_steps", "formation_O",
            "clip_deltas", "lattice_divisions", "shard_range", "gradient_control", "proportional_control",
-           "SA2CLearner", "PPOLearner"]
+           "SA2CLearner", "PPOLearner", "Evaluator", "TrainedAgent"]

@@ -32,6 +32,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_mlp_forward_bf16x3", "dronesim_mlp_forward_f16x2", "dronesim_mlp_bf16x3_stages", "dronesim_mlp_rt_blocks", "dronesim_mlp_rt16_blocks", "dronesim_mlp_forward_f16x2_rt",
            "dronesim_mlp_grad_workspace", "dronesim_mlp_grad", "dronesim_adam_step",
            "dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo",
+           "dronesim_episode_eval", "dronesim_histogram_i32",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -153,6 +154,9 @@ def lib():
     L.dronesim_mlp_grad_ppo.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
     for name in ("dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo"):
         getattr(L, name).restype = C.c_int
+    L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
+    L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+    L.dronesim_episode_eval.restype = L.dronesim_histogram_i32.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

@@ -497,14 +497,16 @@ class drones:
         not depend on the sharding or on how T is split into calls.  ``record_actions`` adds ``actions [T,E,N,2]``."""
         return self.rollout(None, with_pre=with_pre, _random=(int(T), bool(record_actions)))
 
-    def rollout_control(self, kind: str, T, u_max: float = 1.0, record_actions=False, with_pre=False):
+    def rollout_control(self, kind: str, T, u_max: float = 1.0, record_actions=False, with_pre=False, into=None):
         """T fused steps in CLOSED LOOP with a classical controller (the reference's control_test.py:30-45 loop,
         ``proportional_control`` / ``gradient_control`` feeding ``step``): the action of step s is computed inside the
         launch from the positions the env holds before step s -- what ``control(kind, u_max)`` returns on them -- so a
         step costs one launch share instead of two launches.  ``kind`` = "proportional" or "gradient".  Returns the
         dict of `rollout()`; ``record_actions`` adds ``actions [T,E,N,2]`` (replayed through ``rollout(actions)`` they
         reproduce every output bit for bit).  With ``auto_reset`` an env that finishes at step s acts at step s + 1 on
-        its new episode's positions.  Results do not depend on how T is split into calls."""
+        its new episode's positions.  Results do not depend on how T is split into calls.  ``into`` (a
+        `rollout_buffer.RolloutStorage` of exactly T steps): the launch fills the storage's own tensors -- the whole window, with
+        the env's current observation as ``z_pre[0]`` -- instead of new ones, and the dict returned holds views of them."""
         codes = {"proportional": self._native.CONTROL_PROPORTIONAL, "gradient": self._native.CONTROL_GRADIENT}
         if kind not in codes:
             raise ValueError(f"kind must be 'proportional' or 'gradient', got {kind!r}")
@@ -514,9 +516,9 @@ class drones:
         T = int(T)
         if T < 0:
             raise ValueError("T < 0")
-        return self.rollout(None, with_pre=with_pre, _control=(T, bool(record_actions), codes[kind], u_max))
+        return self.rollout(None, with_pre=with_pre, _control=(T, bool(record_actions), codes[kind], u_max), _into=into)
 
-    def rollout(self, actions, with_pre=False, _random=None, _control=None):
+    def rollout(self, actions, with_pre=False, _random=None, _control=None, _into=None):
         """T fused steps in one launch with the actions known up front (RandomAgent-style rollouts,
         SAC_agents.py:9-22 + train_problem.py:82-107).  ``actions``: ``[T,E,N,2]`` float32 device tensor.
         Returns a dict of ``[T, ...]`` tensors with every per-step output of step(); ``with_pre=True`` adds
@@ -528,23 +530,32 @@ class drones:
         E, N, K1, c = self.n_envs, self.n_agents, self.k_closest + 1, self.c
         random_actions = _random is not None
         in_kernel = _random if random_actions else _control          # (T, record the actions, ...): no action pool
+        if _into is not None and (_into.env is not self or in_kernel is None or _into.T != in_kernel[0]
+                                  or (in_kernel[1] and _into.actions is None)):
+            raise ValueError("into= needs a RolloutStorage of this env with exactly T steps (and an actions tensor when they are recorded)")
         if in_kernel is not None:
             T = in_kernel[0]
-            act = torch.empty(T, E, N, 2, dtype=torch.float32, device=self.device) if in_kernel[1] else None
+            act = None if not in_kernel[1] else _into.actions if _into is not None else torch.empty(T, E, N, 2, dtype=torch.float32, device=self.device)
         else:
             act = actions.to(device=self.device, dtype=torch.float32).contiguous()
             T = act.shape[0]
             if tuple(act.shape) != (T, E, N, 2):
                 raise ValueError(f"actions must be [T,{E},{N},2], got {tuple(act.shape)}")
         f32 = dict(dtype=torch.float32, device=self.device)
-        out = dict(reward=torch.empty(T, E, N, **f32), true_reward=torch.empty(T, E, N, **f32),
-                   z=torch.empty(T, E, N, K1 * c, **f32),
-                   nbr_idx=torch.empty(T, E, N, K1, dtype=torch.int32, device=self.device),
-                   n_coll=torch.empty(T, E, dtype=torch.int32, device=self.device),
-                   done=torch.empty(T, E, dtype=torch.uint8, device=self.device))
+        if _into is not None:
+            out = dict(reward=_into.reward, true_reward=_into.true_reward, z=_into.z, nbr_idx=_into.nbr_idx,
+                       n_coll=_into.n_coll, done=_into.done)
+        else:
+            out = dict(reward=torch.empty(T, E, N, **f32), true_reward=torch.empty(T, E, N, **f32),
+                       z=torch.empty(T, E, N, K1 * c, **f32),
+                       nbr_idx=torch.empty(T, E, N, K1, dtype=torch.int32, device=self.device),
+                       n_coll=torch.empty(T, E, dtype=torch.int32, device=self.device),
+                       done=torch.empty(T, E, dtype=torch.uint8, device=self.device))
         if not self.batched:
             self._push_host_state()
         self._rebind_home()
+        if _into is not None:                             # the observation the first action is based on: z_pre[0] of the storage
+            _into.zbuf[0].copy_(self.z); _into.nbrbuf[0].copy_(self.nbr_idx)
         p = self._params()
         z0, nb0 = (self.z.clone(), self.nbr_idx.clone()) if with_pre else (None, None)
         # the rollout kernels address the terminal-observation buffers per STEP ([T][E][N]... like z): a ctl of this

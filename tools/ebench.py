@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Developer benchmark of the evaluation layer (csrc/evaluate.hip, evaluate.py), device events around hipGraph replays:
+
+  1. `dronesim_episode_eval` on a stored window (with and without V; G written) next to its yardstick, `dronesim_returns` on
+     the same rewards in the same session: the scan moves 16 B per element (12 B without V) against the yardstick's 8 B;
+  2. one `Evaluator` round (softmax-16 actor + critic, f16x2) next to the bare loop of examples/rollout_loop.py part 2 (b)
+     without the evaluation.
+
+    python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--out profiles/ebench.jsonl] [--skip-round]
+Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from scalable_collision_avoidance_rl_amd import _native, drones
+from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, episode_eval
+from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+
+
+def gtime(fn, calls=8, reps=9):
+    """Median microseconds per call over `reps` replays of a graph of `calls` calls."""
+    fn(); torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            fn()
+    g.replay(); torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); g.replay(); b.record(); torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3 / calls)
+    return float(np.median(ts)), float(np.min(ts))
+
+
+def kernels(T, E, N, emit):
+    dev = "cuda:0"
+    r, tr, V = (torch.randn(T, E, N, device=dev) for _ in range(3))
+    n_coll = torch.randint(0, 3, (T, E), device=dev, dtype=torch.int32)
+    done = torch.zeros(T, E, dtype=torch.uint8, device=dev); done[-1] = 1
+    done[torch.randint(0, T, (E,), device=dev), torch.arange(E, device=dev)] = 1
+    G = torch.empty_like(r)
+    lib = _native.lib()
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    us_ret, lo_ret = gtime(lambda: _native.check(lib.dronesim_returns(r.data_ptr(), done.data_ptr(), 0.99, G.data_ptr(), T, E, N, stream()), "returns"))
+    emit(dict(what="dronesim_returns", T=T, E=E, N=N, us=us_ret, us_min=lo_ret, bytes_per_element=8, tb_s=r.numel() * 8 / 1e6 / us_ret))
+    full = episode_eval(r, tr, n_coll, done, V, 0.99)
+    for name, v, nbytes in (("dronesim_episode_eval", V, 16), ("dronesim_episode_eval, V = NULL", None, 12)):
+        out = {k: x for k, x in full.items() if v is not None or k != "mean_adv"}
+        us, lo = gtime(lambda: episode_eval(r, tr, n_coll, done, v, 0.99, out=out))
+        emit(dict(what=name, T=T, E=E, N=N, us=us, us_min=lo, bytes_per_element=nbytes, tb_s=r.numel() * nbytes / 1e6 / us,
+                  yardstick_us=us_ret, expected_us=us_ret * nbytes / 8, allowed_us=us_ret * nbytes / 8 * 1.25,
+                  within_allowance=bool(us <= us_ret * nbytes / 8 * 1.25)))
+    tables = {k: x for k, x in full.items() if k != "G"}                              # what Evaluator asks for: G stays in registers
+    us, lo = gtime(lambda: episode_eval(r, tr, n_coll, done, V, 0.99, out=tables))
+    emit(dict(what="dronesim_episode_eval, G = NULL", T=T, E=E, N=N, us=us, us_min=lo, bytes_per_element=12, tb_s=r.numel() * 12 / 1e6 / us,
+              yardstick_us=us_ret))
+
+
+def one_round(E, N, emit):
+    G = 28.0 if N == 64 else max(6.0, 0.45 * N)
+    g = torch.Generator().manual_seed(0)
+    rnd = lambda *s: (torch.rand(*s, generator=g) * 2 - 1) * 0.2
+    wa = [rnd(N, 6, 300), rnd(N, 300), rnd(N, 300, 300), rnd(N, 300), rnd(N, 300, 16), rnd(N, 16)]
+    wc = [rnd(N, 6, 200), rnd(N, 200), rnd(N, 200, 200), rnd(N, 200), rnd(N, 200, 1), rnd(N, 1)]
+    env = drones(N, 0, [G, G], "O", deltas=np.ones(N), simplify_zstate=True, n_envs=E, seed=0, auto_reset=True)
+    actor = BatchedMLP(*wa, 1, 1, device=env.device, seed=1, precision="f16x2")
+    critic = BatchedMLP(*wc, 0, 0, device=env.device, precision="f16x2")
+    ev = Evaluator(env, actor, critic)
+    ev.run(1)
+    us_round, lo_round = gtime(lambda: ev.run(1), calls=1, reps=5)
+    us_loop, lo_loop = gtime(ev.rollout, calls=1, reps=5)
+    s = ev.summary()
+    emit(dict(what="Evaluator round (softmax-16 + critic, f16x2)", T=ev.T, E=E, N=N, us=us_round, us_min=lo_round, bare_loop_us=us_loop,
+              bare_loop_us_min=lo_loop, evaluation_us=us_round - us_loop, agent_steps_per_s=E * N * ev.T / (us_round * 1e-6),
+              mean_return=s["mean_return"], mean_length=s["mean_length"], zero_collision_share=s["zero_collision_share"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=200)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--agents", type=int, default=64)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--skip-round", action="store_true")
+    a = ap.parse_args()
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+    kernels(a.T, a.envs, a.agents, emit)
+    if not a.skip_round:
+        one_round(a.envs, a.agents, emit)
+
+
+if __name__ == "__main__":
+    main()
