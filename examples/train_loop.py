@@ -5,9 +5,14 @@ batched `SA2CAgents.train_NN` (SAC_agents.py:280-357): critic MSE + clip + Adam,
 actor loss + clip + Adam, for all N agents' networks at once in HIP.
 
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
+                                  [--lam X] [--window T]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
+
+``--lam X`` (off by default) switches either learner to bootstrapped lambda-returns, TD(lambda) / GAE: the envs reset
+themselves, so a window cuts the episodes that started inside it, and without a bootstrap from the value of the observation
+after the window's last step their returns are truncated.  With it a window may be shorter than an episode (``--window T``).
 """
 import argparse
 import os
@@ -44,8 +49,10 @@ def main():
     ap.add_argument("--episodes", type=int, default=5)
     ap.add_argument("--learner", choices=("sa2c", "ppo"), default="sa2c")
     ap.add_argument("--epochs", type=int, default=10, help="epochs per window (--learner ppo)")
+    ap.add_argument("--lam", type=float, default=None, help="bootstrapped lambda-returns with this lambda in [0, 1] (default: off)")
+    ap.add_argument("--window", type=int, default=200, help="steps per rollout window (default: one episode, 200)")
     args = ap.parse_args()
-    N, E, T, dev = args.agents, args.envs, 200, "cuda:0"
+    N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
     env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=dev, seed=1, auto_reset=True)
     d_in = env.local_state_space
@@ -55,9 +62,10 @@ def main():
     storage = RolloutStorage(env, T, actions=True)
     # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
     if args.learner == "ppo":
-        learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0)
+        learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
+                             lam=args.lam)
     else:
-        learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0)
+        learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam)
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for ep in range(args.episodes):
         storage.begin()

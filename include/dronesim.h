@@ -300,6 +300,21 @@ int dronesim_episode_stats(const float *reward, const float *true_reward, const 
  *                       nbr_idx as for dronesim_advantage; independent of `done` (nothing runs along t).  */
 int dronesim_returns(const float *reward, const uint8_t *done, float gamma, float *G,
                      int T, int E, int N, void *stream);
+/*   dronesim_lambda_returns   bootstrapped lambda-returns, TD(lambda) / GAE(gamma, lambda), for windows that cut episodes
+ *                       (the reference trains on whole episodes and has no such function).  V [T+1][E][N]: V[t] the value of
+ *                       the observation step t acted on, V[T] that of the observation after the last step.  Per column,
+ *                       backwards from Gn = V[T]:
+ *                         G[t] = r[t]                                                  where done[t] != 0 (terminal: no
+ *                                                                                      bootstrap across an episode end)
+ *                         G[t] = r[t] + gamma ((1 - lam) V[t+1] + lam Gn)              otherwise;        Gn = G[t]
+ *                         A[t] = G[t] - V[t]                                           (GAE; G = A + V is the lambda-return)
+ *                       reward, G, A [T][E][N]; `done` [T][E] uint8, may be NULL; G or A may be NULL, not both.  lam in
+ *                       [0, 1]: 0 is the one-step TD target, 1 Monte-Carlo with a bootstrap at the window's end -- with
+ *                       lam = 1 the columns of envs with done[T-1] != 0 are bit-identical to dronesim_returns.  EINVAL for a
+ *                       NULL reward / V, both outputs NULL, T < 0, E < 0, N < 1, lam outside [0, 1], NaN lam or gamma;
+ *                       T = 0 or E = 0 enqueues nothing.  One kernel launch (no memset nodes: graph-capturable).   */
+int dronesim_lambda_returns(const float *reward, const uint8_t *done, const float *V, float gamma, float lam, float *G, float *A,
+                            int T, int E, int N, void *stream);
 int dronesim_advantage(const float *G, const float *V, const int32_t *nbr_idx, const uint8_t *done,
                        float gamma, float *w, int T, int E, int N, int K1, void *stream);
 int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *nbr_idx, int per_neighbour, float *adv,

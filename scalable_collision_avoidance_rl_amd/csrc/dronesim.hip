@@ -307,6 +307,86 @@ __global__ void __launch_bounds__(256) returns_kernel(const float *__restrict__ 
     else returns_scan<false, V>(reward, done, gamma, G, T, E, EN, col, e, e_first, de, act);
 }
 
+// Bootstrapped lambda-returns (TD(lambda) / GAE): returns_kernel's scan with one more input stream -- the values Vv [T+1][E][N],
+// Vv[t] the value of the observation step t acted on, Vv[T] that of the observation after the window -- and up to two outputs:
+//     G[t] = done[t] ? r[t] : r[t] + gamma ((1 - lam) Vv[t+1] + lam G[t+1]),   G[T] = Vv[T];      A[t] = G[t] - Vv[t]
+// Vv[t+1] of step t is Vv[t] of step t + 1: every row is loaded once and carried in `vn`.  Same staging as returns_scan (the
+// next stage's rows -- now two streams -- are requested before the current stage folds), same done-flag fetch, same column
+// quadruples, non-temporal loads and stores.  At lam = 1 the mix fmaf(1, Gn, 0 * Vn) is Gn itself, so the step is
+// returns_scan's fmaf(Gn, gamma, r) and a column whose window ends with `done` gets dronesim_returns' bits.
+template <int V> struct LamStage {
+    typename RetVec<V>::type r[kRetStageT], v[kRetStageT];
+    DoneStage ds;
+    bool last[kRetStageT];
+};
+
+template <bool COOP, int V>
+__device__ __forceinline__ void lambda_fetch(LamStage<V> &st, const float *__restrict__ reward, const float *__restrict__ Vv,
+                                             const uint8_t *__restrict__ done, size_t EN, size_t col, size_t e, size_t e_first,
+                                             int E, int T, int t0)
+{
+    typedef typename RetVec<V>::type vec;
+    if (COOP) st.ds.fetch(done, e_first, E, T, [&](int u) { return t0 - u; });
+#pragma unroll
+    for (int u = 0; u < kRetStageT; ++u) {
+        const int t = t0 - u;
+        st.r[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(reward + (size_t)t * EN + col)) : vec(0.0f);
+        st.v[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)t * EN + col)) : vec(0.0f);
+        if (!COOP) st.last[u] = done != nullptr && t >= 0 && done[(size_t)t * E + e] != 0;
+    }
+}
+
+template <bool COOP, int V>
+__device__ __forceinline__ void lambda_scan(const float *__restrict__ reward, const uint8_t *__restrict__ done,
+                                            const float *__restrict__ Vv, float gamma, float lam, float *__restrict__ G,
+                                            float *__restrict__ A, int T, int E, size_t EN, size_t col, size_t e,
+                                            size_t e_first, int de, bool act)
+{
+    typedef typename RetVec<V>::type vec;
+    const float oml = 1.0f - lam;
+    LamStage<V> cur, nxt;
+    vec vn = __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)T * EN + col));   // the bootstrap: Gn = Vv[T]
+    lambda_fetch<COOP, V>(cur, reward, Vv, done, EN, col, e, e_first, E, T, T - 1);
+    vec g = vn;
+    for (int t0 = T - 1; t0 >= 0; t0 -= kRetStageT) {
+        if (t0 - kRetStageT >= 0) lambda_fetch<COOP, V>(nxt, reward, Vv, done, EN, col, e, e_first, E, T, t0 - kRetStageT);
+#pragma unroll
+        for (int u = 0; u < kRetStageT; ++u) {
+            const int t = t0 - u;
+            if (t >= 0) {
+                const bool last = COOP ? cur.ds.get(de, u) : cur.last[u];
+                float *gp = reinterpret_cast<float *>(&g);
+                const float *rp = reinterpret_cast<const float *>(&cur.r[u]), *vp = reinterpret_cast<const float *>(&vn);
+#pragma unroll
+                for (int q = 0; q < V; ++q) gp[q] = last ? rp[q] : fmaf(fmaf(lam, gp[q], oml * vp[q]), gamma, rp[q]);
+                vn = cur.v[u];
+                if (act) {
+                    if (G) __builtin_nontemporal_store(g, reinterpret_cast<vec *>(G + (size_t)t * EN + col));
+                    if (A) __builtin_nontemporal_store(g - vn, reinterpret_cast<vec *>(A + (size_t)t * EN + col));
+                }
+            }
+        }
+        cur = nxt;
+    }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) lambda_returns_kernel(const float *__restrict__ reward, const uint8_t *__restrict__ done,
+                                                             const float *__restrict__ Vv, float gamma, float lam,
+                                                             float *__restrict__ G, float *__restrict__ A, int T, int E, int N)
+{
+    const size_t EN = (size_t)E * N;
+    const size_t col0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    const bool act = col0 < EN;                               // (no early exit: the flag fetch is a wave operation)
+    const size_t col = act ? col0 : EN - V;
+    const size_t e = col / N;                                 // (V == 4: N % 4 == 0, the four columns belong to one env)
+    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
+    const int de = (int)(e - e_first);
+    const bool coop = done != nullptr && __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
+    if (coop) lambda_scan<true, V>(reward, done, Vv, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
+    else lambda_scan<false, V>(reward, done, Vv, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
+}
+
 // K1C = K + 1 at compile time (3 for the reference's k_closest = 2: the neighbour triple is one 12-byte load), 0 = any
 // K1 at run time.  A stage of eight steps requests V and the neighbour ids of all eight first, then the G values they
 // name (slot 0 is the agent itself: a coalesced row read; the others fall into the same 4 N-byte row), then folds.
@@ -992,6 +1072,34 @@ int dronesim_returns(const float *reward, const uint8_t *done, float gamma, floa
     else
         hipLaunchKernelGGL(returns_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                            reward, done, gamma, G, T, E, N);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+int dronesim_lambda_returns(const float *reward, const uint8_t *done, const float *V, float gamma, float lam, float *G, float *A,
+                            int T, int E, int N, void *stream)
+{
+    if (!reward || !V) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: reward or V is NULL");
+    if (!G && !A) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: G and A are both NULL");
+    if (T < 0 || E < 0 || N < 1) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: bad T, E or N");
+    if (!(lam >= 0.0f && lam <= 1.0f)) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: lam must be in [0, 1]");
+    if (gamma != gamma) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: gamma is NaN");
+    if (T == 0 || E == 0) return DRONESIM_OK;
+    const size_t cols = (size_t)E * N;
+    // column quadruples as in dronesim_returns: every row of the four [.][E N] arrays 16-byte aligned, agents in fours, and
+    // from its lower bound of 262144 columns (one quadruple wave per SIMD).  The upper bound is lower here: with two staged
+    // streams the quadruple kernel holds 169 VGPRs = two waves per SIMD, so all quadruple waves are resident at once only
+    // below 2 x 1024 x 64 x 4 = 524288 columns; from there on one column per thread (66 VGPRs, seven waves per SIMD)
+    const uintptr_t align = reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(G) |
+                            reinterpret_cast<uintptr_t>(A);
+    const bool v4 = (N % 4) == 0 && (align & 15u) == 0 && cols >= 262144 && cols < 524288;
+    if (v4)
+        hipLaunchKernelGGL(lambda_returns_kernel<4>, dim3((unsigned)((cols / 4 + 255) / 256)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), reward, done, V, gamma, lam, G, A, T, E, N);
+    else
+        hipLaunchKernelGGL(lambda_returns_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), reward, done, V, gamma, lam, G, A, T, E, N);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
     return DRONESIM_OK;

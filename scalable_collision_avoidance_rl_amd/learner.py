@@ -9,6 +9,8 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
   PPOLearner      dronesim_mlp_logp, dronesim_neighbour_advantage, dronesim_mlp_grad_ppo
                                        `SPPOAgents.train` (SAC_agents.py:410-573): clipped probability ratio, `epochs`
                                        critic-and-actor steps per window
+  lam= of both    dronesim_lambda_returns   bootstrapped lambda-returns (TD(lambda) / GAE) from the critic over the storage's
+                                       T+1-slot observation ring, for windows that cut episodes (default off)
 
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
@@ -235,6 +237,38 @@ class BatchedAdam:
         return norm
 
 
+def _check_lam(lam):
+    """``lam=None`` (Monte-Carlo returns inside the window, the reference's rule) or a number in [0, 1]."""
+    if lam is None:
+        return None
+    from .rollout_buffer import check_lam
+    return check_lam(lam)
+
+
+def _ring(storage, T):
+    """The T+1-slot observation ring the bootstrapped returns need (`RolloutStorage.z_all`)."""
+    ring = getattr(storage, "z_all", None)
+    if ring is None:
+        raise ValueError("lam needs the storage's observation ring `z_all` [T+1,E,N,d] (RolloutStorage.z_all: z_pre plus the "
+                         "observation after the window's last step); this storage has none")
+    if ring.shape[0] != T + 1 or tuple(ring.shape[1:]) != tuple(storage.z_pre.shape[1:]) or not ring.is_contiguous():
+        raise ValueError(f"storage.z_all must be a contiguous [T+1,E,N,d] = {(T + 1,) + tuple(storage.z_pre.shape[1:])} tensor, "
+                         f"got {tuple(ring.shape)}")
+    return ring
+
+
+def _lambda_returns(learner, storage, Vall, G):
+    """`dronesim_lambda_returns` of the stored rewards with the values of all T+1 ring slots, into ``G``."""
+    import torch
+    from . import _native
+    T, E, N = learner._shape
+    with torch.cuda.device(learner.critic.device):
+        rc = _native.lib().dronesim_lambda_returns(storage.reward.data_ptr(), storage.done.data_ptr(), Vall.data_ptr(),
+                                                   learner.gamma, learner.lam, G.data_ptr(), None, T, E, N,
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_lambda_returns")
+
+
 class SA2CLearner:
     """`SA2CAgents.train_NN` (SAC_agents.py:280-357) over a `RolloutStorage` window of E envs, T steps:
 
@@ -251,16 +285,32 @@ class SA2CLearner:
     shape; after that the learner allocates nothing itself, BUT every update calls `BatchedMLP.refresh_weights`, whose
     re-packing of the forward images (e.g. `pack_f32_rowtile_stream`) makes temporary tensors through torch's caching
     allocator -- served from its cache eagerly, and from the graph's private pool when captured.  So the issue's "allocates
-    nothing after the first call" holds for the learner's buffers, not for those packing temporaries."""
+    nothing after the first call" holds for the learner's buffers, not for those packing temporaries.
 
-    def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None):
+    ``lam`` chooses the critic target and the G of the advantage:
+
+      ``lam=None``  (default) the steps above, the reference's rule: Monte-Carlo returns of the rewards INSIDE the window.
+                    Right when the window holds whole episodes; a window that cuts an episode (auto_reset, or T below the
+                    episode length) truncates that episode's returns to the rewards the window happens to hold.
+      ``lam=1.0``   Monte-Carlo with a bootstrap at the window's end: G[T-1] = r + gamma V(z after the window).  Not the
+                    same as None; the two agree bit for bit on the columns whose window ends with ``done``.
+      ``lam<1``     TD(lambda): G[t] = r[t] + gamma ((1 - lam) V(z[t+1]) + lam G[t+1]); 0 is the one-step target.
+
+    With a ``lam`` step 1 becomes: 1a. V of the PRE-update critic over all T+1 slots of the storage's observation ring
+    (``storage.z_all``); 1b. G = `dronesim_lambda_returns` of it (an episode end is terminal: nothing is carried across
+    ``done``, and the new episode's values do not leak into the old one); 1c. the critic step on target G.  Steps 2 and 3 are
+    unchanged (V from the POST-update critic over ``z_pre``, `dronesim_advantage` with this G).  Cost: one more critic
+    forward over (T+1) E rows and one scan.  Out of scope: a time-limit end (t >= 199) is terminal here as in the reference,
+    not a truncation to bootstrap from ``z_final`` -- the storage does not record which kind of end a ``done`` was."""
+
+    def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
             raise ValueError("the actor must be a softmax (out_kind 1) or Gaussian (out_kind 2) BatchedMLP")
         if (actor.n_agents, actor.d_in) != (critic.n_agents, critic.d_in):
             raise ValueError("actor and critic must have the same agents and inputs")
-        self.actor, self.critic, self.gamma = actor, critic, float(gamma)
+        self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
@@ -269,6 +319,8 @@ class SA2CLearner:
     def _prepare(self, storage):
         import torch
         T, E, N = storage.reward.shape
+        if self.lam is not None:
+            _ring(storage, T)
         if self._shape == (T, E, N):
             return
         if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
@@ -279,6 +331,8 @@ class SA2CLearner:
         self.G = torch.empty(T, E, N, device=dev)
         self.V = torch.empty(T * E, N, 1, device=dev)
         self.w = torch.empty(T, E, N, device=dev)
+        if self.lam is not None:
+            self.V_all = torch.empty((T + 1) * E, N, 1, device=dev)      # the pre-update critic over the whole ring
         self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
         self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
         self._shape = (T, E, N)
@@ -290,10 +344,14 @@ class SA2CLearner:
         T, E, N = self._shape
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         x = storage.z_pre
-        with torch.cuda.device(self.critic.device):
-            rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
-                                      T, E, N, stream)
-        _native.check(rc, "dronesim_returns")
+        if self.lam is None:
+            with torch.cuda.device(self.critic.device):
+                rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
+                                          T, E, N, stream)
+            _native.check(rc, "dronesim_returns")
+        else:       # bootstrapped lambda-returns from the pre-update critic over all T+1 ring slots
+            self.critic.forward(storage.z_all.view((T + 1) * E, N, -1), out=self.V_all)
+            _lambda_returns(self, storage, self.V_all, self.G)
         # critic (SAC_agents.py:304-324)
         cg, closs = self._critic_grad.run(x, 1.0 / (T * E), target=self.G)
         cnorm = self.critic_opt.step(cg)
@@ -341,12 +399,19 @@ class PPOLearner:
     them); no host synchronisation; the HIP entry points enqueue kernels only (no memset nodes); step counters in device
     memory -- a rollout window and the update can be captured in one ``torch.cuda.graph`` whose replays equal the eager
     sequence.  The forward images are re-packed (`BatchedMLP.refresh_weights`, with the temporaries noted at `SA2CLearner`)
-    once per network per call, after the last epoch: the epochs themselves read the plain weight arrays."""
+    once per network per call, after the last epoch: the epochs themselves read the plain weight arrays.
+
+    ``lam`` as for `SA2CLearner`: ``None`` (default) is step 1 as written, Monte-Carlo returns inside the window; a number in
+    [0, 1] widens step 2's once-per-window critic forward to all T+1 slots of ``storage.z_all`` and takes
+    G = `dronesim_lambda_returns` of it (1.0: Monte-Carlo plus a bootstrap from the value after the window's last step,
+    equal to None bit for bit on columns whose window ends with ``done``; below 1: TD(lambda)); the first T E rows of that
+    forward are step 2's V.  No extra forward, epochs unchanged.  An episode end is terminal, time-limit ends included (the
+    reference's rule; bootstrapping truncations from ``z_final`` is out of scope)."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
-                 baseline="once", rows_per_chunk=None):
+                 baseline="once", rows_per_chunk=None, lam=None):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -359,7 +424,7 @@ class PPOLearner:
             raise ValueError("clip_eps must be in (0, 1)")
         if baseline not in self.BASELINES:
             raise ValueError(f"baseline must be one of {self.BASELINES}")
-        self.actor, self.critic, self.gamma = actor, critic, float(gamma)
+        self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
         self.epochs, self.clip_eps, self.baseline = int(epochs), float(clip_eps), baseline
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
@@ -371,13 +436,19 @@ class PPOLearner:
         if getattr(storage, "actions", None) is None:
             raise ValueError("the learner needs a storage with actions")
         T, E, N = storage.reward.shape
+        if self.lam is not None:
+            _ring(storage, T)
         if self._shape == (T, E, N):
             return
         if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
             raise ValueError("the storage's agents / observation width do not match the networks")
         dev = self.critic.device
         self.G = torch.empty(T, E, N, device=dev)
-        self.V = torch.empty(T * E, N, 1, device=dev)
+        if self.lam is None:
+            self.V = torch.empty(T * E, N, 1, device=dev)
+        else:                                                            # the critic over the whole ring; V = its first T E rows
+            self.V_all = torch.empty((T + 1) * E, N, 1, device=dev)
+            self.V = self.V_all[:T * E]
         self.adv = torch.empty(T, E, N, device=dev)
         self.logp_old = torch.empty(T, E, N, device=dev)
         self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
@@ -394,13 +465,18 @@ class PPOLearner:
         T, E, N = self._shape
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         x, act, nbr = storage.z_pre, storage.actions, storage.nbr_pre
-        with torch.cuda.device(self.critic.device):
-            rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
-                                      T, E, N, stream)
-        _native.check(rc, "dronesim_returns")
+        if self.lam is None:
+            with torch.cuda.device(self.critic.device):
+                rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
+                                          T, E, N, stream)
+            _native.check(rc, "dronesim_returns")
         # the old policy's log-probabilities and the advantage from the pre-update critic, once per window (:484-501, :512-513)
         self._actor_grad.logp(x, act, self.logp_old)
-        self.critic.forward(x.view(T * E, N, -1), out=self.V)
+        if self.lam is None:
+            self.critic.forward(x.view(T * E, N, -1), out=self.V)
+        else:       # the same forward over all T+1 ring slots; the bootstrapped lambda-returns of it
+            self.critic.forward(storage.z_all.view((T + 1) * E, N, -1), out=self.V_all)
+            _lambda_returns(self, storage, self.V_all, self.G)
         with torch.cuda.device(self.critic.device):
             rc = lib.dronesim_neighbour_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(),
                                                   int(self.baseline == "per_neighbour"), self.adv.data_ptr(), T, E, N,

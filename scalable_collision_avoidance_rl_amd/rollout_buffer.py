@@ -7,9 +7,12 @@ called at train_problem.py:96) and scans them per agent at the end of the episod
                                                `drones.step(act, into=(storage, t))` hands slot t's addresses to
                                                `dronesim_step_ex`, so storing a transition costs no launch and no copy
   mc_returns           SAC_agents.py:304-307   G[t] = r[t] + gamma * G[t+1]
+  lambda_returns       (no reference line)     TD(lambda) / GAE with a bootstrap from the value after the window's last step:
+                                               G[t] = r[t] + gamma ((1 - lam) V[t+1] + lam G[t+1]), A = G - V
   neighbour_advantage  SAC_agents.py:333-351   gamma^t / N * sum_{j in Ni[t]} (G_j[t] - V_i[t])
 
-The reductions run in the HIP library (dronesim_returns / dronesim_advantage); there is no CPU fallback."""
+The reductions run in the HIP library (dronesim_returns / dronesim_lambda_returns / dronesim_advantage); there is no CPU
+fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -77,6 +80,8 @@ class RolloutStorage:
     nbr_pre = property(lambda self: self.nbrbuf[:self.T])
     z = property(lambda self: self.zbuf[1:])                 # raw post-step observation (new episode's first one after a reset)
     nbr_idx = property(lambda self: self.nbrbuf[1:])
+    z_all = property(lambda self: self.zbuf)                 # all T+1 ring slots: z_all[T] is the observation after the window
+    nbr_all = property(lambda self: self.nbrbuf)
 
     def begin(self):
         """Start (or restart) filling at slot 0: the env's current observation becomes ring slot 0 (ONE copy per T
@@ -127,6 +132,11 @@ class RolloutStorage:
         """Monte-Carlo returns of the stored rewards, restarting at episode ends (`mc_returns`)."""
         return mc_returns(self.true_reward if true_rewards else self.reward, gamma, self.done)
 
+    def lambda_returns(self, V, gamma, lam=1.0, true_rewards=False, want_adv=False):
+        """Bootstrapped lambda-returns of the stored rewards (`lambda_returns`): ``V [T+1,E,N]`` are the critic's values of
+        all ring slots, e.g. ``critic.forward(st.z_all.view((T+1)*E, N, -1)).view(T+1, E, N)``."""
+        return lambda_returns(self.true_reward if true_rewards else self.reward, V, gamma, lam, self.done, want_adv)
+
     def advantage(self, V, gamma, G=None):
         """Actor-loss weights from the stored pre-step neighbour lists (`neighbour_advantage`)."""
         G = self.returns(gamma) if G is None else G
@@ -171,6 +181,42 @@ def mc_returns(reward, gamma: float, done=None):
                                   G.data_ptr(), T, E, N, C.c_void_p(torch.cuda.current_stream().cuda_stream))
     _native.check(rc, "dronesim_returns")
     return G
+
+
+def check_lam(lam):
+    """``lam`` as a float in [0, 1], else ValueError (numbers only: no strings, no NaN)."""
+    import numbers
+    if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"lam must be a number in [0, 1], got {lam!r}")
+    return float(lam)
+
+
+def lambda_returns(reward, V, gamma: float, lam: float = 1.0, done=None, want_adv=False):
+    """TD(lambda) returns of every (env, agent) column of ``reward [T,E,N]`` for a window that may cut episodes:
+    ``V [T+1,E,N]`` holds the value of the observation each step acted on and, in its last slot, of the observation after
+    the last step, from which the scan bootstraps; ``done [T,E]`` (optional) marks steps that ended an episode -- terminal,
+    nothing is carried across them.  ``lam = 1`` is Monte-Carlo plus the bootstrap at the window's end, ``lam = 0`` the
+    one-step target.  Returns ``G``, or ``(G, A)`` with the GAE(gamma, lam) advantage ``A = G - V[:T]`` when ``want_adv``."""
+    import torch
+    from . import _native
+    lib = _native.lib()
+    lam = check_lam(lam)
+    if torch.is_tensor(reward) and torch.is_tensor(V) and (
+            reward.dim() != 3 or tuple(V.shape) != (reward.shape[0] + 1,) + tuple(reward.shape[1:])):
+        raise ValueError(f"reward must be [T,E,N] and V [T+1,E,N] (one more leading slot: the value after the last step), "
+                         f"got {tuple(reward.shape)} and {tuple(V.shape)}")
+    reward = _prep(reward, torch.float32)
+    T, E, N = reward.shape
+    V = _prep(V, torch.float32, (T + 1, E, N))
+    d = None if done is None else _prep(done, torch.uint8, (T, E))
+    G = torch.empty_like(reward)
+    A = torch.empty_like(reward) if want_adv else None
+    with torch.cuda.device(reward.device):
+        rc = lib.dronesim_lambda_returns(reward.data_ptr(), None if d is None else d.data_ptr(), V.data_ptr(), float(gamma), lam,
+                                         G.data_ptr(), None if A is None else A.data_ptr(), T, E, N,
+                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_lambda_returns")
+    return (G, A) if want_adv else G
 
 
 def neighbour_advantage(G, V, nbr_idx, gamma: float, done=None):

@@ -2,7 +2,13 @@
 """Learner micro-benchmark (developer tool; bench.py stays the project's yardstick): one `SA2CLearner.train` per shape --
 or, with ``--learner ppo``, one `PPOLearner.train` of ``--epochs M`` epochs --, timed with device events after warm-up.
 
-    python tools/lbench.py [--configs c1,c3,c5] [--reps 3] [--warmup 1] [--learner {sa2c,ppo}] [--epochs M]
+    python tools/lbench.py [--configs c1,c3,c5] [--reps 3] [--warmup 1] [--learner {sa2c,ppo}] [--epochs M] [--lam X]
+    python tools/lbench.py --scans [--configs c3,c5] [--reps 9] [--out profiles/lambda_returns_lbench.jsonl]
+
+``--lam X`` times the learner with bootstrapped lambda-returns (one more ring slot of observations; off by default).
+``--scans`` times the learner-side scans alone instead: `dronesim_returns` (the yardstick) and `dronesim_lambda_returns`
+with G only and with G + A, on the same buffers in the same process, device events around ``--calls`` back-to-back calls
+after a warm-up, median and minimum over ``--reps`` repetitions, one JSON line each (appended to ``--out`` when given).
 
 A PPO epoch's cost is the marginal one, (t_3 - t_1) / 2 from runs at ``--epochs 1`` and ``--epochs 3``; the once-per-window
 part (returns, old log-probabilities, baseline, advantage) is t_1 less one epoch.
@@ -37,6 +43,61 @@ def mlp_flop(rows, d_in, h1, h2, nout, backward=True):
     return fwd + 2 * rows * (2 * h2 * nout + 2 * h1 * h2 + d_in * h1)
 
 
+def scans(args):
+    """The scans of a stored window [T][E][N] next to each other: bytes per element 8 (r in, G out), 12 (+ V in), 16 (+ A out)."""
+    import ctypes as C
+    import statistics
+
+    import torch
+    from scalable_collision_avoidance_rl_amd import _native
+    lib, dev = _native.lib(), "cuda:0"
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = []
+    for name in args.configs.split(","):
+        N, E, T, _ = CONFIGS[name]
+        g = torch.Generator(device=dev).manual_seed(0)
+        r = torch.randn(T, E, N, device=dev, generator=g)
+        V = torch.randn(T + 1, E, N, device=dev, generator=g)
+        done = (torch.rand(T, E, device=dev, generator=g) < 0.01).to(torch.uint8)
+        done[-1] = 1
+        G, A = torch.empty_like(r), torch.empty_like(r)
+        lam = 0.95 if args.lam is None else args.lam
+        calls = {"dronesim_returns": (8, lambda: lib.dronesim_returns(r.data_ptr(), done.data_ptr(), 0.99, G.data_ptr(), T, E, N, stream())),
+                 "dronesim_lambda_returns G": (12, lambda: lib.dronesim_lambda_returns(r.data_ptr(), done.data_ptr(), V.data_ptr(), 0.99, lam,
+                                                                                       G.data_ptr(), None, T, E, N, stream())),
+                 "dronesim_lambda_returns G+A": (16, lambda: lib.dronesim_lambda_returns(r.data_ptr(), done.data_ptr(), V.data_ptr(), 0.99, lam,
+                                                                                         G.data_ptr(), A.data_ptr(), T, E, N, stream()))}
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        base = None
+        for what, (bpe, fn) in calls.items():
+            for _ in range(max(1, args.warmup) * args.calls):
+                _native.check(fn(), what)
+            torch.cuda.synchronize()
+            us = []
+            for _ in range(args.reps):
+                ev[0].record()
+                for _ in range(args.calls):
+                    fn()
+                ev[1].record()
+                torch.cuda.synchronize()
+                us.append(ev[0].elapsed_time(ev[1]) * 1e3 / args.calls)
+            med, lo = statistics.median(us), min(us)
+            line = dict(what=what, config=name, N=N, E=E, T=T, lam=None if bpe == 8 else lam, us=round(med, 2), us_min=round(lo, 2),
+                        bytes_per_element=bpe, tb_s=round(r.numel() * bpe / 1e6 / med, 3), calls=args.calls, reps=args.reps)
+            if base is None:
+                base = med
+            else:       # the byte ratio to the yardstick plus 15 % (the longer dependent chain per step, run-to-run spread)
+                line.update(ratio=round(med / base, 3), expected_us=round(base * bpe / 8, 2), allowed_us=round(base * bpe / 8 * 1.15, 2),
+                            inside=bool(med <= base * bpe / 8 * 1.15))
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="c1,c3,c5")
@@ -45,6 +106,10 @@ def main():
     ap.add_argument("--learner", choices=("sa2c", "ppo"), default="sa2c")
     ap.add_argument("--epochs", type=int, default=1, help="epochs per PPOLearner.train (--learner ppo)")
     ap.add_argument("--stats", help="a rocprofv3 kernel_stats.csv to summarise instead of running")
+    ap.add_argument("--lam", type=float, default=None, help="bootstrapped lambda-returns with this lambda (default: off)")
+    ap.add_argument("--scans", action="store_true", help="time dronesim_returns / dronesim_lambda_returns instead of a learner")
+    ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per timed repetition (--scans)")
+    ap.add_argument("--out", help="append the JSON lines to this file")
     args = ap.parse_args()
     if args.stats:
         import csv
@@ -54,10 +119,13 @@ def main():
             print(json.dumps(dict(kernel=r["Name"][:60], calls=int(r["Calls"]), total_ms=round(float(r["TotalDurationNs"]) / 1e6, 3),
                                   share=round(float(r["TotalDurationNs"]) / tot, 4))))
         return
+    if args.scans:
+        return scans(args)
     import torch
     from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
     from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
     dev = "cuda:0"
+    lines = []
     for name in args.configs.split(","):
         N, E, T, kind = CONFIGS[name]
         d_in = 6
@@ -71,14 +139,18 @@ def main():
             aw, ak, (h1a, h2a, noa) = net(400, 400, 4), 2, (400, 400, 4)
             aw[4][:, :200, 2:] = 0; aw[4][:, 200:, :2] = 0
         actor, critic = BatchedMLP(*aw, ak, ak, device=dev), BatchedMLP(*net(200, 200, 1), 0, 0, device=dev)
-        x = (torch.rand(T, E, N, d_in, device=dev, generator=g) * 2 - 1) * 3
+        lam_kw = {} if args.lam is None else dict(lam=args.lam)
+        ring = (torch.rand(T + (args.lam is not None), E, N, d_in, device=dev, generator=g) * 2 - 1) * 3
+        x = ring[:T]
         a = torch.randint(0, 16, (T, E, N), device=dev, generator=g).float() * (2 * math.pi / 16)
         st = SimpleNamespace(z_pre=x, reward=torch.randn(T, E, N, device=dev, generator=g),
                              done=torch.zeros(T, E, dtype=torch.uint8, device=dev), actions=torch.stack([a.cos(), a.sin()], -1),
                              nbr_pre=torch.stack([torch.arange(N, device=dev).expand(T, E, N)] * 3, -1).int().contiguous())
         st.done[-1] = 1
+        if args.lam is not None:        # the T+1-slot observation ring the bootstrap reads (`RolloutStorage.z_all`)
+            st.z_all = ring
         ppo = args.learner == "ppo"
-        learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs) if ppo else SA2CLearner(actor, critic, 0.99)
+        learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs, **lam_kw) if ppo else SA2CLearner(actor, critic, 0.99, **lam_kw)
         for _ in range(args.warmup):
             learner.train(st)
         torch.cuda.synchronize()
@@ -90,15 +162,25 @@ def main():
             times.append(ev[0].elapsed_time(ev[1]))
         rows = T * E * N
         step = mlp_flop(rows, d_in, 200, 200, 1) + mlp_flop(rows, d_in, h1a, h2a, noa)
+        ring_rows = (T + 1) * E * N
         if ppo:     # per window: the old policy's and the critic's forward; per epoch: both gradient chains
-            flop = args.epochs * step + mlp_flop(rows, d_in, h1a, h2a, noa, False) + mlp_flop(rows, d_in, 200, 200, 1, False)
-        else:
-            flop = step + mlp_flop(rows, d_in, 200, 200, 1, False)
+            flop = (args.epochs * step + mlp_flop(rows, d_in, h1a, h2a, noa, False) +
+                    mlp_flop(rows if args.lam is None else ring_rows, d_in, 200, 200, 1, False))
+        else:       # (with --lam: one more critic forward, over the T+1 ring slots)
+            flop = step + mlp_flop(rows, d_in, 200, 200, 1, False) + (0 if args.lam is None else mlp_flop(ring_rows, d_in, 200, 200, 1, False))
         ms = min(times)
         tag = dict(learner="ppo", epochs=args.epochs) if ppo else {}
-        print(json.dumps(dict(config=name, **tag, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3),
-                              ms_all=[round(t, 3) for t in times], flop=flop, tflops=round(flop / ms / 1e9, 2),
-                              peak_share=round(flop / ms / 1e9 / PEAK_TF, 4))), flush=True)
+        if args.lam is not None:
+            tag["lam"] = args.lam
+        lines.append(dict(config=name, **tag, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3),
+                          ms_all=[round(t, 3) for t in times], flop=flop, tflops=round(flop / ms / 1e9, 2),
+                          peak_share=round(flop / ms / 1e9 / PEAK_TF, 4)))
+        print(json.dumps(lines[-1]), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":
