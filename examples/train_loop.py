@@ -5,7 +5,7 @@ batched `SA2CAgents.train_NN` (SAC_agents.py:280-357): critic MSE + clip + Adam,
 actor loss + clip + Adam, for all N agents' networks at once in HIP.
 
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
-                                  [--lam X] [--window T]
+                                  [--lam X] [--window T] [--time-limit {terminal,bootstrap}]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -13,6 +13,10 @@ used for ``--epochs`` critic-and-actor steps with the clipped probability ratio 
 ``--lam X`` (off by default) switches either learner to bootstrapped lambda-returns, TD(lambda) / GAE: the envs reset
 themselves, so a window cuts the episodes that started inside it, and without a bootstrap from the value of the observation
 after the window's last step their returns are truncated.  With it a window may be shorter than an episode (``--window T``).
+
+``--time-limit bootstrap`` (needs ``--lam``) treats an episode that ran into the time limit as truncated, not finished: its
+return bootstraps from the critic's value of its terminal observation.  After the loop the share of truncated among the last
+window's finished episodes is printed (an untrained policy: nearly all of them).
 """
 import argparse
 import os
@@ -51,6 +55,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=10, help="epochs per window (--learner ppo)")
     ap.add_argument("--lam", type=float, default=None, help="bootstrapped lambda-returns with this lambda in [0, 1] (default: off)")
     ap.add_argument("--window", type=int, default=200, help="steps per rollout window (default: one episode, 200)")
+    ap.add_argument("--time-limit", choices=("terminal", "bootstrap"), default="terminal",
+                    help="bootstrap: a time-limit end bootstraps from the value of its terminal observation (needs --lam)")
     args = ap.parse_args()
     N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
     env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
@@ -63,9 +69,10 @@ def main():
     # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
     if args.learner == "ppo":
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
-                             lam=args.lam)
+                             lam=args.lam, time_limit=args.time_limit)
     else:
-        learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam)
+        learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
+                              time_limit=args.time_limit)
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for ep in range(args.episodes):
         storage.begin()
@@ -83,6 +90,11 @@ def main():
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(out['actor_loss'].mean()):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
               f"{float(out['actor_grad_norm'].mean()):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")
+    # one host read after the loop: the kinds of the last window's episode ends
+    _, _, n_trunc = (learner.ends, learner.slot_t, learner.n_trunc) if args.time_limit == "bootstrap" else storage.episode_ends()
+    finished = int(storage.done.sum())
+    print(f"last window: {finished} finished episodes, {int(n_trunc.sum())} of them truncated by the time limit"
+          + (f" ({int(n_trunc.sum()) / finished:.1%})" if finished else ""))
 
 
 if __name__ == "__main__":

@@ -315,6 +315,38 @@ int dronesim_returns(const float *reward, const uint8_t *done, float gamma, floa
  *                       T = 0 or E = 0 enqueues nothing.  One kernel launch (no memset nodes: graph-capturable).   */
 int dronesim_lambda_returns(const float *reward, const uint8_t *done, const float *V, float gamma, float lam, float *G, float *A,
                             int T, int E, int N, void *stream);
+/*   dronesim_episode_ends   the KIND of every episode end of a stored auto_reset window, recovered from the window itself.
+ *                       `done` is "every agent within done_radius of its goal" OR "time limit" (drone_env.py:251), and the
+ *                       terminal observation of every finished episode is in z_final [T][E][N][d] (d = (k+1) c floats per
+ *                       agent, the first two of them the agent's own offset (zx, zy) from its goal).  With
+ *                       outside(t,e,i) = !(sqrtf(fmaf(zy, zy, zx zx)) <= done_radius) -- the step kernel's own test; a
+ *                       non-finite offset is outside --
+ *                         ends[t][e] = 0   where done[t][e] == 0
+ *                                      1   terminal: done, no agent outside (arrival, also on the last allowed step)
+ *                                      2   truncated: done, some agent outside (this can only be the time limit)
+ *                       The truncated ends of env e are ranked from the BACK of the window, k = number of truncated ends of e
+ *                       at later t:  slot_t[k][e] = t ([M][E] int32, -1 where e has no k-th),  z_trunc[k][e] = z_final[t][e]
+ *                       ([M][E][N][d], all zeros where slot_t is -1: every element is written by this call),  n_trunc[e] =
+ *                       their count.  A truncated end with k >= M is demoted to ends = 1 (n_trunc > M tells); nothing is
+ *                       read or written out of range.  EINVAL for a NULL argument, T < 0, E < 0, N < 1, d < 2, M < 1, a NaN
+ *                       done_radius; E = 0 enqueues nothing.  Up to three kernel launches on `stream`, no host
+ *                       synchronisation, no memset nodes, no atomics: graph-capturable and bit-identical run to run.
+ *   dronesim_lambda_returns_ends   dronesim_lambda_returns with `ends` ([T][E] uint8 as above) in the place of `done`, and
+ *                       Vend [M][E][N], the values of the terminal observations z_trunc.  Per column, backwards from
+ *                       Gn = V[T] with a counter k = 0:
+ *                         ends = 0            G[t] = r[t] + gamma ((1 - lam) V[t+1] + lam Gn)     (dronesim_lambda_returns' step)
+ *                         ends = 1            G[t] = r[t]                                         (its done step)
+ *                         ends = 2, k <  M    G[t] = r[t] + gamma Vend[k][e][i],  k += 1          (independent of lam: both terms
+ *                                                                                                 of the mix are that value)
+ *                         ends = 2, k >= M    G[t] = r[t]
+ *                         A[t] = G[t] - V[t]
+ *                       With ends in {0, 1} the outputs are bit-identical to dronesim_lambda_returns with done = ends; Vend is
+ *                       read only at steps with ends = 2.  EINVAL as dronesim_lambda_returns, and for a NULL ends / Vend or
+ *                       M < 1; T = 0 or E = 0 enqueues nothing.  One kernel launch.   */
+int dronesim_episode_ends(const uint8_t *done, const float *z_final, int T, int E, int N, int d, float done_radius,
+                          uint8_t *ends, int32_t *slot_t, int32_t *n_trunc, float *z_trunc, int M, void *stream);
+int dronesim_lambda_returns_ends(const float *reward, const uint8_t *ends, const float *V, const float *Vend, int M, float gamma,
+                                 float lam, float *G, float *A, int T, int E, int N, void *stream);
 int dronesim_advantage(const float *G, const float *V, const int32_t *nbr_idx, const uint8_t *done,
                        float gamma, float *w, int T, int E, int N, int K1, void *stream);
 int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *nbr_idx, int per_neighbour, float *adv,

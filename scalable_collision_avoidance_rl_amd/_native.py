@@ -32,7 +32,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_mlp_forward_bf16x3", "dronesim_mlp_forward_f16x2", "dronesim_mlp_bf16x3_stages", "dronesim_mlp_rt_blocks", "dronesim_mlp_rt16_blocks", "dronesim_mlp_forward_f16x2_rt",
            "dronesim_mlp_grad_workspace", "dronesim_mlp_grad", "dronesim_adam_step",
            "dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo",
-           "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_lambda_returns",
+           "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -131,6 +131,9 @@ def lib():
     L.dronesim_returns.restype = L.dronesim_advantage.restype = C.c_int
     L.dronesim_lambda_returns.argtypes = [vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]
     L.dronesim_lambda_returns.restype = C.c_int
+    L.dronesim_episode_ends.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
+    L.dronesim_lambda_returns_ends.argtypes = [vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, vp]
+    L.dronesim_episode_ends.restype = L.dronesim_lambda_returns_ends.restype = C.c_int
     L.dronesim_mlp_forward.argtypes = [C.POINTER(DroneMlp), vp, vp, vp, vp, u64, u64, i64, vp, vp, i32, vp]
     L.dronesim_mlp_forward.restype = C.c_int
     L.dronesim_mlp_forward_bf16.argtypes = [C.POINTER(DroneMlpBf16), vp, vp, vp, vp, u64, u64, i64, vp, vp, i32, vp]

@@ -226,6 +226,7 @@ struct DoneStage {
         v = (t >= 0 && t < T && e_first + k < (size_t)E) ? done[(size_t)t * E + e_first + k] : 0u;
     }
     __device__ __forceinline__ bool get(int de, int u) const { return __shfl((int)v, 8 * de + u, 64) != 0; }
+    __device__ __forceinline__ unsigned byte(int de, int u) const { return (unsigned)__shfl((int)v, 8 * de + u, 64); }   // (the kind of end)
 };
 
 // The scan is software-pipelined: the rewards (and done flags) of stage s + 1 are requested BEFORE stage s is folded and
@@ -385,6 +386,175 @@ __global__ void __launch_bounds__(256) lambda_returns_kernel(const float *__rest
     const bool coop = done != nullptr && __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
     if (coop) lambda_scan<true, V>(reward, done, Vv, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
     else lambda_scan<false, V>(reward, done, Vv, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
+}
+
+// lambda_returns_kernel's scan with the KIND of every episode end in the place of `done` ("Time-limit ends"):
+//     ends[t][e] = 0   G[t] = r[t] + gamma ((1 - lam) Vv[t+1] + lam G[t+1])                       lambda_scan's step
+//     ends[t][e] = 1   G[t] = r[t]                                              terminal:         lambda_scan's done step
+//     ends[t][e] = 2   G[t] = r[t] + gamma Vend[k][e][i],  k += 1               truncated (time limit): the bootstrap is the
+//                                                                               value of the episode's terminal observation
+// k counts the column's truncated ends from the back of the window; an end with k >= M is folded as terminal.  Same streams,
+// staging, flag fetch (the byte instead of a bool), column quadruples and non-temporal accesses as lambda_scan; the Vend row is
+// loaded at the step that needs it and at no other (about one step in 200 per env: the wave waits for it there).
+template <int V> struct EndsStage {
+    typename RetVec<V>::type r[kRetStageT], v[kRetStageT];
+    DoneStage ds;
+    unsigned kind[kRetStageT];
+};
+
+template <bool COOP, int V>
+__device__ __forceinline__ void ends_fetch(EndsStage<V> &st, const float *__restrict__ reward, const float *__restrict__ Vv,
+                                           const uint8_t *__restrict__ ends, size_t EN, size_t col, size_t e, size_t e_first,
+                                           int E, int T, int t0)
+{
+    typedef typename RetVec<V>::type vec;
+    if (COOP) st.ds.fetch(ends, e_first, E, T, [&](int u) { return t0 - u; });
+#pragma unroll
+    for (int u = 0; u < kRetStageT; ++u) {
+        const int t = t0 - u;
+        st.r[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(reward + (size_t)t * EN + col)) : vec(0.0f);
+        st.v[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)t * EN + col)) : vec(0.0f);
+        if (!COOP) st.kind[u] = t >= 0 ? (unsigned)ends[(size_t)t * E + e] : 0u;
+    }
+}
+
+template <bool COOP, int V>
+__device__ __forceinline__ void ends_scan(const float *__restrict__ reward, const uint8_t *__restrict__ ends,
+                                          const float *__restrict__ Vv, const float *__restrict__ Vend, int M, float gamma,
+                                          float lam, float *__restrict__ G, float *__restrict__ A, int T, int E, size_t EN,
+                                          size_t col, size_t e, size_t e_first, int de, bool act)
+{
+    typedef typename RetVec<V>::type vec;
+    const float oml = 1.0f - lam;
+    EndsStage<V> cur, nxt;
+    vec vn = __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)T * EN + col));   // the bootstrap: Gn = Vv[T]
+    ends_fetch<COOP, V>(cur, reward, Vv, ends, EN, col, e, e_first, E, T, T - 1);
+    vec g = vn;
+    int k = 0;                                                 // truncated ends of this column's env met so far
+    for (int t0 = T - 1; t0 >= 0; t0 -= kRetStageT) {
+        if (t0 - kRetStageT >= 0) ends_fetch<COOP, V>(nxt, reward, Vv, ends, EN, col, e, e_first, E, T, t0 - kRetStageT);
+#pragma unroll
+        for (int u = 0; u < kRetStageT; ++u) {
+            const int t = t0 - u;
+            if (t >= 0) {
+                const unsigned kind = COOP ? cur.ds.byte(de, u) : cur.kind[u];
+                float *gp = reinterpret_cast<float *>(&g);
+                const float *rp = reinterpret_cast<const float *>(&cur.r[u]), *vp = reinterpret_cast<const float *>(&vn);
+                if (kind == 2u && k < M) {                     // rare: the value of the terminal observation, slot k of this env
+                    const vec ve = *reinterpret_cast<const vec *>(Vend + (size_t)k * EN + col);
+                    const float *ep = reinterpret_cast<const float *>(&ve);
+#pragma unroll
+                    for (int q = 0; q < V; ++q) gp[q] = fmaf(ep[q], gamma, rp[q]);
+                    ++k;
+                } else {
+                    const bool last = kind != 0u;
+#pragma unroll
+                    for (int q = 0; q < V; ++q) gp[q] = last ? rp[q] : fmaf(fmaf(lam, gp[q], oml * vp[q]), gamma, rp[q]);
+                }
+                vn = cur.v[u];
+                if (act) {
+                    if (G) __builtin_nontemporal_store(g, reinterpret_cast<vec *>(G + (size_t)t * EN + col));
+                    if (A) __builtin_nontemporal_store(g - vn, reinterpret_cast<vec *>(A + (size_t)t * EN + col));
+                }
+            }
+        }
+        cur = nxt;
+    }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) lambda_returns_ends_kernel(const float *__restrict__ reward, const uint8_t *__restrict__ ends,
+                                                                  const float *__restrict__ Vv, const float *__restrict__ Vend,
+                                                                  int M, float gamma, float lam, float *__restrict__ G,
+                                                                  float *__restrict__ A, int T, int E, int N)
+{
+    const size_t EN = (size_t)E * N;
+    const size_t col0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    const bool act = col0 < EN;                               // (no early exit: the flag fetch is a wave operation)
+    const size_t col = act ? col0 : EN - V;
+    const size_t e = col / N;                                 // (V == 4: N % 4 == 0, the four columns belong to one env)
+    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
+    const int de = (int)(e - e_first);
+    const bool coop = __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
+    if (coop) ends_scan<true, V>(reward, ends, Vv, Vend, M, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
+    else ends_scan<false, V>(reward, ends, Vv, Vend, M, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
+}
+
+// The kind of every episode end of a stored window, recovered from the window itself (dronesim_episode_ends; DESIGN.md,
+// "Time-limit ends").  done = "every agent within done_radius of its goal" OR "time limit", and under auto_reset the terminal
+// observation of every finished episode is in z_final[t]: agent i's offset from its goal is the first two floats of its row.
+// So a set `done` with some agent outside the disk can only be the time limit.
+//
+// Stage 1: ends[t][e] = 0 / 1 (terminal) / 2 (truncated), before any demotion.  A wave takes 64 consecutive entries of `done`
+// in its own [T][E] order (coalesced byte loads) and ballots them; set entries are rare (about E per 200 steps), and for each
+// the WHOLE wave reads that env's N offsets (lane = agent, strided by 64 above 64 agents) and ballots the step kernel's own
+// arrival test, !(sqrt(fma(zy, zy, zx zx)) <= done_radius): a non-finite offset counts as outside.
+__global__ void __launch_bounds__(256) ends_classify_kernel(const uint8_t *__restrict__ done, const float *__restrict__ z_final,
+                                                            size_t total, int N, int d, float done_radius, uint8_t *__restrict__ ends)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+    for (size_t base = wave * 64; base < total; base += nwaves * 64) {      // (wave-uniform trip count: the ballots are wave operations)
+        const size_t idx = base + lane;
+        const bool set = idx < total && done[idx] != 0;
+        unsigned long long m = __builtin_amdgcn_ballot_w64(set);
+        unsigned kind = set ? 1u : 0u;
+        while (m) {
+            const unsigned b = (unsigned)__builtin_ctzll(m);
+            m &= m - 1ull;
+            const float *rows = z_final + (base + b) * (size_t)N * d;       // (base + b < total: its lane saw a set flag)
+            bool outside = false;
+            for (int i = (int)lane; i < N; i += 64) {
+                const float zx = rows[(size_t)i * d], zy = rows[(size_t)i * d + 1];
+                outside |= !(__builtin_amdgcn_sqrtf(fmaf(zy, zy, zx * zx)) <= done_radius);
+            }
+            if (__builtin_amdgcn_ballot_w64(outside) != 0ull && lane == b) kind = 2u;
+        }
+        if (idx < total) ends[idx] = (uint8_t)kind;
+    }
+}
+
+// Stage 2: one thread per env walks ends[:, e] backwards (coalesced across envs, eight steps requested together), ranks the
+// truncated ends from the back of the window -- slot_t[k][e] = t of the k-th, -1 where there is none --, demotes those with
+// k >= M to terminal in place, and writes n_trunc[e], the count before the demotion.
+__global__ void __launch_bounds__(256) ends_rank_kernel(uint8_t *__restrict__ ends, int T, int E, int M, int32_t *__restrict__ slot_t,
+                                                        int32_t *__restrict__ n_trunc)
+{
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= E) return;
+    int k = 0;
+    for (int t0 = T - 1; t0 >= 0; t0 -= kStageT) {
+        unsigned kind[kStageT];
+#pragma unroll
+        for (int u = 0; u < kStageT; ++u) kind[u] = t0 - u >= 0 ? (unsigned)ends[(size_t)(t0 - u) * E + e] : 0u;
+#pragma unroll
+        for (int u = 0; u < kStageT; ++u) {
+            if (kind[u] == 2u) {
+                if (k < M) slot_t[(size_t)k * E + e] = t0 - u;
+                else ends[(size_t)(t0 - u) * E + e] = (uint8_t)1;
+                ++k;
+            }
+        }
+    }
+    n_trunc[e] = k;
+    for (int m = k; m < M; ++m) slot_t[(size_t)m * E + e] = -1;
+}
+
+// Stage 3: z_trunc[m][e] = z_final[slot_t[m][e]][e], all zeros where slot_t is -1: every element is written here (no memset,
+// no uninitialised row reaches the critic).  An (m, e) block is N d floats; VW floats per lane, lanes contiguous.
+template <int VW>
+__global__ void __launch_bounds__(256) ends_gather_kernel(const float *__restrict__ z_final, const int32_t *__restrict__ slot_t,
+                                                          int E, size_t per_block, size_t items, float *__restrict__ z_trunc)
+{
+    typedef typename RetVec<VW>::type vec;
+    for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (size_t)gridDim.x * blockDim.x) {
+        const size_t blk = it / per_block, within = it - blk * per_block;   // blk = m E + e
+        const int t = slot_t[blk];
+        const size_t e = blk % (size_t)E;
+        vec v = vec(0.0f);
+        if (t >= 0) v = __builtin_nontemporal_load(reinterpret_cast<const vec *>(z_final) + ((size_t)t * E + e) * per_block + within);
+        reinterpret_cast<vec *>(z_trunc)[it] = v;
+    }
 }
 
 // K1C = K + 1 at compile time (3 for the reference's k_closest = 2: the neighbour triple is one 12-byte load), 0 = any
@@ -1100,6 +1270,63 @@ int dronesim_lambda_returns(const float *reward, const uint8_t *done, const floa
     else
         hipLaunchKernelGGL(lambda_returns_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
                            static_cast<hipStream_t>(stream), reward, done, V, gamma, lam, G, A, T, E, N);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+int dronesim_episode_ends(const uint8_t *done, const float *z_final, int T, int E, int N, int d, float done_radius,
+                          uint8_t *ends, int32_t *slot_t, int32_t *n_trunc, float *z_trunc, int M, void *stream)
+{
+    if (!done || !z_final) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: done or z_final is NULL");
+    if (!ends || !slot_t || !n_trunc || !z_trunc) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: an output is NULL");
+    if (T < 0 || E < 0 || N < 1 || d < 2) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: bad T, E, N or d");
+    if (M < 1) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: M must be at least 1");
+    if (done_radius != done_radius) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: done_radius is NaN");
+    if (E == 0) return DRONESIM_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t total = (size_t)T * E, ND = (size_t)N * d;
+    const size_t kMaxBlocks = (size_t)1 << 20;                  // (both kernels loop over what a capped grid leaves)
+    const size_t cb = (total + 255) / 256;
+    if (total > 0)
+        hipLaunchKernelGGL(ends_classify_kernel, dim3((unsigned)(cb < kMaxBlocks ? cb : kMaxBlocks)), dim3(256), 0, s,
+                           done, z_final, total, N, d, done_radius, ends);
+    hipLaunchKernelGGL(ends_rank_kernel, dim3((unsigned)(((size_t)E + 255) / 256)), dim3(256), 0, s, ends, T, E, M, slot_t, n_trunc);
+    // the vector width from N d, the floats of one (t, e) block (a row's d is a multiple of two floats only at c = 2), and the
+    // two base addresses: every block of both arrays then starts 16-byte aligned
+    const bool v4 = (ND % 4) == 0 && ((reinterpret_cast<uintptr_t>(z_final) | reinterpret_cast<uintptr_t>(z_trunc)) & 15u) == 0;
+    const size_t per = v4 ? ND / 4 : ND, items = (size_t)M * E * per;
+    const size_t gb = (items + 255) / 256;
+    const dim3 grid((unsigned)(gb < kMaxBlocks ? gb : kMaxBlocks));
+    if (v4) hipLaunchKernelGGL(ends_gather_kernel<4>, grid, dim3(256), 0, s, z_final, slot_t, E, per, items, z_trunc);
+    else hipLaunchKernelGGL(ends_gather_kernel<1>, grid, dim3(256), 0, s, z_final, slot_t, E, per, items, z_trunc);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+int dronesim_lambda_returns_ends(const float *reward, const uint8_t *ends, const float *V, const float *Vend, int M, float gamma,
+                                 float lam, float *G, float *A, int T, int E, int N, void *stream)
+{
+    if (!reward || !V) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: reward or V is NULL");
+    if (!ends || !Vend) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: ends or Vend is NULL");
+    if (!G && !A) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: G and A are both NULL");
+    if (T < 0 || E < 0 || N < 1) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: bad T, E or N");
+    if (M < 1) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: M must be at least 1");
+    if (!(lam >= 0.0f && lam <= 1.0f)) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: lam must be in [0, 1]");
+    if (gamma != gamma) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: gamma is NaN");
+    if (T == 0 || E == 0) return DRONESIM_OK;
+    const size_t cols = (size_t)E * N;
+    // dronesim_lambda_returns' size rule for the column quadruples, with Vend among the arrays that must be 16-byte aligned
+    const uintptr_t align = reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(Vend) |
+                            reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(A);
+    const bool v4 = (N % 4) == 0 && (align & 15u) == 0 && cols >= 262144 && cols < 524288;
+    if (v4)
+        hipLaunchKernelGGL(lambda_returns_ends_kernel<4>, dim3((unsigned)((cols / 4 + 255) / 256)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), reward, ends, V, Vend, M, gamma, lam, G, A, T, E, N);
+    else
+        hipLaunchKernelGGL(lambda_returns_ends_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), reward, ends, V, Vend, M, gamma, lam, G, A, T, E, N);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
     return DRONESIM_OK;

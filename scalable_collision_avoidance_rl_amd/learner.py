@@ -11,6 +11,9 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
                                        critic-and-actor steps per window
   lam= of both    dronesim_lambda_returns   bootstrapped lambda-returns (TD(lambda) / GAE) from the critic over the storage's
                                        T+1-slot observation ring, for windows that cut episodes (default off)
+  time_limit= of both  dronesim_episode_ends, dronesim_lambda_returns_ends   with ``"bootstrap"`` a time-limit episode end is a
+                                       truncation: its return bootstraps from the critic's value of the episode's terminal
+                                       observation (``storage.z_final``) instead of stopping there (default ``"terminal"``)
 
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
@@ -269,6 +272,58 @@ def _lambda_returns(learner, storage, Vall, G):
     _native.check(rc, "dronesim_lambda_returns")
 
 
+TIME_LIMITS = ("terminal", "bootstrap")
+
+
+def _check_time_limit(time_limit, lam):
+    """``"terminal"`` or ``"bootstrap"``; the latter needs the critic in the returns, i.e. a ``lam``."""
+    if not isinstance(time_limit, str) or time_limit not in TIME_LIMITS:
+        raise ValueError(f"time_limit must be one of {TIME_LIMITS}, got {time_limit!r}")
+    if time_limit == "bootstrap" and lam is None:
+        raise ValueError('time_limit="bootstrap" needs bootstrapped lambda-returns: give a lam in [0, 1] (with lam=None the '
+                         "returns are the reference's whole-episode rule, which has no critic in it)")
+    return time_limit
+
+
+def _prepare_ends(learner, storage, T, E, N):
+    """Check the storage for ``time_limit="bootstrap"`` and make the learner's buffers of that path (first call per shape)."""
+    import torch
+    from . import drone_env
+    zf = getattr(storage, "z_final", None)
+    if zf is None:
+        raise ValueError('time_limit="bootstrap" needs the terminal observations `z_final` [T,E,N,d] of an env with '
+                         "auto_reset=True (RolloutStorage.z_final); this storage has none")
+    if tuple(zf.shape) != tuple(storage.z_pre.shape) or not zf.is_contiguous():
+        raise ValueError(f"storage.z_final must be a contiguous [T,E,N,d] = {tuple(storage.z_pre.shape)} tensor, got {tuple(zf.shape)}")
+    if learner._shape == (T, E, N):
+        return
+    dev = learner.critic.device
+    M = learner.M = -(-T // drone_env.max_time_steps)        # two time-limit ends of one env are max_time_steps slots apart
+    learner.ends = torch.empty(T, E, dtype=torch.uint8, device=dev)
+    learner.slot_t = torch.empty(M, E, dtype=torch.int32, device=dev)
+    learner.n_trunc = torch.empty(E, dtype=torch.int32, device=dev)
+    learner.z_trunc = torch.empty(M, E, N, zf.shape[3], device=dev)
+    learner.V_trunc = torch.empty(M * E, N, 1, device=dev)
+
+
+def _lambda_returns_ends(learner, storage, Vall, G):
+    """``time_limit="bootstrap"``: the kinds of the window's episode ends and the terminal observations of the truncated ones
+    (`dronesim_episode_ends`), the PRE-update critic over those into ``V_trunc``, then `dronesim_lambda_returns_ends` into ``G``."""
+    import torch
+    from . import _native, drone_env
+    from .rollout_buffer import _episode_ends
+    T, E, N = learner._shape
+    M = learner.M
+    _episode_ends(storage.done, storage.z_final, drone_env.DONE_RADIUS, M, learner.ends, learner.slot_t, learner.n_trunc,
+                  learner.z_trunc)
+    learner.critic.forward(learner.z_trunc.view(M * E, N, -1), out=learner.V_trunc)
+    with torch.cuda.device(learner.critic.device):
+        rc = _native.lib().dronesim_lambda_returns_ends(storage.reward.data_ptr(), learner.ends.data_ptr(), Vall.data_ptr(),
+                                                        learner.V_trunc.data_ptr(), M, learner.gamma, learner.lam, G.data_ptr(),
+                                                        None, T, E, N, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_lambda_returns_ends")
+
+
 class SA2CLearner:
     """`SA2CAgents.train_NN` (SAC_agents.py:280-357) over a `RolloutStorage` window of E envs, T steps:
 
@@ -300,10 +355,22 @@ class SA2CLearner:
     (``storage.z_all``); 1b. G = `dronesim_lambda_returns` of it (an episode end is terminal: nothing is carried across
     ``done``, and the new episode's values do not leak into the old one); 1c. the critic step on target G.  Steps 2 and 3 are
     unchanged (V from the POST-update critic over ``z_pre``, `dronesim_advantage` with this G).  Cost: one more critic
-    forward over (T+1) E rows and one scan.  Out of scope: a time-limit end (t >= 199) is terminal here as in the reference,
-    not a truncation to bootstrap from ``z_final`` -- the storage does not record which kind of end a ``done`` was."""
+    forward over (T+1) E rows and one scan.
 
-    def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None):
+    ``time_limit`` says what a time-limit episode end (t >= 199 with some agent still outside its goal disk) is to the returns:
+
+      ``"terminal"``   (default) an end like any other, the reference's rule: G[t] = r[t] there, which tells the critic that
+                       the cost-to-go at step 199 is zero.
+      ``"bootstrap"``  a truncation: G[t] = r[t] + gamma V(terminal observation), whatever ``lam`` is.  Needs a ``lam`` and a
+                       storage of an ``auto_reset`` env (``z_final``).  Once per window, ahead of 1b: `dronesim_episode_ends`
+                       recovers the kind of every end from ``done`` and ``z_final`` (``ends``, ``slot_t``, ``n_trunc``) and
+                       gathers the terminal observations of the truncated ones (``z_trunc [M,E,N,d]``, M = ceil(T / 200)); the
+                       PRE-update critic over them gives ``V_trunc [M E,N,1]``; 1b becomes `dronesim_lambda_returns_ends`.  An
+                       arrival is terminal as before, also on the last allowed step.  Steps 2 and 3 are unchanged: the
+                       advantage still restarts at ``done``."""
+
+    def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None,
+                 time_limit="terminal"):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -311,6 +378,7 @@ class SA2CLearner:
         if (actor.n_agents, actor.d_in) != (critic.n_agents, critic.d_in):
             raise ValueError("actor and critic must have the same agents and inputs")
         self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
+        self.time_limit = _check_time_limit(time_limit, self.lam)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
@@ -321,6 +389,8 @@ class SA2CLearner:
         T, E, N = storage.reward.shape
         if self.lam is not None:
             _ring(storage, T)
+        if self.time_limit == "bootstrap":
+            _prepare_ends(self, storage, T, E, N)
         if self._shape == (T, E, N):
             return
         if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
@@ -351,7 +421,7 @@ class SA2CLearner:
             _native.check(rc, "dronesim_returns")
         else:       # bootstrapped lambda-returns from the pre-update critic over all T+1 ring slots
             self.critic.forward(storage.z_all.view((T + 1) * E, N, -1), out=self.V_all)
-            _lambda_returns(self, storage, self.V_all, self.G)
+            (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G)
         # critic (SAC_agents.py:304-324)
         cg, closs = self._critic_grad.run(x, 1.0 / (T * E), target=self.G)
         cnorm = self.critic_opt.step(cg)
@@ -405,13 +475,17 @@ class PPOLearner:
     [0, 1] widens step 2's once-per-window critic forward to all T+1 slots of ``storage.z_all`` and takes
     G = `dronesim_lambda_returns` of it (1.0: Monte-Carlo plus a bootstrap from the value after the window's last step,
     equal to None bit for bit on columns whose window ends with ``done``; below 1: TD(lambda)); the first T E rows of that
-    forward are step 2's V.  No extra forward, epochs unchanged.  An episode end is terminal, time-limit ends included (the
-    reference's rule; bootstrapping truncations from ``z_final`` is out of scope)."""
+    forward are step 2's V.  No extra forward, epochs unchanged.
+
+    ``time_limit`` as for `SA2CLearner`: ``"terminal"`` (default) keeps every episode end terminal, time-limit ends included
+    (the reference's rule); ``"bootstrap"`` (needs a ``lam`` and ``storage.z_final``) classifies the window's ends, runs the
+    same pre-update critic over the terminal observations of the truncated ones (``z_trunc`` -> ``V_trunc``) and takes
+    G = `dronesim_lambda_returns_ends`.  Everything after G is unchanged."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
-                 baseline="once", rows_per_chunk=None, lam=None):
+                 baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal"):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -425,6 +499,7 @@ class PPOLearner:
         if baseline not in self.BASELINES:
             raise ValueError(f"baseline must be one of {self.BASELINES}")
         self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
+        self.time_limit = _check_time_limit(time_limit, self.lam)
         self.epochs, self.clip_eps, self.baseline = int(epochs), float(clip_eps), baseline
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
@@ -438,6 +513,8 @@ class PPOLearner:
         T, E, N = storage.reward.shape
         if self.lam is not None:
             _ring(storage, T)
+        if self.time_limit == "bootstrap":
+            _prepare_ends(self, storage, T, E, N)
         if self._shape == (T, E, N):
             return
         if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
@@ -476,7 +553,7 @@ class PPOLearner:
             self.critic.forward(x.view(T * E, N, -1), out=self.V)
         else:       # the same forward over all T+1 ring slots; the bootstrapped lambda-returns of it
             self.critic.forward(storage.z_all.view((T + 1) * E, N, -1), out=self.V_all)
-            _lambda_returns(self, storage, self.V_all, self.G)
+            (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G)
         with torch.cuda.device(self.critic.device):
             rc = lib.dronesim_neighbour_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(),
                                                   int(self.baseline == "per_neighbour"), self.adv.data_ptr(), T, E, N,

@@ -9,10 +9,14 @@ called at train_problem.py:96) and scans them per agent at the end of the episod
   mc_returns           SAC_agents.py:304-307   G[t] = r[t] + gamma * G[t+1]
   lambda_returns       (no reference line)     TD(lambda) / GAE with a bootstrap from the value after the window's last step:
                                                G[t] = r[t] + gamma ((1 - lam) V[t+1] + lam G[t+1]), A = G - V
+  episode_ends         (no reference line)     the kind of every episode end of an auto_reset window, from `z_final`: 1 terminal
+                                               (arrival), 2 truncated (time limit), and the terminal observations of the
+                                               truncated ones gathered for the critic; `lambda_returns(ends=, Vend=)` bootstraps
+                                               a truncated end from the value of its terminal observation
   neighbour_advantage  SAC_agents.py:333-351   gamma^t / N * sum_{j in Ni[t]} (G_j[t] - V_i[t])
 
-The reductions run in the HIP library (dronesim_returns / dronesim_lambda_returns / dronesim_advantage); there is no CPU
-fallback."""
+The reductions run in the HIP library (dronesim_returns / dronesim_lambda_returns / dronesim_episode_ends /
+dronesim_lambda_returns_ends / dronesim_advantage); there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -74,6 +78,8 @@ class RolloutStorage:
         self.nbr_final = torch.full((self.T, E, N, K1), -1, dtype=torch.int32, device=dev) if final else None
         self._slots = [None] * self.T
         self._generation = None
+        self.z_trunc = None                                  # `episode_ends` allocates its buffers on its first call
+        self._ends = None
 
     # views over the observation ring
     z_pre = property(lambda self: self.zbuf[:self.T])
@@ -132,10 +138,40 @@ class RolloutStorage:
         """Monte-Carlo returns of the stored rewards, restarting at episode ends (`mc_returns`)."""
         return mc_returns(self.true_reward if true_rewards else self.reward, gamma, self.done)
 
-    def lambda_returns(self, V, gamma, lam=1.0, true_rewards=False, want_adv=False):
+    def lambda_returns(self, V, gamma, lam=1.0, true_rewards=False, want_adv=False, Vend=None):
         """Bootstrapped lambda-returns of the stored rewards (`lambda_returns`): ``V [T+1,E,N]`` are the critic's values of
-        all ring slots, e.g. ``critic.forward(st.z_all.view((T+1)*E, N, -1)).view(T+1, E, N)``."""
-        return lambda_returns(self.true_reward if true_rewards else self.reward, V, gamma, lam, self.done, want_adv)
+        all ring slots, e.g. ``critic.forward(st.z_all.view((T+1)*E, N, -1)).view(T+1, E, N)``.  With ``Vend [M,E,N]``, the
+        critic's values of ``z_trunc`` after `episode_ends` (same ``M``), a time-limit end bootstraps from the value of its
+        terminal observation instead of being terminal."""
+        reward = self.true_reward if true_rewards else self.reward
+        if Vend is None:
+            return lambda_returns(reward, V, gamma, lam, self.done, want_adv)
+        if self._ends is None:
+            raise ValueError("Vend needs the kinds of this window's episode ends: call episode_ends() first")
+        return lambda_returns(reward, V, gamma, lam, None, want_adv, ends=self._ends[0], Vend=Vend)
+
+    def episode_ends(self, M=None):
+        """The kind of every episode end of the stored window (`episode_ends`): returns ``(ends [T,E] u8, slot_t [M,E] i32,
+        n_trunc [E] i32)`` and fills ``self.z_trunc [M,E,N,(k+1)c]``, the terminal observations of the truncated (time-limit)
+        ends ranked from the back of the window, zeros where there is none.  ``M`` defaults to ``ceil(T / max_time_steps)``:
+        two time-limit ends of one env are at least ``max_time_steps`` slots apart.  The buffers are allocated on the first
+        call (and again only when ``M`` changes); needs an env with ``auto_reset`` (``z_final``)."""
+        import torch
+        from . import drone_env
+        if self.z_final is None:
+            raise ValueError("episode_ends needs the terminal observations `z_final` of an env with auto_reset=True; "
+                             "this storage has none")
+        M = -(-self.T // drone_env.max_time_steps) if M is None else int(M)
+        if M < 1:
+            raise ValueError(f"M must be at least 1, got {M}")
+        E = self.done.shape[1]
+        if self._ends is None or self._ends[1].shape[0] != M:
+            dev = self.done.device
+            self._ends = (torch.empty_like(self.done), torch.empty(M, E, dtype=torch.int32, device=dev),
+                          torch.empty(E, dtype=torch.int32, device=dev))
+            self.z_trunc = torch.empty((M,) + tuple(self.z_final.shape[1:]), dtype=torch.float32, device=dev)
+        _episode_ends(self.done, self.z_final, drone_env.DONE_RADIUS, M, *self._ends, self.z_trunc)
+        return self._ends
 
     def advantage(self, V, gamma, G=None):
         """Actor-loss weights from the stored pre-step neighbour lists (`neighbour_advantage`)."""
@@ -191,13 +227,62 @@ def check_lam(lam):
     return float(lam)
 
 
-def lambda_returns(reward, V, gamma: float, lam: float = 1.0, done=None, want_adv=False):
+def _episode_ends(done, z_final, done_radius, M, ends, slot_t, n_trunc, z_trunc):
+    """`dronesim_episode_ends` on checked, contiguous device tensors, into the caller's buffers."""
+    import torch
+    from . import _native
+    T, E, N, d = z_final.shape
+    with torch.cuda.device(done.device):
+        rc = _native.lib().dronesim_episode_ends(done.data_ptr(), z_final.data_ptr(), T, E, N, d, float(done_radius),
+                                                 ends.data_ptr(), slot_t.data_ptr(), n_trunc.data_ptr(), z_trunc.data_ptr(), M,
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_episode_ends")
+
+
+def episode_ends(done, z_final, done_radius, M):
+    """The kind of every episode end of a stored auto_reset window, from the window itself: ``done [T,E]`` (u8) and the
+    terminal observations ``z_final [T,E,N,d]`` whose rows start with the agent's own offset (zx, zy) from its goal.
+
+        ends [T,E] u8        0 no end, 1 terminal (done, every agent within ``done_radius``), 2 truncated (done with some agent
+                             outside: the time limit -- an arrival on the last allowed step is terminal)
+        slot_t [M,E] i32     t of env e's k-th truncated end counted from the BACK of the window, -1 where there is none
+        n_trunc [E] i32      the env's truncated ends (an end with k >= M is demoted to ends = 1: ``n_trunc > M`` tells)
+        z_trunc [M,E,N,d]    z_final[slot_t[k,e], e], zeros where slot_t is -1
+
+    Returns ``(ends, slot_t, n_trunc, z_trunc)``.  The test is the step kernel's own, ``!(sqrt(zx^2 + zy^2) <= done_radius)``
+    in float32: a non-finite offset counts as outside."""
+    import torch
+    if not (torch.is_tensor(done) and torch.is_tensor(z_final)) or z_final.dim() != 4 or z_final.shape[3] < 2 or \
+            tuple(done.shape) != tuple(z_final.shape[:2]):
+        raise ValueError(f"done must be [T,E] and z_final [T,E,N,d] with d >= 2, got "
+                         f"{tuple(getattr(done, 'shape', ()))} and {tuple(getattr(z_final, 'shape', ()))}")
+    if isinstance(M, bool) or int(M) != M or M < 1:
+        raise ValueError(f"M must be an integer >= 1, got {M!r}")
+    M = int(M)
+    z_final = _prep(z_final, torch.float32)
+    T, E, N, d = z_final.shape
+    done = _prep(done, torch.uint8, (T, E))
+    dev = done.device
+    out = (torch.empty_like(done), torch.empty(M, E, dtype=torch.int32, device=dev), torch.empty(E, dtype=torch.int32, device=dev),
+           torch.empty(M, E, N, d, dtype=torch.float32, device=dev))
+    _episode_ends(done, z_final, done_radius, M, *out)
+    return out
+
+
+def lambda_returns(reward, V, gamma: float, lam: float = 1.0, done=None, want_adv=False, ends=None, Vend=None):
     """TD(lambda) returns of every (env, agent) column of ``reward [T,E,N]`` for a window that may cut episodes:
     ``V [T+1,E,N]`` holds the value of the observation each step acted on and, in its last slot, of the observation after
     the last step, from which the scan bootstraps; ``done [T,E]`` (optional) marks steps that ended an episode -- terminal,
     nothing is carried across them.  ``lam = 1`` is Monte-Carlo plus the bootstrap at the window's end, ``lam = 0`` the
-    one-step target.  Returns ``G``, or ``(G, A)`` with the GAE(gamma, lam) advantage ``A = G - V[:T]`` when ``want_adv``."""
+    one-step target.  Returns ``G``, or ``(G, A)`` with the GAE(gamma, lam) advantage ``A = G - V[:T]`` when ``want_adv``.
+
+    ``ends [T,E]`` (u8) and ``Vend [M,E,N]`` -- both or neither -- replace ``done`` by the KIND of every end (`episode_ends`):
+    1 is terminal as above; 2, a time-limit end, gives ``G[t] = r[t] + gamma Vend[k]`` with k the number of the env's
+    truncated ends at later t (terminal once k reaches M), whatever ``lam`` is.  ``done`` is not read then."""
     import torch
+    if (ends is None) != (Vend is None):
+        raise ValueError("ends and Vend go together: the kinds of the episode ends [T,E] and the values [M,E,N] of the "
+                         "terminal observations of the truncated ones (episode_ends); got only one of them")
     from . import _native
     lib = _native.lib()
     lam = check_lam(lam)
@@ -205,9 +290,25 @@ def lambda_returns(reward, V, gamma: float, lam: float = 1.0, done=None, want_ad
             reward.dim() != 3 or tuple(V.shape) != (reward.shape[0] + 1,) + tuple(reward.shape[1:])):
         raise ValueError(f"reward must be [T,E,N] and V [T+1,E,N] (one more leading slot: the value after the last step), "
                          f"got {tuple(reward.shape)} and {tuple(V.shape)}")
+    if ends is not None and torch.is_tensor(reward) and reward.dim() == 3:
+        if not torch.is_tensor(Vend) or Vend.dim() != 3 or Vend.shape[0] < 1 or tuple(Vend.shape[1:]) != tuple(reward.shape[1:]):
+            raise ValueError(f"Vend must be [M,E,N] = [M >= 1, {reward.shape[1]}, {reward.shape[2]}], "
+                             f"got {tuple(getattr(Vend, 'shape', ()))}")
+        if not torch.is_tensor(ends) or tuple(ends.shape) != tuple(reward.shape[:2]):
+            raise ValueError(f"ends must be [T,E] = {tuple(reward.shape[:2])}, got {tuple(getattr(ends, 'shape', ()))}")
     reward = _prep(reward, torch.float32)
     T, E, N = reward.shape
     V = _prep(V, torch.float32, (T + 1, E, N))
+    if ends is not None:
+        ends, Vend = _prep(ends, torch.uint8, (T, E)), _prep(Vend, torch.float32)
+        G = torch.empty_like(reward)
+        A = torch.empty_like(reward) if want_adv else None
+        with torch.cuda.device(reward.device):
+            rc = lib.dronesim_lambda_returns_ends(reward.data_ptr(), ends.data_ptr(), V.data_ptr(), Vend.data_ptr(), int(Vend.shape[0]),
+                                                  float(gamma), lam, G.data_ptr(), None if A is None else A.data_ptr(), T, E, N,
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_lambda_returns_ends")
+        return (G, A) if want_adv else G
     d = None if done is None else _prep(done, torch.uint8, (T, E))
     G = torch.empty_like(reward)
     A = torch.empty_like(reward) if want_adv else None
