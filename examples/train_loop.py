@@ -5,7 +5,8 @@ batched `SA2CAgents.train_NN` (SAC_agents.py:280-357): critic MSE + clip + Adam,
 actor loss + clip + Adam, for all N agents' networks at once in HIP.
 
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
-                                  [--lam X] [--window T] [--time-limit {terminal,bootstrap}]
+                                  [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
+                                  [--normalize-advantage]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -17,6 +18,10 @@ after the window's last step their returns are truncated.  With it a window may 
 ``--time-limit bootstrap`` (needs ``--lam``) treats an episode that ran into the time limit as truncated, not finished: its
 return bootstraps from the critic's value of its terminal observation.  After the loop the share of truncated among the last
 window's finished episodes is printed (an untrained policy: nearly all of them).
+
+``--ent-coef X`` adds an entropy bonus to the actor loss (-X x the mean entropy of the policy over the window's rows), and
+``--normalize-advantage`` (``--learner ppo``) standardises each agent's advantages over the window before the epochs; with
+either, every episode line also shows the mean entropy.
 """
 import argparse
 import os
@@ -57,7 +62,12 @@ def main():
     ap.add_argument("--window", type=int, default=200, help="steps per rollout window (default: one episode, 200)")
     ap.add_argument("--time-limit", choices=("terminal", "bootstrap"), default="terminal",
                     help="bootstrap: a time-limit end bootstraps from the value of its terminal observation (needs --lam)")
+    ap.add_argument("--ent-coef", type=float, default=0.0, help="entropy bonus: -X x the mean policy entropy in the actor loss (default: off)")
+    ap.add_argument("--normalize-advantage", action="store_true",
+                    help="standardise each agent's advantages over the window before the epochs (--learner ppo)")
     args = ap.parse_args()
+    if args.normalize_advantage and args.learner != "ppo":
+        ap.error("--normalize-advantage needs --learner ppo (SA2CLearner has no advantage standardisation)")
     N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
     env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=dev, seed=1, auto_reset=True)
@@ -69,10 +79,11 @@ def main():
     # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
     if args.learner == "ppo":
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
-                             lam=args.lam, time_limit=args.time_limit)
+                             lam=args.lam, time_limit=args.time_limit, ent_coef=args.ent_coef,
+                             normalize_advantage=args.normalize_advantage)
     else:
         learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
-                              time_limit=args.time_limit)
+                              time_limit=args.time_limit, ent_coef=args.ent_coef)
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for ep in range(args.episodes):
         storage.begin()
@@ -87,6 +98,8 @@ def main():
         if args.learner == "ppo":       # the last epoch's diagnostics (the first epoch's ratio is exactly 1)
             ppo = (f"  clipped {float(out['clip_fraction'][-1].mean()):.3f}  kl {float(out['approx_kl'][-1].mean()):+.2e}  "
                    f"ratio [{float(out['ratio_min'][-1].min()):.3f}, {float(out['ratio_max'][-1].max()):.3f}]")
+        if "entropy" in out:            # (PPO: the last epoch's)
+            ppo += f"  entropy {float(out['entropy'][-1].mean() if out['entropy'].dim() == 2 else out['entropy'].mean()):.3f}"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(out['actor_loss'].mean()):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
               f"{float(out['actor_grad_norm'].mean()):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")

@@ -560,6 +560,46 @@ int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, float row_sc
 int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1, float beta2,
                        float eps, float max_norm, float *grad_norm, void *stream);
 
+/* Per-agent standardisation of a float32 [R][N] array with the agent on the fastest axis (the layout of a window's advantages
+ * adv [T][E][N], R = T E); y == x (in place) is allowed.  Per agent i, with every float32 widened to float64 first:
+ *   mean_i = (1/R) sum_r x[r][i],   std_i = sqrt((1/R) sum_r (x[r][i] - mean_i)^2)   (the population form),
+ *   y[r][i] = (float)(((double)x[r][i] - mean_i) / (std_i + eps))   (formed as a product with the float64 reciprocal of
+ *   std_i + eps: within 2^-52 of the quotient before the rounding to float; 0 where std_i + eps == 0).
+ * stats, float32 [2][N] = (mean, std), is written by the kernels and may be NULL.  The second moment is taken about values of the
+ * column itself, not as sum x^2 - R mean^2: a column at -500 +- 0.5 keeps its variance.  A column whose values are all equal
+ * gives y = 0 exactly (no NaN, no inf); so does R = 1.
+ * Deterministic: the rows are cut into slabs by a rule that depends on (R, N) only; one launch writes per-slab, per-agent
+ * float64 partials into ws, a second folds them in a fixed ascending order and applies the map.  No float atomics, no memset
+ * node, no host synchronisation: two calls on the same input give the same bits (in place or not, 16-byte aligned or not), and a
+ * call inside a captured graph replays to the eager result.  ws: at least the bytes the workspace query returns for (R, N),
+ * 8-byte aligned.
+ * EINVAL: R < 1, N < 1, NULL x / y / ws, a short ws, eps < 0 (or NaN).                                                         */
+int dronesim_standardize_workspace(int R, int N, size_t *bytes);
+int dronesim_standardize(const float *x, float *y, float *stats, int R, int N, float eps, void *ws, size_t ws_bytes, void *stream);
+
+/* The actor losses above with an entropy bonus, actors only (out_kind 1 or 2; a critic is EINVAL): the chunked chain of the
+ * sibling entry point -- same GEMM launches, same workspace front part -- around a head that also carries the policy's entropy.
+ * The loss of agent i becomes  L_i - ent_scale sum_r H_i(x_r)  (ent_scale = ent_coef / R: -ent_coef x the mean row entropy,
+ * whatever row_scale the other term has); finite ent_scale >= 0.  Per row, in float32, with the expressions the heads form:
+ *   out_kind 1:  lq_j = o_j - lse,  p_j = exp(lq_j),  H = -sum_j p_j lq_j;   dO_j += ent_scale p_j (lq_j + H)
+ *                (H comes from lq, never from log(p): a saturated row has p_j = 0 and stays finite)
+ *   out_kind 2:  H = sum_d 0.5 log(2 pi e var_d);   dO_{2+d} += -0.5 ent_scale (1 - var_d);   the mu outputs get nothing
+ * In the PPO form the entropy's gradient is added on EVERY row, the rows on the clipped branch included.  loss [N] is the whole
+ * objective (the sibling's term minus the entropy term).  entropy float32 [N] (PPO form: stats is float32 [5][N] and
+ * stats[4][i] the entropy, stats[0..3] as above) is OVERWRITTEN with the MEAN row entropy of agent i, reduced from a per-row plane
+ * in the fixed order of the loss.  ws: at least the bytes of the entry point's own workspace query (the sibling's workspace +
+ * 4 N rows_per_chunk for the row entropies).  With ent_scale = 0 gradients, loss and stats[0..3] compare equal, element by
+ * element, to the sibling's on the same inputs (an exact zero is added); the log-probability is the one dronesim_mlp_logp
+ * computes, so with its logp_old the ratio is exactly 1 for any ent_scale.                                                      */
+int dronesim_mlp_grad_ent_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
+int dronesim_mlp_grad_ent(const DroneMlp *m, const float *x, int R, float row_scale, const float *act, const float *weight,
+                          float ent_scale, float *grad, float *loss, float *entropy, int rows_per_chunk, void *ws, size_t ws_bytes,
+                          void *stream);
+int dronesim_mlp_grad_ppo_ent_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
+int dronesim_mlp_grad_ppo_ent(const DroneMlp *m, const float *x, int R, float row_scale, const float *act, const float *logp_old,
+                              const float *adv, float clip_eps, float ent_scale, float *grad, float *loss, float *stats,
+                              int rows_per_chunk, void *ws, size_t ws_bytes, void *stream);
+
 const char *dronesim_last_error(void);
 const char *dronesim_error_string(int code);
 int dronesim_version(void);

@@ -32,6 +32,8 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_mlp_forward_bf16x3", "dronesim_mlp_forward_f16x2", "dronesim_mlp_bf16x3_stages", "dronesim_mlp_rt_blocks", "dronesim_mlp_rt16_blocks", "dronesim_mlp_forward_f16x2_rt",
            "dronesim_mlp_grad_workspace", "dronesim_mlp_grad", "dronesim_adam_step",
            "dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo",
+           "dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
+           "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent",
            "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
@@ -158,6 +160,14 @@ def lib():
     L.dronesim_mlp_logp.argtypes = [PM, vp, i32, vp, vp, i32, vp, C.c_size_t, vp]
     L.dronesim_mlp_grad_ppo.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
     for name in ("dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo"):
+        getattr(L, name).restype = C.c_int
+    L.dronesim_standardize_workspace.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
+    L.dronesim_standardize.argtypes = [vp, vp, vp, i32, i32, f32, vp, C.c_size_t, vp]
+    L.dronesim_mlp_grad_ent_workspace.argtypes = L.dronesim_mlp_grad_ppo_ent_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
+    L.dronesim_mlp_grad_ent.argtypes = [PM, vp, i32, f32, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    L.dronesim_mlp_grad_ppo_ent.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    for name in ("dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
+                 "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent"):
         getattr(L, name).restype = C.c_int
     L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
     L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]

@@ -20,6 +20,11 @@
 // around another head: ppo_head_kernel computes log pi(a | x) with the expressions of the actor kinds above and either stops there
 // (the forward-only pass: the old policy's log-probabilities) or forms the ratio to a stored logp_old, the clipped surrogate's
 // per-row loss and dLoss/dO, plus three per-row diagnostics that ppo_stats_kernel reduces per agent in a fixed order.
+//
+// Two opt-in parts of the learners (include/dronesim.h): the entropy bonus -- head_ent_kernel / ppo_head_ent_kernel, the two actor
+// heads with the policy's entropy in the loss, kernels of their own behind the same chain (dronesim_mlp_grad_ent,
+// dronesim_mlp_grad_ppo_ent) -- and dronesim_standardize, the per-agent standardisation of a window's advantages (float64 sums,
+// two launches, fixed order).
 #include "common.hpp"
 #include "../../include/dronesim.h"
 
@@ -302,6 +307,153 @@ __global__ __launch_bounds__(kThreads) void ppo_stats_kernel(const float *S, lon
     }
 }
 
+// The entropy bonus (include/dronesim.h: dronesim_mlp_grad_ent, dronesim_mlp_grad_ppo_ent): the two actor heads above with the
+// policy's entropy H of the row in the loss, L_i - es sum_r H_i(x_r).  Kernels of their own -- the heads above keep their code
+// -- that form every value the siblings form with the same expressions and ADD the entropy's part, so with es = 0 they give
+// the siblings' values (an exact zero is added) and the log-probability is the one dronesim_mlp_logp computes.
+//   softmax:   lq_j = o_j - lse,  p_j = exp(lq_j),  H = -sum_j p_j lq_j;    dO_j += es p_j (lq_j + H)
+//              (from lq, never log p: a logit 120 below the maximum has p = 0 in float32 and 0 log 0 is NaN)
+//   Gaussian:  H = sum_d 0.5 log(2 pi e var_d);                             dO_{2+d} += -0.5 es (1 - var_d)  (the head's omv)
+// The per-row loss is the whole objective (the sibling's l - es H); H itself goes to the plane E [N][Rc].
+__global__ __launch_bounds__(kThreads) void head_ent_kernel(float *O, float *L, float *E, long long Rc, int rc, long long r0, int N,
+                                                            int nout, int kind, float scale, float es, const float *act,
+                                                            const float *weight)
+{
+    const long long id = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (id >= (long long)rc * N) return;
+    const int i = (int)(id / rc), m = (int)(id % rc);
+    float *o = O + ((long long)i * Rc + m) * nout;
+    const long long src = (r0 + m) * N + i;
+    float loss, H = 0.f;
+    if (kind == 1) {
+        const float ax = act[2 * src], ay = act[2 * src + 1];
+        int a = (int)rintf(atan2f(ay, ax) * (float)nout * 0.15915494309189535f);
+        a = ((a % nout) + nout) % nout;
+        float mx = o[0];
+        for (int j = 1; j < nout; ++j) mx = fmaxf(mx, o[j]);
+        float s = 0.f;
+        for (int j = 0; j < nout; ++j) s += expf(o[j] - mx);
+        const float lse = mx + logf(s);
+        const float c = -scale * weight[src];
+        loss = c * (o[a] - lse);
+        for (int j = 0; j < nout; ++j) {
+            const float lq = o[j] - lse;
+            H -= expf(lq) * lq;
+        }
+        for (int j = 0; j < nout; ++j) {
+            const float p = expf(o[j] - lse);
+            const float g = c * ((j == a ? 1.f : 0.f) - p);
+            o[j] = g + es * (p * ((o[j] - lse) + H));
+        }
+    } else {
+        const float c = -scale * weight[src];
+        float lp = 0.f;
+        for (int d = 0; d < 2; ++d) {
+            const float mu = tanhf(o[d]);
+            const float e = expf(-o[2 + d]);
+            const float var = 1.f / (1.f + e), omv = e / (1.f + e);
+            const float diff = act[2 * src + d] - mu;
+            lp += -0.5f * logf(6.283185307179586f * var) - diff * diff / (2.f * var);
+            H += 0.5f * logf(17.079468445347132f * var);
+            o[d] = c * (diff / var) * (1.f - mu * mu);
+            const float g = c * (-0.5f + diff * diff / (2.f * var)) * omv;
+            o[2 + d] = g - 0.5f * es * omv;
+        }
+        loss = c * lp;
+    }
+    L[(long long)i * Rc + m] = loss - es * H;
+    E[(long long)i * Rc + m] = H;
+}
+
+// ppo_head_kernel's gradient mode with the entropy (no forward-only mode: dronesim_mlp_logp stays the sibling's).  The entropy's
+// gradient is added on EVERY row, the rows on the clipped branch included (there the surrogate's part is 0).
+__global__ __launch_bounds__(kThreads) void ppo_head_ent_kernel(float *O, float *L, float *S, float *E, long long Rc, int rc,
+                                                                long long r0, int N, int nout, int kind, float scale, float es,
+                                                                const float *act, const float *logp_old, const float *adv,
+                                                                float lo, float hi)
+{
+    const long long id = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (id >= (long long)rc * N) return;
+    const int i = (int)(id / rc), m = (int)(id % rc);
+    float *o = O + ((long long)i * Rc + m) * nout;
+    const long long src = (r0 + m) * N + i;
+    float lp, lse = 0.f, H = 0.f;
+    int a = 0;
+    float mu[2], var[2], omv[2], diff[2];
+    if (kind == 1) {
+        const float ax = act[2 * src], ay = act[2 * src + 1];
+        a = (int)rintf(atan2f(ay, ax) * (float)nout * 0.15915494309189535f);
+        a = ((a % nout) + nout) % nout;
+        float mx = o[0];
+        for (int j = 1; j < nout; ++j) mx = fmaxf(mx, o[j]);
+        float s = 0.f;
+        for (int j = 0; j < nout; ++j) s += expf(o[j] - mx);
+        lse = mx + logf(s);
+        lp = o[a] - lse;
+        for (int j = 0; j < nout; ++j) {
+            const float lq = o[j] - lse;
+            H -= expf(lq) * lq;
+        }
+    } else {
+        lp = 0.f;
+        for (int d = 0; d < 2; ++d) {
+            mu[d] = tanhf(o[d]);
+            const float e = expf(-o[2 + d]);
+            var[d] = 1.f / (1.f + e);
+            omv[d] = e / (1.f + e);
+            diff[d] = act[2 * src + d] - mu[d];
+            lp += -0.5f * logf(6.283185307179586f * var[d]) - diff[d] * diff[d] / (2.f * var[d]);
+        }
+        for (int d = 0; d < 2; ++d) H += 0.5f * logf(17.079468445347132f * var[d]);
+    }
+    const float dl = lp - logp_old[src];
+    const float r = expf(dl);
+    const float A = adv[src];
+    const bool clipped = (A > 0.f && r > hi) || (A < 0.f && r < lo);
+    const float c = clipped ? 0.f : -scale * A * r;
+    if (kind == 1) {
+        for (int j = 0; j < nout; ++j) {
+            const float p = expf(o[j] - lse);
+            const float g = c * ((j == a ? 1.f : 0.f) - p);
+            o[j] = g + es * (p * ((o[j] - lse) + H));
+        }
+    } else {
+        for (int d = 0; d < 2; ++d) {
+            o[d] = c * (diff[d] / var[d]) * (1.f - mu[d] * mu[d]);
+            const float g = c * (-0.5f + diff[d] * diff[d] / (2.f * var[d])) * omv[d];
+            o[2 + d] = g - 0.5f * es * omv[d];
+        }
+    }
+    const long long dst = (long long)i * Rc + m, plane = (long long)N * Rc;
+    const float l = -scale * fminf(r * A, fminf(fmaxf(r, lo), hi) * A);
+    L[dst] = l - es * H;
+    S[dst] = clipped ? 1.f : 0.f;
+    S[plane + dst] = -dl;
+    S[2 * plane + dst] = r;
+    E[dst] = H;
+}
+
+// entropy[i] = the mean row entropy of agent i over the chunks, in loss_sum_kernel's fixed order (strided partials, then a fixed
+// tree); the first chunk writes, the last divides by R
+__global__ __launch_bounds__(kThreads) void entropy_sum_kernel(const float *E, long long Rc, int rc, int first, int last, float rows,
+                                                               float *entropy)
+{
+    __shared__ float part[kThreads];
+    const int i = blockIdx.x;
+    float s = 0.f;
+    for (int m = threadIdx.x; m < rc; m += kThreads) s += E[(long long)i * Rc + m];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        s = first ? part[0] : entropy[i] + part[0];
+        entropy[i] = last ? s / rows : s;
+    }
+}
+
 struct Tensors {
     long long size[6];      // per agent: w1, b1, w2, b2, w3, b3
     long long off[6];       // of the [N, ...] tensor in the flat buffer
@@ -430,9 +582,15 @@ struct PpoArgs {
     float *logp_out;       // set: forward + log-probabilities only
 };
 
+// what the entropy entry points add to the chain (NULL for the others): the heads with the entropy term, one more per-row plane
+struct EntArgs {
+    float scale;           // ent_scale
+    float *entropy;        // [N]: the mean row entropy (dronesim_mlp_grad_ppo_ent: stats + 4 N)
+};
+
 // The chunked chain of the header comment over all R rows; arguments validated by the entry points.
 int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const float *target, const float *act, const float *weight,
-              const PpoArgs *ppo, float *grad, float *loss, int rows_per_chunk, void *ws, hipStream_t st)
+              const PpoArgs *ppo, const EntArgs *ent, float *grad, float *loss, int rows_per_chunk, void *ws, hipStream_t st)
 {
     const int N = m->N, din = m->d_in, h1 = m->h1, h2 = m->h2, no = m->nout;
     const long long Rc = rows_per_chunk;
@@ -440,6 +598,7 @@ int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const f
     float *gw1 = grad + t.off[0], *gb1 = grad + t.off[1], *gw2 = grad + t.off[2];
     float *gb2 = grad + t.off[3], *gw3 = grad + t.off[4], *gb3 = grad + t.off[5];
     float *H1 = (float *)ws, *H2 = H1 + N * Rc * h1, *O = H2 + N * Rc * h2, *L = O + N * Rc * no, *S = L + N * Rc;
+    float *En = ppo ? S + 3 * N * Rc : S;         // the row entropies, behind the sibling's workspace
 
     const long long xs = (long long)N * din;      // row stride of x
     for (long long r0 = 0; r0 < R; r0 += Rc) {
@@ -459,7 +618,13 @@ int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const f
         // head
         const long long items = (long long)rc * N;
         const dim3 hgrid((unsigned)((items + kThreads - 1) / kThreads));
-        if (ppo)
+        if (ent && ppo)
+            hipLaunchKernelGGL(ppo_head_ent_kernel, hgrid, dim3(kThreads), 0, st, O, L, S, En, Rc, rc, r0, N, no, m->out_kind, row_scale,
+                               ent->scale, act, ppo->logp_old, ppo->adv, ppo->lo, ppo->hi);
+        else if (ent)
+            hipLaunchKernelGGL(head_ent_kernel, hgrid, dim3(kThreads), 0, st, O, L, En, Rc, rc, r0, N, no, m->out_kind, row_scale,
+                               ent->scale, act, weight);
+        else if (ppo)
             hipLaunchKernelGGL(ppo_head_kernel, hgrid, dim3(kThreads), 0, st, O, L, S, Rc, rc, r0, N, no, m->out_kind, row_scale, act,
                                ppo->logp_old, ppo->adv, ppo->lo, ppo->hi, ppo->logp_out);
         else
@@ -487,6 +652,9 @@ int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const f
         if (ppo)
             hipLaunchKernelGGL(ppo_stats_kernel, dim3(N), dim3(kThreads), 0, st, S, Rc, rc, N, (int)(r0 == 0), (int)(r0 + Rc >= R),
                                (float)R, ppo->stats);
+        if (ent)
+            hipLaunchKernelGGL(entropy_sum_kernel, dim3(N), dim3(kThreads), 0, st, En, Rc, rc, (int)(r0 == 0), (int)(r0 + Rc >= R),
+                               (float)R, ent->entropy);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
@@ -517,7 +685,315 @@ size_t ppo_workspace_bytes(const DroneMlp *m, int rc)
     return workspace_bytes(m, rc) + sizeof(float) * (size_t)m->N * (size_t)rc * 3;
 }
 
+// the entropy heads' row-entropy plane behind the sibling's workspace
+size_t ent_workspace_bytes(const DroneMlp *m, int rc, bool ppo)
+{
+    return (ppo ? ppo_workspace_bytes(m, rc) : workspace_bytes(m, rc)) + sizeof(float) * (size_t)m->N * (size_t)rc;
+}
+
+// Per-agent standardisation of x [R][N] (include/dronesim.h: dronesim_standardize), two launches over one decomposition that
+// depends on (R, N) only:
+//   lane group   V = 4 adjacent columns where N % 4 == 0 (one 16-byte access where the pointers allow it), else 1
+//   column tile  `tw` lane groups: 16 (64 floats, 256 contiguous bytes per row) where N % 64 == 0 -- at N = 64 the whole row --,
+//                else the whole row, capped so that a tile has at most 1024 columns
+//   iteration    a workgroup of 1024 lanes covers q = 1024 / tw rows of its tile at once: lane t holds row t / tw, group t % tw,
+//                i.e. flat position t of the q x tw block (with one tile per row: of the flat array) -- N = 5 or 70 walk the
+//                array contiguously with 1020 / 980 lanes, and a lane meets the same columns in every iteration
+//   slab         `rps` rows (a multiple of q); S slabs x tiles workgroups aim at kStdBlocks, one per CU
+// Pass 1: every lane of a column shifts by the same K, the column's value in the slab's first row (a value of the column: no
+// cancellation at -500 +- 0.5), and accumulates in double the sums of d = x - K and of d^2; the q lanes of a column are folded
+// through LDS by ONE fixed tree (both sums per level) into the slab's sum rows K + sum d and its second moment about the slab's
+// own mean, sum d^2 - (sum d)^2 / rows: ws [S][2][N].  Nothing but the tree and one division per column follows the loop.
+// Pass 2: every workgroup requests its first kStdPre iterations of rows, then folds the S partials of its tile's columns in ONE
+// sweep -- up to kStdRuns contiguous runs of slabs, one lane each, ascending, then the runs ascending: the plain sums (mean), and the
+// moments about slab 0's mean m0, sum_s (m2_s + e_s^2 / n_s) with e_s = sum_s - n_s m0, which - (sum_s e_s)^2 / R is the moment
+// about the mean -- into mean and 1 / (std + eps), and maps its rows.  An all-equal column has K = c, d = 0, sum = rows c and
+// e_s = 0 exactly.  The tile rule keeps that fold at S x 64 x 16 bytes per workgroup for the wide shapes (C5 shard: 64 KiB).
+constexpr int kStdThreads = 1024, kStdBlocks = 256, kStdRuns = 32, kStdPre = 4;
+
+struct StdPlan {
+    int V, tw, tiles, q, S;
+    long long rps;
+};
+
+StdPlan std_plan(int R, int N)
+{
+    StdPlan p;
+    p.V = N % 4 == 0 ? 4 : 1;
+    const int nv = N / p.V, cap = kStdThreads / p.V;
+    p.tw = (p.V == 4 && N % 64 == 0) ? 16 : (nv <= cap ? nv : cap);
+    p.tiles = (nv + p.tw - 1) / p.tw;
+    p.q = kStdThreads / p.tw;
+    const long long iters = ((long long)R + p.q - 1) / p.q;
+    long long want = kStdBlocks / p.tiles;
+    want = want < 1 ? 1 : (want > iters ? iters : want);
+    p.rps = ((iters + want - 1) / want) * p.q;
+    p.S = (int)(((long long)R + p.rps - 1) / p.rps);
+    return p;
+}
+
+typedef float std_f4 __attribute__((ext_vector_type(4)));
+
+// NT: the last use of the element (pass 2 reads a row once more and writes it once), as the return scans do
+template <int V, bool VEC, bool NT>
+__device__ __forceinline__ void std_load(const float *p, float (&v)[V])
+{
+    if (VEC) {
+        const std_f4 f = NT ? __builtin_nontemporal_load(reinterpret_cast<const std_f4 *>(p)) : *reinterpret_cast<const std_f4 *>(p);
+        v[0] = f.x; v[V > 1 ? 1 : 0] = f.y; v[V > 2 ? 2 : 0] = f.z; v[V > 3 ? 3 : 0] = f.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = NT ? __builtin_nontemporal_load(p + k) : p[k];
+    }
+}
+
+template <int V, bool VEC>
+__device__ __forceinline__ void std_store(float *o, const float (&v)[V])
+{
+    if (VEC) {
+        std_f4 f;
+        f.x = v[0]; f.y = v[V > 1 ? 1 : 0]; f.z = v[V > 2 ? 2 : 0]; f.w = v[V > 3 ? 3 : 0];
+        __builtin_nontemporal_store(f, reinterpret_cast<std_f4 *>(o));
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) __builtin_nontemporal_store(v[k], o + k);
+    }
+}
+
+template <int V, bool VEC>
+__global__ __launch_bounds__(kStdThreads) void standardize_sums_kernel(const float *__restrict__ x, double *__restrict__ ws, int R,
+                                                                       int N, int tw, int q, int qp, long long rps)
+{
+    __shared__ double b1[kStdThreads][V], b2[kStdThreads][V];
+    const int t = threadIdx.x, rl = t / tw, g = blockIdx.y * tw + t % tw;
+    const bool lane_on = rl < q && g * V < N;
+    const long long r_begin = (long long)blockIdx.x * rps;
+    const long long r_end = r_begin + rps < R ? r_begin + rps : R;
+    double sd[V], sd2[V], k0[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) sd[k] = sd2[k] = k0[k] = 0.0;
+    if (lane_on) {
+        float v[V];
+        std_load<V, VEC, false>(x + (size_t)r_begin * N + (size_t)g * V, v);   // K: the slab's first row (cached: one read per
+                                                                                 // column tile; its owners meet it again at j = 0)
+#pragma unroll
+        for (int k = 0; k < V; ++k) k0[k] = (double)v[k];
+        if (r_begin + rl < r_end) {
+            const float *p = x + (size_t)(r_begin + rl) * N + (size_t)g * V;
+            const size_t step = (size_t)q * N;
+            const long long n = (r_end - r_begin - rl + q - 1) / q;
+#pragma unroll 4
+            for (long long j = 0; j < n; ++j) {
+                std_load<V, VEC, false>(p + j * step, v);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const double d = (double)v[k] - k0[k];
+                    sd[k] += d;
+                    sd2[k] = fma(d, d, sd2[k]);
+                }
+            }
+        }
+    }
+    // fixed tree over the q lanes (rows) of a column: b[t] += b[t + w tw], w = qp / 2 .. 1 (qp = q rounded up to 2^n)
+#pragma unroll
+    for (int k = 0; k < V; ++k) { b1[t][k] = sd[k]; b2[t][k] = sd2[k]; }
+    for (int w = qp >> 1; w > 0; w >>= 1) {
+        __syncthreads();
+        if (lane_on && rl < w && rl + w < q) {
+#pragma unroll
+            for (int k = 0; k < V; ++k) { b1[t][k] += b1[t + w * tw][k]; b2[t][k] += b2[t + w * tw][k]; }
+        }
+    }
+    if (lane_on && rl == 0) {                                            // (its own sums: the last level's writer)
+        const double rows = (double)(r_end - r_begin);
+        double *o = ws + (size_t)blockIdx.x * 2 * N + (size_t)g * V;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const double s = b1[t][k];
+            o[k] = fma(rows, k0[k], s);
+            o[N + k] = fmax(b2[t][k] - s * s / rows, 0.0);
+        }
+    }
+}
+
+template <int V, bool VEC>
+__global__ __launch_bounds__(kStdThreads) void standardize_apply_kernel(const float *x, float *y, const double *__restrict__ ws,
+                                                                        float *__restrict__ stats, int R, int N, int tw, int q,
+                                                                        long long rps, int S, float eps)
+{
+    __shared__ double part[3][kStdThreads], mean_s[kStdThreads], inv_s[kStdThreads];
+    const int t = threadIdx.x;
+    // the map's first rows, requested before the fold: lane t at row t / tw, group t % tw, as in pass 1
+    const int rl = t / tw, gl = t % tw, g = blockIdx.y * tw + gl;
+    const long long r_begin = (long long)blockIdx.x * rps;
+    const long long r_end = r_begin + rps < R ? r_begin + rps : R;
+    const bool map_on = rl < q && g * V < N && r_begin + rl < r_end;
+    const long long n = map_on ? (r_end - r_begin - rl + q - 1) / q : 0;
+    const size_t at = (size_t)(r_begin + rl) * N + (size_t)g * V, step = (size_t)q * N;
+    float pv[kStdPre][V];
+#pragma unroll
+    for (int u = 0; u < kStdPre; ++u) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) pv[u][k] = 0.f;
+        if (u < n) std_load<V, VEC, true>(x + at + u * step, pv[u]);
+    }
+    const int c0 = blockIdx.y * tw * V;                                  // the tile's first column
+    const int nc = (N - c0) < tw * V ? (N - c0) : tw * V;                // its columns (<= 1024)
+    // the fold: lane (run, column) takes the slabs [run ch, (run + 1) ch) in ascending order, lane (0, column) then the runs
+    const int runs = kStdThreads / nc < kStdRuns ? kStdThreads / nc : kStdRuns, run = t / nc, col = t % nc;
+    const int ch = (S + runs - 1) / runs;
+    const int s_lo = run * ch, s_hi = (s_lo + ch) < S ? (s_lo + ch) : S;
+    const double n_full = (double)(rps < R ? rps : R), n_last = (double)(R - (long long)(S - 1) * rps);
+    double a = 0.0, b = 0.0, e1 = 0.0;
+    if (run < runs && s_lo < s_hi) {
+        const double m0 = ws[c0 + col] / n_full, inv_full = 1.0 / n_full, inv_last = 1.0 / n_last;
+#pragma unroll 8
+        for (int s = s_lo; s < s_hi; ++s) {
+            const double sum = ws[(size_t)s * 2 * N + c0 + col], m2 = ws[(size_t)s * 2 * N + N + c0 + col];
+            const double ns = s == S - 1 ? n_last : n_full, e = fma(-ns, m0, sum);
+            a += sum;
+            e1 += e;
+            b += fma(e * e, s == S - 1 ? inv_last : inv_full, m2);
+        }
+    }
+    part[0][t] = a;
+    part[1][t] = b;
+    part[2][t] = e1;
+    __syncthreads();
+    if (t < nc) {
+        double tot = 0.0, m2 = 0.0, es = 0.0;
+        for (int u = 0; u < runs; ++u) {
+            tot += part[0][u * nc + t];
+            m2 += part[1][u * nc + t];
+            es += part[2][u * nc + t];
+        }
+        const double mean = tot / (double)R;
+        const double sd = sqrt(fmax(m2 - es * es / (double)R, 0.0) / (double)R), den = sd + (double)eps;
+        mean_s[t] = mean;
+        inv_s[t] = den > 0.0 ? 1.0 / den : 0.0;                          // (an all-equal column at eps = 0: y = 0, not 0 / 0)
+        if (stats && blockIdx.x == 0) {
+            stats[c0 + t] = (float)mean;
+            stats[N + c0 + t] = (float)sd;
+        }
+    }
+    __syncthreads();
+    // the map: y = (x - mean) * (1 / (std + eps)) in double (within 2^-52 of the quotient before the rounding to float)
+    if (!map_on) return;
+    double mean[V], inv[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) { mean[k] = mean_s[gl * V + k]; inv[k] = inv_s[gl * V + k]; }
+#pragma unroll
+    for (int u = 0; u < kStdPre; ++u) {
+        if (u < n) {
+            float v[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) v[k] = (float)(((double)pv[u][k] - mean[k]) * inv[k]);
+            std_store<V, VEC>(y + at + u * step, v);
+        }
+    }
+#pragma unroll 4
+    for (long long j = kStdPre; j < n; ++j) {
+        float v[V];
+        std_load<V, VEC, true>(x + at + j * step, v);
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = (float)(((double)v[k] - mean[k]) * inv[k]);
+        std_store<V, VEC>(y + at + j * step, v);
+    }
+}
+
 }  // namespace
+
+extern "C" int dronesim_standardize_workspace(int R, int N, size_t *bytes)
+{
+    if (R < 1 || N < 1) return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize_workspace: R < 1 or N < 1");
+    if (!bytes) return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize_workspace: NULL bytes");
+    *bytes = sizeof(double) * 2 * (size_t)std_plan(R, N).S * (size_t)N;
+    return DRONESIM_OK;
+}
+
+extern "C" int dronesim_standardize(const float *x, float *y, float *stats, int R, int N, float eps, void *ws, size_t ws_bytes,
+                                    void *stream)
+{
+    if (R < 1 || N < 1) return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize: R < 1 or N < 1");
+    if (!x || !y || !ws) return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize: NULL x / y / workspace");
+    if (!(eps >= 0.f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize: eps must be >= 0");
+    const StdPlan p = std_plan(R, N);
+    if (ws_bytes < sizeof(double) * 2 * (size_t)p.S * (size_t)N)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize: workspace smaller than dronesim_standardize_workspace()");
+    if (reinterpret_cast<uintptr_t>(ws) & 7u) return dronesim_fail(DRONESIM_EINVAL, "dronesim_standardize: workspace not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int qp = 1;
+    while (qp < p.q) qp <<= 1;
+    const dim3 grid((unsigned)p.S, (unsigned)p.tiles), block(kStdThreads);
+    double *w = (double *)ws;
+    // 16-byte accesses where every lane group starts 16-byte aligned; the lanes' columns and rows do not depend on it
+    const bool vec = p.V == 4 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
+    if (vec) {
+        hipLaunchKernelGGL((standardize_sums_kernel<4, true>), grid, block, 0, st, x, w, R, N, p.tw, p.q, qp, p.rps);
+        hipLaunchKernelGGL((standardize_apply_kernel<4, true>), grid, block, 0, st, x, y, w, stats, R, N, p.tw, p.q, p.rps, p.S, eps);
+    } else if (p.V == 4) {
+        hipLaunchKernelGGL((standardize_sums_kernel<4, false>), grid, block, 0, st, x, w, R, N, p.tw, p.q, qp, p.rps);
+        hipLaunchKernelGGL((standardize_apply_kernel<4, false>), grid, block, 0, st, x, y, w, stats, R, N, p.tw, p.q, p.rps, p.S, eps);
+    } else {
+        hipLaunchKernelGGL((standardize_sums_kernel<1, false>), grid, block, 0, st, x, w, R, N, p.tw, p.q, qp, p.rps);
+        hipLaunchKernelGGL((standardize_apply_kernel<1, false>), grid, block, 0, st, x, y, w, stats, R, N, p.tw, p.q, p.rps, p.S, eps);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+extern "C" int dronesim_mlp_grad_ent_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
+{
+    const int rc = check_actor_call(m, 1, rows_per_chunk, "dronesim_mlp_grad_ent_workspace");
+    if (rc != DRONESIM_OK) return rc;
+    if (!bytes) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ent_workspace: NULL bytes");
+    *bytes = ent_workspace_bytes(m, rows_per_chunk, false);
+    return DRONESIM_OK;
+}
+
+extern "C" int dronesim_mlp_grad_ppo_ent_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
+{
+    const int rc = check_actor_call(m, 1, rows_per_chunk, "dronesim_mlp_grad_ppo_ent_workspace");
+    if (rc != DRONESIM_OK) return rc;
+    if (!bytes) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_ent_workspace: NULL bytes");
+    *bytes = ent_workspace_bytes(m, rows_per_chunk, true);
+    return DRONESIM_OK;
+}
+
+extern "C" int dronesim_mlp_grad_ent(const DroneMlp *m, const float *x, int R, float row_scale, const float *act, const float *weight,
+                                     float ent_scale, float *grad, float *loss, float *entropy, int rows_per_chunk, void *ws,
+                                     size_t ws_bytes, void *stream)
+{
+    const int rc = check_actor_call(m, R, rows_per_chunk, "dronesim_mlp_grad_ent");
+    if (rc != DRONESIM_OK) return rc;
+    if (!x || !act || !weight || !grad || !loss || !entropy || !ws)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ent: NULL x / act / weight / grad / loss / entropy / workspace");
+    if (!(ent_scale >= 0.f) || isinf(ent_scale)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ent: ent_scale must be finite and >= 0");
+    if (ws_bytes < ent_workspace_bytes(m, rows_per_chunk, false))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ent: workspace smaller than dronesim_mlp_grad_ent_workspace()");
+    EntArgs en = {ent_scale, entropy};
+    return run_chain(m, x, R, row_scale, nullptr, act, weight, nullptr, &en, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+}
+
+extern "C" int dronesim_mlp_grad_ppo_ent(const DroneMlp *m, const float *x, int R, float row_scale, const float *act,
+                                         const float *logp_old, const float *adv, float clip_eps, float ent_scale, float *grad,
+                                         float *loss, float *stats, int rows_per_chunk, void *ws, size_t ws_bytes, void *stream)
+{
+    const int rc = check_actor_call(m, R, rows_per_chunk, "dronesim_mlp_grad_ppo_ent");
+    if (rc != DRONESIM_OK) return rc;
+    if (!x || !act || !logp_old || !adv || !grad || !loss || !stats || !ws)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_ent: NULL x / act / logp_old / adv / grad / loss / stats / workspace");
+    if (!(clip_eps > 0.f && clip_eps < 1.f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_ent: clip_eps must be in (0, 1)");
+    if (!(ent_scale >= 0.f) || isinf(ent_scale))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_ent: ent_scale must be finite and >= 0");
+    if (ws_bytes < ent_workspace_bytes(m, rows_per_chunk, true))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_ent: workspace smaller than dronesim_mlp_grad_ppo_ent_workspace()");
+    PpoArgs p = {};
+    p.logp_old = logp_old; p.adv = adv; p.lo = 1.f - clip_eps; p.hi = 1.f + clip_eps; p.stats = stats;
+    EntArgs en = {ent_scale, stats + 4 * (size_t)m->N};
+    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, &en, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+}
 
 extern "C" int dronesim_mlp_grad_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
 {
@@ -545,7 +1021,7 @@ extern "C" int dronesim_mlp_grad(const DroneMlp *m, const float *x, int R, float
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad: rows_per_chunk must be a positive multiple of 64");
     if (ws_bytes < workspace_bytes(m, rows_per_chunk))
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad: workspace smaller than dronesim_mlp_grad_workspace()");
-    return run_chain(m, x, R, row_scale, target, act, weight, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, row_scale, target, act, weight, nullptr, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_mlp_grad_ppo_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
@@ -568,7 +1044,7 @@ extern "C" int dronesim_mlp_logp(const DroneMlp *m, const float *x, int R, const
     PpoArgs p = {};
     p.logp_out = logp;
     // (grad and loss are not touched by the forward-only chain; the workspace stands in for their base address)
-    return run_chain(m, x, R, 1.f, nullptr, act, nullptr, &p, (float *)ws, nullptr, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, 1.f, nullptr, act, nullptr, &p, nullptr, (float *)ws, nullptr, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, float row_scale, const float *act,
@@ -584,7 +1060,7 @@ extern "C" int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, f
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo: workspace smaller than dronesim_mlp_grad_ppo_workspace()");
     PpoArgs p = {};
     p.logp_old = logp_old; p.adv = adv; p.lo = 1.f - clip_eps; p.hi = 1.f + clip_eps; p.stats = stats;
-    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,

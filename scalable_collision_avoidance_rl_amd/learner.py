@@ -14,6 +14,10 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
   time_limit= of both  dronesim_episode_ends, dronesim_lambda_returns_ends   with ``"bootstrap"`` a time-limit episode end is a
                                        truncation: its return bootstraps from the critic's value of the episode's terminal
                                        observation (``storage.z_final``) instead of stopping there (default ``"terminal"``)
+  ent_coef= of both    dronesim_mlp_grad_ent, dronesim_mlp_grad_ppo_ent   an entropy bonus in the actor loss, -ent_coef x the
+                                       mean row entropy of the window (default 0: off, the calls above)
+  normalize_advantage= of PPOLearner   dronesim_standardize   agent i's advantages standardised over the window's T E rows,
+                                       once per window before the epochs (default off)
 
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
@@ -182,6 +186,65 @@ class GradientRunner:
         _native.check(rc, "dronesim_mlp_grad_ppo")
         return self.grad, loss, stats
 
+    # the entropy forms (actors only): the sibling's chunks and workspace, grown once by the plane of the row entropies
+    def _ent_workspace(self, ppo):
+        import torch
+        from . import _native
+        n = C.c_size_t(0)
+        name = "dronesim_mlp_grad_ppo_ent_workspace" if ppo else "dronesim_mlp_grad_ent_workspace"
+        _native.check(getattr(_native.lib(), name)(C.byref(self._m), self.rc, C.byref(n)), name)
+        if int(n.value) > self.ws.numel() * 4:
+            self.ws = torch.empty(int(n.value) // 4, device=self.mlp.device)
+        if ppo:
+            self.ppo_ent_ws_bytes = int(n.value)
+            self.stats5 = torch.zeros(5, self.mlp.n_agents, device=self.mlp.device)
+        else:
+            self.ent_ws_bytes = int(n.value)
+            self.entropy = torch.zeros(self.mlp.n_agents, device=self.mlp.device)
+
+    def run_ent(self, x, row_scale, act, weight, ent_scale, loss_out=None, entropy_out=None):
+        """`dronesim_mlp_grad_ent`: returns ``(grad, loss [N], entropy [N])`` -- the loss is the whole objective
+        (``run``'s minus ``ent_scale`` x the summed row entropies), entropy the mean row entropy per agent."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, act=(act, 2), weight=(weight, 1))
+        if not hasattr(self, "entropy"):
+            self._ent_workspace(False)
+        loss = self.loss if loss_out is None else loss_out
+        ent = self.entropy if entropy_out is None else entropy_out
+        if ent.dtype != torch.float32 or not ent.is_contiguous() or ent.numel() != mlp.n_agents:
+            raise ValueError(f"entropy must be a contiguous float32 tensor [{mlp.n_agents}]")
+        with torch.cuda.device(mlp.device):
+            rc = _native.lib().dronesim_mlp_grad_ent(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), act.data_ptr(),
+                                                     weight.data_ptr(), float(ent_scale), self.grad.data_ptr(), loss.data_ptr(),
+                                                     ent.data_ptr(), self.rc, self.ws.data_ptr(), self.ent_ws_bytes,
+                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_mlp_grad_ent")
+        return self.grad, loss, ent
+
+    def run_ppo_ent(self, x, row_scale, act, logp_old, adv, clip_eps, ent_scale, loss_out=None, stats_out=None):
+        """`dronesim_mlp_grad_ppo_ent`: returns ``(grad, loss [N], stats [5, N])`` -- ``run_ppo``'s four rows and the mean row
+        entropy; the loss is the whole objective."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, act=(act, 2), logp_old=(logp_old, 1), adv=(adv, 1))
+        if not hasattr(self, "stats5"):
+            self._ent_workspace(True)
+        loss = self.loss if loss_out is None else loss_out
+        stats = self.stats5 if stats_out is None else stats_out
+        if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != 5 * mlp.n_agents:
+            raise ValueError(f"stats must be a contiguous float32 tensor [5, {mlp.n_agents}]")
+        with torch.cuda.device(mlp.device):
+            rc = _native.lib().dronesim_mlp_grad_ppo_ent(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), act.data_ptr(),
+                                                         logp_old.data_ptr(), adv.data_ptr(), float(clip_eps), float(ent_scale),
+                                                         self.grad.data_ptr(), loss.data_ptr(), stats.data_ptr(), self.rc,
+                                                         self.ws.data_ptr(), self.ppo_ent_ws_bytes,
+                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_mlp_grad_ppo_ent")
+        return self.grad, loss, stats
+
 
 def mlp_gradients(mlp, x, target=None, act=None, weight=None, row_scale=None, rows_per_chunk=None):
     """Per-agent gradients of `mlp`'s loss over the rows of ``x [..., N, d_in]`` (e.g. ``storage.z_pre [T,E,N,d_in]``):
@@ -246,6 +309,14 @@ def _check_lam(lam):
         return None
     from .rollout_buffer import check_lam
     return check_lam(lam)
+
+
+def _check_ent_coef(ent_coef):
+    """``ent_coef`` as a finite float >= 0, else ValueError."""
+    import numbers
+    if isinstance(ent_coef, bool) or not isinstance(ent_coef, numbers.Real) or not math.isfinite(ent_coef) or ent_coef < 0:
+        raise ValueError(f"ent_coef must be a finite number >= 0, got {ent_coef!r}")
+    return float(ent_coef)
 
 
 def _ring(storage, T):
@@ -367,10 +438,17 @@ class SA2CLearner:
                        gathers the terminal observations of the truncated ones (``z_trunc [M,E,N,d]``, M = ceil(T / 200)); the
                        PRE-update critic over them gives ``V_trunc [M E,N,1]``; 1b becomes `dronesim_lambda_returns_ends`.  An
                        arrival is terminal as before, also on the last allowed step.  Steps 2 and 3 are unchanged: the
-                       advantage still restarts at ``done``."""
+                       advantage still restarts at ``done``.
+
+    ``ent_coef`` (default 0: off, exactly the calls above) adds an entropy bonus to step 3: the actor loss becomes
+    ``-(1/E) sum w log pi - ent_coef x the mean over the T E rows of H(pi_i(. | x))`` (`dronesim_mlp_grad_ent` with
+    ``ent_scale = ent_coef / (T E)``; the likelihood term keeps its 1 / E), ``actor_loss`` is that whole objective and
+    ``train()`` also returns ``entropy [N]``, the mean row entropy under the pre-update actor.  There is NO advantage
+    standardisation here (`PPOLearner` has it): this learner's weight ``w`` carries gamma^t / N inside `dronesim_advantage`, and
+    standardising it would be another change."""
 
     def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None,
-                 time_limit="terminal"):
+                 time_limit="terminal", ent_coef=0.0):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -379,6 +457,7 @@ class SA2CLearner:
             raise ValueError("actor and critic must have the same agents and inputs")
         self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
         self.time_limit = _check_time_limit(time_limit, self.lam)
+        self.ent_coef = _check_ent_coef(ent_coef)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
@@ -405,6 +484,8 @@ class SA2CLearner:
             self.V_all = torch.empty((T + 1) * E, N, 1, device=dev)      # the pre-update critic over the whole ring
         self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
         self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
+        if self.ent_coef > 0:
+            self._actor_grad._ent_workspace(False)
         self._shape = (T, E, N)
 
     def train(self, storage):
@@ -433,6 +514,10 @@ class SA2CLearner:
                                         self.gamma, self.w.data_ptr(), T, E, N, int(nbr.shape[3]), stream)
         _native.check(rc, "dronesim_advantage")
         # actor (:327-357)
+        if self.ent_coef > 0:
+            ag, aloss, ent = self._actor_grad.run_ent(x, 1.0 / E, storage.actions, self.w, self.ent_coef / (T * E))
+            anorm = self.actor_opt.step(ag)
+            return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm, entropy=ent)
         ag, aloss = self._actor_grad.run(x, 1.0 / E, act=storage.actions, weight=self.w)
         anorm = self.actor_opt.step(ag)
         return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm)
@@ -480,12 +565,29 @@ class PPOLearner:
     ``time_limit`` as for `SA2CLearner`: ``"terminal"`` (default) keeps every episode end terminal, time-limit ends included
     (the reference's rule); ``"bootstrap"`` (needs a ``lam`` and ``storage.z_final``) classifies the window's ends, runs the
     same pre-update critic over the terminal observations of the truncated ones (``z_trunc`` -> ``V_trunc``) and takes
-    G = `dronesim_lambda_returns_ends`.  Everything after G is unchanged."""
+    G = `dronesim_lambda_returns_ends`.  Everything after G is unchanged.
+
+    Two options, both off by default (then ``train()`` issues exactly the calls above and allocates nothing more):
+
+      ``normalize_advantage``  once per window, right after step 2, agent i's advantages are standardised IN PLACE over the
+                    window's T E rows: ``adv = (adv - mean_i) / (std_i + adv_eps)`` (`dronesim_standardize`: float64 sums, the
+                    population std, deterministic).  Each agent has its own network and optimiser, so the scale is per agent.
+                    The pre-normalisation (mean, std) are kept as ``self.adv_stats [2, N]`` and returned as ``adv_mean`` and
+                    ``adv_std``.
+      ``ent_coef``  the actor loss of every epoch becomes ``L_i - ent_coef x the mean over the T E rows of H(pi_i(. | x))``
+                    (`dronesim_mlp_grad_ppo_ent` with ``ent_scale = ent_coef / (T E)``); ``actor_loss`` is that whole objective.
+
+    With either, ``train()`` also returns ``entropy [epochs, N]``: the mean row entropy under the actor each epoch started
+    from.  The diagnostic comes from the entropy head, so ``normalize_advantage`` alone (``ent_coef = 0``) also runs the
+    epochs through `dronesim_mlp_grad_ppo_ent` (adding exact zeros: the sibling's gradients and loss bit for bit), grows the
+    workspace by the row-entropy plane and makes ``_stats`` five rows.  The first epoch's ratio stays exactly 1 with any
+    ``ent_coef``: the old log-probabilities come from the same untouched forward-only pass."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
-                 baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal"):
+                 baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
+                 adv_eps=1e-8):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -501,6 +603,11 @@ class PPOLearner:
         self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
         self.time_limit = _check_time_limit(time_limit, self.lam)
         self.epochs, self.clip_eps, self.baseline = int(epochs), float(clip_eps), baseline
+        self.ent_coef, self.normalize_advantage = _check_ent_coef(ent_coef), bool(normalize_advantage)
+        if isinstance(adv_eps, bool) or not math.isfinite(adv_eps) or adv_eps < 0:
+            raise ValueError(f"adv_eps must be a finite number >= 0, got {adv_eps!r}")
+        self.adv_eps = float(adv_eps)
+        self._ent = self.ent_coef > 0 or self.normalize_advantage           # the entropy form of the head (and its diagnostics)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
@@ -532,7 +639,16 @@ class PPOLearner:
         self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
         self._actor_grad._ppo_workspace()
         self._scalars = torch.zeros(4, self.epochs, N, device=dev)       # critic_loss, actor_loss, critic / actor grad norm
-        self._stats = torch.zeros(self.epochs, 4, N, device=dev)
+        self._stats = torch.zeros(self.epochs, 5 if self._ent else 4, N, device=dev)
+        if self._ent:
+            self._actor_grad._ent_workspace(True)
+        if self.normalize_advantage:
+            from . import _native
+            n = C.c_size_t(0)
+            _native.check(_native.lib().dronesim_standardize_workspace(T * E, N, C.byref(n)), "dronesim_standardize_workspace")
+            self._std_ws_bytes = int(n.value)
+            self._std_ws = torch.empty(self._std_ws_bytes // 8, dtype=torch.float64, device=dev)
+            self.adv_stats = torch.zeros(2, N, device=dev)
         self._shape = (T, E, N)
 
     def train(self, storage):
@@ -559,14 +675,28 @@ class PPOLearner:
                                                   int(self.baseline == "per_neighbour"), self.adv.data_ptr(), T, E, N,
                                                   int(nbr.shape[3]), stream)
         _native.check(rc, "dronesim_neighbour_advantage")
+        if self.normalize_advantage:
+            with torch.cuda.device(self.critic.device):
+                rc = lib.dronesim_standardize(self.adv.data_ptr(), self.adv.data_ptr(), self.adv_stats.data_ptr(), T * E, N,
+                                              self.adv_eps, self._std_ws.data_ptr(), self._std_ws_bytes, stream)
+            _native.check(rc, "dronesim_standardize")
         closs, aloss, cnorm, anorm = self._scalars
         for ep in range(self.epochs):
             last = ep == self.epochs - 1
             cg, _ = self._critic_grad.run(x, 1.0 / (T * E), target=self.G, loss_out=closs[ep])
             self.critic_opt.step(cg, norm_out=cnorm[ep], refresh=last)
-            ag, _, _ = self._actor_grad.run_ppo(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps, loss_out=aloss[ep],
-                                                stats_out=self._stats[ep])
+            if self._ent:
+                ag, _, _ = self._actor_grad.run_ppo_ent(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps,
+                                                        self.ent_coef / (T * E), loss_out=aloss[ep], stats_out=self._stats[ep])
+            else:
+                ag, _, _ = self._actor_grad.run_ppo(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps, loss_out=aloss[ep],
+                                                    stats_out=self._stats[ep])
             self.actor_opt.step(ag, norm_out=anorm[ep], refresh=last)
         st = self._stats
-        return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
-                    clip_fraction=st[:, 0], approx_kl=st[:, 1], ratio_min=st[:, 2], ratio_max=st[:, 3])
+        out = dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
+                   clip_fraction=st[:, 0], approx_kl=st[:, 1], ratio_min=st[:, 2], ratio_max=st[:, 3])
+        if self._ent:
+            out["entropy"] = st[:, 4]
+        if self.normalize_advantage:
+            out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
+        return out

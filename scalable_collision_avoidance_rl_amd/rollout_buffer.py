@@ -341,3 +341,34 @@ def neighbour_advantage(G, V, nbr_idx, gamma: float, done=None):
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
     _native.check(rc, "dronesim_advantage")
     return w
+
+
+def standardize(x, eps=1e-8, out=None, return_stats=False):
+    """Per-agent standardisation of ``x [..., N]`` (e.g. a window's advantages ``[T,E,N]``) over all leading axes:
+    ``(x - mean_i) / (std_i + eps)`` with float64 sums and the population std (`dronesim_standardize`; deterministic, no host
+    synchronisation).  ``out``: a contiguous float32 tensor of x's shape to write into (``out=x`` works in place).  Returns
+    ``y``, or ``(y, stats)`` with ``stats [2, N]`` = (mean, std) of the input when ``return_stats``."""
+    import torch
+    from . import _native
+    lib = _native.lib()
+    x = _prep(x, torch.float32)
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x must be a non-empty [..., N] tensor, got shape {tuple(x.shape)}")
+    N = int(x.shape[-1])
+    R = x.numel() // N
+    if isinstance(eps, bool) or not eps >= 0:
+        raise ValueError(f"eps must be a number >= 0, got {eps!r}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == tuple(x.shape)):
+        raise ValueError(f"out must be a contiguous float32 device tensor of shape {tuple(x.shape)}")
+    n = C.c_size_t(0)
+    _native.check(lib.dronesim_standardize_workspace(R, N, C.byref(n)), "dronesim_standardize_workspace")
+    ws = torch.empty(int(n.value) // 8, dtype=torch.float64, device=x.device)
+    stats = torch.empty(2, N, dtype=torch.float32, device=x.device) if return_stats else None
+    with torch.cuda.device(x.device):
+        rc = lib.dronesim_standardize(x.data_ptr(), out.data_ptr(), None if stats is None else stats.data_ptr(), R, N, float(eps),
+                                      ws.data_ptr(), int(n.value), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_standardize")
+    return (out, stats) if return_stats else out
