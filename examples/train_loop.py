@@ -6,7 +6,7 @@ actor loss + clip + Adam, for all N agents' networks at once in HIP.
 
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
                                   [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
-                                  [--normalize-advantage]
+                                  [--normalize-advantage] [--minibatches K] [--shuffle-seed S]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -22,6 +22,10 @@ window's finished episodes is printed (an untrained policy: nearly all of them).
 ``--ent-coef X`` adds an entropy bonus to the actor loss (-X x the mean entropy of the policy over the window's rows), and
 ``--normalize-advantage`` (``--learner ppo``) standardises each agent's advantages over the window before the epochs; with
 either, every episode line also shows the mean entropy.
+
+``--minibatches K`` (``--learner ppo``; K must divide window x envs) reshuffles the window's rows on the device every epoch and
+takes one critic and one actor step per minibatch: K x ``--epochs`` Adam steps per network per window instead of ``--epochs``.
+``--shuffle-seed S`` keys the permutations; the diagnostics shown are then the last epoch's, averaged over its minibatches.
 """
 import argparse
 import os
@@ -65,7 +69,11 @@ def main():
     ap.add_argument("--ent-coef", type=float, default=0.0, help="entropy bonus: -X x the mean policy entropy in the actor loss (default: off)")
     ap.add_argument("--normalize-advantage", action="store_true",
                     help="standardise each agent's advantages over the window before the epochs (--learner ppo)")
+    ap.add_argument("--minibatches", type=int, default=1, help="shuffled minibatches per epoch (--learner ppo; default 1: whole-window epochs)")
+    ap.add_argument("--shuffle-seed", type=int, default=0, help="key of the per-epoch row permutations (--minibatches)")
     args = ap.parse_args()
+    if args.minibatches != 1 and args.learner != "ppo":
+        ap.error("--minibatches needs --learner ppo (one update per window is what A2C is)")
     if args.normalize_advantage and args.learner != "ppo":
         ap.error("--normalize-advantage needs --learner ppo (SA2CLearner has no advantage standardisation)")
     N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
@@ -80,7 +88,7 @@ def main():
     if args.learner == "ppo":
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                              lam=args.lam, time_limit=args.time_limit, ent_coef=args.ent_coef,
-                             normalize_advantage=args.normalize_advantage)
+                             normalize_advantage=args.normalize_advantage, minibatches=args.minibatches, shuffle_seed=args.shuffle_seed)
     else:
         learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
                               time_limit=args.time_limit, ent_coef=args.ent_coef)
@@ -95,11 +103,11 @@ def main():
         stop.record()
         torch.cuda.synchronize()
         ppo = ""
-        if args.learner == "ppo":       # the last epoch's diagnostics (the first epoch's ratio is exactly 1)
+        if args.learner == "ppo":       # the last epoch's diagnostics (the first epoch's ratio is exactly 1; --minibatches: to rounding)
             ppo = (f"  clipped {float(out['clip_fraction'][-1].mean()):.3f}  kl {float(out['approx_kl'][-1].mean()):+.2e}  "
                    f"ratio [{float(out['ratio_min'][-1].min()):.3f}, {float(out['ratio_max'][-1].max()):.3f}]")
         if "entropy" in out:            # (PPO: the last epoch's)
-            ppo += f"  entropy {float(out['entropy'][-1].mean() if out['entropy'].dim() == 2 else out['entropy'].mean()):.3f}"
+            ppo += f"  entropy {float(out['entropy'][-1].mean() if out['entropy'].dim() >= 2 else out['entropy'].mean()):.3f}"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(out['actor_loss'].mean()):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
               f"{float(out['actor_grad_norm'].mean()):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")

@@ -600,6 +600,40 @@ int dronesim_mlp_grad_ppo_ent(const DroneMlp *m, const float *x, int R, float ro
                               const float *adv, float clip_eps, float ent_scale, float *grad, float *loss, float *stats,
                               int rows_per_chunk, void *ws, size_t ws_bytes, void *stream);
 
+/* Shuffled minibatches (csrc/minibatch.hip).  Both entry points only enqueue one kernel on `stream`: no memset node, no
+ * allocation, no host synchronisation, no atomics; deterministic, and capturable in a graph.
+ *
+ * dronesim_row_permutation: perm (int32 [R], OVERWRITTEN) becomes a permutation of 0..R-1 that is a pure function of
+ * (R, seed, *counter).  counter is a DEVICE pointer to one int32 that the kernel reads: with the counter in device memory (e.g.
+ * the step counter dronesim_adam_step advances) a captured graph draws a fresh permutation on every replay.  One thread per row, no
+ * sort.  The rule, in unsigned 32-bit arithmetic throughout -- a 4-round balanced Feistel network with cycle-walking:
+ *   h = max(1, ceil(bitlen(R - 1) / 2)),  mask = 2^h - 1          (bitlen(0) = 0; R = 2^31 - 1 gives h = 16, the domain 2^32)
+ *   a value v < 2^(2h) is split as  L = v >> h,  Rr = v & mask
+ *   round k = 0..3:  (L, Rr) <- (Rr, L ^ (w0(Rr, k) & mask));  the network's result is (L << h) | Rr
+ *   w0(a, k) = word 0 of Philox4x32-10 with counter (a, k, (uint32_t)*counter, 0) and key ((uint32_t)seed, (uint32_t)(seed >> 32))
+ *   perm[r]: start from v = r and apply the network until the result is < R.
+ * The network is a bijection of [0, 2^(2h)) and 2^(2h) < 4 R for R >= 2, so the walk is a bijection of [0, R) and a thread applies
+ * the network fewer than 4 times on average.  1 <= R <= 2^31 - 1.  EINVAL: R < 1, NULL counter or perm.
+ *
+ * dronesim_gather_rows: ONE launch that gathers the rows of n_arrays (1..8) row-major arrays by perm (int32 [R], device memory,
+ * entries in [0, R); an entry outside that range is skipped: its destination row is left as it was).  src, dst, row_bytes and
+ * block_bytes are HOST arrays of n_arrays entries (read during the call, passed to the kernel by value); src[a] / dst[a] are
+ * device addresses.  The R positions are cut into R / M blocks of M; for position p = b M + j (0 <= j < M) the row of array a is
+ * copied from  src[a] + perm[p] row_bytes[a]  to  dst[a] + b block_bytes[a] + j row_bytes[a].  block_bytes[a] >= M row_bytes[a]: a
+ * caller pads it (say to a multiple of 256) to start every block on an aligned address; the padding bytes are not written.
+ * Rows are positive multiples of 4 bytes, at most DRONESIM_GATHER_MAX_ROW_BYTES, and need not be multiples of 16 (an array whose
+ * row size, block size and two base addresses are all multiples of 16 moves in 16-byte pieces, any other in 4-byte pieces);
+ * src[a], dst[a] and block_bytes[a] are multiples of 4.  The bytes are copied as they are: any element type.
+ * src and dst arrays MUST NOT overlap each other (not checked: it cannot be checked cheaply); src[a] needs R rows, dst[a]
+ * (R / M) block_bytes[a] bytes.
+ * EINVAL: R < 1, M < 1, R % M != 0, n_arrays outside 1..8, a row size that is not a positive multiple of 4 (or above the limit),
+ * block_bytes[a] < M row_bytes[a], a NULL pointer (perm, the four host arrays, any src[a] / dst[a]), an address or block size that
+ * is not a multiple of 4.                                                                                                         */
+#define DRONESIM_GATHER_MAX_ROW_BYTES (1 << 24)
+int dronesim_row_permutation(int R, uint64_t seed, const int32_t *counter, int32_t *perm, void *stream);
+int dronesim_gather_rows(const int32_t *perm, int R, int M, int n_arrays, const void *const *src, void *const *dst,
+                         const int64_t *row_bytes, const int64_t *block_bytes, void *stream);
+
 const char *dronesim_last_error(void);
 const char *dronesim_error_string(int code);
 int dronesim_version(void);

@@ -35,6 +35,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
            "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent",
            "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
+           "dronesim_row_permutation", "dronesim_gather_rows",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -172,6 +173,10 @@ def lib():
     L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
     L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]
     L.dronesim_episode_eval.restype = L.dronesim_histogram_i32.restype = C.c_int
+    # (the four host arrays of dronesim_gather_rows are ctypes arrays: c_void_p / c_int64 times n_arrays)
+    L.dronesim_row_permutation.argtypes = [i32, u64, vp, vp, vp]
+    L.dronesim_gather_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.dronesim_row_permutation.restype = L.dronesim_gather_rows.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

@@ -18,6 +18,10 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
                                        mean row entropy of the window (default 0: off, the calls above)
   normalize_advantage= of PPOLearner   dronesim_standardize   agent i's advantages standardised over the window's T E rows,
                                        once per window before the epochs (default off)
+  minibatches= of PPOLearner           dronesim_row_permutation, dronesim_gather_rows   every epoch reshuffles the window's rows
+                                       on the device (a permutation keyed by ``shuffle_seed`` and the critic's device-resident
+                                       step counter), gathers them into minibatch-ordered buffers with one launch and takes one
+                                       critic and one actor step per minibatch (default 1: off, the whole-window epochs above)
 
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
@@ -395,6 +399,35 @@ def _lambda_returns_ends(learner, storage, Vall, G):
     _native.check(rc, "dronesim_lambda_returns_ends")
 
 
+MINIBATCH_ALIGN = 256               # every minibatch's block of a gathered buffer starts on this boundary (bytes)
+
+
+def _check_minibatches(minibatches, shuffle_seed):
+    """``minibatches`` as an int >= 1 and ``shuffle_seed`` as an int in [0, 2^64), else ValueError."""
+    import numbers
+    if isinstance(minibatches, bool) or not isinstance(minibatches, numbers.Integral) or minibatches < 1:
+        raise ValueError(f"minibatches must be an integer >= 1, got {minibatches!r}")
+    if isinstance(shuffle_seed, bool) or not isinstance(shuffle_seed, numbers.Integral) or not 0 <= shuffle_seed < 2 ** 64:
+        raise ValueError(f"shuffle_seed must be an integer in [0, 2^64), got {shuffle_seed!r}")
+    return int(minibatches), int(shuffle_seed)
+
+
+class GatheredRows:
+    """The minibatch-ordered copy of one ``[R, ...]`` float32 array: K blocks of M rows in one persistent buffer, every block
+    starting on a `MINIBATCH_ALIGN`-byte boundary (``blocks[b]`` is the contiguous ``[M, ...]`` view of block b), so that the
+    gradient entry points see the alignment of a fresh allocation whatever M x the row size is."""
+
+    def __init__(self, row_shape, K, M, device):
+        import torch
+        self.row_bytes = 4 * math.prod(row_shape)
+        self.block_bytes = -(-M * self.row_bytes // MINIBATCH_ALIGN) * MINIBATCH_ALIGN
+        self.buf = torch.zeros(K * self.block_bytes // 4, device=device)
+        if self.buf.is_cuda and self.buf.data_ptr() % MINIBATCH_ALIGN:
+            raise RuntimeError(f"the allocator returned a buffer that is not {MINIBATCH_ALIGN}-byte aligned")
+        n, stride = M * self.row_bytes // 4, self.block_bytes // 4
+        self.blocks = [self.buf[b * stride:b * stride + n].view(M, *row_shape) for b in range(K)]
+
+
 class SA2CLearner:
     """`SA2CAgents.train_NN` (SAC_agents.py:280-357) over a `RolloutStorage` window of E envs, T steps:
 
@@ -581,13 +614,34 @@ class PPOLearner:
     from.  The diagnostic comes from the entropy head, so ``normalize_advantage`` alone (``ent_coef = 0``) also runs the
     epochs through `dronesim_mlp_grad_ppo_ent` (adding exact zeros: the sibling's gradients and loss bit for bit), grows the
     workspace by the row-entropy plane and makes ``_stats`` five rows.  The first epoch's ratio stays exactly 1 with any
-    ``ent_coef``: the old log-probabilities come from the same untouched forward-only pass."""
+    ``ent_coef``: the old log-probabilities come from the same untouched forward-only pass.
+
+    ``minibatches = K`` (default 1: step 3 as written -- exactly the calls above, nothing more allocated) makes step 3 the usual
+    PPO loop of shuffled minibatch epochs.  T E must be a multiple of K (ValueError otherwise; no ragged last minibatch);
+    M = T E / K.  Steps 1 and 2 are unchanged and run once per window in window order -- ``normalize_advantage`` stays per
+    window, not per minibatch.  Then every epoch:
+
+      a. `dronesim_row_permutation` writes a permutation of the T E rows into ``self.perm`` (int32 ``[T E]``; after ``train`` it
+         holds the last epoch's).  It is a pure function of (T E, ``shuffle_seed``, the critic optimiser's step counter of agent
+         0): that counter is read ON THE DEVICE, is different for every epoch of every call, and advances on graph replay, so
+         a captured ``train`` reshuffles on every replay.  No host generator, no sort.
+      b. one `dronesim_gather_rows` copies the permuted rows of ``z_pre``, ``actions``, ``logp_old``, ``adv`` and ``G`` into
+         five persistent `GatheredRows` buffers (``self._mb``): minibatch b is rows ``perm[b M : (b + 1) M]``.
+      c. for b = 0 .. K-1: the critic step on block b, then the actor step on block b -- the same entry points through
+         `GradientRunner`s sized for M rows, with ``row_scale = 1 / M`` and ``ent_scale = ent_coef / M``.
+
+    That is ``epochs x K`` Adam steps per network per call; the forward images are still re-packed once per network, after the
+    last minibatch of the last epoch.  The returned per-step tensors become ``[epochs, K, N]`` (``adv_mean`` / ``adv_std`` stay
+    ``[N]``).  Only the first minibatch of the first epoch sees the weights ``logp_old`` was computed from, and it sees them in
+    another row order and chunking than step 2's forward pass: its ratios are 1 to rounding, not bit for bit.  Everything else
+    holds as above: both actor kinds, ``lam``, ``time_limit``, ``ent_coef``, ``normalize_advantage``, ``baseline``, no host
+    synchronisation, deterministic, capturable with the rollout in one graph."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                  baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
-                 adv_eps=1e-8):
+                 adv_eps=1e-8, minibatches=1, shuffle_seed=0):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -607,6 +661,7 @@ class PPOLearner:
         if isinstance(adv_eps, bool) or not math.isfinite(adv_eps) or adv_eps < 0:
             raise ValueError(f"adv_eps must be a finite number >= 0, got {adv_eps!r}")
         self.adv_eps = float(adv_eps)
+        self.minibatches, self.shuffle_seed = _check_minibatches(minibatches, shuffle_seed)
         self._ent = self.ent_coef > 0 or self.normalize_advantage           # the entropy form of the head (and its diagnostics)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
@@ -626,6 +681,9 @@ class PPOLearner:
             return
         if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
             raise ValueError("the storage's agents / observation width do not match the networks")
+        K = self.minibatches
+        if (T * E) % K:
+            raise ValueError(f"minibatches = {K} does not divide the window's T E = {T} x {E} = {T * E} rows")
         dev = self.critic.device
         self.G = torch.empty(T, E, N, device=dev)
         if self.lam is None:
@@ -635,13 +693,19 @@ class PPOLearner:
             self.V = self.V_all[:T * E]
         self.adv = torch.empty(T, E, N, device=dev)
         self.logp_old = torch.empty(T, E, N, device=dev)
-        self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
-        self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
-        self._actor_grad._ppo_workspace()
-        self._scalars = torch.zeros(4, self.epochs, N, device=dev)       # critic_loss, actor_loss, critic / actor grad norm
-        self._stats = torch.zeros(self.epochs, 5 if self._ent else 4, N, device=dev)
-        if self._ent:
-            self._actor_grad._ent_workspace(True)
+        if K == 1:
+            self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
+            self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
+            self._actor_grad._ppo_workspace()
+            self._scalars = torch.zeros(4, self.epochs, N, device=dev)   # critic_loss, actor_loss, critic / actor grad norm
+            self._stats = torch.zeros(self.epochs, 5 if self._ent else 4, N, device=dev)
+            if self._ent:
+                self._actor_grad._ent_workspace(True)
+        else:
+            # the full-window actor runner is kept ONLY for step 2's forward-only `logp` pass, which needs the plain gradient
+            # workspace and neither the PPO nor the entropy one (the epochs run through `_critic_mb` / `_actor_mb`)
+            self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
+            self._prepare_minibatches(storage, T * E, N, K)
         if self.normalize_advantage:
             from . import _native
             n = C.c_size_t(0)
@@ -650,6 +714,64 @@ class PPOLearner:
             self._std_ws = torch.empty(self._std_ws_bytes // 8, dtype=torch.float64, device=dev)
             self.adv_stats = torch.zeros(2, N, device=dev)
         self._shape = (T, E, N)
+
+    def _prepare_minibatches(self, storage, rows, N, K):
+        """The buffers of ``minibatches = K > 1``: the permutation, the five gathered arrays, the M-row gradient runners and the
+        ``[epochs, K, ...]`` outputs."""
+        import torch
+        dev, M = self.critic.device, rows // K
+        self.perm = torch.zeros(rows, dtype=torch.int32, device=dev)
+        d = storage.z_pre.shape[-1]
+        self._mb = [GatheredRows(shape, K, M, dev) for shape in ((N, d), (N, 2), (N,), (N,), (N,))]   # z_pre, actions, logp_old, adv, G
+        self._mb_dst = (C.c_void_p * 5)(*[g.buf.data_ptr() for g in self._mb])
+        self._mb_row_bytes = (C.c_int64 * 5)(*[g.row_bytes for g in self._mb])
+        self._mb_block_bytes = (C.c_int64 * 5)(*[g.block_bytes for g in self._mb])
+        self._critic_mb = GradientRunner(self.critic, M, self.rows_per_chunk)
+        self._actor_mb = GradientRunner(self.actor, M, self.rows_per_chunk)
+        self._actor_mb._ppo_workspace()
+        if self._ent:
+            self._actor_mb._ent_workspace(True)
+        self._scalars = torch.zeros(4, self.epochs, K, N, device=dev)
+        self._stats = torch.zeros(self.epochs, K, 5 if self._ent else 4, N, device=dev)
+
+    def _train_minibatches(self, storage, lib, stream):
+        """Step 3 with ``minibatches = K > 1``: per epoch a fresh device permutation, one gather, K critic-then-actor steps."""
+        import torch
+        from . import _native
+        T, E, N = self._shape
+        K, rows = self.minibatches, T * E
+        M = rows // K
+        # (z_pre and actions are contiguous float32: step 2's forward-only pass has checked them)
+        src = (C.c_void_p * 5)(storage.z_pre.data_ptr(), storage.actions.data_ptr(), self.logp_old.data_ptr(), self.adv.data_ptr(),
+                               self.G.data_ptr())
+        closs, aloss, cnorm, anorm = self._scalars
+        for ep in range(self.epochs):
+            with torch.cuda.device(self.critic.device):
+                rc = lib.dronesim_row_permutation(rows, self.shuffle_seed, self.critic_opt.steps.data_ptr(), self.perm.data_ptr(), stream)
+                _native.check(rc, "dronesim_row_permutation")
+                rc = lib.dronesim_gather_rows(self.perm.data_ptr(), rows, M, 5, src, self._mb_dst, self._mb_row_bytes,
+                                              self._mb_block_bytes, stream)
+                _native.check(rc, "dronesim_gather_rows")
+            for b in range(K):
+                last = ep == self.epochs - 1 and b == K - 1
+                x, act, logp_old, adv, G = (g.blocks[b] for g in self._mb)
+                cg, _ = self._critic_mb.run(x, 1.0 / M, target=G, loss_out=closs[ep, b])
+                self.critic_opt.step(cg, norm_out=cnorm[ep, b], refresh=last)
+                if self._ent:
+                    ag, _, _ = self._actor_mb.run_ppo_ent(x, 1.0 / M, act, logp_old, adv, self.clip_eps, self.ent_coef / M,
+                                                          loss_out=aloss[ep, b], stats_out=self._stats[ep, b])
+                else:
+                    ag, _, _ = self._actor_mb.run_ppo(x, 1.0 / M, act, logp_old, adv, self.clip_eps, loss_out=aloss[ep, b],
+                                                      stats_out=self._stats[ep, b])
+                self.actor_opt.step(ag, norm_out=anorm[ep, b], refresh=last)
+        st = self._stats
+        out = dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
+                   clip_fraction=st[:, :, 0], approx_kl=st[:, :, 1], ratio_min=st[:, :, 2], ratio_max=st[:, :, 3])
+        if self._ent:
+            out["entropy"] = st[:, :, 4]
+        if self.normalize_advantage:
+            out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
+        return out
 
     def train(self, storage):
         import torch
@@ -680,6 +802,8 @@ class PPOLearner:
                 rc = lib.dronesim_standardize(self.adv.data_ptr(), self.adv.data_ptr(), self.adv_stats.data_ptr(), T * E, N,
                                               self.adv_eps, self._std_ws.data_ptr(), self._std_ws_bytes, stream)
             _native.check(rc, "dronesim_standardize")
+        if self.minibatches > 1:
+            return self._train_minibatches(storage, lib, stream)
         closs, aloss, cnorm, anorm = self._scalars
         for ep in range(self.epochs):
             last = ep == self.epochs - 1

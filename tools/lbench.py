@@ -8,6 +8,8 @@ or, with ``--learner ppo``, one `PPOLearner.train` of ``--epochs M`` epochs --, 
     python tools/lbench.py --scans --time-limit bootstrap [--configs c3,c5] [--reps 9] [--out profiles/timelimit_lbench.jsonl]
     python tools/lbench.py --scans --standardize [--configs c3,c5] [--reps 3] [--out profiles/entropy_lbench.jsonl]
     python tools/lbench.py --learner ppo --epochs M --ent-coef 0.01 --normalize-advantage [--out profiles/entropy_lbench.jsonl]
+    python tools/lbench.py --learner ppo --epochs M --minibatches K [--out profiles/minibatch_lbench.jsonl]
+    python tools/lbench.py --gather [--configs c1,c3,c5] [--reps 5] [--minibatches K] [--out profiles/minibatch_lbench.jsonl]
 
 ``--lam X`` times the learner with bootstrapped lambda-returns (one more ring slot of observations; off by default).
 ``--time-limit bootstrap`` (with ``--lam``) times it with time-limit ends bootstrapped from their terminal observations: the
@@ -20,6 +22,11 @@ per element: read, then read and write), against `dronesim_returns` on an array 
 per element): expected is the yardstick x 1.5, allowed that + 15 %.  A third line, `dronesim_standardize_out_of_place`, is
 the same call with ``y != x`` against the same bound.  ``--ent-coef X`` / ``--normalize-advantage`` time a whole update with the
 entropy bonus / the per-agent advantage standardisation (the latter ``--learner ppo`` only).
+``--minibatches K`` (``--learner ppo``) times the learner with K shuffled minibatches per epoch (K x epochs Adam steps per
+network; per epoch one `dronesim_row_permutation` and one `dronesim_gather_rows`).  ``--gather`` times those two alone, on the
+five learner arrays of a window (z_pre, actions, logp_old, adv, G: 4 N (d_in + 5) bytes per row) cut into K blocks (default 4,
+``--minibatches 1`` is a single block), every block rounded up to 256 bytes as the learner does, next to a plain device-to-device copy of the same five arrays in the same process: device events around
+``--calls`` back-to-back calls, median and minimum over ``--reps``; bytes moved = 2 x the arrays' bytes.
 ``--scans`` times the learner-side scans alone instead: `dronesim_returns` (the yardstick) and `dronesim_lambda_returns`
 with G only and with G + A, on the same buffers in the same process, device events around ``--calls`` back-to-back calls
 after a warm-up, median and minimum over ``--reps`` repetitions, one JSON line each (appended to ``--out`` when given).
@@ -170,6 +177,81 @@ def scans_standardize(args):
                 f.write(json.dumps(line) + "\n")
 
 
+def gather_bench(args):
+    """`dronesim_row_permutation` + `dronesim_gather_rows` of the five learner arrays next to a plain copy of the same bytes."""
+    import ctypes as C
+    import statistics
+
+    import torch
+    from scalable_collision_avoidance_rl_amd import _native
+    from scalable_collision_avoidance_rl_amd.learner import GatheredRows
+    lib, dev = _native.lib(), "cuda:0"
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = []
+    for name in args.configs.split(","):
+        N, E, T, _ = CONFIGS[name]
+        d_in, rows = 6, T * E
+        K = 4 if args.minibatches is None else args.minibatches
+        if rows % K:
+            raise SystemExit(f"--minibatches {K} does not divide the {rows} rows of {name}")
+        M = rows // K
+        g = torch.Generator(device=dev).manual_seed(0)
+        srcs = [torch.randn(rows, *s, device=dev, generator=g) for s in ((N, d_in), (N, 2), (N,), (N,), (N,))]
+        mb = [GatheredRows(tuple(s.shape[1:]), K, M, dev) for s in srcs]
+        plain = [torch.empty_like(s) for s in srcs]
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        perm = torch.empty(rows, dtype=torch.int32, device=dev)
+        arr = lambda ty, vals: (ty * 5)(*vals)
+        src_p, dst_p = arr(C.c_void_p, [s.data_ptr() for s in srcs]), arr(C.c_void_p, [m.buf.data_ptr() for m in mb])
+        rb, bb = arr(C.c_int64, [m.row_bytes for m in mb]), arr(C.c_int64, [m.block_bytes for m in mb])
+        permute = lambda: lib.dronesim_row_permutation(rows, 12345, counter.data_ptr(), perm.data_ptr(), stream())
+        gather = lambda: lib.dronesim_gather_rows(perm.data_ptr(), rows, M, 5, src_p, dst_p, rb, bb, stream())
+
+        def copy():
+            for d, s_ in zip(plain, srcs):
+                d.copy_(s_)
+            return 0
+
+        def both():
+            return permute() or gather()
+
+        nbytes = sum(s.numel() * 4 for s in srcs)
+        _native.check(both(), "permutation + gather")
+        torch.cuda.synchronize()
+        assert all(torch.equal(torch.stack(m.blocks).reshape(s.shape), s[perm.long()]) for m, s in zip(mb, srcs))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        base = None
+        for what, fn in (("plain copy of the five arrays", copy), ("dronesim_row_permutation", permute), ("dronesim_gather_rows", gather),
+                         ("dronesim_row_permutation + dronesim_gather_rows", both)):
+            for _ in range(max(1, args.warmup) * args.calls):
+                _native.check(fn(), what)
+            torch.cuda.synchronize()
+            us = []
+            for _ in range(args.reps):
+                ev[0].record()
+                for _ in range(args.calls):
+                    fn()
+                ev[1].record()
+                torch.cuda.synchronize()
+                us.append(ev[0].elapsed_time(ev[1]) * 1e3 / args.calls)
+            med, lo = statistics.median(us), min(us)
+            line = dict(what=what, config=name, N=N, R=rows, K=K, M=M, row_bytes=[m.row_bytes for m in mb], us=round(med, 2),
+                        us_min=round(lo, 2), us_all=[round(u, 2) for u in us], calls=args.calls, reps=args.reps)
+            if what != "dronesim_row_permutation":
+                line.update(bytes_moved=2 * nbytes, tb_s=round(2 * nbytes / 1e6 / med, 3))
+            if base is None:
+                base = med
+            else:
+                line.update(ratio_to_copy=round(med / base, 3))
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def scans_time_limit(args):
     """`dronesim_lambda_returns_ends` next to its yardstick `dronesim_lambda_returns` (done = ends != 0), and `dronesim_episode_ends`."""
     import ctypes as C
@@ -250,11 +332,20 @@ def main():
     ap.add_argument("--standardize", action="store_true", help="with --scans: time dronesim_standardize against dronesim_returns")
     ap.add_argument("--ent-coef", type=float, default=0.0, help="entropy bonus of the timed learner (default: off)")
     ap.add_argument("--normalize-advantage", action="store_true", help="per-agent advantage standardisation (--learner ppo)")
+    ap.add_argument("--minibatches", type=int, default=None,
+                    help="shuffled minibatches per epoch (--learner ppo; default 1: off); with --gather: the blocks (default 4; 1 = a single block)")
+    ap.add_argument("--gather", action="store_true", help="time dronesim_row_permutation + dronesim_gather_rows against a plain copy")
     ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per timed repetition (--scans)")
     ap.add_argument("--out", help="append the JSON lines to this file")
     args = ap.parse_args()
     if args.normalize_advantage and args.learner != "ppo":
         ap.error("--normalize-advantage needs --learner ppo (SA2CLearner has no advantage standardisation)")
+    if args.minibatches is not None and args.minibatches < 1:
+        ap.error("--minibatches must be >= 1")
+    if args.minibatches not in (None, 1) and not (args.gather or args.learner == "ppo"):
+        ap.error("--minibatches needs --learner ppo (or --gather)")
+    if not args.gather and args.minibatches is None:
+        args.minibatches = 1
     if args.stats:
         import csv
         rows = list(csv.DictReader(open(args.stats)))
@@ -263,6 +354,8 @@ def main():
             print(json.dumps(dict(kernel=r["Name"][:60], calls=int(r["Calls"]), total_ms=round(float(r["TotalDurationNs"]) / 1e6, 3),
                                   share=round(float(r["TotalDurationNs"]) / tot, 4))))
         return
+    if args.gather:
+        return gather_bench(args)
     if args.scans and args.standardize:
         return scans_standardize(args)
     if args.scans:
@@ -305,6 +398,8 @@ def main():
             lam_kw["ent_coef"] = args.ent_coef
         if args.normalize_advantage:
             lam_kw["normalize_advantage"] = True
+        if args.minibatches > 1:
+            lam_kw["minibatches"] = args.minibatches
         learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs, **lam_kw) if ppo else SA2CLearner(actor, critic, 0.99, **lam_kw)
         for _ in range(args.warmup):
             learner.train(st)
@@ -333,6 +428,8 @@ def main():
             tag["ent_coef"] = args.ent_coef
         if args.normalize_advantage:
             tag["normalize_advantage"] = True
+        if args.minibatches > 1:
+            tag["minibatches"] = args.minibatches
         lines.append(dict(config=name, **tag, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3),
                           ms_all=[round(t, 3) for t in times], flop=flop, tflops=round(flop / ms / 1e9, 2),
                           peak_share=round(flop / ms / 1e9 / PEAK_TF, 4)))
