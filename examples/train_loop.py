@@ -6,7 +6,7 @@ actor loss + clip + Adam, for all N agents' networks at once in HIP.
 
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
                                   [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
-                                  [--normalize-advantage] [--minibatches K] [--shuffle-seed S]
+                                  [--normalize-advantage] [--minibatches K] [--shuffle-seed S] [--target-kl X] [--vf-clip X]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -26,6 +26,12 @@ either, every episode line also shows the mean entropy.
 ``--minibatches K`` (``--learner ppo``; K must divide window x envs) reshuffles the window's rows on the device every epoch and
 takes one critic and one actor step per minibatch: K x ``--epochs`` Adam steps per network per window instead of ``--epochs``.
 ``--shuffle-seed S`` keys the permutations; the diagnostics shown are then the last epoch's, averaged over its minibatches.
+
+``--target-kl X`` (``--learner ppo``) stops an agent's actor for the rest of the window once its KL estimate to the policy that
+collected the window passes X -- decided and obeyed on the device, per agent; the critics keep stepping.  The episode line then
+shows the actors' step counts of the window (min / mean / max over the agents), and its means skip the NaN a skipped step
+reports.  ``--vf-clip X`` (``--learner ppo``) clips the value loss against the window's pre-update values; the line shows the
+share of rows it clipped in the last step.
 """
 import argparse
 import os
@@ -71,11 +77,15 @@ def main():
                     help="standardise each agent's advantages over the window before the epochs (--learner ppo)")
     ap.add_argument("--minibatches", type=int, default=1, help="shuffled minibatches per epoch (--learner ppo; default 1: whole-window epochs)")
     ap.add_argument("--shuffle-seed", type=int, default=0, help="key of the per-epoch row permutations (--minibatches)")
+    ap.add_argument("--target-kl", type=float, default=None, help="per-agent KL early stop of the actors (--learner ppo; default: off)")
+    ap.add_argument("--vf-clip", type=float, default=None, help="clipped value loss with this range (--learner ppo; default: off)")
     args = ap.parse_args()
     if args.minibatches != 1 and args.learner != "ppo":
         ap.error("--minibatches needs --learner ppo (one update per window is what A2C is)")
     if args.normalize_advantage and args.learner != "ppo":
         ap.error("--normalize-advantage needs --learner ppo (SA2CLearner has no advantage standardisation)")
+    if (args.target_kl is not None or args.vf_clip is not None) and args.learner != "ppo":
+        ap.error("--target-kl and --vf-clip need --learner ppo")
     N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
     env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=dev, seed=1, auto_reset=True)
@@ -88,7 +98,8 @@ def main():
     if args.learner == "ppo":
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                              lam=args.lam, time_limit=args.time_limit, ent_coef=args.ent_coef,
-                             normalize_advantage=args.normalize_advantage, minibatches=args.minibatches, shuffle_seed=args.shuffle_seed)
+                             normalize_advantage=args.normalize_advantage, minibatches=args.minibatches, shuffle_seed=args.shuffle_seed,
+                             target_kl=args.target_kl, vf_clip=args.vf_clip)
     else:
         learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
                               time_limit=args.time_limit, ent_coef=args.ent_coef)
@@ -103,14 +114,26 @@ def main():
         stop.record()
         torch.cuda.synchronize()
         ppo = ""
-        if args.learner == "ppo":       # the last epoch's diagnostics (the first epoch's ratio is exactly 1; --minibatches: to rounding)
+        mean = torch.nanmean if args.target_kl is not None else torch.mean       # a skipped actor step reports NaN
+        if args.target_kl is not None:  # the gate is on: the last step's diagnostics of the agents that still computed it
+            last = lambda k: out[k][-1][torch.isfinite(out[k][-1])]
+            steps = out["actor_steps"].float()
+            ppo = (f"  actor steps {int(steps.min())} / {float(steps.mean()):.1f} / {int(steps.max())}  "
+                   f"largest kl {float(out['kl'][torch.isfinite(out['kl'])].max()):.2e}")
+            if last("clip_fraction").numel():
+                ppo += (f"  clipped {float(last('clip_fraction').mean()):.3f}  ratio [{float(last('ratio_min').min()):.3f}, "
+                        f"{float(last('ratio_max').max()):.3f}]")
+        elif args.learner == "ppo":       # the last epoch's diagnostics (the first epoch's ratio is exactly 1; --minibatches: to rounding)
             ppo = (f"  clipped {float(out['clip_fraction'][-1].mean()):.3f}  kl {float(out['approx_kl'][-1].mean()):+.2e}  "
                    f"ratio [{float(out['ratio_min'][-1].min()):.3f}, {float(out['ratio_max'][-1].max()):.3f}]")
-        if "entropy" in out:            # (PPO: the last epoch's)
-            ppo += f"  entropy {float(out['entropy'][-1].mean() if out['entropy'].dim() >= 2 else out['entropy'].mean()):.3f}"
+        if "entropy" in out:            # (PPO: the last epoch's; with the gate: over the computed steps)
+            ent = out["entropy"] if args.target_kl is not None or out["entropy"].dim() < 2 else out["entropy"][-1]
+            ppo += f"  entropy {float(mean(ent)):.3f}"
+        if "vf_clip_fraction" in out:
+            ppo += f"  value rows clipped {float(out['vf_clip_fraction'][-1].mean()):.3f}"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
-              f"actor loss {float(out['actor_loss'].mean()):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
-              f"{float(out['actor_grad_norm'].mean()):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")
+              f"actor loss {float(mean(out['actor_loss'])):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
+              f"{float(mean(out['actor_grad_norm'])):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")
     # one host read after the loop: the kinds of the last window's episode ends
     _, _, n_trunc = (learner.ends, learner.slot_t, learner.n_trunc) if args.time_limit == "bootstrap" else storage.episode_ends()
     finished = int(storage.done.sum())

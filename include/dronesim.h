@@ -600,6 +600,55 @@ int dronesim_mlp_grad_ppo_ent(const DroneMlp *m, const float *x, int R, float ro
                               const float *adv, float clip_eps, float ent_scale, float *grad, float *loss, float *stats,
                               int rows_per_chunk, void *ws, size_t ws_bytes, void *stream);
 
+/* Two guards of the PPO learner's repeated steps on one window, both opt-in.  Same contract as the entry points above: kernels
+ * only (no memset node), no allocation, no host synchronisation, no float atomics, bit-identical run to run, capturable in a
+ * graph; an argument error returns DRONESIM_EINVAL before anything touches the device.  They run through the SAME chain, GEMM
+ * and head kernels as their siblings, which take a nullable per-agent gate `active` (int32 [N], DEVICE memory; the older entry
+ * points pass NULL): a workgroup, head row or per-agent sum whose agent has active[i] == 0 returns at entry.
+ *
+ * The per-agent KL early stop (actors only; the critic is never gated):
+ * dronesim_mlp_grad_ppo_gated: dronesim_mlp_grad_ppo_ent plus `active` (NULL: nobody is gated), with stats float32 [6][N].
+ *   stats[5][i] is the NON-NEGATIVE KL estimate of agent i, the mean over the rows of  k = expm1f(dl) - dl,  dl = logp - logp_old
+ *   (the head's own dl): Schulman's (r - 1) - log r, formed without the cancellation of r - 1 (a k that rounds below 0 is 0).
+ *   Per-row plane, reduced per agent in the fixed order of the other stats with float64 partial sums, carried in float64 across
+ *   the chunks.  With the logp_old of dronesim_mlp_logp at the same weights it is exactly 0.  stats[1] (mean logp_old - logp)
+ *   changes sign while a policy moves away and cannot be thresholded; this one can.
+ *   With active == NULL or all ones, grad, loss and stats[0..4] compare equal element by element to dronesim_mlp_grad_ppo_ent's.
+ *   For an agent with active[i] == 0 AT ENTRY no GEMM tile, head row or sum is computed, its slices of grad are left as they
+ *   were, and loss[i] and stats[0..5][i] are written as NaN -- the NaN convention: a skipped step reports NaN, never a stale
+ *   number.  The outputs of the active agents do not depend on which other agents are gated (bit for bit).
+ *   ws: at least dronesim_mlp_grad_ppo_gated_workspace bytes (the sibling's + 4 N rows_per_chunk + 8 N), 8-byte aligned.
+ * dronesim_kl_gate: one small kernel over active, taken (int32 [N], device memory).
+ *   reset != 0 (kl may be NULL):  active[i] = 1, taken[i] = 0.
+ *   otherwise: if active[i] and not (kl[i] <= target_kl): active[i] = 0   (NaN stops; equality continues; a stopped agent
+ *   stays stopped until the next reset);  then, if active[i] is still set, taken[i] += 1.
+ *   target_kl finite and > 0.  EINVAL: N < 1, NULL active / taken, NULL kl without reset, target_kl <= 0, NaN or inf.
+ * dronesim_adam_step_gated: dronesim_adam_step plus `active` (not NULL).  An active agent gets exactly dronesim_adam_step's
+ *   update, bit for bit; for a gated agent the weights, m1, m2, step[i] and its gradient slice are untouched and
+ *   grad_norm[i] = NaN.
+ * The learner's order per actor step is grad_ppo_gated -> kl_gate on that step's stats[5] -> adam_step_gated: the step on which
+ * an agent crosses the threshold computes its gradient and discards it; every later step of the window skips the agent.
+ *
+ * PPO's clipped value loss (critics only, out_kind 0; an actor is EINVAL):
+ * dronesim_mlp_grad_vclip: the critic chain of dronesim_mlp_grad with two more inputs, v_old float32 [R][N] (the values the
+ *   window was collected with) and vf_clip (finite > 0, or +inf: never clamped).  Per row, with V = V_i(x_r), G = target:
+ *     Vc = v_old + clamp(V - v_old, -vf_clip, +vf_clip)   (V itself where it is not clamped),   l = max((V - G)^2, (Vc - G)^2)
+ *     dl/dV = 2 (V - G)  unless the clipped term is the STRICT maximum: there V is clamped and the gradient is 0.
+ *   loss [N] is the clipped objective (times row_scale, summed); clip_fraction float32 [N] the share of zero-gradient rows, from
+ *   one more per-row plane reduced in the fixed order.  Where no row is clamped, grad and loss equal dronesim_mlp_grad's bit
+ *   for bit (the expressions are the same).  ws: at least dronesim_mlp_grad_vclip_workspace bytes (+ 4 N rows_per_chunk).    */
+int dronesim_mlp_grad_ppo_gated_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
+int dronesim_mlp_grad_ppo_gated(const DroneMlp *m, const float *x, int R, float row_scale, const float *act, const float *logp_old,
+                                const float *adv, float clip_eps, float ent_scale, const int32_t *active, float *grad, float *loss,
+                                float *stats, int rows_per_chunk, void *ws, size_t ws_bytes, void *stream);
+int dronesim_kl_gate(const float *kl, float target_kl, int32_t *active, int32_t *taken, int N, int reset, void *stream);
+int dronesim_adam_step_gated(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1, float beta2,
+                             float eps, float max_norm, float *grad_norm, const int32_t *active, void *stream);
+int dronesim_mlp_grad_vclip_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes);
+int dronesim_mlp_grad_vclip(const DroneMlp *m, const float *x, int R, float row_scale, const float *target, const float *v_old,
+                            float vf_clip, float *grad, float *loss, float *clip_fraction, int rows_per_chunk, void *ws,
+                            size_t ws_bytes, void *stream);
+
 /* Shuffled minibatches (csrc/minibatch.hip).  Both entry points only enqueue one kernel on `stream`: no memset node, no
  * allocation, no host synchronisation, no atomics; deterministic, and capturable in a graph.
  *

@@ -34,6 +34,8 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo",
            "dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
            "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent",
+           "dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
+           "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip",
            "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
            "dronesim_row_permutation", "dronesim_gather_rows",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
@@ -169,6 +171,14 @@ def lib():
     L.dronesim_mlp_grad_ppo_ent.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
     for name in ("dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
                  "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent"):
+        getattr(L, name).restype = C.c_int
+    L.dronesim_mlp_grad_ppo_gated_workspace.argtypes = L.dronesim_mlp_grad_vclip_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
+    L.dronesim_mlp_grad_ppo_gated.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    L.dronesim_kl_gate.argtypes = [vp, f32, vp, vp, i32, i32, vp]
+    L.dronesim_adam_step_gated.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp]
+    L.dronesim_mlp_grad_vclip.argtypes = [PM, vp, i32, f32, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    for name in ("dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
+                 "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip"):
         getattr(L, name).restype = C.c_int
     L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
     L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]

@@ -25,6 +25,14 @@
 // heads with the policy's entropy in the loss, kernels of their own behind the same chain (dronesim_mlp_grad_ent,
 // dronesim_mlp_grad_ppo_ent) -- and dronesim_standardize, the per-agent standardisation of a window's advantages (float64 sums,
 // two launches, fixed order).
+//
+// Two guards of the PPO learner's repeated steps on one window (include/dronesim.h), through the SAME chain and kernels: every
+// kernel of the chain takes a nullable per-agent gate `active` (int32 [N], device memory; NULL from the older entry points) --
+// gemm_kernel's batch index is the agent, so a workgroup of a gated agent returns at entry, before any barrier, uniformly; the
+// heads skip its rows and the per-agent sums write NaN for it.  dronesim_mlp_grad_ppo_gated is the PPO-with-entropy chain with
+// that gate and one more per-row plane, the non-negative KL estimate k = expm1(dl) - dl (kl_sum_kernel: float64 partial sums,
+// fixed order); dronesim_kl_gate decides the stop on the device; dronesim_adam_step_gated obeys it.  dronesim_mlp_grad_vclip is
+// the critic chain with PPO's clipped value loss in head_kernel (one more per-row plane of zero-gradient flags).
 #include "common.hpp"
 #include "../../include/dronesim.h"
 
@@ -55,6 +63,7 @@ struct GemmArgs {
     int mode;
     int half_m, half_n;                          // kAccumulate, > 0: outputs with (m < half_m) != (n < half_n) are 0
     int first;                                   // kAccumulate: the window's first chunk WRITES (no separate zeroing)
+    const int32_t *active;                       // NULL, or [batch] in device memory: a batch index with active[b] == 0 is skipped
 };
 
 // 64 x 64 output tile per workgroup, four waves of one 32 x 32 accumulator each; the tile's k-slices go through LDS in k-major
@@ -64,6 +73,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmArgs g)
     __shared__ float As[kBK][kBM + 4];
     __shared__ float Bs[kBK][kBN + 4];
     const int b = blockIdx.z;
+    if (g.active && g.active[b] == 0) return;    // the whole workgroup, before any barrier: a gated agent costs no matrix work
     const float *A = g.A + (long long)b * g.bA;
     const float *B = g.B + (long long)b * g.bB;
     const int m0 = blockIdx.y * kBM, n0 = blockIdx.x * kBN;
@@ -137,9 +147,13 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmArgs g)
 //   kind 0 (critic):       l = (o - G)^2
 //   kind 1 (softmax):      l = -w log softmax(o)[a],  a = the action list's entry nearest to the stored unit action
 //   kind 2 (Gaussian):     l = -w sum_d [-0.5 log(2 pi var_d) - (a_d - mu_d)^2 / (2 var_d)],  mu = tanh, var = sigmoid
+// kind 0 with `v_old` set (dronesim_mlp_grad_vclip) is PPO's clipped value loss: Vc = V clamped to v_old +- vf_clip,
+//   l = max((V - G)^2, (Vc - G)^2); where the clipped term is the STRICT maximum V is clamped and dl/dV = 0, and the row's flag
+//   (0 / 1) goes to the plane Cp [N][Rc].  An unclamped row has Vc = V itself (not v_old + (V - v_old), which rounds): it forms
+//   the plain head's expressions and gives its bits.
 __global__ __launch_bounds__(kThreads) void head_kernel(float *O, float *L, long long Rc, int rc, long long r0, int N, int nout,
                                                         int kind, float scale, const float *target, const float *act,
-                                                        const float *weight)
+                                                        const float *weight, const float *v_old, float vf_clip, float *Cp)
 {
     const long long id = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (id >= (long long)rc * N) return;
@@ -149,8 +163,22 @@ __global__ __launch_bounds__(kThreads) void head_kernel(float *O, float *L, long
     float loss;
     if (kind == 0) {
         const float d = o[0] - target[src];
-        loss = scale * d * d;
-        o[0] = 2.f * scale * d;
+        bool zero = false;
+        float dc = d;
+        if (v_old) {
+            const float vo = v_old[src], dv = o[0] - vo;
+            const float vc = dv > vf_clip ? vo + vf_clip : (dv < -vf_clip ? vo - vf_clip : o[0]);
+            dc = vc - target[src];
+            zero = dc * dc > d * d;
+            Cp[(long long)i * Rc + m] = zero ? 1.f : 0.f;
+        }
+        if (zero) {
+            loss = scale * dc * dc;
+            o[0] = 0.f;
+        } else {
+            loss = scale * d * d;
+            o[0] = 2.f * scale * d;
+        }
     } else if (kind == 1) {
         const float ax = act[2 * src], ay = act[2 * src + 1];
         int a = (int)rintf(atan2f(ay, ax) * (float)nout * 0.15915494309189535f);
@@ -184,11 +212,16 @@ __global__ __launch_bounds__(kThreads) void head_kernel(float *O, float *L, long
 }
 
 // loss[i] (+)= the chunk's per-row losses of agent i, in a fixed order (strided partial sums, then a fixed tree); the first
-// chunk writes
-__global__ __launch_bounds__(kThreads) void loss_sum_kernel(const float *L, long long Rc, int rc, int first, float *loss)
+// chunk writes.  A gated agent (active[i] == 0, uniform over the workgroup) sums nothing: its loss is NaN.
+__global__ __launch_bounds__(kThreads) void loss_sum_kernel(const float *L, long long Rc, int rc, int first, float *loss,
+                                                            const int32_t *active)
 {
     __shared__ float part[kThreads];
     const int i = blockIdx.x;
+    if (active && active[i] == 0) {
+        if (threadIdx.x == 0) loss[i] = __builtin_nanf("");
+        return;
+    }
     float s = 0.f;
     for (int m = threadIdx.x; m < rc; m += kThreads) s += L[(long long)i * Rc + m];
     part[threadIdx.x] = s;
@@ -270,11 +303,16 @@ __global__ __launch_bounds__(kThreads) void ppo_head_kernel(float *O, float *L, 
 
 // stats [4][N] of agent i over the chunks, in loss_sum_kernel's fixed order (strided partials, then a fixed tree): the clipped
 // rows' count, the sum of logp_old - logp, min r, max r; the first chunk writes, the last divides the two sums by R
+// (a gated agent: four NaN)
 __global__ __launch_bounds__(kThreads) void ppo_stats_kernel(const float *S, long long Rc, int rc, int N, int first, int last,
-                                                             float rows, float *stats)
+                                                             float rows, float *stats, const int32_t *active)
 {
     __shared__ float part[4][kThreads];
     const int i = blockIdx.x;
+    if (active && active[i] == 0) {
+        if (threadIdx.x < 4) stats[threadIdx.x * N + i] = __builtin_nanf("");
+        return;
+    }
     const long long plane = (long long)N * Rc;
     const float inf = __builtin_inff();
     float nc = 0.f, kl = 0.f, lo = inf, hi = -inf;
@@ -367,14 +405,18 @@ __global__ __launch_bounds__(kThreads) void head_ent_kernel(float *O, float *L, 
 
 // ppo_head_kernel's gradient mode with the entropy (no forward-only mode: dronesim_mlp_logp stays the sibling's).  The entropy's
 // gradient is added on EVERY row, the rows on the clipped branch included (there the surrogate's part is 0).
+// The gated form (dronesim_mlp_grad_ppo_gated) passes `active` and the plane Kp [N][Rc]: the rows of an agent with
+// active[i] == 0 are skipped, and every other row also stores k = expm1(dl) - dl >= 0, Schulman's (r - 1) - log r formed
+// without the cancellation of r - 1 (exactly 0 at dl = 0).
 __global__ __launch_bounds__(kThreads) void ppo_head_ent_kernel(float *O, float *L, float *S, float *E, long long Rc, int rc,
                                                                 long long r0, int N, int nout, int kind, float scale, float es,
                                                                 const float *act, const float *logp_old, const float *adv,
-                                                                float lo, float hi)
+                                                                float lo, float hi, const int32_t *active, float *Kp)
 {
     const long long id = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (id >= (long long)rc * N) return;
     const int i = (int)(id / rc), m = (int)(id % rc);
+    if (active && active[i] == 0) return;
     float *o = O + ((long long)i * Rc + m) * nout;
     const long long src = (r0 + m) * N + i;
     float lp, lse = 0.f, H = 0.f;
@@ -431,15 +473,21 @@ __global__ __launch_bounds__(kThreads) void ppo_head_ent_kernel(float *O, float 
     S[plane + dst] = -dl;
     S[2 * plane + dst] = r;
     E[dst] = H;
+    if (Kp) Kp[dst] = fmaxf(expm1f(dl) - dl, 0.f);
 }
 
 // entropy[i] = the mean row entropy of agent i over the chunks, in loss_sum_kernel's fixed order (strided partials, then a fixed
 // tree); the first chunk writes, the last divides by R
+// (a gated agent: NaN; dronesim_mlp_grad_vclip reduces its plane of zero-gradient flags with it)
 __global__ __launch_bounds__(kThreads) void entropy_sum_kernel(const float *E, long long Rc, int rc, int first, int last, float rows,
-                                                               float *entropy)
+                                                               float *entropy, const int32_t *active)
 {
     __shared__ float part[kThreads];
     const int i = blockIdx.x;
+    if (active && active[i] == 0) {
+        if (threadIdx.x == 0) entropy[i] = __builtin_nanf("");
+        return;
+    }
     float s = 0.f;
     for (int m = threadIdx.x; m < rc; m += kThreads) s += E[(long long)i * Rc + m];
     part[threadIdx.x] = s;
@@ -452,6 +500,50 @@ __global__ __launch_bounds__(kThreads) void entropy_sum_kernel(const float *E, l
         s = first ? part[0] : entropy[i] + part[0];
         entropy[i] = last ? s / rows : s;
     }
+}
+
+// kl[i] = the mean of the head's k plane of agent i over the chunks, in the same fixed order with float64 partial sums: the
+// running sum stays in acc [N] (float64, workspace) between the chunks, the last chunk writes the float32 mean.  A gated
+// agent: NaN.
+__global__ __launch_bounds__(kThreads) void kl_sum_kernel(const float *Kp, long long Rc, int rc, int first, int last, double rows,
+                                                          double *acc, float *kl, const int32_t *active)
+{
+    __shared__ double part[kThreads];
+    const int i = blockIdx.x;
+    if (active && active[i] == 0) {
+        if (threadIdx.x == 0) kl[i] = __builtin_nanf("");
+        return;
+    }
+    double s = 0.0;
+    for (int m = threadIdx.x; m < rc; m += kThreads) s += (double)Kp[(long long)i * Rc + m];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        s = first ? part[0] : acc[i] + part[0];
+        acc[i] = s;
+        if (last) kl[i] = (float)(s / rows);
+    }
+}
+
+// dronesim_kl_gate: one thread per agent.  reset: every agent active, no step taken.  Otherwise an active agent whose estimate
+// is not <= target_kl (NaN included) stops, and stays stopped; an agent that is still active has one more step counted.
+__global__ __launch_bounds__(kThreads) void kl_gate_kernel(const float *kl, float target_kl, int32_t *active, int32_t *taken, int N,
+                                                           int reset)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= N) return;
+    if (reset) {
+        active[i] = 1;
+        taken[i] = 0;
+        return;
+    }
+    int a = active[i];
+    if (a && !(kl[i] <= target_kl)) active[i] = a = 0;
+    if (a) taken[i] = taken[i] + 1;
 }
 
 struct Tensors {
@@ -473,10 +565,16 @@ Tensors tensors_of(const DroneMlp *m)
 struct Params { float *p[6]; };
 
 // the pre-clip gradient norm of agent i over its six tensors (double partial sums, fixed order); advances the step counter
-__global__ __launch_bounds__(kThreads) void grad_norm_kernel(const float *grad, Tensors t, int32_t *step, float *grad_norm)
+// (dronesim_adam_step_gated: an agent with active[i] == 0 keeps its counter and reports NaN)
+__global__ __launch_bounds__(kThreads) void grad_norm_kernel(const float *grad, Tensors t, int32_t *step, float *grad_norm,
+                                                             const int32_t *active)
 {
     __shared__ double part[kThreads];
     const int i = blockIdx.x;
+    if (active && active[i] == 0) {
+        if (threadIdx.x == 0) grad_norm[i] = __builtin_nanf("");
+        return;
+    }
     double s = 0.0;
     for (int j = 0; j < 6; ++j) {
         const float *g = grad + t.off[j] + (long long)i * t.size[j];
@@ -497,9 +595,10 @@ __global__ __launch_bounds__(kThreads) void grad_norm_kernel(const float *grad, 
 // clip (coef = min(1, max_norm / (norm + 1e-6)), the clipped gradient is written back) and one Adam step, torch's formulas
 __global__ __launch_bounds__(kThreads) void adam_kernel(float *grad, float *m1, float *m2, Params prm, Tensors t,
                                                         const int32_t *step, const float *grad_norm, float lr, float beta1,
-                                                        float beta2, float eps, float max_norm)
+                                                        float beta2, float eps, float max_norm, const int32_t *active)
 {
     const int i = blockIdx.y;
+    if (active && active[i] == 0) return;        // weights, moments and the gradient slice stay as they are
     // the agent's bias corrections (torch: step_size = lr / (1 - beta1^step), sqrt(1 - beta2^step)), once per workgroup
     __shared__ float corr[2];
     if (threadIdx.x == 0) {
@@ -526,9 +625,10 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(float *grad, float *m1, 
     *p = *p - step_size * (m / denom);
 }
 
-int launch_gemm(const GemmArgs &g, int batch, hipStream_t st)
+int launch_gemm(GemmArgs g, int batch, hipStream_t st, const int32_t *active)
 {
     if (g.M <= 0 || g.N <= 0) return DRONESIM_OK;
+    g.active = active;
     dim3 grid((g.N + kBN - 1) / kBN, (g.M + kBM - 1) / kBM, batch);
     hipLaunchKernelGGL(gemm_kernel, grid, dim3(kThreads), 0, st, g);
     return DRONESIM_OK;
@@ -588,9 +688,24 @@ struct EntArgs {
     float *entropy;        // [N]: the mean row entropy (dronesim_mlp_grad_ppo_ent: stats + 4 N)
 };
 
+// what dronesim_mlp_grad_ppo_gated adds to the PPO-with-entropy chain (NULL for the others): the per-agent gate every kernel of
+// the chain obeys, and the k plane + its float64 running sums behind the sibling's workspace
+struct GateArgs {
+    const int32_t *active; // [N], device memory; may be NULL (nothing gated)
+    float *kl;             // [N]: stats + 5 N
+};
+
+// what dronesim_mlp_grad_vclip adds to the critic chain (NULL for the others): the plane of zero-gradient flags sits at S
+struct VclipArgs {
+    const float *v_old;
+    float vf_clip;
+    float *clip_fraction;  // [N]
+};
+
 // The chunked chain of the header comment over all R rows; arguments validated by the entry points.
 int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const float *target, const float *act, const float *weight,
-              const PpoArgs *ppo, const EntArgs *ent, float *grad, float *loss, int rows_per_chunk, void *ws, hipStream_t st)
+              const PpoArgs *ppo, const EntArgs *ent, const GateArgs *gate, const VclipArgs *vc, float *grad, float *loss,
+              int rows_per_chunk, void *ws, hipStream_t st)
 {
     const int N = m->N, din = m->d_in, h1 = m->h1, h2 = m->h2, no = m->nout;
     const long long Rc = rows_per_chunk;
@@ -599,6 +714,9 @@ int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const f
     float *gb2 = grad + t.off[3], *gw3 = grad + t.off[4], *gb3 = grad + t.off[5];
     float *H1 = (float *)ws, *H2 = H1 + N * Rc * h1, *O = H2 + N * Rc * h2, *L = O + N * Rc * no, *S = L + N * Rc;
     float *En = ppo ? S + 3 * N * Rc : S;         // the row entropies, behind the sibling's workspace
+    float *Kp = gate ? En + N * Rc : nullptr;     // the gated form's k plane, then its float64 running sums [N]
+    double *Kacc = gate ? (double *)(Kp + N * Rc) : nullptr;
+    const int32_t *active = gate ? gate->active : nullptr;
 
     const long long xs = (long long)N * din;      // row stride of x
     for (long long r0 = 0; r0 < R; r0 += Rc) {
@@ -608,19 +726,19 @@ int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const f
         // forward
         g = gemm(X, xs, 1, din, m->w1, h1, 1, (long long)din * h1, H1, h1, Rc * h1, rc, h1, din, kReluBias);
         g.bias = m->b1; g.bBias = h1;
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         g = gemm(H1, h1, 1, Rc * h1, m->w2, h2, 1, (long long)h1 * h2, H2, h2, Rc * h2, rc, h2, h1, kReluBias);
         g.bias = m->b2; g.bBias = h2;
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         g = gemm(H2, h2, 1, Rc * h2, m->w3, no, 1, (long long)h2 * no, O, no, Rc * no, rc, no, h2, kBias);
         g.bias = m->b3; g.bBias = no;
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         // head
         const long long items = (long long)rc * N;
         const dim3 hgrid((unsigned)((items + kThreads - 1) / kThreads));
         if (ent && ppo)
             hipLaunchKernelGGL(ppo_head_ent_kernel, hgrid, dim3(kThreads), 0, st, O, L, S, En, Rc, rc, r0, N, no, m->out_kind, row_scale,
-                               ent->scale, act, ppo->logp_old, ppo->adv, ppo->lo, ppo->hi);
+                               ent->scale, act, ppo->logp_old, ppo->adv, ppo->lo, ppo->hi, active, Kp);
         else if (ent)
             hipLaunchKernelGGL(head_ent_kernel, hgrid, dim3(kThreads), 0, st, O, L, En, Rc, rc, r0, N, no, m->out_kind, row_scale,
                                ent->scale, act, weight);
@@ -629,32 +747,38 @@ int run_chain(const DroneMlp *m, const float *x, int R, float row_scale, const f
                                ppo->logp_old, ppo->adv, ppo->lo, ppo->hi, ppo->logp_out);
         else
             hipLaunchKernelGGL(head_kernel, hgrid, dim3(kThreads), 0, st, O, L, Rc, rc, r0, N, no, m->out_kind, row_scale, target, act,
-                               weight);
+                               weight, vc ? vc->v_old : nullptr, vc ? vc->vf_clip : 0.f, S);
         if (ppo && ppo->logp_out) continue;
         // layer 3: dW3 += H2^T dO (+ db3), then dH2 = (dO W3^T) . [H2 > 0] in place of H2
         g = gemm(H2, 1, h2, Rc * h2, O, no, 1, Rc * no, gw3, no, (long long)h2 * no, h2 + 1, no, rc, kAccumulate);
         g.ones_row = h2; g.Cb = gb3; g.bCb = no; g.first = r0 == 0;
         if (m->out_kind == 2) { g.half_m = h2 / 2; g.half_n = no / 2; }
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         g = gemm(O, no, 1, Rc * no, m->w3, 1, no, (long long)h2 * no, H2, h2, Rc * h2, rc, h2, no, kMask);
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         // layer 2: dW2 += H1^T dH2 (+ db2), then dH1 = (dH2 W2^T) . [H1 > 0] in place of H1
         g = gemm(H1, 1, h1, Rc * h1, H2, h2, 1, Rc * h2, gw2, h2, (long long)h1 * h2, h1 + 1, h2, rc, kAccumulate);
         g.ones_row = h1; g.Cb = gb2; g.bCb = h2; g.first = r0 == 0;
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         g = gemm(H2, h2, 1, Rc * h2, m->w2, 1, h2, (long long)h1 * h2, H1, h1, Rc * h1, rc, h1, h2, kMask);
-        launch_gemm(g, N, st);
+        launch_gemm(g, N, st, active);
         // layer 1: dW1 += X^T dH1 (+ db1)
         g = gemm(X, 1, xs, din, H1, h1, 1, Rc * h1, gw1, h1, (long long)din * h1, din + 1, h1, rc, kAccumulate);
         g.ones_row = din; g.Cb = gb1; g.bCb = h1; g.first = r0 == 0;
-        launch_gemm(g, N, st);
-        hipLaunchKernelGGL(loss_sum_kernel, dim3(N), dim3(kThreads), 0, st, L, Rc, rc, (int)(r0 == 0), loss);
+        launch_gemm(g, N, st, active);
+        hipLaunchKernelGGL(loss_sum_kernel, dim3(N), dim3(kThreads), 0, st, L, Rc, rc, (int)(r0 == 0), loss, active);
         if (ppo)
             hipLaunchKernelGGL(ppo_stats_kernel, dim3(N), dim3(kThreads), 0, st, S, Rc, rc, N, (int)(r0 == 0), (int)(r0 + Rc >= R),
-                               (float)R, ppo->stats);
+                               (float)R, ppo->stats, active);
         if (ent)
             hipLaunchKernelGGL(entropy_sum_kernel, dim3(N), dim3(kThreads), 0, st, En, Rc, rc, (int)(r0 == 0), (int)(r0 + Rc >= R),
-                               (float)R, ent->entropy);
+                               (float)R, ent->entropy, active);
+        if (gate)
+            hipLaunchKernelGGL(kl_sum_kernel, dim3(N), dim3(kThreads), 0, st, Kp, Rc, rc, (int)(r0 == 0), (int)(r0 + Rc >= R),
+                               (double)R, Kacc, gate->kl, active);
+        if (vc)
+            hipLaunchKernelGGL(entropy_sum_kernel, dim3(N), dim3(kThreads), 0, st, S, Rc, rc, (int)(r0 == 0), (int)(r0 + Rc >= R),
+                               (float)R, vc->clip_fraction, active);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
@@ -689,6 +813,18 @@ size_t ppo_workspace_bytes(const DroneMlp *m, int rc)
 size_t ent_workspace_bytes(const DroneMlp *m, int rc, bool ppo)
 {
     return (ppo ? ppo_workspace_bytes(m, rc) : workspace_bytes(m, rc)) + sizeof(float) * (size_t)m->N * (size_t)rc;
+}
+
+// the gated PPO form's k plane and the N float64 running sums behind the entropy form's workspace (a multiple of 256 bytes)
+size_t gated_workspace_bytes(const DroneMlp *m, int rc)
+{
+    return ent_workspace_bytes(m, rc, true) + sizeof(float) * (size_t)m->N * (size_t)rc + sizeof(double) * (size_t)m->N;
+}
+
+// the clipped value head's plane of zero-gradient flags behind the gradient workspace
+size_t vclip_workspace_bytes(const DroneMlp *m, int rc)
+{
+    return workspace_bytes(m, rc) + sizeof(float) * (size_t)m->N * (size_t)rc;
 }
 
 // Per-agent standardisation of x [R][N] (include/dronesim.h: dronesim_standardize), two launches over one decomposition that
@@ -973,7 +1109,7 @@ extern "C" int dronesim_mlp_grad_ent(const DroneMlp *m, const float *x, int R, f
     if (ws_bytes < ent_workspace_bytes(m, rows_per_chunk, false))
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ent: workspace smaller than dronesim_mlp_grad_ent_workspace()");
     EntArgs en = {ent_scale, entropy};
-    return run_chain(m, x, R, row_scale, nullptr, act, weight, nullptr, &en, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, row_scale, nullptr, act, weight, nullptr, &en, nullptr, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_mlp_grad_ppo_ent(const DroneMlp *m, const float *x, int R, float row_scale, const float *act,
@@ -992,7 +1128,7 @@ extern "C" int dronesim_mlp_grad_ppo_ent(const DroneMlp *m, const float *x, int 
     PpoArgs p = {};
     p.logp_old = logp_old; p.adv = adv; p.lo = 1.f - clip_eps; p.hi = 1.f + clip_eps; p.stats = stats;
     EntArgs en = {ent_scale, stats + 4 * (size_t)m->N};
-    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, &en, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, &en, nullptr, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_mlp_grad_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
@@ -1021,7 +1157,7 @@ extern "C" int dronesim_mlp_grad(const DroneMlp *m, const float *x, int R, float
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad: rows_per_chunk must be a positive multiple of 64");
     if (ws_bytes < workspace_bytes(m, rows_per_chunk))
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad: workspace smaller than dronesim_mlp_grad_workspace()");
-    return run_chain(m, x, R, row_scale, target, act, weight, nullptr, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, row_scale, target, act, weight, nullptr, nullptr, nullptr, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_mlp_grad_ppo_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
@@ -1044,7 +1180,7 @@ extern "C" int dronesim_mlp_logp(const DroneMlp *m, const float *x, int R, const
     PpoArgs p = {};
     p.logp_out = logp;
     // (grad and loss are not touched by the forward-only chain; the workspace stands in for their base address)
-    return run_chain(m, x, R, 1.f, nullptr, act, nullptr, &p, nullptr, (float *)ws, nullptr, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, 1.f, nullptr, act, nullptr, &p, nullptr, nullptr, nullptr, (float *)ws, nullptr, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
 extern "C" int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, float row_scale, const float *act,
@@ -1060,27 +1196,129 @@ extern "C" int dronesim_mlp_grad_ppo(const DroneMlp *m, const float *x, int R, f
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo: workspace smaller than dronesim_mlp_grad_ppo_workspace()");
     PpoArgs p = {};
     p.logp_old = logp_old; p.adv = adv; p.lo = 1.f - clip_eps; p.hi = 1.f + clip_eps; p.stats = stats;
-    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
+    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, nullptr, nullptr, nullptr, grad, loss, rows_per_chunk, ws, (hipStream_t)stream);
 }
 
-extern "C" int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
-                                  float beta2, float eps, float max_norm, float *grad_norm, void *stream)
+namespace {
+
+int adam_step(const char *where, const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
+              float beta2, float eps, float max_norm, float *grad_norm, const int32_t *active, void *stream)
 {
-    int rc = check_mlp(m, "dronesim_adam_step");
+    int rc = check_mlp(m, where);
     if (rc != DRONESIM_OK) return rc;
-    if (!grad || !m1 || !m2 || !step || !grad_norm)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_adam_step: NULL grad / m1 / m2 / step / grad_norm");
+    if (!grad || !m1 || !m2 || !step || !grad_norm) return fail_at(where, "NULL grad / m1 / m2 / step / grad_norm");
     if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) || !(max_norm > 0.f))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_adam_step: need lr >= 0, 0 <= beta < 1, eps > 0, max_norm > 0");
+        return fail_at(where, "need lr >= 0, 0 <= beta < 1, eps > 0, max_norm > 0");
     hipStream_t st = (hipStream_t)stream;
     const Tensors t = tensors_of(m);
     Params p;
     const float *w[6] = {m->w1, m->b1, m->w2, m->b2, m->w3, m->b3};
     for (int j = 0; j < 6; ++j) p.p[j] = const_cast<float *>(w[j]);
-    hipLaunchKernelGGL(grad_norm_kernel, dim3(m->N), dim3(kThreads), 0, st, grad, t, step, grad_norm);
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(m->N), dim3(kThreads), 0, st, grad, t, step, grad_norm, active);
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((t.per_agent + kThreads - 1) / kThreads), m->N), dim3(kThreads), 0, st,
-                       grad, m1, m2, p, t, step, grad_norm, lr, beta1, beta2, eps, max_norm);
+                       grad, m1, m2, p, t, step, grad_norm, lr, beta1, beta2, eps, max_norm, active);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
     return DRONESIM_OK;
+}
+
+}  // namespace
+
+extern "C" int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
+                                  float beta2, float eps, float max_norm, float *grad_norm, void *stream)
+{
+    return adam_step("dronesim_adam_step", m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, nullptr, stream);
+}
+
+extern "C" int dronesim_adam_step_gated(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
+                                        float beta2, float eps, float max_norm, float *grad_norm, const int32_t *active,
+                                        void *stream)
+{
+    if (!active) return dronesim_fail(DRONESIM_EINVAL, "dronesim_adam_step_gated: NULL active");
+    return adam_step("dronesim_adam_step_gated", m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, active, stream);
+}
+
+extern "C" int dronesim_mlp_grad_ppo_gated_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
+{
+    const int rc = check_actor_call(m, 1, rows_per_chunk, "dronesim_mlp_grad_ppo_gated_workspace");
+    if (rc != DRONESIM_OK) return rc;
+    if (!bytes) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_ppo_gated_workspace: NULL bytes");
+    *bytes = gated_workspace_bytes(m, rows_per_chunk);
+    return DRONESIM_OK;
+}
+
+extern "C" int dronesim_mlp_grad_ppo_gated(const DroneMlp *m, const float *x, int R, float row_scale, const float *act,
+                                           const float *logp_old, const float *adv, float clip_eps, float ent_scale,
+                                           const int32_t *active, float *grad, float *loss, float *stats, int rows_per_chunk,
+                                           void *ws, size_t ws_bytes, void *stream)
+{
+    const char *where = "dronesim_mlp_grad_ppo_gated";
+    const int rc = check_actor_call(m, R, rows_per_chunk, where);
+    if (rc != DRONESIM_OK) return rc;
+    if (!x || !act || !logp_old || !adv || !grad || !loss || !stats || !ws)
+        return fail_at(where, "NULL x / act / logp_old / adv / grad / loss / stats / workspace");
+    if (!(clip_eps > 0.f && clip_eps < 1.f)) return fail_at(where, "clip_eps must be in (0, 1)");
+    if (!(ent_scale >= 0.f) || isinf(ent_scale)) return fail_at(where, "ent_scale must be finite and >= 0");
+    if (ws_bytes < gated_workspace_bytes(m, rows_per_chunk))
+        return fail_at(where, "workspace smaller than dronesim_mlp_grad_ppo_gated_workspace()");
+    if (reinterpret_cast<uintptr_t>(ws) & 7u) return fail_at(where, "workspace not 8-byte aligned");
+    PpoArgs p = {};
+    p.logp_old = logp_old; p.adv = adv; p.lo = 1.f - clip_eps; p.hi = 1.f + clip_eps; p.stats = stats;
+    EntArgs en = {ent_scale, stats + 4 * (size_t)m->N};
+    GateArgs ga = {active, stats + 5 * (size_t)m->N};
+    return run_chain(m, x, R, row_scale, nullptr, act, nullptr, &p, &en, &ga, nullptr, grad, loss, rows_per_chunk, ws,
+                     (hipStream_t)stream);
+}
+
+extern "C" int dronesim_kl_gate(const float *kl, float target_kl, int32_t *active, int32_t *taken, int N, int reset, void *stream)
+{
+    if (N < 1) return dronesim_fail(DRONESIM_EINVAL, "dronesim_kl_gate: N < 1");
+    if (!active || !taken) return dronesim_fail(DRONESIM_EINVAL, "dronesim_kl_gate: NULL active / taken");
+    if (!reset && !kl) return dronesim_fail(DRONESIM_EINVAL, "dronesim_kl_gate: NULL kl (only reset may omit it)");
+    if (!(target_kl > 0.f) || isinf(target_kl)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_kl_gate: target_kl must be finite and > 0");
+    hipLaunchKernelGGL(kl_gate_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, kl,
+                       target_kl, active, taken, N, reset);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
+    return DRONESIM_OK;
+}
+
+namespace {
+
+int check_vclip_call(const DroneMlp *m, int R, int rows_per_chunk, const char *where)
+{
+    const int rc = check_mlp(m, where);
+    if (rc != DRONESIM_OK) return rc;
+    if (m->out_kind != 0) return fail_at(where, "needs a critic (out_kind 0), not an actor");
+    if (R < 1) return fail_at(where, "R < 1");
+    if (rows_per_chunk < 64 || rows_per_chunk % 64 != 0) return fail_at(where, "rows_per_chunk must be a positive multiple of 64");
+    return DRONESIM_OK;
+}
+
+}  // namespace
+
+extern "C" int dronesim_mlp_grad_vclip_workspace(const DroneMlp *m, int rows_per_chunk, size_t *bytes)
+{
+    const int rc = check_vclip_call(m, 1, rows_per_chunk, "dronesim_mlp_grad_vclip_workspace");
+    if (rc != DRONESIM_OK) return rc;
+    if (!bytes) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_grad_vclip_workspace: NULL bytes");
+    *bytes = vclip_workspace_bytes(m, rows_per_chunk);
+    return DRONESIM_OK;
+}
+
+extern "C" int dronesim_mlp_grad_vclip(const DroneMlp *m, const float *x, int R, float row_scale, const float *target,
+                                       const float *v_old, float vf_clip, float *grad, float *loss, float *clip_fraction,
+                                       int rows_per_chunk, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *where = "dronesim_mlp_grad_vclip";
+    const int rc = check_vclip_call(m, R, rows_per_chunk, where);
+    if (rc != DRONESIM_OK) return rc;
+    if (!x || !target || !v_old || !grad || !loss || !clip_fraction || !ws)
+        return fail_at(where, "NULL x / target / v_old / grad / loss / clip_fraction / workspace");
+    if (!(vf_clip > 0.f)) return fail_at(where, "vf_clip must be > 0 (finite, or +inf: never clamped)");
+    if (ws_bytes < vclip_workspace_bytes(m, rows_per_chunk))
+        return fail_at(where, "workspace smaller than dronesim_mlp_grad_vclip_workspace()");
+    VclipArgs vc = {v_old, vf_clip, clip_fraction};
+    return run_chain(m, x, R, row_scale, target, nullptr, nullptr, nullptr, nullptr, nullptr, &vc, grad, loss, rows_per_chunk, ws,
+                     (hipStream_t)stream);
 }

@@ -18,6 +18,12 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
                                        mean row entropy of the window (default 0: off, the calls above)
   normalize_advantage= of PPOLearner   dronesim_standardize   agent i's advantages standardised over the window's T E rows,
                                        once per window before the epochs (default off)
+  target_kl= of PPOLearner             dronesim_mlp_grad_ppo_gated, dronesim_kl_gate, dronesim_adam_step_gated   per-agent KL early
+                                       stop decided and obeyed on the device: an actor whose non-negative KL estimate to the
+                                       window's old policy passes the threshold takes no further step on this window and costs no
+                                       matrix work in the remaining ones; the critic is never gated (default None: off)
+  vf_clip= of PPOLearner               dronesim_mlp_grad_vclip   PPO's clipped value loss against the pre-update values of the
+                                       window (default None: off)
   minibatches= of PPOLearner           dronesim_row_permutation, dronesim_gather_rows   every epoch reshuffles the window's rows
                                        on the device (a permutation keyed by ``shuffle_seed`` and the critic's device-resident
                                        step counter), gathers them into minibatch-ordered buffers with one launch and takes one
@@ -249,6 +255,78 @@ class GradientRunner:
         _native.check(rc, "dronesim_mlp_grad_ppo_ent")
         return self.grad, loss, stats
 
+    # the gated PPO form (actors only): the entropy form's chunks and workspace, grown once by the k plane and its running sums
+    def _gated_workspace(self):
+        import torch
+        from . import _native
+        n = C.c_size_t(0)
+        _native.check(_native.lib().dronesim_mlp_grad_ppo_gated_workspace(C.byref(self._m), self.rc, C.byref(n)),
+                      "dronesim_mlp_grad_ppo_gated_workspace")
+        if int(n.value) > self.ws.numel() * 4:
+            self.ws = torch.empty((int(n.value) + 3) // 4, device=self.mlp.device)
+        self.gated_ws_bytes = int(n.value)
+        self.stats6 = torch.zeros(6, self.mlp.n_agents, device=self.mlp.device)
+
+    def run_ppo_gated(self, x, row_scale, act, logp_old, adv, clip_eps, ent_scale, active=None, loss_out=None, stats_out=None):
+        """`dronesim_mlp_grad_ppo_gated`: returns ``(grad, loss [N], stats [6, N])`` -- ``run_ppo_ent``'s five rows and the
+        non-negative KL estimate (mean of ``expm1(dl) - dl``).  ``active``: int32 ``[N]`` on the device or None; an agent with
+        ``active[i] == 0`` is skipped (its gradient slice untouched, its loss and stats NaN)."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, act=(act, 2), logp_old=(logp_old, 1), adv=(adv, 1))
+        if not hasattr(self, "stats6"):
+            self._gated_workspace()
+        loss = self.loss if loss_out is None else loss_out
+        stats = self.stats6 if stats_out is None else stats_out
+        if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != 6 * mlp.n_agents:
+            raise ValueError(f"stats must be a contiguous float32 tensor [6, {mlp.n_agents}]")
+        if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != mlp.n_agents
+                                   or active.device != self.grad.device):
+            raise ValueError(f"active must be a contiguous int32 tensor [{mlp.n_agents}] on {self.grad.device}")
+        with torch.cuda.device(mlp.device):
+            rc = _native.lib().dronesim_mlp_grad_ppo_gated(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale),
+                                                           act.data_ptr(), logp_old.data_ptr(), adv.data_ptr(), float(clip_eps),
+                                                           float(ent_scale), None if active is None else active.data_ptr(),
+                                                           self.grad.data_ptr(), loss.data_ptr(), stats.data_ptr(), self.rc,
+                                                           self.ws.data_ptr(), self.gated_ws_bytes,
+                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_mlp_grad_ppo_gated")
+        return self.grad, loss, stats
+
+    # the clipped value loss (critics only): the plain chunks and workspace, grown once by the plane of zero-gradient flags
+    def _vclip_workspace(self):
+        import torch
+        from . import _native
+        n = C.c_size_t(0)
+        _native.check(_native.lib().dronesim_mlp_grad_vclip_workspace(C.byref(self._m), self.rc, C.byref(n)),
+                      "dronesim_mlp_grad_vclip_workspace")
+        if int(n.value) > self.ws.numel() * 4:
+            self.ws = torch.empty(int(n.value) // 4, device=self.mlp.device)
+        self.vclip_ws_bytes = int(n.value)
+        self.clip_fraction = torch.zeros(self.mlp.n_agents, device=self.mlp.device)
+
+    def run_vclip(self, x, row_scale, target, v_old, vf_clip, loss_out=None, clip_out=None):
+        """`dronesim_mlp_grad_vclip`: returns ``(grad, loss [N], clip_fraction [N])`` -- the loss is the clipped objective
+        ``row_scale sum max((V - G)^2, (Vc - G)^2)``, clip_fraction the share of rows whose gradient is zero."""
+        import torch
+        from . import _native
+        mlp = self.mlp
+        self._check(x, target=(target, 1), v_old=(v_old, 1))
+        if not hasattr(self, "clip_fraction"):
+            self._vclip_workspace()
+        loss = self.loss if loss_out is None else loss_out
+        clip = self.clip_fraction if clip_out is None else clip_out
+        if clip.dtype != torch.float32 or not clip.is_contiguous() or clip.numel() != mlp.n_agents:
+            raise ValueError(f"clip_fraction must be a contiguous float32 tensor [{mlp.n_agents}]")
+        with torch.cuda.device(mlp.device):
+            rc = _native.lib().dronesim_mlp_grad_vclip(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale),
+                                                       target.data_ptr(), v_old.data_ptr(), float(vf_clip), self.grad.data_ptr(),
+                                                       loss.data_ptr(), clip.data_ptr(), self.rc, self.ws.data_ptr(),
+                                                       self.vclip_ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_mlp_grad_vclip")
+        return self.grad, loss, clip
+
 
 def mlp_gradients(mlp, x, target=None, act=None, weight=None, row_scale=None, rows_per_chunk=None):
     """Per-agent gradients of `mlp`'s loss over the rows of ``x [..., N, d_in]`` (e.g. ``storage.z_pre [T,E,N,d_in]``):
@@ -274,7 +352,9 @@ def mlp_gradients(mlp, x, target=None, act=None, weight=None, row_scale=None, ro
 class BatchedAdam:
     """clip_grad_norm_(max_norm) + torch.optim.Adam (torch defaults: no weight decay, no amsgrad) for the N networks of
     one `BatchedMLP`, one optimiser state per agent: flat moments ``m1`` / ``m2`` and a per-agent step counter in device
-    memory (a captured graph advances it on every replay).  ``step(grad)`` returns the pre-clip norms ``[N]``."""
+    memory (a captured graph advances it on every replay).  ``step(grad)`` returns the pre-clip norms ``[N]``.
+    ``step(grad, active=a)`` (int32 ``[N]`` on the device) is `dronesim_adam_step_gated`: an agent with ``a[i] == 0`` keeps its
+    weights, moments, counter and gradient slice, and its norm is NaN."""
 
     def __init__(self, mlp, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=10.0):
         import torch
@@ -288,20 +368,30 @@ class BatchedAdam:
         self.grad_norm = torch.zeros(mlp.n_agents, device=mlp.device)
         self._m = plain_struct(mlp)
 
-    def step(self, grad, norm_out=None, refresh=True):
+    def step(self, grad, norm_out=None, refresh=True, active=None):
         """``norm_out``: a float32 ``[N]`` device tensor that receives the norms instead of ``self.grad_norm``;
-        ``refresh=False`` leaves the network's forward images stale (the caller refreshes them before the next forward)."""
+        ``refresh=False`` leaves the network's forward images stale (the caller refreshes them before the next forward);
+        ``active``: the per-agent gate of `dronesim_adam_step_gated` (None: `dronesim_adam_step`)."""
         import torch
         from . import _native
         norm = self.grad_norm if norm_out is None else norm_out
         if grad.dtype != torch.float32 or not grad.is_contiguous() or grad.numel() != self.numel or grad.device != self.m1.device:
             raise ValueError(f"grad must be the flat float32 gradient buffer ({self.numel} elements) on {self.m1.device}")
+        if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != self.mlp.n_agents
+                                   or active.device != self.m1.device):
+            raise ValueError(f"active must be a contiguous int32 tensor [{self.mlp.n_agents}] on {self.m1.device}")
         with torch.cuda.device(self.mlp.device):
-            rc = _native.lib().dronesim_adam_step(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
-                                                  self.steps.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                  self.max_norm, norm.data_ptr(),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_adam_step")
+            if active is None:
+                rc = _native.lib().dronesim_adam_step(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
+                                                      self.steps.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                                                      self.max_norm, norm.data_ptr(),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            else:
+                rc = _native.lib().dronesim_adam_step_gated(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(),
+                                                            self.m2.data_ptr(), self.steps.data_ptr(), self.lr, self.betas[0],
+                                                            self.betas[1], self.eps, self.max_norm, norm.data_ptr(),
+                                                            active.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_adam_step" if active is None else "dronesim_adam_step_gated")
         if refresh:
             self.mlp.refresh_weights()
         return norm
@@ -321,6 +411,16 @@ def _check_ent_coef(ent_coef):
     if isinstance(ent_coef, bool) or not isinstance(ent_coef, numbers.Real) or not math.isfinite(ent_coef) or ent_coef < 0:
         raise ValueError(f"ent_coef must be a finite number >= 0, got {ent_coef!r}")
     return float(ent_coef)
+
+
+def _check_positive(name, value):
+    """None (off) or a finite float > 0, else ValueError."""
+    import numbers
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value <= 0:
+        raise ValueError(f"{name} must be None or a finite number > 0, got {value!r}")
+    return float(value)
 
 
 def _ring(storage, T):
@@ -635,13 +735,38 @@ class PPOLearner:
     ``[N]``).  Only the first minibatch of the first epoch sees the weights ``logp_old`` was computed from, and it sees them in
     another row order and chunking than step 2's forward pass: its ratios are 1 to rounding, not bit for bit.  Everything else
     holds as above: both actor kinds, ``lam``, ``time_limit``, ``ent_coef``, ``normalize_advantage``, ``baseline``, no host
-    synchronisation, deterministic, capturable with the rollout in one graph."""
+    synchronisation, deterministic, capturable with the rollout in one graph.
+
+    Two guards of those repeated steps on one window, both None by default (then nothing above changes and nothing more is
+    allocated); each is a finite number > 0, and both compose with every option above:
+
+      ``target_kl``  per-agent KL early stop.  Nothing in step 3 bounds how far ``epochs x K`` steps carry a policy from the one
+                    that collected the window: the ratio clip zeroes the gradient of rows already outside 1 +- clip_eps, it does
+                    not stop the walk; and ``approx_kl`` (mean logp_old - logp) changes sign while a policy moves away, so it
+                    cannot be thresholded.  The loop cannot ``break`` either (no host synchronisation), so the stop is decided
+                    and obeyed ON THE DEVICE through ``self.active`` (int32 ``[N]``): `dronesim_kl_gate` with ``reset`` at the
+                    start of every ``train()``; then every actor step, whole-window or minibatch, is
+                    `dronesim_mlp_grad_ppo_gated` -> `dronesim_kl_gate` on that step's ``kl`` -> `dronesim_adam_step_gated`.
+                    ``kl`` is the non-negative estimate mean(expm1(dl) - dl), dl = logp - logp_old (Schulman's (r - 1) - log r);
+                    an agent stops when not ``kl <= target_kl`` (NaN stops, equality continues).  The step on which an agent
+                    crosses computes its gradient and discards it; every later actor step of the window skips the agent -- no
+                    GEMM tile, head row or sum is computed for it.  The gate is per agent because the agents own their networks
+                    and optimisers, and ONLY ACTORS are gated: KL says nothing about the critic, and the row permutation is
+                    keyed on the critic's step counter, which must keep advancing.  New outputs: ``kl`` ``[epochs(, K), N]``,
+                    ``entropy`` (this is the entropy form of the head, as with ``normalize_advantage``) and ``actor_steps``
+                    (int32 ``[N]``: the Adam steps each actor took this window).  The NaN convention: every per-step actor output
+                    of a skipped step is NaN; in the crossing step they are real except ``actor_grad_norm``, which is NaN.
+      ``vf_clip``   PPO's clipped value loss, the critic's counterpart: its steps go through `dronesim_mlp_grad_vclip` with
+                    ``v_old = self.V``, step 2's pre-update values (no extra forward): per row
+                    ``max((V - G)^2, (clamp(V, v_old +- vf_clip) - G)^2)``, gradient 0 where the clipped term is the strict
+                    maximum.  ``critic_loss`` is that objective; new output ``vf_clip_fraction`` ``[epochs(, K), N]``, the share
+                    of zero-gradient rows (exactly 0 in the first step).  With ``minibatches > 1`` V is a sixth gathered array."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                  baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
-                 adv_eps=1e-8, minibatches=1, shuffle_seed=0):
+                 adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -662,7 +787,10 @@ class PPOLearner:
             raise ValueError(f"adv_eps must be a finite number >= 0, got {adv_eps!r}")
         self.adv_eps = float(adv_eps)
         self.minibatches, self.shuffle_seed = _check_minibatches(minibatches, shuffle_seed)
-        self._ent = self.ent_coef > 0 or self.normalize_advantage           # the entropy form of the head (and its diagnostics)
+        self.target_kl, self.vf_clip = _check_positive("target_kl", target_kl), _check_positive("vf_clip", vf_clip)
+        # the entropy form of the head (and its diagnostics); the gated head is that form
+        self._ent = self.ent_coef > 0 or self.normalize_advantage or self.target_kl is not None
+        self._stat_rows = 6 if self.target_kl is not None else (5 if self._ent else 4)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
@@ -698,9 +826,14 @@ class PPOLearner:
             self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
             self._actor_grad._ppo_workspace()
             self._scalars = torch.zeros(4, self.epochs, N, device=dev)   # critic_loss, actor_loss, critic / actor grad norm
-            self._stats = torch.zeros(self.epochs, 5 if self._ent else 4, N, device=dev)
-            if self._ent:
+            self._stats = torch.zeros(self.epochs, self._stat_rows, N, device=dev)
+            if self.target_kl is not None:
+                self._actor_grad._gated_workspace()
+            elif self._ent:
                 self._actor_grad._ent_workspace(True)
+            if self.vf_clip is not None:
+                self._critic_grad._vclip_workspace()
+                self._vclip = torch.zeros(self.epochs, N, device=dev)
         else:
             # the full-window actor runner is kept ONLY for step 2's forward-only `logp` pass, which needs the plain gradient
             # workspace and neither the PPO nor the entropy one (the epochs run through `_critic_mb` / `_actor_mb`)
@@ -713,6 +846,9 @@ class PPOLearner:
             self._std_ws_bytes = int(n.value)
             self._std_ws = torch.empty(self._std_ws_bytes // 8, dtype=torch.float64, device=dev)
             self.adv_stats = torch.zeros(2, N, device=dev)
+        if self.target_kl is not None:
+            self.active = torch.ones(N, dtype=torch.int32, device=dev)
+            self.actor_steps = torch.zeros(N, dtype=torch.int32, device=dev)
         self._shape = (T, E, N)
 
     def _prepare_minibatches(self, storage, rows, N, K):
@@ -722,17 +858,26 @@ class PPOLearner:
         dev, M = self.critic.device, rows // K
         self.perm = torch.zeros(rows, dtype=torch.int32, device=dev)
         d = storage.z_pre.shape[-1]
-        self._mb = [GatheredRows(shape, K, M, dev) for shape in ((N, d), (N, 2), (N,), (N,), (N,))]   # z_pre, actions, logp_old, adv, G
-        self._mb_dst = (C.c_void_p * 5)(*[g.buf.data_ptr() for g in self._mb])
-        self._mb_row_bytes = (C.c_int64 * 5)(*[g.row_bytes for g in self._mb])
-        self._mb_block_bytes = (C.c_int64 * 5)(*[g.block_bytes for g in self._mb])
+        shapes = ((N, d), (N, 2), (N,), (N,), (N,))                      # z_pre, actions, logp_old, adv, G
+        if self.vf_clip is not None:
+            shapes += ((N,),)                                            # and step 2's V, the clipped value loss's v_old
+        n = len(shapes)
+        self._mb = [GatheredRows(shape, K, M, dev) for shape in shapes]
+        self._mb_dst = (C.c_void_p * n)(*[g.buf.data_ptr() for g in self._mb])
+        self._mb_row_bytes = (C.c_int64 * n)(*[g.row_bytes for g in self._mb])
+        self._mb_block_bytes = (C.c_int64 * n)(*[g.block_bytes for g in self._mb])
         self._critic_mb = GradientRunner(self.critic, M, self.rows_per_chunk)
         self._actor_mb = GradientRunner(self.actor, M, self.rows_per_chunk)
         self._actor_mb._ppo_workspace()
-        if self._ent:
+        if self.target_kl is not None:
+            self._actor_mb._gated_workspace()
+        elif self._ent:
             self._actor_mb._ent_workspace(True)
+        if self.vf_clip is not None:
+            self._critic_mb._vclip_workspace()
+            self._vclip = torch.zeros(self.epochs, K, N, device=dev)
         self._scalars = torch.zeros(4, self.epochs, K, N, device=dev)
-        self._stats = torch.zeros(self.epochs, K, 5 if self._ent else 4, N, device=dev)
+        self._stats = torch.zeros(self.epochs, K, self._stat_rows, N, device=dev)
 
     def _train_minibatches(self, storage, lib, stream):
         """Step 3 with ``minibatches = K > 1``: per epoch a fresh device permutation, one gather, K critic-then-actor steps."""
@@ -742,21 +887,30 @@ class PPOLearner:
         K, rows = self.minibatches, T * E
         M = rows // K
         # (z_pre and actions are contiguous float32: step 2's forward-only pass has checked them)
-        src = (C.c_void_p * 5)(storage.z_pre.data_ptr(), storage.actions.data_ptr(), self.logp_old.data_ptr(), self.adv.data_ptr(),
-                               self.G.data_ptr())
+        arrays = [storage.z_pre, storage.actions, self.logp_old, self.adv, self.G] + ([self.V] if self.vf_clip is not None else [])
+        n_arrays = len(arrays)
+        src = (C.c_void_p * n_arrays)(*[t.data_ptr() for t in arrays])
         closs, aloss, cnorm, anorm = self._scalars
         for ep in range(self.epochs):
             with torch.cuda.device(self.critic.device):
                 rc = lib.dronesim_row_permutation(rows, self.shuffle_seed, self.critic_opt.steps.data_ptr(), self.perm.data_ptr(), stream)
                 _native.check(rc, "dronesim_row_permutation")
-                rc = lib.dronesim_gather_rows(self.perm.data_ptr(), rows, M, 5, src, self._mb_dst, self._mb_row_bytes,
+                rc = lib.dronesim_gather_rows(self.perm.data_ptr(), rows, M, n_arrays, src, self._mb_dst, self._mb_row_bytes,
                                               self._mb_block_bytes, stream)
                 _native.check(rc, "dronesim_gather_rows")
             for b in range(K):
                 last = ep == self.epochs - 1 and b == K - 1
-                x, act, logp_old, adv, G = (g.blocks[b] for g in self._mb)
-                cg, _ = self._critic_mb.run(x, 1.0 / M, target=G, loss_out=closs[ep, b])
+                x, act, logp_old, adv, G = (g.blocks[b] for g in self._mb[:5])
+                if self.vf_clip is not None:
+                    cg, _, _ = self._critic_mb.run_vclip(x, 1.0 / M, G, self._mb[5].blocks[b], self.vf_clip, loss_out=closs[ep, b],
+                                                         clip_out=self._vclip[ep, b])
+                else:
+                    cg, _ = self._critic_mb.run(x, 1.0 / M, target=G, loss_out=closs[ep, b])
                 self.critic_opt.step(cg, norm_out=cnorm[ep, b], refresh=last)
+                if self.target_kl is not None:
+                    self._gated_actor_step(self._actor_mb, x, 1.0 / M, act, logp_old, adv, self.ent_coef / M, aloss[ep, b],
+                                           self._stats[ep, b], anorm[ep, b], last, lib, stream)
+                    continue
                 if self._ent:
                     ag, _, _ = self._actor_mb.run_ppo_ent(x, 1.0 / M, act, logp_old, adv, self.clip_eps, self.ent_coef / M,
                                                           loss_out=aloss[ep, b], stats_out=self._stats[ep, b])
@@ -771,7 +925,26 @@ class PPOLearner:
             out["entropy"] = st[:, :, 4]
         if self.normalize_advantage:
             out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
+        if self.target_kl is not None:
+            out.update(kl=st[:, :, 5], actor_steps=self.actor_steps)
+        if self.vf_clip is not None:
+            out["vf_clip_fraction"] = self._vclip
         return out
+
+    def _kl_gate(self, kl, reset, lib, stream):
+        import torch
+        from . import _native
+        with torch.cuda.device(self.critic.device):
+            rc = lib.dronesim_kl_gate(None if kl is None else kl.data_ptr(), self.target_kl, self.active.data_ptr(),
+                                      self.actor_steps.data_ptr(), self.actor.n_agents, int(reset), stream)
+        _native.check(rc, "dronesim_kl_gate")
+
+    def _gated_actor_step(self, runner, x, row_scale, act, logp_old, adv, ent_scale, loss_out, stats_out, norm_out, last, lib, stream):
+        """One actor step under ``target_kl``: the gated gradient, the gate on this step's KL estimate, the gated Adam step."""
+        ag, _, st = runner.run_ppo_gated(x, row_scale, act, logp_old, adv, self.clip_eps, ent_scale, active=self.active,
+                                         loss_out=loss_out, stats_out=stats_out)
+        self._kl_gate(st[5], False, lib, stream)
+        self.actor_opt.step(ag, norm_out=norm_out, refresh=last, active=self.active)
 
     def train(self, storage):
         import torch
@@ -780,6 +953,8 @@ class PPOLearner:
         T, E, N = self._shape
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         x, act, nbr = storage.z_pre, storage.actions, storage.nbr_pre
+        if self.target_kl is not None:
+            self._kl_gate(None, True, lib, stream)
         if self.lam is None:
             with torch.cuda.device(self.critic.device):
                 rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
@@ -807,8 +982,16 @@ class PPOLearner:
         closs, aloss, cnorm, anorm = self._scalars
         for ep in range(self.epochs):
             last = ep == self.epochs - 1
-            cg, _ = self._critic_grad.run(x, 1.0 / (T * E), target=self.G, loss_out=closs[ep])
+            if self.vf_clip is not None:
+                cg, _, _ = self._critic_grad.run_vclip(x, 1.0 / (T * E), self.G, self.V, self.vf_clip, loss_out=closs[ep],
+                                                       clip_out=self._vclip[ep])
+            else:
+                cg, _ = self._critic_grad.run(x, 1.0 / (T * E), target=self.G, loss_out=closs[ep])
             self.critic_opt.step(cg, norm_out=cnorm[ep], refresh=last)
+            if self.target_kl is not None:
+                self._gated_actor_step(self._actor_grad, x, 1.0 / (T * E), act, self.logp_old, self.adv, self.ent_coef / (T * E),
+                                       aloss[ep], self._stats[ep], anorm[ep], last, lib, stream)
+                continue
             if self._ent:
                 ag, _, _ = self._actor_grad.run_ppo_ent(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps,
                                                         self.ent_coef / (T * E), loss_out=aloss[ep], stats_out=self._stats[ep])
@@ -823,4 +1006,8 @@ class PPOLearner:
             out["entropy"] = st[:, 4]
         if self.normalize_advantage:
             out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
+        if self.target_kl is not None:
+            out.update(kl=st[:, 5], actor_steps=self.actor_steps)
+        if self.vf_clip is not None:
+            out["vf_clip_fraction"] = self._vclip
         return out

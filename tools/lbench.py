@@ -10,6 +10,8 @@ or, with ``--learner ppo``, one `PPOLearner.train` of ``--epochs M`` epochs --, 
     python tools/lbench.py --learner ppo --epochs M --ent-coef 0.01 --normalize-advantage [--out profiles/entropy_lbench.jsonl]
     python tools/lbench.py --learner ppo --epochs M --minibatches K [--out profiles/minibatch_lbench.jsonl]
     python tools/lbench.py --gather [--configs c1,c3,c5] [--reps 5] [--minibatches K] [--out profiles/minibatch_lbench.jsonl]
+    python tools/lbench.py --learner ppo --epochs M [--target-kl X] [--vf-clip X] [--out profiles/target_kl_lbench.jsonl]
+    python tools/lbench.py --gate-compare [--configs c3,c5] [--reps 3] [--out profiles/target_kl_lbench.jsonl]
 
 ``--lam X`` times the learner with bootstrapped lambda-returns (one more ring slot of observations; off by default).
 ``--time-limit bootstrap`` (with ``--lam``) times it with time-limit ends bootstrapped from their terminal observations: the
@@ -27,6 +29,12 @@ network; per epoch one `dronesim_row_permutation` and one `dronesim_gather_rows`
 five learner arrays of a window (z_pre, actions, logp_old, adv, G: 4 N (d_in + 5) bytes per row) cut into K blocks (default 4,
 ``--minibatches 1`` is a single block), every block rounded up to 256 bytes as the learner does, next to a plain device-to-device copy of the same five arrays in the same process: device events around
 ``--calls`` back-to-back calls, median and minimum over ``--reps``; bytes moved = 2 x the arrays' bytes.
+``--target-kl X`` / ``--vf-clip X`` (``--learner ppo``) time a whole update with the per-agent KL early stop / the clipped value
+loss; with either, the line also carries ``critic_epoch_ms``, a critic-only epoch (the critic's gradient chain + its Adam step)
+timed in the same process.  ``--gate-compare`` answers "does a stopped agent cost no matrix work": in ONE process, alternating
+after a warm-up, it times `PPOLearner.train` at 2 and at 6 epochs with ``target_kl = 1e-30`` (every agent stops on its second
+step) and without the gate, and the critic-only epoch.  The marginal cost of a later gated epoch, (t_gated(6) - t_gated(2)) / 4,
+is allowed the critic-only epoch + 15 %; it is also reported as a share of the ungated marginal epoch.
 ``--scans`` times the learner-side scans alone instead: `dronesim_returns` (the yardstick) and `dronesim_lambda_returns`
 with G only and with G + A, on the same buffers in the same process, device events around ``--calls`` back-to-back calls
 after a warm-up, median and minimum over ``--reps`` repetitions, one JSON line each (appended to ``--out`` when given).
@@ -317,6 +325,100 @@ def scans_time_limit(args):
                 f.write(json.dumps(line) + "\n")
 
 
+def window_of(torch, name, dev="cuda:0", lam=None, boot=False):
+    """The seeded networks and the storage-like window of one shape: (actor weights, actor kind, critic weights, storage, widths)."""
+    N, E, T, kind = CONFIGS[name]
+    d_in = 6
+    g = torch.Generator(device=dev).manual_seed(0)
+    u = lambda *s, fan: (torch.rand(*s, device=dev, generator=g) * 2 - 1) / math.sqrt(fan)
+    net = lambda h1, h2, no: [u(N, d_in, h1, fan=d_in), u(N, h1, fan=d_in), u(N, h1, h2, fan=h1), u(N, h2, fan=h1),
+                              u(N, h2, no, fan=h2), u(N, no, fan=h2)]
+    if kind == "softmax":
+        aw, ak, widths = net(300, 300, 16), 1, (300, 300, 16)
+    else:
+        aw, ak, widths = net(400, 400, 4), 2, (400, 400, 4)
+        aw[4][:, :200, 2:] = 0; aw[4][:, 200:, :2] = 0
+    cw = net(200, 200, 1)
+    ring = (torch.rand(T + (lam is not None), E, N, d_in, device=dev, generator=g) * 2 - 1) * 3
+    a = torch.randint(0, 16, (T, E, N), device=dev, generator=g).float() * (2 * math.pi / 16)
+    st = SimpleNamespace(z_pre=ring[:T], reward=torch.randn(T, E, N, device=dev, generator=g),
+                         done=torch.zeros(T, E, dtype=torch.uint8, device=dev), actions=torch.stack([a.cos(), a.sin()], -1),
+                         nbr_pre=torch.stack([torch.arange(N, device=dev).expand(T, E, N)] * 3, -1).int().contiguous())
+    st.done[-1] = 1
+    if lam is not None:        # the T+1-slot observation ring the bootstrap reads (`RolloutStorage.z_all`)
+        st.z_all = ring
+    if boot:                        # every episode ends at the window's last step with all agents outside the goal disk
+        st.z_final = torch.ones(T, E, N, d_in, device=dev)
+    return aw, ak, cw, st, widths
+
+
+def critic_epoch_ms(torch, learner, st, reps):
+    """A critic-only epoch of a whole-window `PPOLearner` that has trained once: its gradient chain + its Adam step (best of reps)."""
+    T, E, N = learner._shape
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    times = []
+    for _ in range(reps + 1):
+        ev[0].record()
+        if learner.vf_clip is not None:
+            cg, _, _ = learner._critic_grad.run_vclip(st.z_pre, 1.0 / (T * E), learner.G, learner.V, learner.vf_clip)
+        else:
+            cg, _ = learner._critic_grad.run(st.z_pre, 1.0 / (T * E), target=learner.G)
+        learner.critic_opt.step(cg, refresh=False)
+        ev[1].record()
+        torch.cuda.synchronize()
+        times.append(ev[0].elapsed_time(ev[1]))
+    return min(times[1:])
+
+
+def gate_compare(args):
+    """`PPOLearner.train` at 2 and 6 epochs, gated (target_kl = 1e-30: every agent stops on its second step) and not, alternating in
+    one process after a warm-up, next to the critic-only epoch."""
+    import statistics
+
+    import torch
+    from scalable_collision_avoidance_rl_amd.learner import PPOLearner
+    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+    dev = "cuda:0"
+    lines = []
+    for name in args.configs.split(","):
+        N, E, T, kind = CONFIGS[name]
+        aw, ak, cw, st, _ = window_of(torch, name)
+        runs = {}
+        for what, kw in (("gated_2", dict(epochs=2, target_kl=1e-30)), ("gated_6", dict(epochs=6, target_kl=1e-30)),
+                         ("plain_2", dict(epochs=2)), ("plain_6", dict(epochs=6))):
+            actor = BatchedMLP(*[w.clone() for w in aw], ak, ak, device=dev)
+            critic = BatchedMLP(*[w.clone() for w in cw], 0, 0, device=dev)
+            runs[what] = PPOLearner(actor, critic, 0.99, **kw)
+        for learner in runs.values():
+            for _ in range(max(1, args.warmup)):
+                learner.train(st)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        times = {k: [] for k in runs}
+        for _ in range(args.reps):
+            for what, learner in runs.items():
+                ev[0].record(); out = learner.train(st); ev[1].record()
+                torch.cuda.synchronize()
+                times[what].append(ev[0].elapsed_time(ev[1]))
+                if what.startswith("gated"):
+                    assert out["actor_steps"].tolist() == [1] * N, out["actor_steps"]
+        critic_ms = critic_epoch_ms(torch, runs["plain_2"], st, args.reps)
+        med = {k: statistics.median(v) for k, v in times.items()}
+        gated, plain = (med["gated_6"] - med["gated_2"]) / 4, (med["plain_6"] - med["plain_2"]) / 4
+        line = dict(what="marginal epoch with every agent stopped", config=name, N=N, E=E, T=T, actor=kind,
+                    ms={k: round(v, 3) for k, v in med.items()}, ms_all={k: [round(t, 3) for t in v] for k, v in times.items()},
+                    gated_marginal_epoch_ms=round(gated, 3), plain_marginal_epoch_ms=round(plain, 3),
+                    critic_epoch_ms=round(critic_ms, 3), allowed_ms=round(critic_ms * 1.15, 3), inside=bool(gated <= critic_ms * 1.15),
+                    share_of_plain_epoch=round(gated / plain, 4), reps=args.reps)
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="c1,c3,c5")
@@ -335,6 +437,11 @@ def main():
     ap.add_argument("--minibatches", type=int, default=None,
                     help="shuffled minibatches per epoch (--learner ppo; default 1: off); with --gather: the blocks (default 4; 1 = a single block)")
     ap.add_argument("--gather", action="store_true", help="time dronesim_row_permutation + dronesim_gather_rows against a plain copy")
+    ap.add_argument("--target-kl", type=float, default=None, help="per-agent KL early stop of the actors (--learner ppo; default: off)")
+    ap.add_argument("--vf-clip", type=float, default=None, help="clipped value loss with this range (--learner ppo; default: off)")
+    ap.add_argument("--gate-compare", action="store_true",
+                    help="gated against ungated PPOLearner.train at 2 and 6 epochs and the critic-only epoch, in one process")
+    ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per timed repetition (--scans)")
     ap.add_argument("--out", help="append the JSON lines to this file")
     args = ap.parse_args()
@@ -354,6 +461,10 @@ def main():
             print(json.dumps(dict(kernel=r["Name"][:60], calls=int(r["Calls"]), total_ms=round(float(r["TotalDurationNs"]) / 1e6, 3),
                                   share=round(float(r["TotalDurationNs"]) / tot, 4))))
         return
+    if (args.target_kl is not None or args.vf_clip is not None) and args.learner != "ppo":
+        ap.error("--target-kl and --vf-clip need --learner ppo")
+    if args.gate_compare:
+        return gate_compare(args)
     if args.gather:
         return gather_bench(args)
     if args.scans and args.standardize:
@@ -368,31 +479,12 @@ def main():
     for name in args.configs.split(","):
         N, E, T, kind = CONFIGS[name]
         d_in = 6
-        g = torch.Generator(device=dev).manual_seed(0)
-        u = lambda *s, fan: (torch.rand(*s, device=dev, generator=g) * 2 - 1) / math.sqrt(fan)
-        net = lambda h1, h2, no: [u(N, d_in, h1, fan=d_in), u(N, h1, fan=d_in), u(N, h1, h2, fan=h1), u(N, h2, fan=h1),
-                                  u(N, h2, no, fan=h2), u(N, no, fan=h2)]
-        if kind == "softmax":
-            aw, ak, (h1a, h2a, noa) = net(300, 300, 16), 1, (300, 300, 16)
-        else:
-            aw, ak, (h1a, h2a, noa) = net(400, 400, 4), 2, (400, 400, 4)
-            aw[4][:, :200, 2:] = 0; aw[4][:, 200:, :2] = 0
-        actor, critic = BatchedMLP(*aw, ak, ak, device=dev), BatchedMLP(*net(200, 200, 1), 0, 0, device=dev)
         lam_kw = {} if args.lam is None else dict(lam=args.lam)
         boot = args.time_limit == "bootstrap"
         if boot:
             lam_kw["time_limit"] = "bootstrap"
-        ring = (torch.rand(T + (args.lam is not None), E, N, d_in, device=dev, generator=g) * 2 - 1) * 3
-        x = ring[:T]
-        a = torch.randint(0, 16, (T, E, N), device=dev, generator=g).float() * (2 * math.pi / 16)
-        st = SimpleNamespace(z_pre=x, reward=torch.randn(T, E, N, device=dev, generator=g),
-                             done=torch.zeros(T, E, dtype=torch.uint8, device=dev), actions=torch.stack([a.cos(), a.sin()], -1),
-                             nbr_pre=torch.stack([torch.arange(N, device=dev).expand(T, E, N)] * 3, -1).int().contiguous())
-        st.done[-1] = 1
-        if args.lam is not None:        # the T+1-slot observation ring the bootstrap reads (`RolloutStorage.z_all`)
-            st.z_all = ring
-        if boot:                        # every episode ends at the window's last step with all agents outside the goal disk
-            st.z_final = torch.ones(T, E, N, d_in, device=dev)
+        aw, ak, cw, st, (h1a, h2a, noa) = window_of(torch, name, dev, args.lam, boot)
+        actor, critic = BatchedMLP(*aw, ak, ak, device=dev), BatchedMLP(*cw, 0, 0, device=dev)
         ppo = args.learner == "ppo"
         if args.ent_coef:
             lam_kw["ent_coef"] = args.ent_coef
@@ -400,6 +492,10 @@ def main():
             lam_kw["normalize_advantage"] = True
         if args.minibatches > 1:
             lam_kw["minibatches"] = args.minibatches
+        if args.target_kl is not None:
+            lam_kw["target_kl"] = args.target_kl
+        if args.vf_clip is not None:
+            lam_kw["vf_clip"] = args.vf_clip
         learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs, **lam_kw) if ppo else SA2CLearner(actor, critic, 0.99, **lam_kw)
         for _ in range(args.warmup):
             learner.train(st)
@@ -430,6 +526,14 @@ def main():
             tag["normalize_advantage"] = True
         if args.minibatches > 1:
             tag["minibatches"] = args.minibatches
+        if args.target_kl is not None:
+            tag.update(target_kl=args.target_kl, actor_steps=[int(v) for v in (learner.actor_steps.min(), learner.actor_steps.max())])
+        if args.vf_clip is not None:
+            tag["vf_clip"] = args.vf_clip
+        if (args.target_kl is not None or args.vf_clip is not None) and args.minibatches == 1:
+            tag["critic_epoch_ms"] = round(critic_epoch_ms(torch, learner, st, args.reps), 3)
+        if args.tag:
+            tag["tag"] = args.tag
         lines.append(dict(config=name, **tag, N=N, E=E, T=T, actor=kind, ms_per_update=round(ms, 3),
                           ms_all=[round(t, 3) for t in times], flop=flop, tflops=round(flop / ms / 1e9, 2),
                           peak_share=round(flop / ms / 1e9 / PEAK_TF, 4)))
