@@ -112,7 +112,16 @@ def default_rows_per_chunk(rows, mlp=None, cap=8192, budget=WORKSPACE_BUDGET):
 
 
 class GradientRunner:
-    """`dronesim_mlp_grad` for one network with its own persistent buffers: ``run()`` allocates nothing."""
+    """`dronesim_mlp_grad` and its forms for one network with its own persistent buffers: a call allocates nothing after the
+    first of its form."""
+
+    # the forms with a per-agent result beside the loss, by entry point `dronesim_mlp_<form>`: the attribute that keeps the
+    # form's workspace bytes, the attribute of the lazily made result tensor, its name in messages and its leading shape
+    _FORMS = {"grad_ppo": ("ppo_ws_bytes", "stats", "stats", (4,)),                  # actors: the head's per-row diagnostics
+              "grad_ent": ("ent_ws_bytes", "entropy", "entropy", ()),                # actors: + the plane of the row entropies
+              "grad_ppo_ent": ("ppo_ent_ws_bytes", "stats5", "stats", (5,)),
+              "grad_ppo_gated": ("gated_ws_bytes", "stats6", "stats", (6,)),         # + the k plane and its running sums
+              "grad_vclip": ("vclip_ws_bytes", "clip_fraction", "clip_fraction", ())}    # critics: + the zero-gradient flags
 
     def __init__(self, mlp, rows, rows_per_chunk=None):
         import torch
@@ -134,198 +143,91 @@ class GradientRunner:
             if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.rows * mlp.n_agents * k):
                 raise ValueError(f"{name} must be a contiguous float32 tensor of {self.rows} x {mlp.n_agents} x {k}")
 
+    def _workspace(self, form):
+        """The workspace bytes and the result tensor of one of `_FORMS`; the first call per form asks the library, grows the one
+        shared workspace where this form needs more, and makes the tensor."""
+        import torch
+        from . import _native
+        bytes_attr, out_attr, _, lead = self._FORMS[form]
+        if not hasattr(self, out_attr):
+            name, n = f"dronesim_mlp_{form}_workspace", C.c_size_t(0)
+            _native.check(getattr(_native.lib(), name)(C.byref(self._m), self.rc, C.byref(n)), name)
+            if int(n.value) > self.ws.numel() * 4:
+                self.ws = torch.empty((int(n.value) + 3) // 4, device=self.mlp.device)
+            setattr(self, bytes_attr, int(n.value))
+            setattr(self, out_attr, torch.zeros(*lead, self.mlp.n_agents, device=self.mlp.device))
+        return getattr(self, bytes_attr), getattr(self, out_attr)
+
+    def _call(self, form, x, row_scale, head, loss_out=None, out=None):
+        """The one call path: ``dronesim_mlp_<form>(m, x, rows, row_scale, *head, grad, loss[, result], chunk, workspace, stream)``
+        -- ``head`` are the form's own arguments (tensors, None or numbers) in the entry point's order; ``logp`` has neither
+        ``row_scale`` nor gradient and loss.  ``loss_out`` / ``out`` replace ``self.loss`` / the form's own result tensor.
+        Returns ``(grad, loss[, result])``."""
+        import torch
+        from . import _native
+        loss = self.loss if loss_out is None else loss_out
+        ws_bytes, results = self.ws_bytes, () if form == "logp" else (self.grad.data_ptr(), loss.data_ptr())
+        if form in self._FORMS:
+            ws_bytes, own = self._workspace(form)
+            out = own if out is None else out
+            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != own.numel():
+                raise ValueError(f"{self._FORMS[form][2]} must be a contiguous float32 tensor {list(own.shape)}")
+            results += (out.data_ptr(),)
+        name, scale = "dronesim_mlp_" + form, () if form == "logp" else (float(row_scale),)
+        ptr = lambda t: t.data_ptr() if hasattr(t, "data_ptr") else t
+        with torch.cuda.device(self.mlp.device):
+            rc = getattr(_native.lib(), name)(C.byref(self._m), x.data_ptr(), self.rows, *scale, *map(ptr, head), *results, self.rc,
+                                              self.ws.data_ptr(), ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, name)
+        return (self.grad, loss) if out is None else (self.grad, loss, out)
+
     def run(self, x, row_scale, target=None, act=None, weight=None, loss_out=None):
         """``loss_out``: a float32 ``[N]`` device tensor that receives the losses instead of ``self.loss``."""
-        import torch
-        from . import _native
-        mlp = self.mlp
         self._check(x, target=(target, 1), act=(act, 2), weight=(weight, 1))
-        loss = self.loss if loss_out is None else loss_out
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_grad(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), ptr(target),
-                                                 ptr(act), ptr(weight), self.grad.data_ptr(), loss.data_ptr(), self.rc,
-                                                 self.ws.data_ptr(), self.ws_bytes,
-                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_grad")
-        return self.grad, loss
-
-    # the PPO path (actors only): same chunks, same workspace (grown once by the head's three per-row diagnostics)
-    def _ppo_workspace(self):
-        import torch
-        from . import _native
-        n = C.c_size_t(0)
-        _native.check(_native.lib().dronesim_mlp_grad_ppo_workspace(C.byref(self._m), self.rc, C.byref(n)),
-                      "dronesim_mlp_grad_ppo_workspace")
-        if int(n.value) > self.ws.numel() * 4:
-            self.ws = torch.empty(int(n.value) // 4, device=self.mlp.device)
-        self.ppo_ws_bytes = int(n.value)
-        self.stats = torch.zeros(4, self.mlp.n_agents, device=self.mlp.device)
+        return self._call("grad", x, row_scale, (target, act, weight), loss_out)
 
     def logp(self, x, act, out):
         """`dronesim_mlp_logp`: ``out [rows, N]`` (float32, overwritten) = log pi_i(act | x) under the current weights."""
-        import torch
-        from . import _native
-        mlp = self.mlp
         self._check(x, act=(act, 2), logp=(out, 1))
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_logp(C.byref(self._m), x.data_ptr(), self.rows, act.data_ptr(), out.data_ptr(), self.rc,
-                                                 self.ws.data_ptr(), self.ws_bytes,
-                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_logp")
+        self._call("logp", x, None, (act, out))
         return out
 
     def run_ppo(self, x, row_scale, act, logp_old, adv, clip_eps, loss_out=None, stats_out=None):
         """`dronesim_mlp_grad_ppo`: returns ``(grad, loss [N], stats [4, N])`` -- stats rows: clipped share, mean
         ``logp_old - logp``, min and max ratio."""
-        import torch
-        from . import _native
-        mlp = self.mlp
         self._check(x, act=(act, 2), logp_old=(logp_old, 1), adv=(adv, 1))
-        if not hasattr(self, "stats"):
-            self._ppo_workspace()
-        loss = self.loss if loss_out is None else loss_out
-        stats = self.stats if stats_out is None else stats_out
-        if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != 4 * mlp.n_agents:
-            raise ValueError(f"stats must be a contiguous float32 tensor [4, {mlp.n_agents}]")
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_grad_ppo(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), act.data_ptr(),
-                                                     logp_old.data_ptr(), adv.data_ptr(), float(clip_eps), self.grad.data_ptr(),
-                                                     loss.data_ptr(), stats.data_ptr(), self.rc, self.ws.data_ptr(),
-                                                     self.ppo_ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_grad_ppo")
-        return self.grad, loss, stats
-
-    # the entropy forms (actors only): the sibling's chunks and workspace, grown once by the plane of the row entropies
-    def _ent_workspace(self, ppo):
-        import torch
-        from . import _native
-        n = C.c_size_t(0)
-        name = "dronesim_mlp_grad_ppo_ent_workspace" if ppo else "dronesim_mlp_grad_ent_workspace"
-        _native.check(getattr(_native.lib(), name)(C.byref(self._m), self.rc, C.byref(n)), name)
-        if int(n.value) > self.ws.numel() * 4:
-            self.ws = torch.empty(int(n.value) // 4, device=self.mlp.device)
-        if ppo:
-            self.ppo_ent_ws_bytes = int(n.value)
-            self.stats5 = torch.zeros(5, self.mlp.n_agents, device=self.mlp.device)
-        else:
-            self.ent_ws_bytes = int(n.value)
-            self.entropy = torch.zeros(self.mlp.n_agents, device=self.mlp.device)
+        return self._call("grad_ppo", x, row_scale, (act, logp_old, adv, float(clip_eps)), loss_out, stats_out)
 
     def run_ent(self, x, row_scale, act, weight, ent_scale, loss_out=None, entropy_out=None):
         """`dronesim_mlp_grad_ent`: returns ``(grad, loss [N], entropy [N])`` -- the loss is the whole objective
         (``run``'s minus ``ent_scale`` x the summed row entropies), entropy the mean row entropy per agent."""
-        import torch
-        from . import _native
-        mlp = self.mlp
         self._check(x, act=(act, 2), weight=(weight, 1))
-        if not hasattr(self, "entropy"):
-            self._ent_workspace(False)
-        loss = self.loss if loss_out is None else loss_out
-        ent = self.entropy if entropy_out is None else entropy_out
-        if ent.dtype != torch.float32 or not ent.is_contiguous() or ent.numel() != mlp.n_agents:
-            raise ValueError(f"entropy must be a contiguous float32 tensor [{mlp.n_agents}]")
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_grad_ent(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), act.data_ptr(),
-                                                     weight.data_ptr(), float(ent_scale), self.grad.data_ptr(), loss.data_ptr(),
-                                                     ent.data_ptr(), self.rc, self.ws.data_ptr(), self.ent_ws_bytes,
-                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_grad_ent")
-        return self.grad, loss, ent
+        return self._call("grad_ent", x, row_scale, (act, weight, float(ent_scale)), loss_out, entropy_out)
 
     def run_ppo_ent(self, x, row_scale, act, logp_old, adv, clip_eps, ent_scale, loss_out=None, stats_out=None):
         """`dronesim_mlp_grad_ppo_ent`: returns ``(grad, loss [N], stats [5, N])`` -- ``run_ppo``'s four rows and the mean row
         entropy; the loss is the whole objective."""
-        import torch
-        from . import _native
-        mlp = self.mlp
         self._check(x, act=(act, 2), logp_old=(logp_old, 1), adv=(adv, 1))
-        if not hasattr(self, "stats5"):
-            self._ent_workspace(True)
-        loss = self.loss if loss_out is None else loss_out
-        stats = self.stats5 if stats_out is None else stats_out
-        if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != 5 * mlp.n_agents:
-            raise ValueError(f"stats must be a contiguous float32 tensor [5, {mlp.n_agents}]")
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_grad_ppo_ent(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale), act.data_ptr(),
-                                                         logp_old.data_ptr(), adv.data_ptr(), float(clip_eps), float(ent_scale),
-                                                         self.grad.data_ptr(), loss.data_ptr(), stats.data_ptr(), self.rc,
-                                                         self.ws.data_ptr(), self.ppo_ent_ws_bytes,
-                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_grad_ppo_ent")
-        return self.grad, loss, stats
-
-    # the gated PPO form (actors only): the entropy form's chunks and workspace, grown once by the k plane and its running sums
-    def _gated_workspace(self):
-        import torch
-        from . import _native
-        n = C.c_size_t(0)
-        _native.check(_native.lib().dronesim_mlp_grad_ppo_gated_workspace(C.byref(self._m), self.rc, C.byref(n)),
-                      "dronesim_mlp_grad_ppo_gated_workspace")
-        if int(n.value) > self.ws.numel() * 4:
-            self.ws = torch.empty((int(n.value) + 3) // 4, device=self.mlp.device)
-        self.gated_ws_bytes = int(n.value)
-        self.stats6 = torch.zeros(6, self.mlp.n_agents, device=self.mlp.device)
+        return self._call("grad_ppo_ent", x, row_scale, (act, logp_old, adv, float(clip_eps), float(ent_scale)), loss_out, stats_out)
 
     def run_ppo_gated(self, x, row_scale, act, logp_old, adv, clip_eps, ent_scale, active=None, loss_out=None, stats_out=None):
         """`dronesim_mlp_grad_ppo_gated`: returns ``(grad, loss [N], stats [6, N])`` -- ``run_ppo_ent``'s five rows and the
         non-negative KL estimate (mean of ``expm1(dl) - dl``).  ``active``: int32 ``[N]`` on the device or None; an agent with
         ``active[i] == 0`` is skipped (its gradient slice untouched, its loss and stats NaN)."""
         import torch
-        from . import _native
         mlp = self.mlp
         self._check(x, act=(act, 2), logp_old=(logp_old, 1), adv=(adv, 1))
-        if not hasattr(self, "stats6"):
-            self._gated_workspace()
-        loss = self.loss if loss_out is None else loss_out
-        stats = self.stats6 if stats_out is None else stats_out
-        if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() != 6 * mlp.n_agents:
-            raise ValueError(f"stats must be a contiguous float32 tensor [6, {mlp.n_agents}]")
         if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != mlp.n_agents
                                    or active.device != self.grad.device):
             raise ValueError(f"active must be a contiguous int32 tensor [{mlp.n_agents}] on {self.grad.device}")
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_grad_ppo_gated(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale),
-                                                           act.data_ptr(), logp_old.data_ptr(), adv.data_ptr(), float(clip_eps),
-                                                           float(ent_scale), None if active is None else active.data_ptr(),
-                                                           self.grad.data_ptr(), loss.data_ptr(), stats.data_ptr(), self.rc,
-                                                           self.ws.data_ptr(), self.gated_ws_bytes,
-                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_grad_ppo_gated")
-        return self.grad, loss, stats
-
-    # the clipped value loss (critics only): the plain chunks and workspace, grown once by the plane of zero-gradient flags
-    def _vclip_workspace(self):
-        import torch
-        from . import _native
-        n = C.c_size_t(0)
-        _native.check(_native.lib().dronesim_mlp_grad_vclip_workspace(C.byref(self._m), self.rc, C.byref(n)),
-                      "dronesim_mlp_grad_vclip_workspace")
-        if int(n.value) > self.ws.numel() * 4:
-            self.ws = torch.empty(int(n.value) // 4, device=self.mlp.device)
-        self.vclip_ws_bytes = int(n.value)
-        self.clip_fraction = torch.zeros(self.mlp.n_agents, device=self.mlp.device)
+        return self._call("grad_ppo_gated", x, row_scale, (act, logp_old, adv, float(clip_eps), float(ent_scale), active), loss_out,
+                          stats_out)
 
     def run_vclip(self, x, row_scale, target, v_old, vf_clip, loss_out=None, clip_out=None):
         """`dronesim_mlp_grad_vclip`: returns ``(grad, loss [N], clip_fraction [N])`` -- the loss is the clipped objective
         ``row_scale sum max((V - G)^2, (Vc - G)^2)``, clip_fraction the share of rows whose gradient is zero."""
-        import torch
-        from . import _native
-        mlp = self.mlp
         self._check(x, target=(target, 1), v_old=(v_old, 1))
-        if not hasattr(self, "clip_fraction"):
-            self._vclip_workspace()
-        loss = self.loss if loss_out is None else loss_out
-        clip = self.clip_fraction if clip_out is None else clip_out
-        if clip.dtype != torch.float32 or not clip.is_contiguous() or clip.numel() != mlp.n_agents:
-            raise ValueError(f"clip_fraction must be a contiguous float32 tensor [{mlp.n_agents}]")
-        with torch.cuda.device(mlp.device):
-            rc = _native.lib().dronesim_mlp_grad_vclip(C.byref(self._m), x.data_ptr(), self.rows, float(row_scale),
-                                                       target.data_ptr(), v_old.data_ptr(), float(vf_clip), self.grad.data_ptr(),
-                                                       loss.data_ptr(), clip.data_ptr(), self.rc, self.ws.data_ptr(),
-                                                       self.vclip_ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_mlp_grad_vclip")
-        return self.grad, loss, clip
+        return self._call("grad_vclip", x, row_scale, (target, v_old, float(vf_clip)), loss_out, clip_out)
 
 
 def mlp_gradients(mlp, x, target=None, act=None, weight=None, row_scale=None, rows_per_chunk=None):
@@ -618,7 +520,7 @@ class SA2CLearner:
         self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
         self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
         if self.ent_coef > 0:
-            self._actor_grad._ent_workspace(False)
+            self._actor_grad._workspace("grad_ent")
         self._shape = (T, E, N)
 
     def train(self, storage):
@@ -824,15 +726,10 @@ class PPOLearner:
         if K == 1:
             self._critic_grad = GradientRunner(self.critic, T * E, self.rows_per_chunk)
             self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
-            self._actor_grad._ppo_workspace()
+            self._prepare_forms(self._critic_grad, self._actor_grad)
             self._scalars = torch.zeros(4, self.epochs, N, device=dev)   # critic_loss, actor_loss, critic / actor grad norm
             self._stats = torch.zeros(self.epochs, self._stat_rows, N, device=dev)
-            if self.target_kl is not None:
-                self._actor_grad._gated_workspace()
-            elif self._ent:
-                self._actor_grad._ent_workspace(True)
             if self.vf_clip is not None:
-                self._critic_grad._vclip_workspace()
                 self._vclip = torch.zeros(self.epochs, N, device=dev)
         else:
             # the full-window actor runner is kept ONLY for step 2's forward-only `logp` pass, which needs the plain gradient
@@ -851,6 +748,14 @@ class PPOLearner:
             self.actor_steps = torch.zeros(N, dtype=torch.int32, device=dev)
         self._shape = (T, E, N)
 
+    def _prepare_forms(self, critic_grad, actor_grad):
+        """Grow the two runners' workspaces for the forms the epochs call, ahead of the first step."""
+        actor_grad._workspace("grad_ppo")
+        if self._ent:
+            actor_grad._workspace("grad_ppo_gated" if self.target_kl is not None else "grad_ppo_ent")
+        if self.vf_clip is not None:
+            critic_grad._workspace("grad_vclip")
+
     def _prepare_minibatches(self, storage, rows, N, K):
         """The buffers of ``minibatches = K > 1``: the permutation, the five gathered arrays, the M-row gradient runners and the
         ``[epochs, K, ...]`` outputs."""
@@ -868,13 +773,8 @@ class PPOLearner:
         self._mb_block_bytes = (C.c_int64 * n)(*[g.block_bytes for g in self._mb])
         self._critic_mb = GradientRunner(self.critic, M, self.rows_per_chunk)
         self._actor_mb = GradientRunner(self.actor, M, self.rows_per_chunk)
-        self._actor_mb._ppo_workspace()
-        if self.target_kl is not None:
-            self._actor_mb._gated_workspace()
-        elif self._ent:
-            self._actor_mb._ent_workspace(True)
+        self._prepare_forms(self._critic_mb, self._actor_mb)
         if self.vf_clip is not None:
-            self._critic_mb._vclip_workspace()
             self._vclip = torch.zeros(self.epochs, K, N, device=dev)
         self._scalars = torch.zeros(4, self.epochs, K, N, device=dev)
         self._stats = torch.zeros(self.epochs, K, self._stat_rows, N, device=dev)
@@ -890,7 +790,6 @@ class PPOLearner:
         arrays = [storage.z_pre, storage.actions, self.logp_old, self.adv, self.G] + ([self.V] if self.vf_clip is not None else [])
         n_arrays = len(arrays)
         src = (C.c_void_p * n_arrays)(*[t.data_ptr() for t in arrays])
-        closs, aloss, cnorm, anorm = self._scalars
         for ep in range(self.epochs):
             with torch.cuda.device(self.critic.device):
                 rc = lib.dronesim_row_permutation(rows, self.shuffle_seed, self.critic_opt.steps.data_ptr(), self.perm.data_ptr(), stream)
@@ -899,37 +798,9 @@ class PPOLearner:
                                               self._mb_block_bytes, stream)
                 _native.check(rc, "dronesim_gather_rows")
             for b in range(K):
-                last = ep == self.epochs - 1 and b == K - 1
-                x, act, logp_old, adv, G = (g.blocks[b] for g in self._mb[:5])
-                if self.vf_clip is not None:
-                    cg, _, _ = self._critic_mb.run_vclip(x, 1.0 / M, G, self._mb[5].blocks[b], self.vf_clip, loss_out=closs[ep, b],
-                                                         clip_out=self._vclip[ep, b])
-                else:
-                    cg, _ = self._critic_mb.run(x, 1.0 / M, target=G, loss_out=closs[ep, b])
-                self.critic_opt.step(cg, norm_out=cnorm[ep, b], refresh=last)
-                if self.target_kl is not None:
-                    self._gated_actor_step(self._actor_mb, x, 1.0 / M, act, logp_old, adv, self.ent_coef / M, aloss[ep, b],
-                                           self._stats[ep, b], anorm[ep, b], last, lib, stream)
-                    continue
-                if self._ent:
-                    ag, _, _ = self._actor_mb.run_ppo_ent(x, 1.0 / M, act, logp_old, adv, self.clip_eps, self.ent_coef / M,
-                                                          loss_out=aloss[ep, b], stats_out=self._stats[ep, b])
-                else:
-                    ag, _, _ = self._actor_mb.run_ppo(x, 1.0 / M, act, logp_old, adv, self.clip_eps, loss_out=aloss[ep, b],
-                                                      stats_out=self._stats[ep, b])
-                self.actor_opt.step(ag, norm_out=anorm[ep, b], refresh=last)
-        st = self._stats
-        out = dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
-                   clip_fraction=st[:, :, 0], approx_kl=st[:, :, 1], ratio_min=st[:, :, 2], ratio_max=st[:, :, 3])
-        if self._ent:
-            out["entropy"] = st[:, :, 4]
-        if self.normalize_advantage:
-            out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
-        if self.target_kl is not None:
-            out.update(kl=st[:, :, 5], actor_steps=self.actor_steps)
-        if self.vf_clip is not None:
-            out["vf_clip_fraction"] = self._vclip
-        return out
+                self._step(self._critic_mb, self._actor_mb, M, *(g.blocks[b] for g in self._mb), at=(ep, b),
+                           last=ep == self.epochs - 1 and b == K - 1, lib=lib, stream=stream)
+        return self._outputs()
 
     def _kl_gate(self, kl, reset, lib, stream):
         import torch
@@ -939,12 +810,41 @@ class PPOLearner:
                                       self.actor_steps.data_ptr(), self.actor.n_agents, int(reset), stream)
         _native.check(rc, "dronesim_kl_gate")
 
-    def _gated_actor_step(self, runner, x, row_scale, act, logp_old, adv, ent_scale, loss_out, stats_out, norm_out, last, lib, stream):
-        """One actor step under ``target_kl``: the gated gradient, the gate on this step's KL estimate, the gated Adam step."""
-        ag, _, st = runner.run_ppo_gated(x, row_scale, act, logp_old, adv, self.clip_eps, ent_scale, active=self.active,
-                                         loss_out=loss_out, stats_out=stats_out)
-        self._kl_gate(st[5], False, lib, stream)
-        self.actor_opt.step(ag, norm_out=norm_out, refresh=last, active=self.active)
+    def _step(self, critic_grad, actor_grad, rows, x, act, logp_old, adv, G, V=None, *, at, last, lib, stream):
+        """One critic step, then one actor step, on these ``rows`` rows (the window, or one minibatch's block of every gathered
+        array; ``V`` only with ``vf_clip``), results into slot ``at`` of the per-step outputs.  ``last``: re-pack the forward
+        images.  Under ``target_kl`` the actor step is the gated gradient, the gate on this step's KL estimate, the gated Adam
+        step."""
+        closs, aloss, cnorm, anorm = (t[at] for t in self._scalars)
+        if self.vf_clip is not None:
+            cg = critic_grad.run_vclip(x, 1.0 / rows, G, V, self.vf_clip, loss_out=closs, clip_out=self._vclip[at])[0]
+        else:
+            cg = critic_grad.run(x, 1.0 / rows, target=G, loss_out=closs)[0]
+        self.critic_opt.step(cg, norm_out=cnorm, refresh=last)
+        ppo, out = (x, 1.0 / rows, act, logp_old, adv, self.clip_eps), dict(loss_out=aloss, stats_out=self._stats[at])
+        if self.target_kl is not None:
+            ag, _, st = actor_grad.run_ppo_gated(*ppo, self.ent_coef / rows, active=self.active, **out)
+            self._kl_gate(st[5], False, lib, stream)
+            self.actor_opt.step(ag, norm_out=anorm, refresh=last, active=self.active)
+            return
+        ag = (actor_grad.run_ppo_ent(*ppo, self.ent_coef / rows, **out) if self._ent else actor_grad.run_ppo(*ppo, **out))[0]
+        self.actor_opt.step(ag, norm_out=anorm, refresh=last)
+
+    def _outputs(self):
+        """What ``train()`` returns, from the per-step buffers ``[epochs(, K), ...]``."""
+        closs, aloss, cnorm, anorm = self._scalars
+        st = self._stats
+        out = dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
+                   clip_fraction=st[..., 0, :], approx_kl=st[..., 1, :], ratio_min=st[..., 2, :], ratio_max=st[..., 3, :])
+        if self._ent:
+            out["entropy"] = st[..., 4, :]
+        if self.normalize_advantage:
+            out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
+        if self.target_kl is not None:
+            out.update(kl=st[..., 5, :], actor_steps=self.actor_steps)
+        if self.vf_clip is not None:
+            out["vf_clip_fraction"] = self._vclip
+        return out
 
     def train(self, storage):
         import torch
@@ -979,35 +879,7 @@ class PPOLearner:
             _native.check(rc, "dronesim_standardize")
         if self.minibatches > 1:
             return self._train_minibatches(storage, lib, stream)
-        closs, aloss, cnorm, anorm = self._scalars
         for ep in range(self.epochs):
-            last = ep == self.epochs - 1
-            if self.vf_clip is not None:
-                cg, _, _ = self._critic_grad.run_vclip(x, 1.0 / (T * E), self.G, self.V, self.vf_clip, loss_out=closs[ep],
-                                                       clip_out=self._vclip[ep])
-            else:
-                cg, _ = self._critic_grad.run(x, 1.0 / (T * E), target=self.G, loss_out=closs[ep])
-            self.critic_opt.step(cg, norm_out=cnorm[ep], refresh=last)
-            if self.target_kl is not None:
-                self._gated_actor_step(self._actor_grad, x, 1.0 / (T * E), act, self.logp_old, self.adv, self.ent_coef / (T * E),
-                                       aloss[ep], self._stats[ep], anorm[ep], last, lib, stream)
-                continue
-            if self._ent:
-                ag, _, _ = self._actor_grad.run_ppo_ent(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps,
-                                                        self.ent_coef / (T * E), loss_out=aloss[ep], stats_out=self._stats[ep])
-            else:
-                ag, _, _ = self._actor_grad.run_ppo(x, 1.0 / (T * E), act, self.logp_old, self.adv, self.clip_eps, loss_out=aloss[ep],
-                                                    stats_out=self._stats[ep])
-            self.actor_opt.step(ag, norm_out=anorm[ep], refresh=last)
-        st = self._stats
-        out = dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm,
-                   clip_fraction=st[:, 0], approx_kl=st[:, 1], ratio_min=st[:, 2], ratio_max=st[:, 3])
-        if self._ent:
-            out["entropy"] = st[:, 4]
-        if self.normalize_advantage:
-            out.update(adv_mean=self.adv_stats[0], adv_std=self.adv_stats[1])
-        if self.target_kl is not None:
-            out.update(kl=st[:, 5], actor_steps=self.actor_steps)
-        if self.vf_clip is not None:
-            out["vf_clip_fraction"] = self._vclip
-        return out
+            self._step(self._critic_grad, self._actor_grad, T * E, x, act, self.logp_old, self.adv, self.G, self.V, at=ep,
+                       last=ep == self.epochs - 1, lib=lib, stream=stream)
+        return self._outputs()

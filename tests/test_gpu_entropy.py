@@ -1,5 +1,5 @@
-"""GPU tests of the learners' entropy bonus and per-agent advantage standardisation (csrc/learner.hip: the standardisation
-kernels, the entropy heads; `rollout_buffer.standardize`, `learner.GradientRunner.run_ent / run_ppo_ent`, the ``ent_coef`` and
+"""GPU tests of the learners' entropy bonus and per-agent advantage standardisation (csrc/standardize.hip: the standardisation
+kernels; csrc/learner.hip: the entropy heads; `rollout_buffer.standardize`, `learner.GradientRunner.run_ent / run_ppo_ent`, the ``ent_coef`` and
 ``normalize_advantage`` options of `PPOLearner` / `SA2CLearner`) against the float64 restatement tests/entropy_ref.py."""
 import numpy as np
 import pytest

@@ -2,7 +2,14 @@
 """Compare the gfx950 code objects of two builds of libdronesim.so kernel by kernel: instruction streams
 (llvm-objdump -d, addresses and encodings stripped) must be identical for a refactoring that claims "no code change".
 
-    python tools/co_diff.py before.so after.so"""
+    python tools/co_diff.py before.so after.so [--pair OLD=NEW ...] [--fp-only]
+
+--pair OLD=NEW (repeatable) compares the kernel of before.so whose name contains OLD with the kernel of after.so whose name
+contains NEW (each substring must match exactly one kernel), for kernels a refactoring renamed or merged; several OLD may name
+the same NEW.  --fp-only compares only the sequence of the floating-point vector instructions' opcodes -- no operands, v_fmac /
+v_fma and the _e32 / _e64 encodings spelt alike: "the same arithmetic in the same order" where scalar code, addressing or
+register allocation moved."""
+import argparse
 import os
 import re
 import subprocess
@@ -13,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_resources import code_objects
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+FP_OPCODE = re.compile(r"^v_\w*_(f16|f32|f64|bf16)(_|$)|^v_cvt_|^v_mfma_")
 
 
 def kernels(path):
@@ -34,18 +42,52 @@ def kernels(path):
     return out
 
 
+def fp_only(stream):
+    """The opcodes of the floating-point vector instructions of an instruction stream, spelling variants folded."""
+    ops = (ins.split()[0] for ins in stream)
+    ops = (re.sub(r"_(e32|e64)$", "", op).replace("v_fmac_", "v_fma_") for op in ops)
+    return [op for op in ops if FP_OPCODE.match(op)]
+
+
+def the_kernel(names, part, which):
+    hits = [n for n in names if part in n]
+    if len(hits) != 1:
+        sys.exit(f"--pair: {part!r} matches {len(hits)} kernels of the {which} library, need exactly 1: {[h[:80] for h in hits]}")
+    return hits[0]
+
+
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("before")
+    ap.add_argument("after")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("--fp-only", action="store_true")
+    args = ap.parse_args()
+    a, b = kernels(args.before), kernels(args.after)
+    view = fp_only if args.fp_only else (lambda stream: stream)
+    pairs = []
+    for spec in args.pair:
+        old, _, new = spec.partition("=")
+        pairs.append((the_kernel(a, old, "first"), the_kernel(b, new, "second")))
+    paired_a, paired_b = {o for o, _ in pairs}, {n for _, n in pairs}
     same = diff = 0
-    for name in sorted(set(a) | set(b)):
+    for old, new in pairs:
+        x, y = view(a[old]), view(b[new])
+        if x != y:
+            n = sum(p != q for p, q in zip(x, y)) + abs(len(x) - len(y))
+            print(f"DIFFERENT ({len(x)} vs {len(y)} instructions, {n} differing lines)", old[:70], "->", new[:70]); diff += 1
+        else:
+            print(f"identical ({len(x)} instructions)", old[:70], "->", new[:70]); same += 1
+    for name in sorted((set(a) - paired_a) | (set(b) - paired_b)):
         if name not in a or name not in b:
             print("only in", "after " if name in b else "before", name[:110]); diff += 1
-        elif a[name] != b[name]:
-            n = sum(x != y for x, y in zip(a[name], b[name])) + abs(len(a[name]) - len(b[name]))
-            print(f"DIFFERENT ({len(a[name])} vs {len(b[name])} instructions, {n} differing lines)", name[:110]); diff += 1
+        elif view(a[name]) != view(b[name]):
+            x, y = view(a[name]), view(b[name])
+            n = sum(p != q for p, q in zip(x, y)) + abs(len(x) - len(y))
+            print(f"DIFFERENT ({len(x)} vs {len(y)} instructions, {n} differing lines)", name[:110]); diff += 1
         else:
             same += 1
-    print(f"{same} kernels identical, {diff} different")
+    print(f"{same} kernels identical, {diff} different" + (" (floating-point opcode sequences)" if args.fp_only else ""))
     return 1 if diff else 0
 
 
