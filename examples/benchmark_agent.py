@@ -7,6 +7,10 @@ each (E x rounds >= --episodes), every step of every env in one launch, and the 
 
     python examples/benchmark_agent.py --critics discrete-A2Ccritics.pth --actors discrete-A2Cactors.pth [--models models]
     python examples/benchmark_agent.py --controller proportional            # the commented alternatives of :76-77
+    python examples/benchmark_agent.py ... --obs-norm stats.pt             # the observation statistics the networks were trained with
+
+``--obs-norm FILE``: an `ObsNormalizer.state_dict()` saved with ``torch.save``; the actor and the critic then read the normalised
+observation (the reference's files carry no statistics, so there is none by default).
 """
 import argparse
 import os
@@ -17,6 +21,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import scalable_collision_avoidance_rl_amd.drone_env as drone_env          # was: import drone_env
 from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, TrainedAgent    # was: from SAC_agents import *
+from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
 
 
 def main():
@@ -29,6 +34,7 @@ def main():
     ap.add_argument("--episodes", type=int, default=1500)
     ap.add_argument("--envs", type=int, default=512)
     ap.add_argument("--precision", default="f32")
+    ap.add_argument("--obs-norm", default=None, help="a torch.save'd ObsNormalizer.state_dict() (network actors only)")
     a = ap.parse_args()
 
     if a.controller:
@@ -47,7 +53,11 @@ def main():
           f"(T = {drone_env.max_time_steps * drone_env.dt}s, dt = {drone_env.dt}s)")
     print(f"N of agents = {env.n_agents}, collision weight b = {env.collision_weight}")
 
-    ev = Evaluator(env, actor, critic, gamma=0.99)
+    obs_norm = None
+    if a.obs_norm:
+        import torch
+        obs_norm = ObsNormalizer(n_agents, env.local_state_space, env.device).load_state_dict(torch.load(a.obs_norm))
+    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm)
     ev.run(rounds)
     s = ev.summary()
     print(f"Episodes {s['episodes']} - Average Reward/Collisions/Steps: {s['mean_return']:.1f}/{s['mean_collisions']:.2f}/"

@@ -683,6 +683,32 @@ int dronesim_row_permutation(int R, uint64_t seed, const int32_t *counter, int32
 int dronesim_gather_rows(const int32_t *perm, int R, int M, int n_arrays, const void *const *src, void *const *dst,
                          const int64_t *row_bytes, const int64_t *block_bytes, void *stream);
 
+/* Observation normalisation (csrc/obsnorm.hip): running per-column statistics of float32 row matrices x [R][C], kept and applied
+ * on the device.  C = N d_in columns, one per (agent, input column); a window z [T][E][N][d] or one step's observation
+ * [E][N][k+1][c] is such a matrix without a copy.  state is float64 [3][C] = (count, mean, m2), table float64 [2][C] = (mean, inv),
+ * both DEVICE memory that only the kernels read and write.  Kernels only: no memset node, no allocation, no host
+ * synchronisation, no float atomics; one fixed reduction order that depends on (R, C) only -- the same bits run to run, for
+ * 16-byte-aligned and merely 4-byte-aligned x, and inside a captured graph.
+ *
+ * dronesim_obsnorm_update: per column, over the FINITE values of x (NaN and +-inf are not counted), n_b, mean_b and M2_b, the sum
+ *   of squared deviations from mean_b; every float32 is widened to float64 and shifted by a finite value of its column (or 0)
+ *   before it is squared, so a column at -500 +- 0.5 keeps its variance.  Then Chan's rule, with d = mean_b - mean:
+ *     n' = n + n_b,   mean' = mean + d n_b / n',   m2' = m2 + M2_b + d^2 n n_b / n'
+ *   (a column with n_b = 0 keeps the bits of its state; count is a float64 holding an exact integer), and the table is rewritten:
+ *     mean,  inv = 1 / sqrt(m2 / count + eps)   (0 where m2 / count + eps == 0);   count == 0:  mean = 0, inv = 1, the identity.
+ *   An all-equal column has mean = the value and m2 = 0 exactly.  Two launches: per-slab partials into ws, then the fold, the
+ *   merge and the table.  ws: at least dronesim_obsnorm_workspace(R, C) bytes, 8-byte aligned.
+ *   EINVAL: R < 1, C < 1, NULL x / state / table / ws, eps < 0 (or NaN), a short or misaligned ws.
+ * dronesim_obsnorm_apply: y[r][c] = (float)(((double)x[r][c] - mean_c) inv_c), then clamped to [-clip, clip] when clip is finite
+ *   and > 0 (clip <= 0 or +inf: no clamp).  NaN in gives NaN out (the clamp is two comparisons, not fminf / fmaxf); +-inf gives
+ *   +-clip, or +-inf without a clamp.  y == x (in place) is allowed.  16 bytes per lane where C % 4 == 0 and both pointers are
+ *   16-byte aligned, else 4 bytes with the same lane-to-element map; a matrix of 32 MiB or more streams through non-temporal
+ *   accesses.  EINVAL: R < 1, C < 1, NULL x / y / table.                                                                        */
+int dronesim_obsnorm_workspace(int R, int C, size_t *bytes);
+int dronesim_obsnorm_update(const float *x, int R, int C, double *state, double *table, double eps, void *ws, size_t ws_bytes,
+                            void *stream);
+int dronesim_obsnorm_apply(const float *x, float *y, int R, int C, const double *table, float clip, void *stream);
+
 const char *dronesim_last_error(void);
 const char *dronesim_error_string(int code);
 int dronesim_version(void);

@@ -101,6 +101,8 @@ class Evaluator:
 
     ``actor``: a `BatchedMLP` with a sampling head, or "proportional" / "gradient" (the classical baselines, one
     `rollout_control` launch per round).  ``critic``: a `BatchedMLP` value network (adds ``mean_adv``), network actors only.
+    ``obs_norm``: the `ObsNormalizer` the networks were trained with -- both read ``obs_norm(env.z)``; its statistics are never
+    updated here; network actors only.
 
     A round is ``env.reset()``, ``T = max_time_steps`` steps into an owned `RolloutStorage`, then the two reductions.  Every env
     contributes exactly one episode per round -- its first one: a fresh episode always ends inside ``max_time_steps``
@@ -111,7 +113,7 @@ class Evaluator:
     Buffers are allocated by the first ``run`` (and again only when ``rounds`` changes); one round can be captured in a
     ``torch.cuda.graph`` after an eager warm-up call."""
 
-    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32):
+    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None):
         from .drone_env import max_time_steps
         if not getattr(env, "batched", False):
             raise ValueError("Evaluator needs the batched (tensor) API of `drones`")
@@ -124,6 +126,8 @@ class Evaluator:
                 raise ValueError(f"actor must be a BatchedMLP or one of {CONTROLLERS}, got {actor!r}")
             if critic is not None:
                 raise ValueError("a critic is evaluated along a network actor's loop; the controller rounds are one launch")
+            if obs_norm is not None:
+                raise ValueError("the controllers read positions, not observations: they take no obs_norm")
         else:
             if not getattr(actor, "sample_kind", 0):
                 raise ValueError("the actor needs a sampling head (softmax or Gaussian BatchedMLP)")
@@ -133,7 +137,9 @@ class Evaluator:
                                      f"{env.n_agents} x {env.local_state_space}")
             if critic is not None and critic.nout != 1:
                 raise ValueError("the critic must have one output")
-        self.actor, self.critic = actor, critic
+            if obs_norm is not None:
+                obs_norm.check_networks(actor, critic)
+        self.actor, self.critic, self.obs_norm = actor, critic, obs_norm
         self.T = int(max_time_steps)
         self.storage = None
         self.tables = None
@@ -163,12 +169,13 @@ class Evaluator:
         if self.controller is not None:
             env.rollout_control(self.controller, self.T, record_actions=True, into=st)
             return st
-        actor, critic = self.actor, self.critic
+        actor, critic, norm = self.actor, self.critic, self.obs_norm
         st.begin()
         for t in range(self.T):                                                 # :69-94
+            z = env.z if norm is None else norm(env.z)                          # (the statistics are never updated here)
             if critic is not None:
-                critic.forward(env.z, out=st.values[t])
-            actor.sample_action(env.z, env=env, act_out=st.actions[t])          # :78
+                critic.forward(z, out=st.values[t])
+            actor.sample_action(z, env=env, act_out=st.actions[t])              # :78
             env.step(st.actions[t], into=(st, t))                               # :81-83
         return st
 

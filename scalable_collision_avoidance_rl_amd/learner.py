@@ -29,6 +29,10 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
                                        step counter), gathers them into minibatch-ordered buffers with one launch and takes one
                                        critic and one actor step per minibatch (default 1: off, the whole-window epochs above)
 
+  obs_norm= of both    dronesim_obsnorm_apply, dronesim_obsnorm_update   an `ObsNormalizer`: everything a network reads is
+                                       normalised first, with the table as it stands, into learner-owned buffers; the window's
+                                       T E pre-step rows are merged into the statistics as ``train()``'s last work (default None)
+
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
 ``BatchedMLP.w1 .. b3``; after an update `BatchedAdam.step` re-packs the forward images (`refresh_weights`).
@@ -393,12 +397,43 @@ def _lambda_returns_ends(learner, storage, Vall, G):
     M = learner.M
     _episode_ends(storage.done, storage.z_final, drone_env.DONE_RADIUS, M, learner.ends, learner.slot_t, learner.n_trunc,
                   learner.z_trunc)
-    learner.critic.forward(learner.z_trunc.view(M * E, N, -1), out=learner.V_trunc)
+    z_trunc = learner.z_trunc                                # (the kinds were decided on the RAW z_final: geometry)
+    if learner.obs_norm is not None:
+        z_trunc = learner.obs_norm.norm(z_trunc, out=learner._xn_trunc)
+    learner.critic.forward(z_trunc.view(M * E, N, -1), out=learner.V_trunc)
     with torch.cuda.device(learner.critic.device):
         rc = _native.lib().dronesim_lambda_returns_ends(storage.reward.data_ptr(), learner.ends.data_ptr(), Vall.data_ptr(),
                                                         learner.V_trunc.data_ptr(), M, learner.gamma, learner.lam, G.data_ptr(),
                                                         None, T, E, N, C.c_void_p(torch.cuda.current_stream().cuda_stream))
     _native.check(rc, "dronesim_lambda_returns_ends")
+
+
+def _check_obs_norm(obs_norm, actor, critic):
+    """None, or an `ObsNormalizer` whose (N, d) is the networks'."""
+    if obs_norm is not None:
+        obs_norm.check_networks(actor, critic)
+    return obs_norm
+
+
+def _prepare_obs_norm(learner, storage):
+    """The learner's buffers for the normalised observations (first call per shape): the window, or with a ``lam`` the whole
+    ring, and under ``time_limit="bootstrap"`` the terminal observations of the truncated ends."""
+    import torch
+    src = storage.z_pre if learner.lam is None else storage.z_all
+    learner._xn = torch.empty(tuple(src.shape), device=learner.critic.device)
+    if learner.time_limit == "bootstrap":
+        learner._xn_trunc = torch.empty_like(learner.z_trunc)
+
+
+def _normalised(learner, storage, T):
+    """``(x, ring)``: what the networks read of this window -- the storage's own ``z_pre`` / ``z_all`` without an ``obs_norm``,
+    else their images under the normaliser's table as it stands (``x`` is the ring's first T slots)."""
+    if learner.obs_norm is None:
+        return storage.z_pre, (None if learner.lam is None else storage.z_all)
+    if learner.lam is None:
+        return learner.obs_norm.norm(storage.z_pre, out=learner._xn), None
+    ring = learner.obs_norm.norm(storage.z_all, out=learner._xn)
+    return ring[:T], ring
 
 
 MINIBATCH_ALIGN = 256               # every minibatch's block of a gathered buffer starts on this boundary (bytes)
@@ -480,10 +515,18 @@ class SA2CLearner:
     ``ent_scale = ent_coef / (T E)``; the likelihood term keeps its 1 / E), ``actor_loss`` is that whole objective and
     ``train()`` also returns ``entropy [N]``, the mean row entropy under the pre-update actor.  There is NO advantage
     standardisation here (`PPOLearner` has it): this learner's weight ``w`` carries gamma^t / N inside `dronesim_advantage`, and
-    standardising it would be another change."""
+    standardising it would be another change.
+
+    ``obs_norm`` (default None: exactly the calls above, nothing more allocated) is an `ObsNormalizer` for the networks' (N, d).
+    ``train()`` then starts by normalising, with the table as it stands, everything a network reads into buffers of its own --
+    ``z_pre``, or with a ``lam`` the whole ring ``z_all`` (x is its first T slots), and under ``time_limit="bootstrap"`` the
+    gathered ``z_trunc`` (the kinds of the ends are still decided on the RAW ``z_final``: that is geometry) -- and the table is
+    not touched until the last step has been enqueued: the rollout that collected the window and every step of the update see
+    one map.  Its last enqueued work, unless ``update_obs_norm=False``, is ``obs_norm.update(storage.z_pre)``: the T E pre-step
+    rows only, ring slot T is the next window's slot 0.  A normaliser of another shape raises ValueError."""
 
     def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None,
-                 time_limit="terminal", ent_coef=0.0):
+                 time_limit="terminal", ent_coef=0.0, obs_norm=None, update_obs_norm=True):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -493,6 +536,7 @@ class SA2CLearner:
         self.actor, self.critic, self.gamma, self.lam = actor, critic, float(gamma), _check_lam(lam)
         self.time_limit = _check_time_limit(time_limit, self.lam)
         self.ent_coef = _check_ent_coef(ent_coef)
+        self.obs_norm, self.update_obs_norm = _check_obs_norm(obs_norm, actor, critic), bool(update_obs_norm)
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
@@ -521,6 +565,8 @@ class SA2CLearner:
         self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
         if self.ent_coef > 0:
             self._actor_grad._workspace("grad_ent")
+        if self.obs_norm is not None:
+            _prepare_obs_norm(self, storage)
         self._shape = (T, E, N)
 
     def train(self, storage):
@@ -529,14 +575,14 @@ class SA2CLearner:
         self._prepare(storage)
         T, E, N = self._shape
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        x = storage.z_pre
+        x, ring = _normalised(self, storage, T)
         if self.lam is None:
             with torch.cuda.device(self.critic.device):
                 rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
                                           T, E, N, stream)
             _native.check(rc, "dronesim_returns")
         else:       # bootstrapped lambda-returns from the pre-update critic over all T+1 ring slots
-            self.critic.forward(storage.z_all.view((T + 1) * E, N, -1), out=self.V_all)
+            self.critic.forward(ring.view((T + 1) * E, N, -1), out=self.V_all)
             (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G)
         # critic (SAC_agents.py:304-324)
         cg, closs = self._critic_grad.run(x, 1.0 / (T * E), target=self.G)
@@ -552,10 +598,18 @@ class SA2CLearner:
         if self.ent_coef > 0:
             ag, aloss, ent = self._actor_grad.run_ent(x, 1.0 / E, storage.actions, self.w, self.ent_coef / (T * E))
             anorm = self.actor_opt.step(ag)
+            self._update_obs_norm(storage)
             return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm, entropy=ent)
         ag, aloss = self._actor_grad.run(x, 1.0 / E, act=storage.actions, weight=self.w)
         anorm = self.actor_opt.step(ag)
+        self._update_obs_norm(storage)
         return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm)
+
+    def _update_obs_norm(self, storage):
+        """``train()``'s last enqueued work: the window's T E pre-step rows into the statistics (ring slot T is the next window's
+        slot 0 and is counted there)."""
+        if self.obs_norm is not None and self.update_obs_norm:
+            self.obs_norm.update(storage.z_pre)
 
 
 class PPOLearner:
@@ -662,13 +716,18 @@ class PPOLearner:
                     ``v_old = self.V``, step 2's pre-update values (no extra forward): per row
                     ``max((V - G)^2, (clamp(V, v_old +- vf_clip) - G)^2)``, gradient 0 where the clipped term is the strict
                     maximum.  ``critic_loss`` is that objective; new output ``vf_clip_fraction`` ``[epochs(, K), N]``, the share
-                    of zero-gradient rows (exactly 0 in the first step).  With ``minibatches > 1`` V is a sixth gathered array."""
+                    of zero-gradient rows (exactly 0 in the first step).  With ``minibatches > 1`` V is a sixth gathered array.
+
+    ``obs_norm`` / ``update_obs_norm`` as for `SA2CLearner` (default None: nothing above changes): the window (or ring, and
+    ``z_trunc``) is normalised once at the start of ``train()`` with the table as it stands, ``logp_old``, every epoch and the
+    minibatch gather read that normalised x -- the first epoch's ratio stays exactly 1 -- and the T E pre-step rows are merged
+    into the statistics as the call's last enqueued work."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                  baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
-                 adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None):
+                 adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None, obs_norm=None, update_obs_norm=True):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -690,6 +749,7 @@ class PPOLearner:
         self.adv_eps = float(adv_eps)
         self.minibatches, self.shuffle_seed = _check_minibatches(minibatches, shuffle_seed)
         self.target_kl, self.vf_clip = _check_positive("target_kl", target_kl), _check_positive("vf_clip", vf_clip)
+        self.obs_norm, self.update_obs_norm = _check_obs_norm(obs_norm, actor, critic), bool(update_obs_norm)
         # the entropy form of the head (and its diagnostics); the gated head is that form
         self._ent = self.ent_coef > 0 or self.normalize_advantage or self.target_kl is not None
         self._stat_rows = 6 if self.target_kl is not None else (5 if self._ent else 4)
@@ -746,6 +806,8 @@ class PPOLearner:
         if self.target_kl is not None:
             self.active = torch.ones(N, dtype=torch.int32, device=dev)
             self.actor_steps = torch.zeros(N, dtype=torch.int32, device=dev)
+        if self.obs_norm is not None:
+            _prepare_obs_norm(self, storage)
         self._shape = (T, E, N)
 
     def _prepare_forms(self, critic_grad, actor_grad):
@@ -779,7 +841,7 @@ class PPOLearner:
         self._scalars = torch.zeros(4, self.epochs, K, N, device=dev)
         self._stats = torch.zeros(self.epochs, K, self._stat_rows, N, device=dev)
 
-    def _train_minibatches(self, storage, lib, stream):
+    def _train_minibatches(self, storage, x, lib, stream):
         """Step 3 with ``minibatches = K > 1``: per epoch a fresh device permutation, one gather, K critic-then-actor steps."""
         import torch
         from . import _native
@@ -787,7 +849,7 @@ class PPOLearner:
         K, rows = self.minibatches, T * E
         M = rows // K
         # (z_pre and actions are contiguous float32: step 2's forward-only pass has checked them)
-        arrays = [storage.z_pre, storage.actions, self.logp_old, self.adv, self.G] + ([self.V] if self.vf_clip is not None else [])
+        arrays = [x, storage.actions, self.logp_old, self.adv, self.G] + ([self.V] if self.vf_clip is not None else [])
         n_arrays = len(arrays)
         src = (C.c_void_p * n_arrays)(*[t.data_ptr() for t in arrays])
         for ep in range(self.epochs):
@@ -852,7 +914,8 @@ class PPOLearner:
         self._prepare(storage)
         T, E, N = self._shape
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        x, act, nbr = storage.z_pre, storage.actions, storage.nbr_pre
+        act, nbr = storage.actions, storage.nbr_pre
+        x, ring = _normalised(self, storage, T)
         if self.target_kl is not None:
             self._kl_gate(None, True, lib, stream)
         if self.lam is None:
@@ -865,7 +928,7 @@ class PPOLearner:
         if self.lam is None:
             self.critic.forward(x.view(T * E, N, -1), out=self.V)
         else:       # the same forward over all T+1 ring slots; the bootstrapped lambda-returns of it
-            self.critic.forward(storage.z_all.view((T + 1) * E, N, -1), out=self.V_all)
+            self.critic.forward(ring.view((T + 1) * E, N, -1), out=self.V_all)
             (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G)
         with torch.cuda.device(self.critic.device):
             rc = lib.dronesim_neighbour_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(),
@@ -878,8 +941,13 @@ class PPOLearner:
                                               self.adv_eps, self._std_ws.data_ptr(), self._std_ws_bytes, stream)
             _native.check(rc, "dronesim_standardize")
         if self.minibatches > 1:
-            return self._train_minibatches(storage, lib, stream)
-        for ep in range(self.epochs):
-            self._step(self._critic_grad, self._actor_grad, T * E, x, act, self.logp_old, self.adv, self.G, self.V, at=ep,
-                       last=ep == self.epochs - 1, lib=lib, stream=stream)
-        return self._outputs()
+            out = self._train_minibatches(storage, x, lib, stream)
+        else:
+            for ep in range(self.epochs):
+                self._step(self._critic_grad, self._actor_grad, T * E, x, act, self.logp_old, self.adv, self.G, self.V, at=ep,
+                           last=ep == self.epochs - 1, lib=lib, stream=stream)
+            out = self._outputs()
+        if self.obs_norm is not None and self.update_obs_norm:
+            # the last enqueued work: the T E pre-step rows only (ring slot T is the next window's slot 0 and is counted there)
+            self.obs_norm.update(storage.z_pre)
+        return out

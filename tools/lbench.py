@@ -12,6 +12,8 @@ or, with ``--learner ppo``, one `PPOLearner.train` of ``--epochs M`` epochs --, 
     python tools/lbench.py --gather [--configs c1,c3,c5] [--reps 5] [--minibatches K] [--out profiles/minibatch_lbench.jsonl]
     python tools/lbench.py --learner ppo --epochs M [--target-kl X] [--vf-clip X] [--out profiles/target_kl_lbench.jsonl]
     python tools/lbench.py --gate-compare [--configs c3,c5] [--reps 3] [--out profiles/target_kl_lbench.jsonl]
+    python tools/lbench.py --scans --obsnorm [--configs c3,c5] [--reps 9] [--out profiles/obsnorm_lbench.jsonl]
+    python tools/lbench.py [--learner ppo --epochs M] --obs-norm [--out profiles/obsnorm_lbench.jsonl]
 
 ``--lam X`` times the learner with bootstrapped lambda-returns (one more ring slot of observations; off by default).
 ``--time-limit bootstrap`` (with ``--lam``) times it with time-limit ends bootstrapped from their terminal observations: the
@@ -35,6 +37,12 @@ timed in the same process.  ``--gate-compare`` answers "does a stopped agent cos
 after a warm-up, it times `PPOLearner.train` at 2 and at 6 epochs with ``target_kl = 1e-30`` (every agent stops on its second
 step) and without the gate, and the critic-only epoch.  The marginal cost of a later gated epoch, (t_gated(6) - t_gated(2)) / 4,
 is allowed the critic-only epoch + 15 %; it is also reported as a share of the ungated marginal epoch.
+``--scans --obsnorm`` times the observation normaliser's two entry points on a window's observations x [T E][N d] against
+`dronesim_returns` on that shape's [T,E,N] rewards in the same process (8 bytes per [T,E,N] element): `dronesim_obsnorm_update`
+reads 4 bytes per x element (expected: the yardstick x d / 2), `dronesim_obsnorm_apply` reads and writes 8 (expected: x d),
+allowed = expected + 15 %.  For c3 it then times the captured rollout loop (softmax-16 actor ``precision="f16x2"`` + step) with and
+without `norm(env.z)` in front of the policy: required <= 1.05 x the loop without it.  ``--obs-norm`` times a whole update with
+an `ObsNormalizer` (normalise first, update last).
 ``--scans`` times the learner-side scans alone instead: `dronesim_returns` (the yardstick) and `dronesim_lambda_returns`
 with G only and with G + A, on the same buffers in the same process, device events around ``--calls`` back-to-back calls
 after a warm-up, median and minimum over ``--reps`` repetitions, one JSON line each (appended to ``--out`` when given).
@@ -178,6 +186,124 @@ def scans_standardize(args):
                             inside=bool(lo <= base * 1.5 * 1.15), workspace_bytes=int(n.value))
             lines.append(line)
             print(json.dumps(line), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+def scans_obsnorm(args):
+    """`dronesim_obsnorm_update` / `dronesim_obsnorm_apply` next to their yardstick `dronesim_returns`, and the captured C3
+    rollout loop with and without the per-step map."""
+    import ctypes as C
+    import statistics
+
+    import numpy as np
+    import torch
+    from scalable_collision_avoidance_rl_amd import _native, drones
+    from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
+    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+    lib, dev = _native.lib(), "cuda:0"
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    lines = []
+
+    def timed(fn, what):
+        for _ in range(max(1, args.warmup) * args.calls):
+            _native.check(fn(), what)
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(args.reps):
+            ev[0].record()
+            for _ in range(args.calls):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            us.append(ev[0].elapsed_time(ev[1]) * 1e3 / args.calls)
+        return statistics.median(us), min(us)
+
+    for name in args.configs.split(","):
+        N, E, T, _ = CONFIGS[name]
+        d = 6
+        g = torch.Generator(device=dev).manual_seed(0)
+        r = torch.randn(T, E, N, device=dev, generator=g)
+        done = (torch.rand(T, E, device=dev, generator=g) < 0.01).to(torch.uint8)
+        done[-1] = 1
+        G = torch.empty_like(r)
+        x = torch.randn(T, E, N, d, device=dev, generator=g) * 30 + 100
+        y = torch.empty_like(x)
+        norm = ObsNormalizer(N, d, dev)
+        norm.update(x)
+        ws, wsb = norm._workspace(T * E)
+        R_, C_ = T * E, N * d
+        calls = [("dronesim_returns", 8 * r.numel(), None,
+                  lambda: lib.dronesim_returns(r.data_ptr(), done.data_ptr(), 0.99, G.data_ptr(), T, E, N, stream())),
+                 ("dronesim_obsnorm_update", 4 * x.numel(), d / 2,
+                  lambda: lib.dronesim_obsnorm_update(x.data_ptr(), R_, C_, norm.state.data_ptr(), norm.table.data_ptr(), norm.eps,
+                                                      ws.data_ptr(), wsb, stream())),
+                 ("dronesim_obsnorm_apply", 8 * x.numel(), float(d),
+                  lambda: lib.dronesim_obsnorm_apply(x.data_ptr(), y.data_ptr(), R_, C_, norm.table.data_ptr(), 10.0, stream())),
+                 ("dronesim_obsnorm_apply_in_place", 8 * x.numel(), float(d),
+                  lambda: lib.dronesim_obsnorm_apply(y.data_ptr(), y.data_ptr(), R_, C_, norm.table.data_ptr(), 10.0, stream()))]
+        base = None
+        for what, nbytes, factor, fn in calls:
+            med, lo = timed(fn, what)
+            line = dict(what=what, config=name, R=R_, C=C_, N=N, us=round(med, 2), us_min=round(lo, 2), bytes=nbytes,
+                        tb_s=round(nbytes / 1e6 / med, 3), calls=args.calls, reps=args.reps)
+            if base is None:
+                base = med
+            else:
+                line.update(ratio=round(med / base, 3), expected_us=round(base * factor, 2), allowed_us=round(base * factor * 1.15, 2),
+                            inside=bool(med <= base * factor * 1.15))
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+        del r, G, x, y, norm
+        if name != "c3":
+            continue
+        # the captured rollout loop: policy -> step, with and without the map in front of the policy (same session, alternating)
+        from tools.kbench import PRESETS
+        Np, Ep, Gp, delta = PRESETS["c3"]
+        steps, graphs, keep = 50, {}, []                 # (keep: what a captured graph reads and writes must outlive its replays)
+        for with_norm in (False, True):
+            env = drones(Np, 0, [Gp, Gp], "O", deltas=np.ones(Np) * delta, simplify_zstate=True, n_envs=Ep, batched=True, seed=1,
+                         auto_reset=True)
+            gp = torch.Generator().manual_seed(4321)
+            rw = lambda *sh: (torch.rand(*sh, generator=gp) * 2 - 1) * 0.2
+            actor = BatchedMLP(rw(Np, 6, 300), rw(Np, 300), rw(Np, 300, 300), rw(Np, 300), rw(Np, 300, 16), rw(Np, 16), 1, 1,
+                               device=dev, seed=1234, precision="f16x2")
+            act = torch.zeros(Ep, Np, 2, device=dev)
+            norm = ObsNormalizer(Np, env.local_state_space, dev)
+            norm.update(env.z)
+
+            def loop(n, env=env, actor=actor, act=act, norm=norm, with_norm=with_norm):
+                for _ in range(n):
+                    actor.sample_action(norm(env.z) if with_norm else env.z, env=env, act_out=act)
+                    env.step(act)
+
+            loop(3)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                loop(steps)
+            graph.replay()
+            torch.cuda.synchronize()
+            graphs[with_norm] = graph
+            keep.append((env, actor, act, norm, loop))
+        us = {False: [], True: []}
+        for _ in range(args.reps):
+            for with_norm, graph in graphs.items():
+                ev[0].record(); graph.replay(); ev[1].record()
+                torch.cuda.synchronize()
+                us[with_norm].append(ev[0].elapsed_time(ev[1]) * 1e3 / steps)
+        plain, normed = statistics.median(us[False]), statistics.median(us[True])
+        line = dict(what="captured rollout step, softmax-16 f16x2 + step, without / with norm(env.z)", config=name, N=Np, E=Ep,
+                    us_without=round(plain, 2), us_with=round(normed, 2), ratio=round(normed / plain, 4), required=1.05,
+                    inside=bool(normed <= 1.05 * plain), us_all_without=[round(u, 2) for u in us[False]],
+                    us_all_with=[round(u, 2) for u in us[True]], steps=steps, reps=args.reps)
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+        del graphs, keep
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:
@@ -432,6 +558,8 @@ def main():
                     help="bootstrap: time-limit ends bootstrap from their terminal observations (needs --lam; with --scans: the new scan)")
     ap.add_argument("--scans", action="store_true", help="time dronesim_returns / dronesim_lambda_returns instead of a learner")
     ap.add_argument("--standardize", action="store_true", help="with --scans: time dronesim_standardize against dronesim_returns")
+    ap.add_argument("--obsnorm", action="store_true", help="with --scans: time dronesim_obsnorm_update / _apply against dronesim_returns")
+    ap.add_argument("--obs-norm", action="store_true", help="time the learner with an ObsNormalizer (normalise first, update last)")
     ap.add_argument("--ent-coef", type=float, default=0.0, help="entropy bonus of the timed learner (default: off)")
     ap.add_argument("--normalize-advantage", action="store_true", help="per-agent advantage standardisation (--learner ppo)")
     ap.add_argument("--minibatches", type=int, default=None,
@@ -469,6 +597,8 @@ def main():
         return gather_bench(args)
     if args.scans and args.standardize:
         return scans_standardize(args)
+    if args.scans and args.obsnorm:
+        return scans_obsnorm(args)
     if args.scans:
         return scans_time_limit(args) if args.time_limit == "bootstrap" else scans(args)
     import torch
@@ -496,6 +626,9 @@ def main():
             lam_kw["target_kl"] = args.target_kl
         if args.vf_clip is not None:
             lam_kw["vf_clip"] = args.vf_clip
+        if args.obs_norm:
+            from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
+            lam_kw["obs_norm"] = ObsNormalizer(N, d_in, dev)
         learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs, **lam_kw) if ppo else SA2CLearner(actor, critic, 0.99, **lam_kw)
         for _ in range(args.warmup):
             learner.train(st)
@@ -530,6 +663,8 @@ def main():
             tag.update(target_kl=args.target_kl, actor_steps=[int(v) for v in (learner.actor_steps.min(), learner.actor_steps.max())])
         if args.vf_clip is not None:
             tag["vf_clip"] = args.vf_clip
+        if args.obs_norm:
+            tag["obs_norm"] = True
         if (args.target_kl is not None or args.vf_clip is not None) and args.minibatches == 1:
             tag["critic_epoch_ms"] = round(critic_epoch_ms(torch, learner, st, args.reps), 3)
         if args.tag:
