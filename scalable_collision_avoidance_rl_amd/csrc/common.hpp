@@ -29,9 +29,17 @@ constexpr bool kPairParallelStep = false;
 #endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dronesim.h"
 
 // records the thread-local error string returned by dronesim_last_error() and returns `code`
 __attribute__((visibility("hidden"))) int dronesim_fail(int code, const char *msg);
+
+// the end of an entry point that has enqueued its kernels: DRONESIM_ELAUNCH with HIP's text if a launch was refused
+inline int dronesim_launched()
+{
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e)) : DRONESIM_OK;
+}
 
 // 32 x 32 -> 64-bit product (multiplier: a wave-uniform constant)
 __device__ __forceinline__ uint64_t mul_wide_u32(uint32_t k, uint32_t x)

@@ -1,5 +1,5 @@
 // dronesim.hip -- C ABI (include/dronesim.h) of the batched drone_env hot path on gfx950 (MI355X / CDNA4), plus the
-// small kernels around the step kernel: reset, classical controllers, learner-side scans, episode reductions.
+// small kernels around the step kernel: reset, classical controllers, episode reductions (learner-side scans: scans.hip).
 // The step / observe / rollout kernel itself lives in drone_kernel.hpp and is instantiated per k_closest value in
 // drone_kernel_k.hip; this file fills its arguments and dispatches.
 #include "drone_kernel.hpp"
@@ -202,479 +202,6 @@ __global__ void __launch_bounds__(1024) control_kernel(const CArgs a)
         u = control_gradient(xi, yi, xFx, xFy, xLx, xLy, t2x, t2y, a.u_max);   // :633, :646-647
     }
     if (valid) (reinterpret_cast<float2 *>(a.act) + wga0)[lane] = u;
-}
-
-// ---------------------------------------------------------------------------------------
-// Learner-side scans over a stored rollout [T][E][N] (SAC_agents.py:304-307, 333-351).  One thread per
-// (env, agent) column; consecutive threads touch consecutive addresses at every t (coalesced streams).
-// One thread per (env, agent) column walks the T axis.  The streams are touched once (streaming loads / stores) and
-// kStageT time steps are requested together before the sequential recurrence consumes them.
-constexpr int kStageT = 8;
-
-// done[t][e] for the eight time steps t_of(0..7) of a stage, fetched by the WAVE with one load instruction instead of
-// eight per thread: lane 8 k + u reads the flag of (step u, k-th env the wave touches), every thread then picks its
-// env's flags with a lane permute.  (One 1-byte load per thread and step -- all lanes of a wave on the same address --
-// made the returns scan 2x slower than a copy of the same size: 147 us against 74 without the flags at T = 200 x C3.)
-// Valid when the wave's columns span at most 8 envs (`coop`, wave-uniform); otherwise threads read their own flags.
-struct DoneStage {
-    unsigned v;
-    template <typename TOf>
-    __device__ __forceinline__ void fetch(const uint8_t *done, size_t e_first, int E, int T, TOf t_of)
-    {
-        const int lane = threadIdx.x & 63, k = lane >> 3, u = lane & 7;
-        const int t = t_of(u);
-        v = (t >= 0 && t < T && e_first + k < (size_t)E) ? done[(size_t)t * E + e_first + k] : 0u;
-    }
-    __device__ __forceinline__ bool get(int de, int u) const { return __shfl((int)v, 8 * de + u, 64) != 0; }
-    __device__ __forceinline__ unsigned byte(int de, int u) const { return (unsigned)__shfl((int)v, 8 * de + u, 64); }   // (the kind of end)
-};
-
-// The scan is software-pipelined: the rewards (and done flags) of stage s + 1 are requested BEFORE stage s is folded and
-// stored, so that a thread always has kStageT .. 2 kStageT loads in flight and the sequential recurrence runs in the shadow
-// of the next stage's HBM round trip.  (Round 4 requested a stage, waited for all of it, folded, stored, and only then
-// requested the next: 4 waves per SIMD x 8 loads did not cover the round trip -- 84 us = 0.62 of the roofline against
-// 74 us for a copy of the same bytes.)  The recurrence itself is unchanged: G[t] = fma(G[t+1], gamma, r[t]), in order.
-constexpr int kRetStageT = 8;      // (the done-flag fetch of DoneStage covers 8 steps: see returns_fetch)
-// V = 4: a thread owns FOUR adjacent columns (agents of one env: N % 4 == 0) and moves them as 16-byte loads / stores --
-// a quarter of the memory instructions for the same bytes in flight (round 5; the un-pipelined round-4 scan lost with
-// four columns per thread because a wave then had nothing to overlap its stage wait with).  V = 1: any shape.
-template <int V> struct RetVec;
-template <> struct RetVec<1> { typedef float type; };
-template <> struct RetVec<4> { typedef float type __attribute__((ext_vector_type(4))); };
-template <int V> struct RetStage {
-    typename RetVec<V>::type r[kRetStageT];
-    DoneStage ds;
-    bool last[kRetStageT];
-};
-
-template <bool COOP, int V>
-__device__ __forceinline__ void returns_fetch(RetStage<V> &st, const float *__restrict__ reward, const uint8_t *__restrict__ done,
-                                              size_t EN, size_t col, size_t e, size_t e_first, int E, int T, int t0)
-{
-    typedef typename RetVec<V>::type vec;
-    if (COOP) st.ds.fetch(done, e_first, E, T, [&](int u) { return t0 - u; });
-#pragma unroll
-    for (int u = 0; u < kRetStageT; ++u) {
-        const int t = t0 - u;
-        st.r[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(reward + (size_t)t * EN + col)) : vec(0.0f);
-        if (!COOP) st.last[u] = t == T - 1 || (done != nullptr && t >= 0 && done[(size_t)t * E + e] != 0);
-    }
-}
-
-template <bool COOP, int V>
-__device__ __forceinline__ void returns_scan(const float *__restrict__ reward, const uint8_t *__restrict__ done, float gamma,
-                                             float *__restrict__ G, int T, int E, size_t EN, size_t col, size_t e,
-                                             size_t e_first, int de, bool act)
-{
-    typedef typename RetVec<V>::type vec;
-    vec g = vec(0.0f);
-    RetStage<V> cur, nxt;
-    returns_fetch<COOP, V>(cur, reward, done, EN, col, e, e_first, E, T, T - 1);
-    for (int t0 = T - 1; t0 >= 0; t0 -= kRetStageT) {
-        if (t0 - kRetStageT >= 0) returns_fetch<COOP, V>(nxt, reward, done, EN, col, e, e_first, E, T, t0 - kRetStageT);
-#pragma unroll
-        for (int u = 0; u < kRetStageT; ++u) {
-            const int t = t0 - u;
-            if (t >= 0) {
-                const bool last = COOP ? (t == T - 1 || cur.ds.get(de, u)) : cur.last[u];
-                if (V == 1) {
-                    g = last ? cur.r[u] : vec(fmaf(*reinterpret_cast<float *>(&g), gamma, *reinterpret_cast<const float *>(&cur.r[u])));   // :306  Gt[t] = Gt[t+1]*discount + r[t]
-                } else {
-                    float *gp = reinterpret_cast<float *>(&g);
-                    const float *rp = reinterpret_cast<const float *>(&cur.r[u]);
-#pragma unroll
-                    for (int q = 0; q < V; ++q) gp[q] = last ? rp[q] : fmaf(gp[q], gamma, rp[q]);                                         // :306
-                }
-                if (act) __builtin_nontemporal_store(g, reinterpret_cast<vec *>(G + (size_t)t * EN + col));
-            }
-        }
-        cur = nxt;
-    }
-}
-
-template <int V>
-__global__ void __launch_bounds__(256) returns_kernel(const float *__restrict__ reward, const uint8_t *__restrict__ done,
-                                                      float gamma, float *__restrict__ G, int T, int E, int N)
-{
-    const size_t EN = (size_t)E * N;
-    const size_t col0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-    const bool act = col0 < EN;                               // (no early exit: the flag fetch is a wave operation)
-    const size_t col = act ? col0 : EN - V;
-    const size_t e = col / N;                                 // (V == 4: N % 4 == 0, the four columns belong to one env)
-    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
-    const int de = (int)(e - e_first);
-    const bool coop = done != nullptr && __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
-    if (coop) returns_scan<true, V>(reward, done, gamma, G, T, E, EN, col, e, e_first, de, act);
-    else returns_scan<false, V>(reward, done, gamma, G, T, E, EN, col, e, e_first, de, act);
-}
-
-// Bootstrapped lambda-returns (TD(lambda) / GAE): returns_kernel's scan with one more input stream -- the values Vv [T+1][E][N],
-// Vv[t] the value of the observation step t acted on, Vv[T] that of the observation after the window -- and up to two outputs:
-//     G[t] = done[t] ? r[t] : r[t] + gamma ((1 - lam) Vv[t+1] + lam G[t+1]),   G[T] = Vv[T];      A[t] = G[t] - Vv[t]
-// Vv[t+1] of step t is Vv[t] of step t + 1: every row is loaded once and carried in `vn`.  Same staging as returns_scan (the
-// next stage's rows -- now two streams -- are requested before the current stage folds), same done-flag fetch, same column
-// quadruples, non-temporal loads and stores.  At lam = 1 the mix fmaf(1, Gn, 0 * Vn) is Gn itself, so the step is
-// returns_scan's fmaf(Gn, gamma, r) and a column whose window ends with `done` gets dronesim_returns' bits.
-template <int V> struct LamStage {
-    typename RetVec<V>::type r[kRetStageT], v[kRetStageT];
-    DoneStage ds;
-    bool last[kRetStageT];
-};
-
-template <bool COOP, int V>
-__device__ __forceinline__ void lambda_fetch(LamStage<V> &st, const float *__restrict__ reward, const float *__restrict__ Vv,
-                                             const uint8_t *__restrict__ done, size_t EN, size_t col, size_t e, size_t e_first,
-                                             int E, int T, int t0)
-{
-    typedef typename RetVec<V>::type vec;
-    if (COOP) st.ds.fetch(done, e_first, E, T, [&](int u) { return t0 - u; });
-#pragma unroll
-    for (int u = 0; u < kRetStageT; ++u) {
-        const int t = t0 - u;
-        st.r[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(reward + (size_t)t * EN + col)) : vec(0.0f);
-        st.v[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)t * EN + col)) : vec(0.0f);
-        if (!COOP) st.last[u] = done != nullptr && t >= 0 && done[(size_t)t * E + e] != 0;
-    }
-}
-
-template <bool COOP, int V>
-__device__ __forceinline__ void lambda_scan(const float *__restrict__ reward, const uint8_t *__restrict__ done,
-                                            const float *__restrict__ Vv, float gamma, float lam, float *__restrict__ G,
-                                            float *__restrict__ A, int T, int E, size_t EN, size_t col, size_t e,
-                                            size_t e_first, int de, bool act)
-{
-    typedef typename RetVec<V>::type vec;
-    const float oml = 1.0f - lam;
-    LamStage<V> cur, nxt;
-    vec vn = __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)T * EN + col));   // the bootstrap: Gn = Vv[T]
-    lambda_fetch<COOP, V>(cur, reward, Vv, done, EN, col, e, e_first, E, T, T - 1);
-    vec g = vn;
-    for (int t0 = T - 1; t0 >= 0; t0 -= kRetStageT) {
-        if (t0 - kRetStageT >= 0) lambda_fetch<COOP, V>(nxt, reward, Vv, done, EN, col, e, e_first, E, T, t0 - kRetStageT);
-#pragma unroll
-        for (int u = 0; u < kRetStageT; ++u) {
-            const int t = t0 - u;
-            if (t >= 0) {
-                const bool last = COOP ? cur.ds.get(de, u) : cur.last[u];
-                float *gp = reinterpret_cast<float *>(&g);
-                const float *rp = reinterpret_cast<const float *>(&cur.r[u]), *vp = reinterpret_cast<const float *>(&vn);
-#pragma unroll
-                for (int q = 0; q < V; ++q) gp[q] = last ? rp[q] : fmaf(fmaf(lam, gp[q], oml * vp[q]), gamma, rp[q]);
-                vn = cur.v[u];
-                if (act) {
-                    if (G) __builtin_nontemporal_store(g, reinterpret_cast<vec *>(G + (size_t)t * EN + col));
-                    if (A) __builtin_nontemporal_store(g - vn, reinterpret_cast<vec *>(A + (size_t)t * EN + col));
-                }
-            }
-        }
-        cur = nxt;
-    }
-}
-
-template <int V>
-__global__ void __launch_bounds__(256) lambda_returns_kernel(const float *__restrict__ reward, const uint8_t *__restrict__ done,
-                                                             const float *__restrict__ Vv, float gamma, float lam,
-                                                             float *__restrict__ G, float *__restrict__ A, int T, int E, int N)
-{
-    const size_t EN = (size_t)E * N;
-    const size_t col0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-    const bool act = col0 < EN;                               // (no early exit: the flag fetch is a wave operation)
-    const size_t col = act ? col0 : EN - V;
-    const size_t e = col / N;                                 // (V == 4: N % 4 == 0, the four columns belong to one env)
-    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
-    const int de = (int)(e - e_first);
-    const bool coop = done != nullptr && __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
-    if (coop) lambda_scan<true, V>(reward, done, Vv, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
-    else lambda_scan<false, V>(reward, done, Vv, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
-}
-
-// lambda_returns_kernel's scan with the KIND of every episode end in the place of `done` ("Time-limit ends"):
-//     ends[t][e] = 0   G[t] = r[t] + gamma ((1 - lam) Vv[t+1] + lam G[t+1])                       lambda_scan's step
-//     ends[t][e] = 1   G[t] = r[t]                                              terminal:         lambda_scan's done step
-//     ends[t][e] = 2   G[t] = r[t] + gamma Vend[k][e][i],  k += 1               truncated (time limit): the bootstrap is the
-//                                                                               value of the episode's terminal observation
-// k counts the column's truncated ends from the back of the window; an end with k >= M is folded as terminal.  Same streams,
-// staging, flag fetch (the byte instead of a bool), column quadruples and non-temporal accesses as lambda_scan; the Vend row is
-// loaded at the step that needs it and at no other (about one step in 200 per env: the wave waits for it there).
-template <int V> struct EndsStage {
-    typename RetVec<V>::type r[kRetStageT], v[kRetStageT];
-    DoneStage ds;
-    unsigned kind[kRetStageT];
-};
-
-template <bool COOP, int V>
-__device__ __forceinline__ void ends_fetch(EndsStage<V> &st, const float *__restrict__ reward, const float *__restrict__ Vv,
-                                           const uint8_t *__restrict__ ends, size_t EN, size_t col, size_t e, size_t e_first,
-                                           int E, int T, int t0)
-{
-    typedef typename RetVec<V>::type vec;
-    if (COOP) st.ds.fetch(ends, e_first, E, T, [&](int u) { return t0 - u; });
-#pragma unroll
-    for (int u = 0; u < kRetStageT; ++u) {
-        const int t = t0 - u;
-        st.r[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(reward + (size_t)t * EN + col)) : vec(0.0f);
-        st.v[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)t * EN + col)) : vec(0.0f);
-        if (!COOP) st.kind[u] = t >= 0 ? (unsigned)ends[(size_t)t * E + e] : 0u;
-    }
-}
-
-template <bool COOP, int V>
-__device__ __forceinline__ void ends_scan(const float *__restrict__ reward, const uint8_t *__restrict__ ends,
-                                          const float *__restrict__ Vv, const float *__restrict__ Vend, int M, float gamma,
-                                          float lam, float *__restrict__ G, float *__restrict__ A, int T, int E, size_t EN,
-                                          size_t col, size_t e, size_t e_first, int de, bool act)
-{
-    typedef typename RetVec<V>::type vec;
-    const float oml = 1.0f - lam;
-    EndsStage<V> cur, nxt;
-    vec vn = __builtin_nontemporal_load(reinterpret_cast<const vec *>(Vv + (size_t)T * EN + col));   // the bootstrap: Gn = Vv[T]
-    ends_fetch<COOP, V>(cur, reward, Vv, ends, EN, col, e, e_first, E, T, T - 1);
-    vec g = vn;
-    int k = 0;                                                 // truncated ends of this column's env met so far
-    for (int t0 = T - 1; t0 >= 0; t0 -= kRetStageT) {
-        if (t0 - kRetStageT >= 0) ends_fetch<COOP, V>(nxt, reward, Vv, ends, EN, col, e, e_first, E, T, t0 - kRetStageT);
-#pragma unroll
-        for (int u = 0; u < kRetStageT; ++u) {
-            const int t = t0 - u;
-            if (t >= 0) {
-                const unsigned kind = COOP ? cur.ds.byte(de, u) : cur.kind[u];
-                float *gp = reinterpret_cast<float *>(&g);
-                const float *rp = reinterpret_cast<const float *>(&cur.r[u]), *vp = reinterpret_cast<const float *>(&vn);
-                if (kind == 2u && k < M) {                     // rare: the value of the terminal observation, slot k of this env
-                    const vec ve = *reinterpret_cast<const vec *>(Vend + (size_t)k * EN + col);
-                    const float *ep = reinterpret_cast<const float *>(&ve);
-#pragma unroll
-                    for (int q = 0; q < V; ++q) gp[q] = fmaf(ep[q], gamma, rp[q]);
-                    ++k;
-                } else {
-                    const bool last = kind != 0u;
-#pragma unroll
-                    for (int q = 0; q < V; ++q) gp[q] = last ? rp[q] : fmaf(fmaf(lam, gp[q], oml * vp[q]), gamma, rp[q]);
-                }
-                vn = cur.v[u];
-                if (act) {
-                    if (G) __builtin_nontemporal_store(g, reinterpret_cast<vec *>(G + (size_t)t * EN + col));
-                    if (A) __builtin_nontemporal_store(g - vn, reinterpret_cast<vec *>(A + (size_t)t * EN + col));
-                }
-            }
-        }
-        cur = nxt;
-    }
-}
-
-template <int V>
-__global__ void __launch_bounds__(256) lambda_returns_ends_kernel(const float *__restrict__ reward, const uint8_t *__restrict__ ends,
-                                                                  const float *__restrict__ Vv, const float *__restrict__ Vend,
-                                                                  int M, float gamma, float lam, float *__restrict__ G,
-                                                                  float *__restrict__ A, int T, int E, int N)
-{
-    const size_t EN = (size_t)E * N;
-    const size_t col0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-    const bool act = col0 < EN;                               // (no early exit: the flag fetch is a wave operation)
-    const size_t col = act ? col0 : EN - V;
-    const size_t e = col / N;                                 // (V == 4: N % 4 == 0, the four columns belong to one env)
-    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
-    const int de = (int)(e - e_first);
-    const bool coop = __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
-    if (coop) ends_scan<true, V>(reward, ends, Vv, Vend, M, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
-    else ends_scan<false, V>(reward, ends, Vv, Vend, M, gamma, lam, G, A, T, E, EN, col, e, e_first, de, act);
-}
-
-// The kind of every episode end of a stored window, recovered from the window itself (dronesim_episode_ends; DESIGN.md,
-// "Time-limit ends").  done = "every agent within done_radius of its goal" OR "time limit", and under auto_reset the terminal
-// observation of every finished episode is in z_final[t]: agent i's offset from its goal is the first two floats of its row.
-// So a set `done` with some agent outside the disk can only be the time limit.
-//
-// Stage 1: ends[t][e] = 0 / 1 (terminal) / 2 (truncated), before any demotion.  A wave takes 64 consecutive entries of `done`
-// in its own [T][E] order (coalesced byte loads) and ballots them; set entries are rare (about E per 200 steps), and for each
-// the WHOLE wave reads that env's N offsets (lane = agent, strided by 64 above 64 agents) and ballots the step kernel's own
-// arrival test, !(sqrt(fma(zy, zy, zx zx)) <= done_radius): a non-finite offset counts as outside.
-__global__ void __launch_bounds__(256) ends_classify_kernel(const uint8_t *__restrict__ done, const float *__restrict__ z_final,
-                                                            size_t total, int N, int d, float done_radius, uint8_t *__restrict__ ends)
-{
-    const unsigned lane = threadIdx.x & 63u;
-    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
-    for (size_t base = wave * 64; base < total; base += nwaves * 64) {      // (wave-uniform trip count: the ballots are wave operations)
-        const size_t idx = base + lane;
-        const bool set = idx < total && done[idx] != 0;
-        unsigned long long m = __builtin_amdgcn_ballot_w64(set);
-        unsigned kind = set ? 1u : 0u;
-        while (m) {
-            const unsigned b = (unsigned)__builtin_ctzll(m);
-            m &= m - 1ull;
-            const float *rows = z_final + (base + b) * (size_t)N * d;       // (base + b < total: its lane saw a set flag)
-            bool outside = false;
-            for (int i = (int)lane; i < N; i += 64) {
-                const float zx = rows[(size_t)i * d], zy = rows[(size_t)i * d + 1];
-                outside |= !(__builtin_amdgcn_sqrtf(fmaf(zy, zy, zx * zx)) <= done_radius);
-            }
-            if (__builtin_amdgcn_ballot_w64(outside) != 0ull && lane == b) kind = 2u;
-        }
-        if (idx < total) ends[idx] = (uint8_t)kind;
-    }
-}
-
-// Stage 2: one thread per env walks ends[:, e] backwards (coalesced across envs, eight steps requested together), ranks the
-// truncated ends from the back of the window -- slot_t[k][e] = t of the k-th, -1 where there is none --, demotes those with
-// k >= M to terminal in place, and writes n_trunc[e], the count before the demotion.
-__global__ void __launch_bounds__(256) ends_rank_kernel(uint8_t *__restrict__ ends, int T, int E, int M, int32_t *__restrict__ slot_t,
-                                                        int32_t *__restrict__ n_trunc)
-{
-    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (e >= E) return;
-    int k = 0;
-    for (int t0 = T - 1; t0 >= 0; t0 -= kStageT) {
-        unsigned kind[kStageT];
-#pragma unroll
-        for (int u = 0; u < kStageT; ++u) kind[u] = t0 - u >= 0 ? (unsigned)ends[(size_t)(t0 - u) * E + e] : 0u;
-#pragma unroll
-        for (int u = 0; u < kStageT; ++u) {
-            if (kind[u] == 2u) {
-                if (k < M) slot_t[(size_t)k * E + e] = t0 - u;
-                else ends[(size_t)(t0 - u) * E + e] = (uint8_t)1;
-                ++k;
-            }
-        }
-    }
-    n_trunc[e] = k;
-    for (int m = k; m < M; ++m) slot_t[(size_t)m * E + e] = -1;
-}
-
-// Stage 3: z_trunc[m][e] = z_final[slot_t[m][e]][e], all zeros where slot_t is -1: every element is written here (no memset,
-// no uninitialised row reaches the critic).  An (m, e) block is N d floats; VW floats per lane, lanes contiguous.
-template <int VW>
-__global__ void __launch_bounds__(256) ends_gather_kernel(const float *__restrict__ z_final, const int32_t *__restrict__ slot_t,
-                                                          int E, size_t per_block, size_t items, float *__restrict__ z_trunc)
-{
-    typedef typename RetVec<VW>::type vec;
-    for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (size_t)gridDim.x * blockDim.x) {
-        const size_t blk = it / per_block, within = it - blk * per_block;   // blk = m E + e
-        const int t = slot_t[blk];
-        const size_t e = blk % (size_t)E;
-        vec v = vec(0.0f);
-        if (t >= 0) v = __builtin_nontemporal_load(reinterpret_cast<const vec *>(z_final) + ((size_t)t * E + e) * per_block + within);
-        reinterpret_cast<vec *>(z_trunc)[it] = v;
-    }
-}
-
-// K1C = K + 1 at compile time (3 for the reference's k_closest = 2: the neighbour triple is one 12-byte load), 0 = any
-// K1 at run time.  A stage of eight steps requests V and the neighbour ids of all eight first, then the G values they
-// name (slot 0 is the agent itself: a coalesced row read; the others fall into the same 4 N-byte row), then folds.
-template <int K1C>
-__global__ void __launch_bounds__(256) advantage_kernel(const float *__restrict__ G, const float *__restrict__ V,
-                                                        const int *__restrict__ nbr, const uint8_t *__restrict__ done,
-                                                        float gamma, float *__restrict__ w, int T, int E, int N, int K1)
-{
-    const size_t EN = (size_t)E * N;
-    const size_t col0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = col0 < EN;
-    const size_t col = act ? col0 : EN - 1;
-    const size_t e = col / N;
-    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
-    const int de = (int)(e - e_first);
-    const bool coop = done != nullptr && __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
-    double disc = 1.0;                                         // gamma^t kept in double: 200 products stay exact to f32
-    const float inv_n = 1.0f / (float)N;
-    for (int t0 = 0; t0 < T; t0 += kStageT) {
-        DoneStage ds;
-        if (coop) ds.fetch(done, e_first, E, T, [&](int u) { return t0 + u; });
-        if (K1C > 0) {
-            float v[kStageT], adv[kStageT];
-            int j[kStageT][K1C > 0 ? K1C : 1];
-            float g[kStageT][K1C > 0 ? K1C : 1];
-#pragma unroll
-            for (int u = 0; u < kStageT; ++u) {
-                const int t = min(t0 + u, T - 1);
-                const size_t o = (size_t)t * EN + col;
-                v[u] = __builtin_nontemporal_load(V + o);
-#pragma unroll
-                for (int q = 0; q < K1C; ++q) j[u][q] = __builtin_nontemporal_load(nbr + o * K1C + q);
-            }
-#pragma unroll
-            for (int u = 0; u < kStageT; ++u) {
-                const int t = min(t0 + u, T - 1);
-                const float *Grow = G + (size_t)t * EN + e * N;
-#pragma unroll
-                for (int q = 0; q < K1C; ++q) g[u][q] = Grow[max(j[u][q], 0)];
-            }
-            // (all 8 K1 gathers are requested above before the first is used, and the "no neighbour" case is an AND mask:
-            // written as `j >= 0 ? gq - v : 0` hipcc puts a branch around every gather and waits for each in turn --
-            // 24 round trips in series per stage, found in the ISA in round 4)
-#pragma unroll
-            for (int u = 0; u < kStageT; ++u) {
-                float a = 0.0f;
-#pragma unroll
-                for (int q = 0; q < K1C; ++q)
-                    a += __uint_as_float(__float_as_uint(g[u][q] - v[u]) & (j[u][q] >= 0 ? 0xffffffffu : 0u));   // :345-346  (i itself is slot 0)
-                adv[u] = a;
-            }
-#pragma unroll
-            for (int u = 0; u < kStageT; ++u) {
-                const int t = t0 + u;
-                if (t < T) {
-                    if (act) __builtin_nontemporal_store(inv_n * (float)disc * adv[u], w + (size_t)t * EN + col);   // :351
-                    const bool d = coop ? ds.get(de, u) : (done != nullptr && done[(size_t)t * E + e] != 0);
-                    disc = d ? 1.0 : disc * (double)gamma;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < kStageT; ++u) {
-                const int t = t0 + u;
-                if (t < T) {
-                    const size_t o = (size_t)t * EN + col;
-                    const float v = V[o];
-                    const int *nb = nbr + o * K1;
-                    const float *Grow = G + (size_t)t * EN + e * N;
-                    float adv = 0.0f;
-                    for (int q = 0; q < K1; ++q) {
-                        const int jq = nb[q];
-                        if (jq >= 0) adv += Grow[jq] - v;      // :345-346  (i itself is slot 0)
-                    }
-                    if (act) w[o] = inv_n * (float)disc * adv; // :351
-                    const bool d = coop ? ds.get(de, u) : (done != nullptr && done[(size_t)t * E + e] != 0);
-                    disc = d ? 1.0 : disc * (double)gamma;
-                }
-            }
-        }
-    }
-}
-
-// advantage_kernel's sibling for the PPO learner (SAC_agents.py:498-501, :512-513): the neighbour sum of the returns less the
-// agent's own baseline, with no gamma^t and no 1 / N, so nothing runs along t and a thread owns one (t, e, i):
-//   adv = sum_{j in Ni[t]} G[t, e, j] - c V[t, e, i],   c = 1 (the reference's form) or |Ni[t]| (per_neighbour).
-// Coalesced reads of V and the neighbour rows and a coalesced store; the gathers of G fall into the env's own 4 N-byte row.
-template <int K1C>
-__global__ void __launch_bounds__(256) neighbour_advantage_kernel(const float *__restrict__ G, const float *__restrict__ V,
-                                                                  const int *__restrict__ nbr, int per_neighbour,
-                                                                  float *__restrict__ adv, size_t rows, int N, int K1)
-{
-    const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= rows * N) return;
-    const float *Grow = G + (o / N) * N;
-    const int k1 = K1C > 0 ? K1C : K1;
-    float q = 0.0f;
-    int cnt = 0;
-    if (K1C > 0) {
-        int j[K1C > 0 ? K1C : 1];
-        float g[K1C > 0 ? K1C : 1];
-#pragma unroll
-        for (int s = 0; s < K1C; ++s) j[s] = __builtin_nontemporal_load(nbr + o * K1C + s);
-#pragma unroll
-        for (int s = 0; s < K1C; ++s) g[s] = Grow[max(j[s], 0)];
-#pragma unroll
-        for (int s = 0; s < K1C; ++s) {
-            q += j[s] >= 0 ? g[s] : 0.0f;
-            cnt += j[s] >= 0;
-        }
-    } else {
-        for (int s = 0; s < k1; ++s) {
-            const int js = nbr[o * k1 + s];
-            if (js >= 0) { q += Grow[js]; ++cnt; }
-        }
-    }
-    const float c = per_neighbour ? (float)cnt : 1.0f;
-    adv[o] = q - c * V[o];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -986,9 +513,7 @@ int launch(int mode, const DroneParams *p, KArgs &a, int E, void *stream, int ct
                  g.lds, hipGetErrorString(static_cast<hipError_t>(le)));
         return fail(DRONESIM_ELAUNCH, msg);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 }   // namespace
@@ -1163,9 +688,7 @@ int reset_impl(const DroneParams *p, int div_x, int div_y, float pitch, uint64_t
     a.shift = 32 - __builtin_ctz((unsigned)a.nt);
     const size_t lds = sizeof(int2) * (size_t)g.epb * a.nt;
     hipLaunchKernelGGL(reset_kernel, dim3(g.blocks), dim3(g.threads), lds, static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 }   // namespace
 
@@ -1184,9 +707,7 @@ int dronesim_episode_reduce(const DroneEpisodeAcc *acc, int E, double *out, void
     if (!acc || !out || E < 0) return fail(DRONESIM_EINVAL, "dronesim_episode_reduce: bad argument");
     hipLaunchKernelGGL(episode_reduce_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const double *>(acc), E, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 int dronesim_control(const DroneParams *p, int kind, const float *pos, float *act, float u_max,
@@ -1219,154 +740,7 @@ int dronesim_control(const DroneParams *p, int kind, const float *pos, float *ac
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (g.P > 0) hipLaunchKernelGGL(control_kernel<true>, dim3(g.blocks), dim3(g.threads), lds, s, a);
     else hipLaunchKernelGGL(control_kernel<false>, dim3(g.blocks), dim3(g.threads), lds, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
-int dronesim_returns(const float *reward, const uint8_t *done, float gamma, float *G,
-                     int T, int E, int N, void *stream)
-{
-    if (!reward || !G || T < 0 || E < 0 || N < 1) return fail(DRONESIM_EINVAL, "dronesim_returns: bad argument");
-    if (T == 0 || E == 0) return DRONESIM_OK;
-    const size_t cols = (size_t)E * N;
-    // 16-byte column quadruples when every row of the [T][E N] arrays starts 16-byte aligned, an env's agents come in fours
-    // and the quadruples still fill the chip: below one wave per SIMD (1024 x 64 x 4 columns) half the SIMDs idle -- T = 200 x
-    // 512 x 256: 38.6 us with one column per thread, 45.6 with four --, at C3's 262144 columns four per thread win (78.1 ->
-    // 69.8 us: 0.75 of the roofline), from a million columns up one per thread is 3 % ahead again (profiles/r5_retbench.log)
-    const bool v4 = (N % 4) == 0 && ((reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(G)) & 15u) == 0 &&
-                    cols >= 262144 && cols < 1048576;
-    if (v4)
-        hipLaunchKernelGGL(returns_kernel<4>, dim3((unsigned)((cols / 4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           reward, done, gamma, G, T, E, N);
-    else
-        hipLaunchKernelGGL(returns_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           reward, done, gamma, G, T, E, N);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
-int dronesim_lambda_returns(const float *reward, const uint8_t *done, const float *V, float gamma, float lam, float *G, float *A,
-                            int T, int E, int N, void *stream)
-{
-    if (!reward || !V) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: reward or V is NULL");
-    if (!G && !A) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: G and A are both NULL");
-    if (T < 0 || E < 0 || N < 1) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: bad T, E or N");
-    if (!(lam >= 0.0f && lam <= 1.0f)) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: lam must be in [0, 1]");
-    if (gamma != gamma) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns: gamma is NaN");
-    if (T == 0 || E == 0) return DRONESIM_OK;
-    const size_t cols = (size_t)E * N;
-    // column quadruples as in dronesim_returns: every row of the four [.][E N] arrays 16-byte aligned, agents in fours, and
-    // from its lower bound of 262144 columns (one quadruple wave per SIMD).  The upper bound is lower here: with two staged
-    // streams the quadruple kernel holds 169 VGPRs = two waves per SIMD, so all quadruple waves are resident at once only
-    // below 2 x 1024 x 64 x 4 = 524288 columns; from there on one column per thread (66 VGPRs, seven waves per SIMD)
-    const uintptr_t align = reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(G) |
-                            reinterpret_cast<uintptr_t>(A);
-    const bool v4 = (N % 4) == 0 && (align & 15u) == 0 && cols >= 262144 && cols < 524288;
-    if (v4)
-        hipLaunchKernelGGL(lambda_returns_kernel<4>, dim3((unsigned)((cols / 4 + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), reward, done, V, gamma, lam, G, A, T, E, N);
-    else
-        hipLaunchKernelGGL(lambda_returns_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), reward, done, V, gamma, lam, G, A, T, E, N);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
-int dronesim_episode_ends(const uint8_t *done, const float *z_final, int T, int E, int N, int d, float done_radius,
-                          uint8_t *ends, int32_t *slot_t, int32_t *n_trunc, float *z_trunc, int M, void *stream)
-{
-    if (!done || !z_final) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: done or z_final is NULL");
-    if (!ends || !slot_t || !n_trunc || !z_trunc) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: an output is NULL");
-    if (T < 0 || E < 0 || N < 1 || d < 2) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: bad T, E, N or d");
-    if (M < 1) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: M must be at least 1");
-    if (done_radius != done_radius) return fail(DRONESIM_EINVAL, "dronesim_episode_ends: done_radius is NaN");
-    if (E == 0) return DRONESIM_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t total = (size_t)T * E, ND = (size_t)N * d;
-    const size_t kMaxBlocks = (size_t)1 << 20;                  // (both kernels loop over what a capped grid leaves)
-    const size_t cb = (total + 255) / 256;
-    if (total > 0)
-        hipLaunchKernelGGL(ends_classify_kernel, dim3((unsigned)(cb < kMaxBlocks ? cb : kMaxBlocks)), dim3(256), 0, s,
-                           done, z_final, total, N, d, done_radius, ends);
-    hipLaunchKernelGGL(ends_rank_kernel, dim3((unsigned)(((size_t)E + 255) / 256)), dim3(256), 0, s, ends, T, E, M, slot_t, n_trunc);
-    // the vector width from N d, the floats of one (t, e) block (a row's d is a multiple of two floats only at c = 2), and the
-    // two base addresses: every block of both arrays then starts 16-byte aligned
-    const bool v4 = (ND % 4) == 0 && ((reinterpret_cast<uintptr_t>(z_final) | reinterpret_cast<uintptr_t>(z_trunc)) & 15u) == 0;
-    const size_t per = v4 ? ND / 4 : ND, items = (size_t)M * E * per;
-    const size_t gb = (items + 255) / 256;
-    const dim3 grid((unsigned)(gb < kMaxBlocks ? gb : kMaxBlocks));
-    if (v4) hipLaunchKernelGGL(ends_gather_kernel<4>, grid, dim3(256), 0, s, z_final, slot_t, E, per, items, z_trunc);
-    else hipLaunchKernelGGL(ends_gather_kernel<1>, grid, dim3(256), 0, s, z_final, slot_t, E, per, items, z_trunc);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
-int dronesim_lambda_returns_ends(const float *reward, const uint8_t *ends, const float *V, const float *Vend, int M, float gamma,
-                                 float lam, float *G, float *A, int T, int E, int N, void *stream)
-{
-    if (!reward || !V) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: reward or V is NULL");
-    if (!ends || !Vend) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: ends or Vend is NULL");
-    if (!G && !A) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: G and A are both NULL");
-    if (T < 0 || E < 0 || N < 1) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: bad T, E or N");
-    if (M < 1) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: M must be at least 1");
-    if (!(lam >= 0.0f && lam <= 1.0f)) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: lam must be in [0, 1]");
-    if (gamma != gamma) return fail(DRONESIM_EINVAL, "dronesim_lambda_returns_ends: gamma is NaN");
-    if (T == 0 || E == 0) return DRONESIM_OK;
-    const size_t cols = (size_t)E * N;
-    // dronesim_lambda_returns' size rule for the column quadruples, with Vend among the arrays that must be 16-byte aligned
-    const uintptr_t align = reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(Vend) |
-                            reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(A);
-    const bool v4 = (N % 4) == 0 && (align & 15u) == 0 && cols >= 262144 && cols < 524288;
-    if (v4)
-        hipLaunchKernelGGL(lambda_returns_ends_kernel<4>, dim3((unsigned)((cols / 4 + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), reward, ends, V, Vend, M, gamma, lam, G, A, T, E, N);
-    else
-        hipLaunchKernelGGL(lambda_returns_ends_kernel<1>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), reward, ends, V, Vend, M, gamma, lam, G, A, T, E, N);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
-int dronesim_advantage(const float *G, const float *V, const int32_t *nbr_idx, const uint8_t *done,
-                       float gamma, float *w, int T, int E, int N, int K1, void *stream)
-{
-    if (!G || !V || !nbr_idx || !w || T < 0 || E < 0 || N < 1 || K1 < 1)
-        return fail(DRONESIM_EINVAL, "dronesim_advantage: bad argument");
-    if (T == 0 || E == 0) return DRONESIM_OK;
-    const size_t cols = (size_t)E * N;
-    if (K1 == 3)
-        hipLaunchKernelGGL(advantage_kernel<3>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           G, V, nbr_idx, done, gamma, w, T, E, N, K1);
-    else
-        hipLaunchKernelGGL(advantage_kernel<0>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           G, V, nbr_idx, done, gamma, w, T, E, N, K1);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
-int dronesim_neighbour_advantage(const float *G, const float *V, const int32_t *nbr_idx, int per_neighbour, float *adv,
-                                 int T, int E, int N, int K1, void *stream)
-{
-    if (!G || !V || !nbr_idx || !adv || T < 0 || E < 0 || N < 1 || K1 < 1 || per_neighbour < 0 || per_neighbour > 1)
-        return fail(DRONESIM_EINVAL, "dronesim_neighbour_advantage: bad argument");
-    if (T == 0 || E == 0) return DRONESIM_OK;
-    const size_t rows = (size_t)T * E, items = rows * N;
-    const dim3 grid((unsigned)((items + 255) / 256));
-    if (K1 == 3)
-        hipLaunchKernelGGL(neighbour_advantage_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
-                           G, V, nbr_idx, per_neighbour, adv, rows, N, K1);
-    else
-        hipLaunchKernelGGL(neighbour_advantage_kernel<0>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
-                           G, V, nbr_idx, per_neighbour, adv, rows, N, K1);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 int dronesim_episode_stats(const float *reward, const float *true_reward, const int32_t *n_coll, int E, int N,
@@ -1377,9 +751,7 @@ int dronesim_episode_stats(const float *reward, const float *true_reward, const 
     if (E == 0) return DRONESIM_OK;
     hipLaunchKernelGGL(stats_kernel, dim3(kStatBlocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reward, true_reward, n_coll, E, N, acc, scratch);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 // developer hook (tools/trace_*.py with a -DDRONESIM_TRACE build; not declared in include/dronesim.h): without that build

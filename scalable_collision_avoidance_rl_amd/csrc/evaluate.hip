@@ -1,42 +1,18 @@
 // Policy evaluation over a stored rollout window [T][E][N] (benchmark_agent.py:59-106, :148-156): the per-episode table of
 // the FIRST episode of every env -- length, collisions, per-agent and per-env returns, the critic's mean advantage
-// G_t - V(z_t) -- and the collision histogram.  dronesim.hip's episode layer keeps sums over the finished episodes of an env;
+// G_t - V(z_t) -- and the collision histogram.  The env's episode layer (dronesim.hip) keeps sums over the finished episodes of an env;
 // a table, a histogram and a per-agent critic check need the episodes themselves.
 //
-// episode_eval_kernel is returns_kernel's scan (dronesim.hip) with three float64 accumulators per column riding along: one
-// thread per (env, agent) column walks the window backwards, eight steps requested ahead of the eight being folded, four
-// adjacent columns as 16-byte accesses when N % 4 == 0, the done bytes of a stage fetched by the wave with one load.  Every
-// accumulator restarts where `done` is set, so at t = 0 it holds the first episode and the last flag seen gives its length.
-// reward, true_reward and V are read once, G is written once.  The per-env pieces (collisions, the mean over agents in
-// ascending agent order) are a second small launch: no float atomics anywhere, results are bit-identical run to run.
-#include "common.hpp"
+// episode_eval_kernel is returns_kernel's scan (scans.hip; shared pieces in scan_common.hpp) with three float64 accumulators
+// per column riding along: one thread per (env, agent) column walks the window backwards, eight steps requested ahead of the
+// eight being folded, four adjacent columns as 16-byte accesses when N % 4 == 0, the done bytes of a stage fetched by the wave
+// with one load.  Every accumulator restarts where `done` is set, so at t = 0 it holds the first episode and the last flag
+// seen gives its length.  reward, true_reward and V are read once, G is written once.  The per-env pieces (collisions, the mean
+// over agents in ascending agent order) are a second small launch: no float atomics anywhere, bit-identical run to run.
+#include "scan_common.hpp"
 #include "dronesim.h"
 
 namespace {
-
-constexpr int kEvStageT = 8;      // steps per stage (EvDone covers eight: lane 8 k + u)
-
-// done[t][e] of a stage's eight steps for up to eight envs, one load per lane (dronesim.hip: DoneStage has the measurement)
-struct EvDone {
-    unsigned v;
-    __device__ __forceinline__ void fetch(const uint8_t *done, size_t e_first, int E, int T, int t0)
-    {
-        const int lane = threadIdx.x & 63, k = lane >> 3, u = lane & 7;
-        const int t = t0 - u;
-        v = (t >= 0 && t < T && e_first + k < (size_t)E) ? done[(size_t)t * E + e_first + k] : 0u;
-    }
-    __device__ __forceinline__ bool get(int de, int u) const { return __shfl((int)v, 8 * de + u, 64) != 0; }
-};
-
-template <int V> struct EvVec;
-template <> struct EvVec<1> { typedef float type; };
-template <> struct EvVec<4> { typedef float type __attribute__((ext_vector_type(4))); };
-
-template <int V, bool HASV> struct EvStage {
-    typename EvVec<V>::type r[kEvStageT], tr[kEvStageT], v[HASV ? kEvStageT : 1];
-    EvDone ds;
-    bool dn[kEvStageT];
-};
 
 struct EvalArgs {
     const float *reward, *true_reward, *V;
@@ -48,13 +24,19 @@ struct EvalArgs {
     int T, E, N;
 };
 
+template <int V, bool HASV> struct EvStage {
+    typename ColVec<V>::type r[kStageT], tr[kStageT], v[HASV ? kStageT : 1];
+    DoneStage ds;
+    bool dn[kStageT];
+};
+
 template <bool COOP, int V, bool HASV>
 __device__ __forceinline__ void eval_fetch(EvStage<V, HASV> &st, const EvalArgs &a, size_t EN, size_t col, size_t e, size_t e_first, int t0)
 {
-    typedef typename EvVec<V>::type vec;
-    if (COOP) st.ds.fetch(a.done, e_first, a.E, a.T, t0);
+    typedef typename ColVec<V>::type vec;
+    if (COOP) st.ds.fetch(a.done, e_first, a.E, a.T, [&](int u) { return t0 - u; });
 #pragma unroll
-    for (int u = 0; u < kEvStageT; ++u) {
+    for (int u = 0; u < kStageT; ++u) {
         const int t = t0 - u;
         const size_t at = (size_t)(t >= 0 ? t : 0) * EN + col;
         st.r[u] = t >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const vec *>(a.reward + at)) : vec(0.0f);
@@ -67,7 +49,7 @@ __device__ __forceinline__ void eval_fetch(EvStage<V, HASV> &st, const EvalArgs 
 template <bool COOP, int V, bool HASV>
 __device__ __forceinline__ void eval_scan(const EvalArgs &a, size_t EN, size_t col, size_t e, size_t e_first, int de, bool act)
 {
-    typedef typename EvVec<V>::type vec;
+    typedef typename ColVec<V>::type vec;
     const int T = a.T;
     const float gamma = a.gamma;
     vec g = vec(0.0f);
@@ -77,10 +59,10 @@ __device__ __forceinline__ void eval_scan(const EvalArgs &a, size_t EN, size_t c
     int L = 0;
     EvStage<V, HASV> cur, nxt;
     eval_fetch<COOP, V, HASV>(cur, a, EN, col, e, e_first, T - 1);
-    for (int t0 = T - 1; t0 >= 0; t0 -= kEvStageT) {
-        if (t0 - kEvStageT >= 0) eval_fetch<COOP, V, HASV>(nxt, a, EN, col, e, e_first, t0 - kEvStageT);
+    for (int t0 = T - 1; t0 >= 0; t0 -= kStageT) {
+        if (t0 - kStageT >= 0) eval_fetch<COOP, V, HASV>(nxt, a, EN, col, e, e_first, t0 - kStageT);
 #pragma unroll
-        for (int u = 0; u < kEvStageT; ++u) {
+        for (int u = 0; u < kStageT; ++u) {
             const int t = t0 - u;
             if (t >= 0) {                                                         // (wave-uniform: the flag pick is a wave operation)
                 const bool dn = COOP ? cur.ds.get(de, u) : cur.dn[u];
@@ -115,16 +97,10 @@ __device__ __forceinline__ void eval_scan(const EvalArgs &a, size_t EN, size_t c
 template <int V, bool HASV>
 __global__ void __launch_bounds__(256) episode_eval_kernel(const EvalArgs a)
 {
-    const size_t EN = (size_t)a.E * a.N;
-    const size_t col0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-    const bool act = col0 < EN;                               // (no early exit: the flag fetch is a wave operation)
-    const size_t col = act ? col0 : EN - V;
-    const size_t e = col / a.N;                               // (V == 4: N % 4 == 0, the four columns belong to one env)
-    const size_t e_first = (size_t)__shfl((long long)e, 0, 64);
-    const int de = (int)(e - e_first);
-    const bool coop = __builtin_amdgcn_ballot_w64(de >= 8) == 0ull;
-    if (coop) eval_scan<true, V, HASV>(a, EN, col, e, e_first, de, act);
-    else eval_scan<false, V, HASV>(a, EN, col, e, e_first, de, act);
+    const ScanCols<V> c(a.E, a.N);
+    const bool coop = c.within_stage();
+    if (coop) eval_scan<true, V, HASV>(a, c.EN, c.col, c.e, c.e_first, c.de, c.act);
+    else eval_scan<false, V, HASV>(a, c.EN, c.col, c.e, c.e_first, c.de, c.act);
 }
 
 // Per env: the collisions of the first episode and the means over agents, agents in ascending order.  One thread per (task,
@@ -208,10 +184,9 @@ int dronesim_episode_eval(const float *reward, const float *true_reward, const i
     a.reward = reward; a.true_reward = true_reward; a.V = mean_adv ? V : nullptr; a.done = done; a.G = G; a.ep_len = ep_len;
     a.agent_return = agent_return; a.agent_true_return = agent_true_return; a.mean_adv = mean_adv;
     a.gamma = gamma; a.T = T; a.E = E; a.N = N;
-    // dronesim_returns' rule for the 16-byte column quadruples (dronesim.hip has the measurements), over every [T][E N] array
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(true_reward) |
-                           reinterpret_cast<uintptr_t>(a.V) | reinterpret_cast<uintptr_t>(G);
-    const bool v4 = (N % 4) == 0 && (bits & 15u) == 0 && cols >= 262144 && cols < 1048576;
+    // the returns scan's window for the column quadruples (scan_common.hpp has the measurements), over every [T][E N] array
+    const bool v4 = column_quads(N, cols, 1048576, reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(true_reward) |
+                                                   reinterpret_cast<uintptr_t>(a.V) | reinterpret_cast<uintptr_t>(G));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(((v4 ? cols / 4 : cols) + 255) / 256));
     if (v4) {
@@ -221,15 +196,11 @@ int dronesim_episode_eval(const float *reward, const float *true_reward, const i
         if (a.V) hipLaunchKernelGGL((episode_eval_kernel<1, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((episode_eval_kernel<1, false>), grid, dim3(256), 0, s, a);
     }
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(err));
-    if (ep_collisions || ep_return || ep_true_return) {
-        hipLaunchKernelGGL(episode_env_kernel, dim3((unsigned)((3 * (size_t)E + 255) / 256)), dim3(256), 0, s, n_coll, ep_len, agent_return,
-                           agent_true_return, ep_collisions, ep_return, ep_true_return, E, N);
-        err = hipGetLastError();
-        if (err != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(err));
-    }
-    return DRONESIM_OK;
+    const int rc = dronesim_launched();
+    if (rc != DRONESIM_OK || !(ep_collisions || ep_return || ep_true_return)) return rc;
+    hipLaunchKernelGGL(episode_env_kernel, dim3((unsigned)((3 * (size_t)E + 255) / 256)), dim3(256), 0, s, n_coll, ep_len, agent_return,
+                       agent_true_return, ep_collisions, ep_return, ep_true_return, E, N);
+    return dronesim_launched();
 }
 
 int dronesim_histogram_i32(const int32_t *values, const uint8_t *valid, int E, int n_bins, int64_t *counts, int accumulate,
@@ -239,9 +210,7 @@ int dronesim_histogram_i32(const int32_t *values, const uint8_t *valid, int E, i
         return dronesim_fail(DRONESIM_EINVAL, "dronesim_histogram_i32: bad argument");
     hipLaunchKernelGGL(histogram_kernel, dim3(1), dim3(kHistThreads), 0, static_cast<hipStream_t>(stream), values, valid, E, n_bins,
                        reinterpret_cast<long long *>(counts), accumulate);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(err));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 }   // extern "C"

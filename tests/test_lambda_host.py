@@ -87,6 +87,25 @@ def test_entry_point_rejects_bad_arguments_on_the_host():
     assert call(T=0, G=None) == _native.OK and call(E=0, A=None, done=None) == _native.OK
 
 
+def test_quadruple_rule_at_its_edges():
+    """The one host helper behind the four entry points (csrc/scan_common.hpp: column_quads) against the expressions they each
+    carried: agents in fours, every base 16-byte aligned, 262144 <= columns < the caller's bound (1048576 for
+    dronesim_returns / dronesim_episode_eval, 524288 for the two lambda scans)."""
+    fn = _native.lib().dronesim_debug_column_quads
+    fn.argtypes, fn.restype = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64], C.c_int
+    base = 0x7F0000001000
+    for upper in (1048576, 524288):
+        for cols in (262140, 262144, 524284, 524288, 1048572, 1048576):
+            for N in (3, 4):
+                for addresses in (base, base | (base + 4), base | (base + 16), 0):
+                    old = N % 4 == 0 and (addresses & 15) == 0 and cols >= 262144 and cols < upper
+                    assert fn(N, cols, upper, addresses) == int(old), (N, cols, upper, hex(addresses))
+    assert fn(4, 262144, 524288, base) == 1 and fn(4, 262140, 524288, base) == 0          # the lower bound, everywhere
+    assert fn(4, 524284, 524288, base) == 1 and fn(4, 524288, 524288, base) == 0          # the lambda scans' upper bound
+    assert fn(4, 524288, 1048576, base) == 1 and fn(4, 1048572, 1048576, base) == 1 and fn(4, 1048576, 1048576, base) == 0
+    assert fn(3, 262144, 1048576, base) == 0 and fn(4, 262144, 1048576, base | (base + 4)) == 0
+
+
 GOOD_LAM, BAD_LAM = (None, 0.0, 1.0, 0.95), (-0.1, 1.5, float("nan"), "1")
 
 

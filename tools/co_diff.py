@@ -39,6 +39,10 @@ def kernels(path):
                 ins = re.sub(r"<[^>]*\+0x[0-9a-f]+>", "<L>", ins)
                 if ins and ins != "...":       # "...": objdump's mark for the zero padding up to the NEXT kernel's alignment --
                     out[name].append(ins)      # no instruction, and absent behind the last kernel of a code object
+    for stream in out.values():                # the s_nop run the assembler pads the end of a text section with (instruction prefetch):
+        end = max((i for i, ins in enumerate(stream) if ins.startswith(("s_endpgm", "s_branch", "s_cbranch"))), default=None)
+        if end is not None and end + 1 < len(stream) and all(ins == "s_nop 0" for ins in stream[end + 1:]):
+            del stream[end + 1:]               # only a run that is ALL s_nop behind the kernel's final s_endpgm / branch: never executed
     return out
 
 

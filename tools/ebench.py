@@ -6,7 +6,7 @@
   2. one `Evaluator` round (softmax-16 actor + critic, f16x2) next to the bare loop of examples/rollout_loop.py part 2 (b)
      without the evaluation.
 
-    python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--out profiles/ebench.jsonl] [--skip-round]
+    python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
 Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
 import argparse
 import ctypes as C
@@ -90,9 +90,12 @@ def main():
     ap.add_argument("--agents", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-round", action="store_true")
+    ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     a = ap.parse_args()
 
     def emit(rec):
+        if a.tag:
+            rec["tag"] = a.tag
         line = json.dumps(rec)
         print(line, flush=True)
         if a.out:

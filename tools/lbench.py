@@ -126,6 +126,8 @@ def scans(args):
             else:       # the byte ratio to the yardstick plus 15 % (the longer dependent chain per step, run-to-run spread)
                 line.update(ratio=round(med / base, 3), expected_us=round(base * bpe / 8, 2), allowed_us=round(base * bpe / 8 * 1.15, 2),
                             inside=bool(med <= base * bpe / 8 * 1.15))
+            if args.tag:
+                line["tag"] = args.tag
             lines.append(line)
             print(json.dumps(line), flush=True)
     if args.out:
@@ -442,6 +444,8 @@ def scans_time_limit(args):
                     base = med
                 else:       # the same bytes (+ M / T of one V stream): the yardstick plus 15 % (one more select and a counter, spread)
                     line.update(ratio=round(med / base, 3), allowed_us=round(base * 1.15, 2), inside=bool(med <= base * 1.15))
+            if args.tag:
+                line["tag"] = args.tag
             lines.append(line)
             print(json.dumps(line), flush=True)
     if args.out:

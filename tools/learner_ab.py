@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Bit-for-bit A/B of the learner's native entry points between two builds of libdronesim.so, for refactorings of
-csrc/learner.hip / csrc/standardize.hip that claim "same results".  Two runs, two processes, the library chosen by DRONESIM_LIB:
+"""Bit-for-bit A/B of the learner-side native entry points between two builds of libdronesim.so, for refactorings of
+csrc/learner.hip / csrc/standardize.hip / csrc/scans.hip / csrc/evaluate.hip (scan_common.hpp) that claim "same results".
+Two runs, two processes, the library chosen by DRONESIM_LIB:
 
     DRONESIM_LIB=before.so python tools/learner_ab.py --dump ab.npz
     DRONESIM_LIB=after.so  python tools/learner_ab.py --compare ab.npz
@@ -10,7 +11,12 @@ agent equals itself); --compare requires equality of all of them and exits 1 oth
 every branch: N = 3 agents, R = 200 rows in chunks of 64 (first chunk writes, two accumulate, the last has 8 rows and divides),
 d_in = 7, h1 = 48, h2 = 80 (tile edges inside both hidden widths); a critic, a softmax actor (nout = 5; agent 2's last logit is
 125 below the others: p = 0 in float32) and a Gaussian actor; advantages of both signs, logp_old off by up to +-0.5 (both clip
-branches and unclipped rows), a vf_clip that clamps some rows, active = [1, 0, 1]."""
+branches and unclipped rows), a vf_clip that clamps some rows, active = [1, 0, 1].
+The scans (`run_scans`): windows of T = 1, 8, 9, 17 steps (a partial stage, one stage, a stage + 1, two stages + 1) over
+E x N = 333 x 2 (one column per thread, ragged last wave, a wave spans 32 envs: per-thread flags) and 5 x 64 (cooperative
+flags), and T = 9 over 65536 x 4 and 1025 x 256 (column quadruples without and with cooperative flags, ragged last
+workgroup); `done` set at t = 0, t = T - 1 and in between, or NULL; ends of M = 2 slots with 0 .. 3 truncated ends per env;
+G only, A only and both; the evaluation with and without V; the advantages with K1 = 3 and 2 and a -1 neighbour."""
 import argparse
 import ctypes as C
 import os
@@ -83,7 +89,81 @@ def run_all():
         _native.check(lib.dronesim_standardize(v.data_ptr(), y.data_ptr(), stats.data_ptr(), rows, cols, 1e-8, ws.data_ptr(), n.value,
                                                None), "dronesim_standardize")
         keep(f"standardize.{rows}x{cols}", y, stats)
+    run_scans(out)
     return out
+
+
+SCAN_SHAPES = ((333, 2, (1, 8, 9, 17)), (5, 64, (1, 8, 9, 17)), (65536, 4, (9,)), (1025, 256, (9,)))
+
+
+def run_scans(out):
+    """Every entry point of csrc/scans.hip and `dronesim_episode_eval` on the smallest windows that reach every path."""
+    lib, gen = _native.lib(), torch.Generator().manual_seed(20250311)
+    rnd = lambda *shape: (torch.rand(*shape, generator=gen) * 2 - 1).to(DEV)
+    ptr = lambda t: None if t is None else t.data_ptr()
+
+    def keep(name, *tensors):
+        torch.cuda.synchronize()
+        for k, t in enumerate(tensors):
+            t = t.detach().contiguous()
+            out[f"{name}.{k}"] = (t if t.element_size() in (4, 8) else t.to(torch.int32)).view(torch.int32).cpu().numpy().copy()
+
+    for E, N, Ts in SCAN_SHAPES:
+        for T in Ts:
+            tag, M, gamma, lam = f"scan.{E}x{N}.T{T}", 2, 0.97, 0.9
+            r, tr, V, Vend = rnd(T, E, N), rnd(T, E, N), rnd(T + 1, E, N), rnd(M, E, N)
+            done = (torch.rand(T, E, generator=gen) < 0.2).to(torch.uint8)
+            done[0, 0::3] = 1; done[T - 1, 1::3] = 1; done[T // 2, 2::3] = 1
+            done = done.to(DEV)
+            # env e carries e % 4 truncated ends (as many as T holds) from the back of the window, terminal ends elsewhere
+            ends = done.clone().cpu()
+            for k in range(min(3, T)):
+                ends[T - 1 - 2 * k if T > 2 * k else k, torch.arange(E) % 4 > k] = 2
+            ends = ends.to(DEV)
+            new = lambda: torch.zeros(T, E, N, device=DEV)
+            for dn, d in (("done", done), ("null", None)):
+                G = new()
+                _native.check(lib.dronesim_returns(ptr(r), ptr(d), gamma, ptr(G), T, E, N, None), "dronesim_returns")
+                keep(f"{tag}.returns.{dn}", G)
+                for what, (wg, wa) in (("G", (1, 0)), ("A", (0, 1)), ("GA", (1, 1))):
+                    G, A = new() if wg else None, new() if wa else None
+                    _native.check(lib.dronesim_lambda_returns(ptr(r), ptr(d), ptr(V), gamma, lam, ptr(G), ptr(A), T, E, N, None),
+                                  "dronesim_lambda_returns")
+                    keep(f"{tag}.lambda.{dn}.{what}", *[t for t in (G, A) if t is not None])
+            for what, (wg, wa) in (("G", (1, 0)), ("A", (0, 1)), ("GA", (1, 1))):
+                G, A = new() if wg else None, new() if wa else None
+                _native.check(lib.dronesim_lambda_returns_ends(ptr(r), ptr(ends), ptr(V), ptr(Vend), M, gamma, lam, ptr(G), ptr(A),
+                                                               T, E, N, None), "dronesim_lambda_returns_ends")
+                keep(f"{tag}.ends.{what}", *[t for t in (G, A) if t is not None])
+            # the ends' classification: rows of d floats (N d a multiple of four or not), about half the agents outside the disk
+            for d in (2, 5):
+                z_final = rnd(T, E, N, d) * 0.3
+                res = (torch.zeros(T, E, dtype=torch.uint8, device=DEV), torch.zeros(M, E, dtype=torch.int32, device=DEV),
+                       torch.zeros(E, dtype=torch.int32, device=DEV), torch.full((M, E, N, d), 7.0, device=DEV))
+                _native.check(lib.dronesim_episode_ends(ptr(done), ptr(z_final), T, E, N, d, 0.2, *[ptr(t) for t in res], M, None),
+                              "dronesim_episode_ends")
+                keep(f"{tag}.episode_ends.d{d}", *res)
+            n_coll = torch.randint(0, 3, (T, E), generator=gen, dtype=torch.int32).to(DEV)
+            for what, v in (("V", V[:T].contiguous()), ("noV", None)):
+                i32, f64 = lambda *sh: torch.zeros(*sh, dtype=torch.int32, device=DEV), lambda *sh: torch.zeros(*sh, dtype=torch.float64, device=DEV)
+                res = [i32(E), i32(E), f64(E, N), f64(E, N), f64(E), f64(E), new(), f64(E, N) if v is not None else None]
+                _native.check(lib.dronesim_episode_eval(ptr(r), ptr(tr), ptr(n_coll), ptr(done), ptr(v), gamma, *[ptr(t) for t in res],
+                                                        T, E, N, None), "dronesim_episode_eval")
+                keep(f"{tag}.eval.{what}", *[t for t in res if t is not None])
+            for K1 in (3, 2):
+                nbr = torch.randint(-1, N, (T, E, N, K1), generator=gen, dtype=torch.int32)
+                nbr[..., 0] = torch.arange(N, dtype=torch.int32)                       # slot 0 is the agent itself
+                nbr, G = nbr.to(DEV), rnd(T, E, N)
+                for dn, d in (("done", done), ("null", None)):
+                    w = new()
+                    _native.check(lib.dronesim_advantage(ptr(G), ptr(V), ptr(nbr), ptr(d), gamma, ptr(w), T, E, N, K1, None),
+                                  "dronesim_advantage")
+                    keep(f"{tag}.advantage.K{K1}.{dn}", w)
+                for per in (0, 1):
+                    adv = new()
+                    _native.check(lib.dronesim_neighbour_advantage(ptr(G), ptr(V), ptr(nbr), per, ptr(adv), T, E, N, K1, None),
+                                  "dronesim_neighbour_advantage")
+                    keep(f"{tag}.neighbour_advantage.K{K1}.per{per}", adv)
 
 
 def main():
