@@ -204,7 +204,8 @@ __device__ __forceinline__ void nbr_insert(unsigned long long (&list)[K + 1], un
 //                the j > i) needs the index, and a partner can only reach it with d <= d_ii -- exactly coincident
 //                agents, or a larger partner overlapping a smaller agent's centre.  That case takes the general
 //                insertion, wave-uniformly; everything else inserts behind entry 0 with 5 instructions per stage
-//                instead of 8 on 64-bit keys.
+//                instead of 8 on 64-bit keys.  Partners of exactly equal distance (two coincident agents in a third
+//                agent's row) keep their order of arrival, the lower index first.
 template <int K, bool ASC> struct NbrList;
 template <int K> struct NbrList<K, false> {
     unsigned long long key[K + 1];
@@ -259,15 +260,20 @@ template <int K> struct NbrList<K, true> {
             }
             return;
         }
+        // once the new partner has taken a slot, every later entry moves down by one, whatever its distance (`moved`: a lane
+        // mask, one scalar OR per stage).  A displaced entry that was only COMPARED stayed behind an entry of exactly its own
+        // distance: two coincident partners, as a third agent sees them, swapped when a closer partner arrived later.
         float kd = dn;
         unsigned kj = (unsigned)jn;
+        bool moved = false;
 #pragma unroll
         for (int s = 1; s <= K; ++s) {
-            const bool lt = kd < d[s];
+            const bool lt = moved | (kd < d[s]);
             const float cd = d[s];
             const unsigned cj = j[s];
             d[s] = lt ? kd : cd; j[s] = lt ? kj : cj;
             kd = lt ? cd : kd; kj = lt ? cj : kj;
+            moved = lt;
         }
     }
     __device__ __forceinline__ unsigned index(int kth) const { return j[kth]; }
