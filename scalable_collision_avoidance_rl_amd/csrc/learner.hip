@@ -18,8 +18,8 @@
 //
 // The heads are two templates on the entropy bonus, a2c_head_kernel<kEnt> (critic with the optional clipped value loss, softmax
 // actor, Gaussian actor) and ppo_head_kernel<kEnt> (the clipped surrogate of both actor kinds; <false> is also the forward-only
-// log-probability pass, <true> also the gated form with the KL plane); action_of and log_sum_exp are shared by all four
-// instantiations.  The per-agent results are block_sum reductions in one fixed order: row_sum_kernel (loss, mean entropy, share
+// log-probability pass, <true> also the gated form with the KL plane); action_of, log_sum_exp, softmax_grad and the two
+// cancellation-free factors one_minus_tanh2 / one_minus_sigmoid are shared by all four instantiations.  The per-agent results are block_sum reductions in one fixed order: row_sum_kernel (loss, mean entropy, share
 // of zero-gradient rows), kl_sum_kernel and grad_norm_kernel (float64), and ppo_stats_kernel (four values per level).
 //
 // An entry point describes its call as a ChainJob -- the form (which options), the pointers and scalars that form reads -- after
@@ -148,15 +148,47 @@ __device__ __forceinline__ int action_of(const float *act, long long src, int no
     return ((a % nout) + nout) % nout;
 }
 
-// log sum_j exp(o_j) of one row of logits, shifted by the row's maximum
-__device__ __forceinline__ float log_sum_exp(const float *o, int nout)
+// log sum_j exp(o_j) of one row of logits in two parts, the row's maximum `mx` (its first occurrence) and the returned
+// ls = log1p(sum of the OTHER logits' exp(o_j - mx)): a log-probability is lq_j = (o_j - mx) - ls.  The sum mx + ls is never formed:
+// it rounds at ulp(mx), which at a saturated policy (ls ~ 1e-7 and below) is all of log p_max.
+__device__ __forceinline__ float log_sum_exp(const float *o, int nout, float &mx)
 {
-    float mx = o[0];
-    for (int j = 1; j < nout; ++j) mx = fmaxf(mx, o[j]);
+    int jm = 0;
+    mx = o[0];
+    for (int j = 1; j < nout; ++j)
+        if (o[j] > mx) { mx = o[j]; jm = j; }
     float s = 0.f;
-    for (int j = 0; j < nout; ++j) s += expf(o[j] - mx);
-    return mx + logf(s);
+    for (int j = 0; j < nout; ++j)
+        if (j != jm) s += expf(o[j] - mx);
+    return log1pf(s);
 }
+
+// The softmax head's dLoss/dO in place of the logits o: c (onehot_a - p) (+ the entropy's es p_j (lq_j + H) with kEnt).  The chosen
+// logit's 1 - p_a is the sum of the other probabilities, not a difference of two numbers near 1.
+template <bool kEnt>
+__device__ __forceinline__ void softmax_grad(float *o, int nout, int a, float mx, float ls, float c, float es, float H)
+{
+    float others = 0.f;
+    for (int j = 0; j < nout; ++j)
+        if (j != a) others += expf((o[j] - mx) - ls);
+    for (int j = 0; j < nout; ++j) {
+        const float lq = (o[j] - mx) - ls;
+        const float p = expf(lq);
+        const float g = c * (j == a ? others : -p);
+        o[j] = kEnt ? g + es * (p * (lq + H)) : g;
+    }
+}
+
+// The two factors of the Gaussian head's chain rule that cancel when formed from mu and var: 1 - tanh^2(o) = 4 t / (1 + t)^2 with
+// t = exp(-2 |o|) (1 - mu mu is 0 from |o| = 9 on, and noise well before), and 1 - sigmoid(s) = sigmoid(-s) from its own
+// exponential (e / (1 + e) with e = exp(-s) is inf / inf for s < -88).
+__device__ __forceinline__ float one_minus_tanh2(float o)
+{
+    const float t = expf(-2.f * fabsf(o));
+    return 4.f * t / ((1.f + t) * (1.f + t));
+}
+
+__device__ __forceinline__ float one_minus_sigmoid(float s) { return 1.f / (1.f + expf(s)); }
 
 // The A2C loss head of one (row, agent): per-row loss (times `scale`) into L, dLoss/dO (pre-activation outputs) in place of O.
 //   kind 0 (critic, <false> only):  l = (o - G)^2
@@ -167,10 +199,13 @@ __device__ __forceinline__ float log_sum_exp(const float *o, int nout)
 //   An unclamped row has Vc = V itself (not v_old + (V - v_old), which rounds): it forms the plain expressions and gives their bits.
 // <true> is the entropy bonus of the two actor kinds, L_i - es sum_r H_i(x_r): every value of <false> is formed by the same
 //   expressions and the entropy's part is ADDED, so es = 0 gives <false>'s values (an exact zero is added).
-//     softmax:   lq_j = o_j - lse,  p_j = exp(lq_j),  H = -sum_j p_j lq_j;    dO_j += es p_j (lq_j + H)
+//     softmax:   lq_j = (o_j - max) - ls,  p_j = exp(lq_j),  H = -sum_j p_j lq_j;    dO_j += es p_j (lq_j + H)
 //                (from lq, never log p: a logit 120 below the maximum has p = 0 in float32 and 0 log 0 is NaN)
 //     Gaussian:  H = sum_d 0.5 log(2 pi e var_d);                             dO_{2+d} += -0.5 es (1 - var_d)  (the head's omv)
 //   The per-row loss is the whole objective l - es H; H itself goes to the plane P [N][Rc].
+// The heads stay accurate at saturated policies (p_max = 0.999..., a mean against tanh's +-1): the factors that cancel there come
+// from log_sum_exp's two parts, softmax_grad, one_minus_tanh2 and one_minus_sigmoid; mu = tanh(o), var and the Gaussian log pi are
+// formed as they always were.
 template <bool kEnt>
 __global__ __launch_bounds__(kThreads) void a2c_head_kernel(float *O, float *L, float *P, long long Rc, int rc, long long r0, int N,
                                                             int nout, int kind, float scale, float es, const float *target,
@@ -203,31 +238,27 @@ __global__ __launch_bounds__(kThreads) void a2c_head_kernel(float *O, float *L, 
         }
     } else if (kind == 1) {
         const int a = action_of(act, src, nout);
-        const float lse = log_sum_exp(o, nout);
+        float mx;
+        const float ls = log_sum_exp(o, nout, mx);
         const float c = -scale * weight[src];
-        loss = c * (o[a] - lse);
+        loss = c * ((o[a] - mx) - ls);
         if (kEnt) {
             for (int j = 0; j < nout; ++j) {
-                const float lq = o[j] - lse;
+                const float lq = (o[j] - mx) - ls;
                 H -= expf(lq) * lq;
             }
         }
-        for (int j = 0; j < nout; ++j) {
-            const float p = expf(o[j] - lse);
-            const float g = c * ((j == a ? 1.f : 0.f) - p);
-            o[j] = kEnt ? g + es * (p * ((o[j] - lse) + H)) : g;
-        }
+        softmax_grad<kEnt>(o, nout, a, mx, ls, c, es, H);
     } else {
         const float c = -scale * weight[src];
         float lp = 0.f;
         for (int d = 0; d < 2; ++d) {
-            const float mu = tanhf(o[d]);
-            const float e = expf(-o[2 + d]);
-            const float var = 1.f / (1.f + e), omv = e / (1.f + e);
+            const float mu = tanhf(o[d]), omm = one_minus_tanh2(o[d]);
+            const float var = 1.f / (1.f + expf(-o[2 + d])), omv = one_minus_sigmoid(o[2 + d]);
             const float diff = act[2 * src + d] - mu;
             lp += -0.5f * logf(6.283185307179586f * var) - diff * diff / (2.f * var);
             if (kEnt) H += 0.5f * logf(17.079468445347132f * var);
-            o[d] = c * (diff / var) * (1.f - mu * mu);
+            o[d] = c * (diff / var) * omm;
             const float g = c * (-0.5f + diff * diff / (2.f * var)) * omv;
             o[2 + d] = kEnt ? g - 0.5f * es * omv : g;
         }
@@ -262,27 +293,26 @@ __global__ __launch_bounds__(kThreads) void ppo_head_kernel(float *O, float *L, 
     if (kEnt && active && active[i] == 0) return;
     float *o = O + ((long long)i * Rc + m) * nout;
     const long long src = (r0 + m) * N + i;
-    float lp, lse = 0.f, H = 0.f;
+    float lp, mx = 0.f, ls = 0.f, H = 0.f;
     int a = 0;
-    float mu[2], var[2], omv[2], diff[2];
+    float omm[2], var[2], omv[2], diff[2];
     if (kind == 1) {
         a = action_of(act, src, nout);
-        lse = log_sum_exp(o, nout);
-        lp = o[a] - lse;
+        ls = log_sum_exp(o, nout, mx);
+        lp = (o[a] - mx) - ls;
         if (kEnt) {
             for (int j = 0; j < nout; ++j) {
-                const float lq = o[j] - lse;
+                const float lq = (o[j] - mx) - ls;
                 H -= expf(lq) * lq;
             }
         }
     } else {
         lp = 0.f;
         for (int d = 0; d < 2; ++d) {
-            mu[d] = tanhf(o[d]);
-            const float e = expf(-o[2 + d]);
-            var[d] = 1.f / (1.f + e);
-            omv[d] = e / (1.f + e);
-            diff[d] = act[2 * src + d] - mu[d];
+            omm[d] = one_minus_tanh2(o[d]);
+            var[d] = 1.f / (1.f + expf(-o[2 + d]));
+            omv[d] = one_minus_sigmoid(o[2 + d]);
+            diff[d] = act[2 * src + d] - tanhf(o[d]);
             lp += -0.5f * logf(6.283185307179586f * var[d]) - diff[d] * diff[d] / (2.f * var[d]);
         }
         if (kEnt) {
@@ -299,14 +329,10 @@ __global__ __launch_bounds__(kThreads) void ppo_head_kernel(float *O, float *L, 
     const bool clipped = (A > 0.f && r > hi) || (A < 0.f && r < lo);
     const float c = clipped ? 0.f : -scale * A * r;
     if (kind == 1) {
-        for (int j = 0; j < nout; ++j) {
-            const float p = expf(o[j] - lse);
-            const float g = c * ((j == a ? 1.f : 0.f) - p);
-            o[j] = kEnt ? g + es * (p * ((o[j] - lse) + H)) : g;
-        }
+        softmax_grad<kEnt>(o, nout, a, mx, ls, c, es, H);
     } else {
         for (int d = 0; d < 2; ++d) {
-            o[d] = c * (diff[d] / var[d]) * (1.f - mu[d] * mu[d]);
+            o[d] = c * (diff[d] / var[d]) * omm[d];
             const float g = c * (-0.5f + diff[d] * diff[d] / (2.f * var[d])) * omv[d];
             o[2 + d] = kEnt ? g - 0.5f * es * omv[d] : g;
         }

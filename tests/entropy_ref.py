@@ -189,9 +189,10 @@ def ppo_train(kind, Wa, Wc, x, reward, done, act, nbr, gamma, epochs=10, clip_ep
 
 
 def sa2c_train(kind, Wa, Wc, x, reward, done, act, nbr, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, state=None,
-               ent_coef=0.0):
+               ent_coef=0.0, a2c_grads=None):
     """`learner_ref.sa2c_train` whose actor loss carries -ent_coef x the mean row entropy (the likelihood term keeps its
-    1 / E).  Adds ``entropy`` [N] and ``actor_mag`` to the returned dict."""
+    1 / E).  Adds ``entropy`` [N] and ``actor_mag`` to the returned dict.  ``a2c_grads``: another statement of this module's
+    function of that name (tests/saturation_ref.py: the heads written without cancellation)."""
     T, E, N = reward.shape
     rows = T * E
     out = R.sa2c_train(kind, Wa, Wc, x, reward, done, act, nbr, gamma, lr_actor, lr_critic, max_norm, state)
@@ -199,7 +200,7 @@ def sa2c_train(kind, Wa, Wc, x, reward, done, act, nbr, gamma, lr_actor=1e-3, lr
         zeros = lambda W: [torch.zeros_like(w, dtype=torch.float64) for w in W]
         state = dict(am1=zeros(Wa), am2=zeros(Wa), step=0)
     xr = x.reshape(rows, N, -1).double()
-    a = a2c_grads(kind, Wa, xr, 1.0 / E, act.reshape(rows, N, 2), out["w"].reshape(rows, N), ent_coef / rows)
+    a = (a2c_grads or globals()["a2c_grads"])(kind, Wa, xr, 1.0 / E, act.reshape(rows, N, 2), out["w"].reshape(rows, N), ent_coef / rows)
     Wa2, am1, am2, na = R.clip_adam(Wa, a["grad"], state["am1"], state["am2"], state["step"] + 1, lr_actor, max_norm)
     out["state"].update(am1=am1, am2=am2)
     out.update(actor_grad=a["grad"], actor_mag=a["mag"], actor_loss=a["loss"], actor_norm=na, actor_post=Wa2, entropy=a["entropy"])

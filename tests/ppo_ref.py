@@ -38,13 +38,13 @@ def advantage(G, V, nbr, baseline="once"):
     return neighbour_sum(G, nbr) - c * V.double()
 
 
-def ratio_terms(lp, logp_old, adv, clip_eps):
+def ratio_terms(lp, logp_old, adv, clip_eps, margin=EDGE_MARGIN):
     """(r, clipped, near): the ratio, the rows where the clipped branch is the strict minimum, and the rows within
-    EDGE_MARGIN (relative) of a clip edge; all [R, N]."""
+    ``margin`` (relative; a number or a tensor [R, N], default EDGE_MARGIN) of a clip edge; all [R, N]."""
     r = torch.exp(lp.double() - logp_old.double())
     adv = adv.double()
     clipped = ((adv > 0) & (r > 1 + clip_eps)) | ((adv < 0) & (r < 1 - clip_eps))
-    near = ((r / (1 + clip_eps) - 1).abs() <= EDGE_MARGIN) | ((r / (1 - clip_eps) - 1).abs() <= EDGE_MARGIN)
+    near = ((r / (1 + clip_eps) - 1).abs() <= margin) | ((r / (1 - clip_eps) - 1).abs() <= margin)
     return r, clipped, near
 
 
@@ -68,16 +68,16 @@ def actor_grads(kind, W, x, act, logp_old, adv, clip_eps):
                 ratio_min=r.min(0).values, ratio_max=r.max(0).values)
 
 
-def draw_logp_old(lp, adv, clip_eps, gen, spread=math.log(2.0)):
+def draw_logp_old(lp, adv, clip_eps, gen, spread=math.log(2.0), margin=EDGE_MARGIN):
     """``logp_old = lp - u`` with a continuous offset u uniform in [-spread, spread] (r = exp(u) spreads over [0.5, 2] at the
-    default), offsets of rows within EDGE_MARGIN of a clip edge redrawn (as `learner_ref.clean_rows` does for relu kinks).
+    default), offsets of rows within ``margin`` of a clip edge redrawn (as `learner_ref.clean_rows` does for relu kinks).
     lp, adv CPU float64 [R, N].  Returns (logp_old float32 -- what the kernel is given --, share of rows redrawn)."""
     draw = lambda n: (torch.rand(n, generator=gen, dtype=torch.float64) * 2 - 1) * spread
     u = draw(lp.numel()).view_as(lp)
     redrawn = torch.zeros_like(lp, dtype=torch.bool)
     for _ in range(20):
         old = (lp - u).float()                        # the float32 value the kernel reads decides the float64 ratio
-        _, _, near = ratio_terms(lp, old, adv, clip_eps)
+        _, _, near = ratio_terms(lp, old, adv, clip_eps, margin)
         if not near.any():
             return old, float(redrawn.double().mean())
         redrawn |= near
@@ -86,10 +86,11 @@ def draw_logp_old(lp, adv, clip_eps, gen, spread=math.log(2.0)):
 
 
 def ppo_train(kind, Wa, Wc, x, reward, done, act, nbr, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3,
-              max_norm=10.0, baseline="once", state=None):
+              max_norm=10.0, baseline="once", state=None, actor_grads=None, logp=None):
     """One `SPPOAgents.train` over a window: x [T,E,N,d], reward [T,E,N], done [T,E], act [T,E,N,2], nbr [T,E,N,k+1].
-    ``state``: the Adam state of earlier calls (None = fresh optimisers).  Returns a dict: G, Q, V (pre-update critic), adv,
-    logp_old [T,E,N]; per epoch lists ``critic_loss, critic_norm, critic_grad, actor_loss, actor_norm, actor`` (the
+    ``state``: the Adam state of earlier calls (None = fresh optimisers).  ``actor_grads`` / ``logp``: other statements of
+    this module's functions of those names (tests/saturation_ref.py: the heads written without cancellation).
+    Returns a dict: G, Q, V (pre-update critic), adv, logp_old [T,E,N]; per epoch lists ``critic_loss, critic_norm, critic_grad, actor_loss, actor_norm, actor`` (the
     `actor_grads` dict); the post-update weights and the new Adam ``state``."""
     T, E, N = reward.shape
     rows = T * E
@@ -100,6 +101,7 @@ def ppo_train(kind, Wa, Wc, x, reward, done, act, nbr, gamma, epochs=10, clip_ep
     zeros = lambda W: [torch.zeros_like(w) for w in W]
     if state is None:
         state = dict(cm1=zeros(Wc), cm2=zeros(Wc), am1=zeros(Wa), am2=zeros(Wa), step=0)
+    actor_grads, logp = actor_grads or globals()["actor_grads"], logp or globals()["logp"]
     logp_old = logp(kind, Wa, xr, actr).detach()
     V = R.forward(Wc, xr)[2][..., 0].transpose(0, 1).reshape(T, E, N)
     adv = advantage(G, V, nbr, baseline)
