@@ -508,9 +508,38 @@ __host__ __device__ constexpr int bucket_cells(int geo, bool rollout)
 }
 // workgroup-per-env geometries: float2 entries of the position tile (N, the over-read slack, even for 16-byte alignment)
 __host__ __device__ constexpr int block_pos_entries(int N) { return (N + kPad + 1) & ~1; }
+// The other regions of the carve-up, each in the integer type the kernel's expression has: the kernel carves with them and the
+// host (dronesim.hip: step_lds) adds the same calls up -- the LDS layout has no second definition.
+// packed geometries: float2 entries of one copy of an env slot's positions (even), and of the [epb][2 copies] tile
+__host__ __device__ constexpr int pos_stride(int N) { return 2 * N + kPad; }
+__host__ __device__ constexpr size_t packed_pos_entries(int epb, int N) { return (size_t)epb * 2 * pos_stride(N); }
+// float2 entries of one copy of the (Delta_j, l_j) table (even: 16 bytes)
+__host__ __device__ constexpr int const_entries(int N) { return N + (N & 1); }
+// verdict words of a workgroup's `epb_c` envs, two each, in whole 16 bytes
+__host__ __device__ constexpr int red_words(int epb_c) { return 2 * epb_c + ((2 * epb_c) & 3 ? 4 - ((2 * epb_c) & 3) : 0); }
+// staging words per wave: [64 lanes][zc (K+1) z words] + [64 lanes][K+1 Ni words]  (zc = columns of a staged z row: 2, or 5)
+__host__ __device__ constexpr int stage_words(int zc, int K) { return kWave * (zc * (K + 1) + (K + 1)); }
+// 8-byte words of the generic bucket tables per env slot: [2 axes][W words of 64 agents][cells]
+__host__ __device__ constexpr int table_words(int geo, bool rollout, int W) { return 2 * bucket_cells(geo, rollout) * W; }
+// tail (episode layer): floats of the per-wave partial sums, [nwaves rounded to even][2], in front of the sampling tables
+__host__ __device__ constexpr int tail_part_floats(int nwaves) { return 2 * ((nwaves + 1) & ~1); }
+// entries of the in-kernel reset's sampling table per env slot: the power of two >= 2 N (int2 each)
+__host__ __device__ constexpr int samp_table_entries(int N)
+{
+    int nt = 4;
+    while (nt < 2 * N) nt <<= 1;
+    return nt;
+}
 // kSym64's LDS block per wave: [64 positions][staging: 64 x (z row + Ni row)][x cells | y cells] -- see the carve-up
-// (zc = columns of a staged z row: 2, or 5 for the FAR variant with c = 5 rows)
-constexpr int sym_wave_bytes(int K, int zc = 2) { return 64 * 8 + 64 * (zc + 1) * (K + 1) * 4 + 2 * kCells * 8; }
+// (zc = columns of a staged z row: 2, or 5 for the FAR variant with c = 5 rows): byte offsets of the two inner regions, and the size
+__host__ __device__ constexpr int sym_stage_offset() { return 64 * 8; }
+__host__ __device__ constexpr int sym_cells_offset(int K, int zc) { return sym_stage_offset() + stage_words(zc, K) * 4; }
+__host__ __device__ constexpr int sym_wave_bytes(int K, int zc = 2) { return sym_cells_offset(K, zc) + 2 * kCells * 8; }
+
+// What travels in the preloaded scalar arguments next to their own value (launch_one packs, drone_kernel unpacks):
+// `epb`: which parts of DroneEpisodeCtl are in use and the closed-loop rollout's controller, above kFlagShift;
+// `P` (<= 64): the number of workgroups in whole groups of 256 (the XCD map), under kXcdBlocks.
+enum LaunchWord : unsigned { kFlagRecords = 1u, kFlagAutoReset = 2u, kFlagRandAct = 4u, kFlagGradient = 8u, kFlagShift = 16u, kXcdBlocks = ~255u };
 
 template <bool WAVE_LOCAL>
 __device__ __forceinline__ void group_sync()
@@ -546,10 +575,10 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // for the kernel-argument fetch ahead of the first pos / act loads
     // (bit 19: the closed-loop rollout's controller is gradient_control -- kRolloutCtrl, with or without the episode layer)
     constexpr bool CTRL = MODE == kRolloutCtrl;              // the action source is a controller evaluated in this launch
-    const int epi_flags = (EPI || CTRL) ? (epb >> 16) : 0;
-    if (EPI || CTRL) epb &= 0xffff;
-    const unsigned xcd_blocks = (unsigned)P & ~255u;         // workgroups in whole groups of 256 (XCD map below)
-    a.pos = pos; a.P = P & 255; a.epb = epb; a.E = E; a.N = n_agents;
+    const int epi_flags = (EPI || CTRL) ? (epb >> kFlagShift) : 0;
+    if (EPI || CTRL) epb &= (1 << kFlagShift) - 1;
+    const unsigned xcd_blocks = (unsigned)P & kXcdBlocks;    // workgroups in whole groups of 256 (XCD map below)
+    a.pos = pos; a.P = P & (int)~kXcdBlocks; a.epb = epb; a.E = E; a.N = n_agents;
     if (MODE == kObserve) a.vel = const_cast<float *>(vel_or_act); else a.act = vel_or_act;
     constexpr bool WL = GeoTraits<GEO>::kWaveLocal;
     constexpr bool SYM = GEO == kSym64;
@@ -633,9 +662,9 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // them as 64-bit lane masks and spends a v_cndmask / v_cmp pair on each negation)
     int epi_word = epi_flags;
     if (!kTrace && SYM && EPI && !is_rollout(MODE)) asm volatile("" : "+s"(epi_word));
-#define has_acc (EPI && (epi_word & 1) != 0)
-#define auto_reset (EPI && (epi_word & 2) != 0)
-    const bool rand_act = MODE == kRolloutRand ? true : (MODE == kRolloutPool || CTRL) ? false : (EPI && is_rollout(MODE) && (epi_flags & 4) != 0);
+#define has_acc (EPI && (epi_word & kFlagRecords) != 0)
+#define auto_reset (EPI && (epi_word & kFlagAutoReset) != 0)
+    const bool rand_act = MODE == kRolloutRand ? true : (MODE == kRolloutPool || CTRL) ? false : (EPI && is_rollout(MODE) && (epi_flags & kFlagRandAct) != 0);
     // the 32 hot bytes of the env's record live in registers for the whole launch, split over two lanes so that one
     // load and one store instruction move them: agent 0 holds (ep_return, ep_true_return) as two doubles, agent 1
     // holds (ep_collisions, ep_len, episodes, reserved) as four ints
@@ -742,19 +771,23 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     //      its own copy of the (Delta_j, l_j) table so that no cross-wave barrier is ever needed
     // positions of one env slot: S0[m] = dup[m] and S1[m + 1] = dup[m], dup = x_0..x_{N-1}, x_0..x_{N-1}
     // (two copies one element apart, so every lane has a copy in which its partner window is 16-byte aligned)
-    const int stride = 2 * N + kPad;                         // float2 per copy (even)
+    const int stride = pos_stride(N);                        // float2 per copy (even)
     const int nconst = WL ? nwaves : 1;
     float2 *spos = reinterpret_cast<float2 *>(smem);                                       // [epb][2][stride]
     // (workgroup-per-env: always the bucket filter, so only the N positions themselves -- read by agent index -- plus the
     // slack the crowded path's 16-partner reads may run into: 2.2 instead of 8.5 KB at N = 256)
-    float2 *sconst_all = spos + (BLOCKGEO ? (size_t)block_pos_entries(N) : (size_t)a.epb * 2 * stride);   // [nconst][N + (N&1)]
-    int *sred = reinterpret_cast<int *>(sconst_all + (size_t)nconst * (N + (N & 1)));      // [epb][2]
+    float2 *sconst_all = spos + (BLOCKGEO ? (size_t)block_pos_entries(N) : packed_pos_entries(a.epb, N));   // [nconst][N + (N&1)]
+    int *sred = reinterpret_cast<int *>(sconst_all + (size_t)nconst * const_entries(N));   // [epb][2]
     const int epb_c = BLOCKGEO ? 1 : a.epb;                  // envs per workgroup
-    const int nred = 2 * epb_c + ((2 * epb_c) & 3 ? 4 - ((2 * epb_c) & 3) : 0);
+    const int nred = 2 * epb_c + ((2 * epb_c) & 3 ? 4 - ((2 * epb_c) & 3) : 0);   // = red_words(epb_c), literal like the stride below
     unsigned *sstage = reinterpret_cast<unsigned *>(sred + nred);
     // c = 2: [64][kZRow] z words + [64][kNRow] Ni words per wave; FAR with staged c = 5 rows: 5 (K+1) z words per lane
     const int zrow_w = (FAR && a.stage5) ? 5 * (K + 1) : kZRow;
     unsigned *stage_z = sstage + (size_t)wave * kWave * (zrow_w + kNRow);
+    // (the verdict words and the staging area keep their literal sizes here -- written through red_words / stage_words some
+    // kernels are re-scheduled or change their instruction counts -- and the compile-time one is tied to the function the
+    // host sizes it with)
+    static_assert(kWave * (kZRow + kNRow) == stage_words(2, K) && kWave * (5 * (K + 1) + kNRow) == stage_words(5, K), "staging words per wave");
     // kSym64 (uniform constants, one env per wave) has its own, smaller carve-up: one block per wave of
     // [64 positions | staging area | x cells | y cells] = sym_wave_bytes(K) (3840 B at k = 2: with the episode layer's
     // tail 9.5 KiB per two-wave workgroup, 16 workgroups = 8 waves per SIMD per CU).  No (Delta_j, l_j) table, no per-env
@@ -763,9 +796,9 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // not written before the epilogue, and the rows' neighbour positions are read from the first 64 entries only.
     const int sym_zc = (FAR && a.stage5) ? 5 : 2;            // (FAR: the reference's default construction at N = 64, round 4)
     char *const sym_block = smem + (size_t)wave * sym_wave_bytes(K, sym_zc);
-    if (SYM) stage_z = reinterpret_cast<unsigned *>(sym_block + 64 * 8);
+    if (SYM) stage_z = reinterpret_cast<unsigned *>(sym_block + sym_stage_offset());
     unsigned *stage_n = stage_z + kWave * zrow_w;
-    float2 *sconst = sconst_all + (WL ? (size_t)wave * (N + (N & 1)) : 0);
+    float2 *sconst = sconst_all + (WL ? (size_t)wave * const_entries(N) : 0);
     // bucket filter tables.  kSym64: per wave, cell -> lane mask, entries -1..64 of (x mask, y mask).
     // Other geometries: per env slot, [axis][W words of 64 agents][64 cells].
     unsigned long long *sbt_all = reinterpret_cast<unsigned long long *>(sstage + (size_t)nwaves * kWave * (zrow_w + kNRow));
@@ -774,8 +807,8 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // table and reads cells c-1, c, c+1 without a guard row or an edge test.  (Round 2 kept (x, y) pairs at a 16-byte
     // stride: cells c and c + 8 then shared their banks -- 2-3 way conflicts on the ds_or / ds_read of every launch,
     // 40 % of the kernel's LDS cycles; at 8 bytes per cell the 23 cells of C3 are conflict-free.)
-    unsigned long long *sbx = SYM ? reinterpret_cast<unsigned long long *>(sym_block + 64 * 8 + 64 * (sym_zc + 1) * (K + 1) * 4)
-                                  : sbt_all + (size_t)wave * (2 * kCells);
+    unsigned long long *sbx = SYM ? reinterpret_cast<unsigned long long *>(sym_block + sym_cells_offset(K, sym_zc))
+                                  : sbt_all + (size_t)wave * table_words(kPacked, false, 1);
     unsigned long long *sby = sbx + kCells;
     const int W = BU ? 4 : BLOCKGEO ? nwaves : 1;
     const bool use_bucket = !SYM && (BLOCKGEO || a.bucket != 0);                           // launch-uniform
@@ -784,7 +817,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // zeroed at every rebuild: 128 cells measured +0.4 ... +0.9 % there, profiles/r5_abtest_block_cells.log)
     // (N > 256 keeps 64 as well: 16 words of 128 cells on two axes are 32 KiB of an LDS tile that N = 1024 with k = 8 fills)
     constexpr int NCELL = bucket_cells(GEO, is_rollout(MODE));
-    unsigned long long *sbt = sbt_all + (size_t)slot * (2 * NCELL) * W;                    // this lane's env
+    unsigned long long *sbt = sbt_all + (size_t)slot * table_words(GEO, is_rollout(MODE), W);                 // this lane's env
     // tail (episode bookkeeping): per-wave partial reward sums [nwaves][2], then the sampling tables of the in-kernel
     // reset, [epb][samp_tbl] x (node, owner)
     float *spart = reinterpret_cast<float *>(smem + a.lds_tail);
@@ -820,7 +853,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
     // two, and no zeroing loop, between the loads' return and the first mask read.
     constexpr bool EARLY_TABLES = BLOCKGEO && !is_rollout(MODE);
     if (EARLY_TABLES) {
-        for (int o = tid; o < 2 * NCELL * W; o += blockDim.x) sbt_all[o] = 0ull;
+        for (int o = tid; o < table_words(GEO, is_rollout(MODE), W); o += blockDim.x) sbt_all[o] = 0ull;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
 
@@ -927,7 +960,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
         // exactly: node ids bit-identical to oracle_reset), then the hot path below observes the new state straight from
         // registers / LDS -- no second launch, no round trip of the state through HBM (round 6: C3 12.5 us as two launches)
         const int nt = a.samp_tbl;
-        int2 *tbl = reinterpret_cast<int2 *>(reinterpret_cast<float *>(smem + a.lds_tail) + 2 * ((nwaves + 1) & ~1)) + (size_t)slot * nt;
+        int2 *tbl = reinterpret_cast<int2 *>(reinterpret_cast<float *>(smem + a.lds_tail) + tail_part_floats(nwaves)) + (size_t)slot * nt;
         const bool rs = valid;
         int node = -1;
         uint32_t round = 0;
@@ -1032,7 +1065,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
             // ---- closed loop: the controller's action on the positions the env holds BEFORE this step.  They sit in LDS by
             // agent index: the previous step wrote them (its integrated positions, or the new episode's where the in-kernel
             // reset ran) and ended on a barrier; the first step of a launch writes them here.
-            const bool gradient = (epi_flags & 8) != 0;       // launch-uniform
+            const bool gradient = (epi_flags & kFlagGradient) != 0;       // launch-uniform
             if (!gradient) {
                 u0 = control_proportional(xi, yi, xFx, xFy, xLx, xLy, a.u_max);
             } else {
@@ -1097,7 +1130,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
         int bcx = 0, bcy = 0;
         if (use_bucket) {
             if (WL) { for (int o = lane; o < a.P * 2 * kCells; o += kWave) sbt_all[(size_t)wave * a.P * 2 * kCells + o] = 0ull; }
-            else if (!EARLY_TABLES) { for (int o = tid; o < 2 * NCELL * W; o += blockDim.x) sbt_all[o] = 0ull; }
+            else if (!EARLY_TABLES) { for (int o = tid; o < table_words(GEO, is_rollout(MODE), W); o += blockDim.x) sbt_all[o] = 0ull; }
             bcx = (int)__builtin_floorf(xi * inv_cell) & (NCELL - 1);
             bcy = (int)__builtin_floorf(yi * inv_cell) & (NCELL - 1);
         }
@@ -1955,7 +1988,7 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
                 // (workgroup-per-env geometries, single-step launches: the table shares the cell tables' region -- dead since pass 1;
                 // sized on the host as max(cell tables, sampling table).  The fused rollouts keep their own: sharing measured +2 % there)
                 int2 *tbl = (BLOCKGEO && !is_rollout(MODE)) ? reinterpret_cast<int2 *>(sbt_all)
-                                     : reinterpret_cast<int2 *>(reinterpret_cast<float *>(smem + ca.lds_tail) + 2 * ((nwaves + 1) & ~1)) + (size_t)slot * nt;
+                                     : reinterpret_cast<int2 *>(reinterpret_cast<float *>(smem + ca.lds_tail) + tail_part_floats(nwaves)) + (size_t)slot * nt;
                 const uint32_t gid_c = ca.gid_base + (uint32_t)env;
                 int node = -1;
                 uint32_t round = 0;
@@ -2139,10 +2172,12 @@ __global__ void __launch_bounds__(GeoTraits<GEO>::kMaxThreads, GeoTraits<GEO>::m
 }
 
 
+// What plan_step_launch (dronesim.hip) decides about a launch next to the fields of KArgs
 struct Geometry {
     int P, epb, threads, blocks, geo;
     size_t lds;
     int ctrl;                       // closed-loop rollout: 1 + DRONESIM_CONTROL_* (0: the actions come from a pool / the Philox stream)
+    int far, epi;                   // the FAR instances; the EPI instances (DroneEpisodeCtl in use: records, auto-reset or in-kernel actions)
 };
 
 // more than 48 KiB of dynamic LDS (envs of several hundred agents) has to be opted into once per kernel
@@ -2171,9 +2206,9 @@ hipError_t launch_one(const KArgs &a, const Geometry &g, hipStream_t s)
     }
     hipLaunchKernelGGL((drone_kernel<K, FAR, MODE, GEO, EPI>), dim3(g.blocks), dim3(g.threads), g.lds, s,
                        a.pos, MODE == kObserve ? static_cast<const float *>(a.vel) : a.act,
-                       (int)((unsigned)a.P | ((unsigned)g.blocks & ~255u)),   // P <= 64; whole groups of 256 workgroups (XCD map)
-                       (EPI || MODE == kRolloutCtrl) ? (a.epb | ((a.acc != nullptr ? 1 : 0) | (a.auto_reset ? 2 : 0) | (a.rand_act ? 4 : 0) |
-                                                                  (g.ctrl == 1 + DRONESIM_CONTROL_GRADIENT ? 8 : 0)) << 16) : a.epb,
+                       (int)((unsigned)a.P | ((unsigned)g.blocks & kXcdBlocks)),   // P <= 64; whole groups of 256 workgroups (XCD map)
+                       (EPI || MODE == kRolloutCtrl) ? (int)(a.epb | ((a.acc != nullptr ? kFlagRecords : 0u) | (a.auto_reset ? kFlagAutoReset : 0u) | (a.rand_act ? kFlagRandAct : 0u) |
+                                                                      (g.ctrl == 1 + DRONESIM_CONTROL_GRADIENT ? kFlagGradient : 0u)) << kFlagShift) : a.epb,
                        a.E, a.N, a);
     return hipSuccess;
 }
@@ -2181,41 +2216,30 @@ hipError_t launch_one(const KArgs &a, const Geometry &g, hipStream_t s)
 template <int K, bool FAR, int GEO>
 hipError_t launch_mode(int mode, const KArgs &a, const Geometry &g, hipStream_t s)
 {
-    bool epi = a.acc != nullptr || a.auto_reset != 0 || a.rand_act != 0;   // DroneEpisodeCtl in use
-    switch (mode) {
-    case kStep: return epi ? launch_one<K, FAR, kStep, GEO, true>(a, g, s) : launch_one<K, FAR, kStep, GEO, false>(a, g, s);
-    case kObserve: return launch_one<K, FAR, kObserve, GEO, false>(a, g, s);
-    default:
-        if (g.ctrl != 0)               // closed-loop rollout: the controller is the action source, with or without the episode layer
-            return epi ? launch_one<K, FAR, kRolloutCtrl, GEO, true>(a, g, s) : launch_one<K, FAR, kRolloutCtrl, GEO, false>(a, g, s);
-        if (!epi) return launch_one<K, FAR, kRollout, GEO, false>(a, g, s);
-        if constexpr (GEO == kSym64)   // the action source at compile time (see Mode)
-            return a.rand_act ? launch_one<K, FAR, kRolloutRand, GEO, true>(a, g, s) : launch_one<K, FAR, kRolloutPool, GEO, true>(a, g, s);
-        else
-            return launch_one<K, FAR, kRollout, GEO, true>(a, g, s);
+    constexpr bool U256 = GEO == kBlockU256;   // fused rollouts only (plan_step_launch picks it for kRollout): no step / observe instances
+    if constexpr (!U256) {
+        if (mode == kStep) return g.epi ? launch_one<K, FAR, kStep, GEO, true>(a, g, s) : launch_one<K, FAR, kStep, GEO, false>(a, g, s);
+        if (mode == kObserve) return launch_one<K, FAR, kObserve, GEO, false>(a, g, s);
     }
+    if (g.ctrl != 0)                       // closed-loop rollout: the controller is the action source, with or without the episode layer
+        return g.epi ? launch_one<K, FAR, kRolloutCtrl, GEO, true>(a, g, s) : launch_one<K, FAR, kRolloutCtrl, GEO, false>(a, g, s);
+    if (!g.epi) return launch_one<K, FAR, kRollout, GEO, false>(a, g, s);
+    if constexpr (GEO == kSym64 || U256)   // the action source at compile time (see Mode)
+        return a.rand_act ? launch_one<K, FAR, kRolloutRand, GEO, true>(a, g, s) : launch_one<K, FAR, kRolloutPool, GEO, true>(a, g, s);
+    else
+        return launch_one<K, FAR, kRollout, GEO, true>(a, g, s);
 }
 
 template <int K>
-hipError_t launch_k(int mode, bool far, const KArgs &a, const Geometry &g, hipStream_t s)
+hipError_t launch_k(int mode, const KArgs &a, const Geometry &g, hipStream_t s)
 {
     switch (g.geo) {
-    case kSym64: return far ? launch_mode<K, true, kSym64>(mode, a, g, s) : launch_mode<K, false, kSym64>(mode, a, g, s);
-    case kPacked:
-        return far ? launch_mode<K, true, kPacked>(mode, a, g, s) : launch_mode<K, false, kPacked>(mode, a, g, s);
-    case kBlock256:
-        return far ? launch_mode<K, true, kBlock256>(mode, a, g, s) : launch_mode<K, false, kBlock256>(mode, a, g, s);
-    case kBlockU256: {                              // rollouts only (launch() picks it for mode == kRollout)
-        const bool epi = a.acc != nullptr || a.auto_reset != 0 || a.rand_act != 0;
-        if (g.ctrl != 0)
-            return epi ? launch_one<K, false, kRolloutCtrl, kBlockU256, true>(a, g, s) : launch_one<K, false, kRolloutCtrl, kBlockU256, false>(a, g, s);
-        if (epi) return a.rand_act ? launch_one<K, false, kRolloutRand, kBlockU256, true>(a, g, s) : launch_one<K, false, kRolloutPool, kBlockU256, true>(a, g, s);
-        return launch_one<K, false, kRollout, kBlockU256, false>(a, g, s);
-    }
-    default:
-        return far ? launch_mode<K, true, kBlock1024>(mode, a, g, s) : launch_mode<K, false, kBlock1024>(mode, a, g, s);
+    case kSym64: return g.far ? launch_mode<K, true, kSym64>(mode, a, g, s) : launch_mode<K, false, kSym64>(mode, a, g, s);
+    case kPacked: return g.far ? launch_mode<K, true, kPacked>(mode, a, g, s) : launch_mode<K, false, kPacked>(mode, a, g, s);
+    case kBlock256: return g.far ? launch_mode<K, true, kBlock256>(mode, a, g, s) : launch_mode<K, false, kBlock256>(mode, a, g, s);
+    case kBlockU256: return launch_mode<K, false, kBlockU256>(mode, a, g, s);   // (never FAR)
+    default: return g.far ? launch_mode<K, true, kBlock1024>(mode, a, g, s) : launch_mode<K, false, kBlock1024>(mode, a, g, s);
     }
 }
-
 
 }   // namespace

@@ -6,8 +6,8 @@
 #define DRONESIM_LAUNCH_K2(n) dronesim_launch_k##n
 #define DRONESIM_LAUNCH_K(n) DRONESIM_LAUNCH_K2(n)
 extern "C" __attribute__((visibility("hidden")))
-int DRONESIM_LAUNCH_K(DRONESIM_K)(int mode, int far, const void *a, const void *g, void *s)
+int DRONESIM_LAUNCH_K(DRONESIM_K)(int mode, const void *a, const void *g, void *s)
 {
-    return (int)launch_k<DRONESIM_K>(mode, far != 0, *static_cast<const KArgs *>(a), *static_cast<const Geometry *>(g),
+    return (int)launch_k<DRONESIM_K>(mode, *static_cast<const KArgs *>(a), *static_cast<const Geometry *>(g),
                                      static_cast<hipStream_t>(s));
 }

@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(256) stats_kernel(const float *__restrict__ re
     const size_t n = (size_t)E * N;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     // 16 bytes per lane when the arrays allow it (E * N a multiple of 4 and 16-byte aligned bases), else 4
-    const bool wide = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(true_reward)) & 15u) == 0;
+    const bool wide = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(reward) | reinterpret_cast<uintptr_t>(true_reward)) & 15u) == 0;
     if (wide) {
         const float4 *r4 = reinterpret_cast<const float4 *>(reward), *t4 = reinterpret_cast<const float4 *>(true_reward);
         for (size_t i = (size_t)blockIdx.x * 256 + tid; i < n / 4; i += (size_t)gridDim.x * 256) {
@@ -305,10 +305,9 @@ __attribute__((visibility("hidden"))) int dronesim_fail(int code, const char *ms
 
 namespace {
 
-
-Geometry geometry(int N, int E)
+constexpr Geometry geometry(int N, int E)
 {
-    Geometry g;
+    Geometry g{};
     if (N <= kWave) {                  // 4 (or 2) independent waves per workgroup, floor(64/N) envs per wave
         g.P = kWave / N;
         // one env per wave (N > 32): two waves per workgroup -- measured against 4 (the round-1 choice), 8 and 16 at C3:
@@ -318,59 +317,78 @@ Geometry geometry(int N, int E)
         g.threads = wpb * kWave;
         g.epb = wpb * g.P;
         g.geo = kPacked;
-    } else {
-        g.P = 0;
+    } else {                           // (P = 0)
         g.threads = ((N + kWave - 1) / kWave) * kWave;
         g.epb = 1;
         g.geo = g.threads <= 256 ? kBlock256 : kBlock1024;
     }
     g.blocks = (E + g.epb - 1) / g.epb;
-    g.lds = 0;
-    g.ctrl = 0;
     return g;
 }
 
-// dynamic LDS of drone_kernel (must mirror the carve-up in the kernel)
-// zc: columns of a staged z row (2, or 5 when those fit); samp: bytes of the in-kernel reset's sampling table when it shares the
-// cell tables' region (workgroup-per-env geometries, see drone_lds_tail_bytes)
-size_t drone_lds_bytes(const Geometry &g, int N, int k, int zc = 2, bool rollout = false, size_t samp = 0)
+constexpr size_t kLdsTile = 160 * 1024;                                   // LDS of a CU: the most a workgroup can ask for
+constexpr size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// Dynamic LDS of drone_kernel: the sum of the region functions the kernel carves with (drone_kernel.hpp) -- the total, and the
+// offsets the kernel is told (KArgs.lds_vel, lds_tail) with the choice that moves them (KArgs.stage5).
+//   [positions][(Delta_j, l_j) tables][verdict words][staging area][cell tables]   or kSym64's block per wave
+//   [velocities]   c = 5 with staged rows (stage5): the rows of the k nearest carry them
+//   [tail]         episode layer (`epi_regions`): per-wave partial sums, then the in-kernel reset's sampling tables -- unless the
+//                  tables share the cell tables' region (`shared_table`: workgroup-per-env geometries, single-step launches, round 5;
+//                  a reset runs behind the step's last use of the cell tables: 25.8 -> 21.7 KiB per workgroup at N = 256, 7 instead
+//                  of 6 workgroups per CU, 256 x 4096 envs 20.0 -> 19.5 us; the fused rollouts keep the table in the tail, sharing
+//                  measured +2 % there: profiles/r5_abtest_sampling_table_alias.log)
+struct StepLds { size_t total; int lds_vel, lds_tail, stage5; };
+
+constexpr StepLds step_lds(int geo, int P, int epb, int threads, int N, int k, int c, bool rollout, bool epi_regions, bool tail_table,
+                           bool shared_table)
 {
-    const size_t nwaves = (size_t)g.threads / kWave;
-    const size_t nconst = g.P > 0 ? nwaves : 1;
-    size_t b = sizeof(float2) * ((g.P > 0 ? (size_t)g.epb * 2 * (2 * (size_t)N + kPad) : (size_t)block_pos_entries(N)) +
-                                 nconst * ((size_t)N + (N & 1)));
-    size_t red = 2 * (size_t)g.epb;
-    red += (red & 3) ? 4 - (red & 3) : 0;
-    b += sizeof(int) * red;
-    b += sizeof(unsigned) * nwaves * kWave * (size_t)(zc + 1) * (size_t)(k + 1);   // z (zc words) + Ni (1 word) per slot and lane
-    // bucket filter tables: [2 axes][64 cells][words] per env slot, or kSym64's per-wave rows (whichever is larger)
-    const size_t slots = g.P > 0 ? (size_t)g.epb : 1, words = g.P > 0 ? 1 : nwaves;
-    size_t generic = (g.P > 0 && N < kBucketMinN) ? 0 : sizeof(unsigned long long) * slots * 2 * (size_t)bucket_cells(g.geo, rollout) * words;
-    if (g.P == 0 && samp > generic) generic = samp;
-    const size_t sym = g.P > 0 ? sizeof(ulonglong2) * nwaves * kBucketRows : 0;
-    b += generic > sym ? generic : sym;
-    return b;
+    const size_t nwaves = (size_t)threads / kWave;
+    const size_t samp = sizeof(int2) * (size_t)epb * samp_table_entries(N);
+    const size_t tail = epi_regions ? sizeof(float) * tail_part_floats((int)nwaves) + (tail_table ? samp : 0) : 0;
+    // bucket filter tables: per env slot, or the floor of 66 x 16 bytes per wave the packed geometries keep (whichever is larger)
+    size_t tables = (P > 0 && N < kBucketMinN) ? 0 : sizeof(unsigned long long) * (P > 0 ? (size_t)epb : 1) * table_words(geo, rollout, P > 0 ? 1 : (int)nwaves);
+    if (shared_table && samp > tables) tables = samp;
+    if (P > 0 && sizeof(ulonglong2) * nwaves * kBucketRows > tables) tables = sizeof(ulonglong2) * nwaves * kBucketRows;
+    const size_t fixed = sizeof(float2) * ((P > 0 ? packed_pos_entries(epb, N) : (size_t)block_pos_entries(N)) + (P > 0 ? nwaves : 1) * const_entries(N)) +
+                         sizeof(int) * red_words(epb) + tables;
+    // zc: columns of a staged z row (2, or 5 when those fit)
+    const auto body = [=](int zc) { return geo == kSym64 ? nwaves * sym_wave_bytes(k, zc) : fixed + sizeof(unsigned) * nwaves * stage_words(zc, k); };
+    // c = 5 rows: staged through LDS like the c = 2 ones, and the agents' velocities kept in LDS for the rows of the k nearest,
+    // when the env's tile still fits (it does up to N = 1024 at k <= 3, and always in kSym64's; the rows leave as 4-byte stores
+    // at a 60-byte stride otherwise, as they all did through round 2)
+    // (the velocity region is rounded up to 16 bytes: the episode layer reads its per-wave partial sums behind it as
+    // ds_read_b128 -- 8 N bytes with odd N left `lds_tail` 8-byte aligned)
+    const size_t vel = round16(sizeof(float2) * (size_t)epb * (size_t)N);
+    StepLds r{};
+    r.stage5 = (c == 5 && (geo == kSym64 || body(5) + vel + tail <= kLdsTile)) ? 1 : 0;
+    size_t b = body(r.stage5 ? 5 : 2);
+    if (r.stage5) { r.lds_vel = (int)b; b += vel; }
+    r.lds_tail = (int)round16(b);                          // the tail's float4 reads (per-wave partial sums) need 16 bytes
+    r.total = (size_t)r.lds_tail + tail;
+    return r;
 }
 
-// entries of the in-kernel reset's sampling table per env slot: the power of two >= 2 N
-int samp_table_entries(int N)
+// The layout's promises, over every launchable (N, k): each region a whole number of 16-byte units (the carve-up relies on it
+// for its 16-byte LDS accesses), and kSym64's block the sum of its parts.
+constexpr bool step_lds_regions_ok()
 {
-    int nt = 4;
-    while (nt < 2 * N) nt <<= 1;
-    return nt;
+    bool ok = sym_stage_offset() % 16 == 0;
+    for (int k = 1; k <= DRONESIM_MAX_K; ++k)              // (no region depends on both N and k: one loop each)
+        for (int zc = 2; zc <= 5; zc += 3)
+            ok = ok && sizeof(unsigned) * stage_words(zc, k) % 16 == 0 && sym_cells_offset(k, zc) % 16 == 0 && sym_wave_bytes(k, zc) % 16 == 0 &&
+                 sym_wave_bytes(k, zc) == sym_stage_offset() + 4 * stage_words(zc, k) + 2 * kCells * 8;
+    for (int N = 2; N <= DRONESIM_MAX_AGENTS; ++N) {
+        const Geometry g = geometry(N, 1);
+        const int nwaves = g.threads / kWave, W = g.P > 0 ? 1 : nwaves;
+        const size_t regions[] = {sizeof(float2) * pos_stride(N), sizeof(float2) * block_pos_entries(N), sizeof(float2) * const_entries(N),
+                                  sizeof(int) * red_words(g.epb), sizeof(float) * tail_part_floats(nwaves), sizeof(int2) * samp_table_entries(N),
+                                  sizeof(unsigned long long) * table_words(g.geo, false, W), sizeof(unsigned long long) * table_words(g.geo, true, W)};
+        for (const size_t r : regions) ok = ok && r % 16 == 0;
+    }
+    return ok;
 }
-
-// bookkeeping regions behind the bucket tables: [nwaves rounded to even][2] floats + [epb][table] int2
-// Workgroup-per-env geometries, single-step launches (round 5): the sampling table of the in-kernel reset lives in the CELL
-// TABLES' region -- a reset runs behind the step's last use of the tables -- so the tail holds the partial sums only: 25.8 ->
-// 21.7 KiB per workgroup at N = 256 with the episode layer, 7 instead of 6 workgroups per CU (256 x 4096 envs: 20.0 -> 19.5 us).
-// The fused rollouts keep the table in the tail (sharing measured +2 % there: profiles/r5_abtest_sampling_table_alias.log).
-size_t drone_samp_bytes(const Geometry &g, int N) { return sizeof(int2) * (size_t)g.epb * samp_table_entries(N); }
-size_t drone_lds_tail_bytes(const Geometry &g, int N, bool single_step)
-{
-    const size_t nwaves = (size_t)g.threads / kWave;
-    return sizeof(float) * 2 * ((nwaves + 1) & ~(size_t)1) + ((g.P == 0 && single_step) ? 0 : drone_samp_bytes(g, N));
-}
+static_assert(step_lds_regions_ok(), "an LDS region of drone_kernel is not a multiple of 16 bytes, or sym_wave_bytes is not the sum of its parts");
 
 int check_params(const DroneParams *p, int E)
 {
@@ -388,22 +406,30 @@ int check_params(const DroneParams *p, int E)
 
 }   // namespace
 
-extern "C" {    // drone_kernel_k.hip, one translation unit per k
-int dronesim_launch_k1(int, int, const void *, const void *, void *);
-int dronesim_launch_k2(int, int, const void *, const void *, void *);
-int dronesim_launch_k3(int, int, const void *, const void *, void *);
-int dronesim_launch_k4(int, int, const void *, const void *, void *);
-int dronesim_launch_k5(int, int, const void *, const void *, void *);
-int dronesim_launch_k6(int, int, const void *, const void *, void *);
-int dronesim_launch_k7(int, int, const void *, const void *, void *);
-int dronesim_launch_k8(int, int, const void *, const void *, void *);
-}
+// drone_kernel_k.hip, one translation unit per k: dronesim_launch_k<k>(mode, KArgs, Geometry, stream)
+#define DRONESIM_EACH_K(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#define DRONESIM_DECLARE_K(k) extern "C" int dronesim_launch_k##k(int, const void *, const void *, void *);
+DRONESIM_EACH_K(DRONESIM_DECLARE_K)
 
 namespace {
 
-int reset_impl(const DroneParams *p, int div_x, int div_y, float pitch, uint64_t seed, int64_t env_base,
-               const uint8_t *mask, float *pos, float *vel, int32_t *t, int32_t *episode, int32_t *node_out,
-               double *acc, int E, void *stream);
+// the lattice a reset draws from: div_x x div_y nodes, at least N of them, fewer than 2^32 (`bad_size`: the caller's text for div < 1)
+int check_lattice(int div_x, int div_y, int N, const char *bad_size, uint32_t *M_out)
+{
+    if (div_x < 1 || div_y < 1) return fail(DRONESIM_EINVAL, bad_size);
+    const uint64_t M = (uint64_t)div_x * (uint64_t)div_y;
+    if (M < (uint64_t)N) return fail(DRONESIM_EINVAL, "lattice has fewer nodes than agents (random.sample would raise)");
+    if (M > 0xFFFFFFFFull) return fail(DRONESIM_EUNSUPPORTED, "lattice larger than 2^32 nodes");
+    *M_out = (uint32_t)M;
+    return DRONESIM_OK;
+}
+
+// the Philox stream of an env's resets and in-kernel actions (DroneEpisodeCtl -> kernel arguments)
+void set_stream(const DroneEpisodeCtl *ctl, KArgs &a)
+{
+    a.episode = ctl->episode; a.gid_base = (uint32_t)ctl->env_base;
+    a.key0 = (uint32_t)ctl->seed; a.key1 = (uint32_t)(ctl->seed >> 32);
+}
 
 // DroneEpisodeCtl -> kernel arguments (include/dronesim.h)
 int apply_ctl(const DroneParams *p, const DroneEpisodeCtl *ctl, bool rand_act, KArgs &a)
@@ -414,99 +440,111 @@ int apply_ctl(const DroneParams *p, const DroneEpisodeCtl *ctl, bool rand_act, K
     a.auto_reset = ctl->auto_reset != 0 ? 1 : 0;
     if (a.auto_reset || rand_act) {
         if (!ctl->episode) return fail(DRONESIM_EINVAL, "DroneEpisodeCtl.episode is NULL");
-        a.episode = ctl->episode;
-        a.key0 = (uint32_t)ctl->seed;
-        a.key1 = (uint32_t)(ctl->seed >> 32);
-        a.gid_base = (uint32_t)ctl->env_base;
+        set_stream(ctl, a);
     }
     if (a.auto_reset) {
-        if (ctl->div_x < 1 || ctl->div_y < 1) return fail(DRONESIM_EINVAL, "DroneEpisodeCtl: bad lattice size");
-        const uint64_t M = (uint64_t)ctl->div_x * (uint64_t)ctl->div_y;
-        if (M < (uint64_t)p->N) return fail(DRONESIM_EINVAL, "lattice has fewer nodes than agents (random.sample would raise)");
-        if (M > 0xFFFFFFFFull) return fail(DRONESIM_EUNSUPPORTED, "lattice larger than 2^32 nodes");
-        a.lat_M = (uint32_t)M; a.div_y = ctl->div_y; a.pitch = ctl->pitch;
+        const int rc = check_lattice(ctl->div_x, ctl->div_y, p->N, "DroneEpisodeCtl: bad lattice size", &a.lat_M);
+        if (rc) return rc;
+        a.div_y = ctl->div_y; a.pitch = ctl->pitch;
         a.z_final = ctl->z_final; a.nbr_final = ctl->nbr_final; a.pos_final = ctl->pos_final;
     }
     return DRONESIM_OK;
 }
 
-// ctrl: closed-loop rollout (mode kRollout), 1 + DRONESIM_CONTROL_* -- the kRolloutCtrl instances
-int launch(int mode, const DroneParams *p, KArgs &a, int E, void *stream, int ctrl = 0)
+// state and output buffers of a launch -> kernel arguments (observe: `vel` is read, and t / act / done stay NULL)
+KArgs step_args(float *pos, float *vel, int32_t *t, const float *act, float *reward, float *true_reward, float *z, int32_t *nbr_idx,
+                int32_t *n_coll, uint8_t *done, int T)
 {
+    KArgs a{};
+    a.pos = pos; a.vel = vel; a.t = t; a.act = act; a.reward = reward; a.true_reward = true_reward;
+    a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll; a.done = done; a.T = T;
+    return a;
+}
+
+int reset_impl(const DroneParams *p, int div_x, int div_y, float pitch, uint64_t seed, int64_t env_base,
+               const uint8_t *mask, float *pos, float *vel, int32_t *t, int32_t *episode, int32_t *node_out,
+               double *acc, int E, void *stream)
+{
+    if (!p) return fail(DRONESIM_EINVAL, "params is NULL");
+    if (p->N < 1 || p->N > DRONESIM_MAX_AGENTS) return fail(DRONESIM_EUNSUPPORTED, "N must be in 1..1024");
+    if (E < 0 || div_x < 1 || div_y < 1) return fail(DRONESIM_EINVAL, "bad E / lattice size");
+    if (!pos || !vel || !t || !episode) return fail(DRONESIM_EINVAL, "dronesim_reset: required buffer is NULL");
+    RArgs a{};
+    const int rc = check_lattice(div_x, div_y, p->N, "bad E / lattice size", &a.M);   // (its size test: made above, ahead of the buffers')
+    if (rc) return rc;
     if (E == 0) return DRONESIM_OK;
-    Geometry g = geometry(p->N, E);
+    const Geometry g = geometry(p->N, E);
+    a.N = p->N; a.E = E; a.P = g.P; a.epb = g.epb; a.div_y = div_y;
+    a.key0 = (uint32_t)seed;
+    a.key1 = (uint32_t)(seed >> 32);
+    a.env_base = env_base; a.pitch = pitch; a.mask = mask;
+    a.pos = pos; a.vel = vel; a.t = t; a.episode = episode; a.node_out = node_out; a.acc = acc;
+    a.nt = samp_table_entries(p->N);
+    a.shift = 32 - __builtin_ctz((unsigned)a.nt);
+    const size_t lds = sizeof(int2) * (size_t)g.epb * a.nt;
+    hipLaunchKernelGGL(reset_kernel, dim3(g.blocks), dim3(g.threads), lds, static_cast<hipStream_t>(stream), a);
+    return dronesim_launched();
+}
+
+// the reach of an agent's partners, d_hat + 2 l at their largest; the fused rollouts' candidate list keeps kSkin of it as slack
+float reach_max(const DroneParams *p) { return p->d_hat_max + 2.0f * p->radius_max; }
+float skin(const DroneParams *p) { return kSkin * reach_max(p); }
+
+// The plan of a step / observe / rollout launch, without a HIP call: which instance runs (g.geo, g.far, g.epi, g.ctrl: closed-loop
+// rollout of mode kRollout, 1 + DRONESIM_CONTROL_*), its grid and LDS, and every kernel argument that follows from the
+// parameters -- or the refusal.  `a` arrives with its buffers and the episode layer's fields (apply_ctl) set.
+int plan_step_launch(int mode, const DroneParams *p, KArgs &a, int E, int ctrl, Geometry &g)
+{
+    const int N = p->N;
+    const bool rollout = mode == kRollout;
+    g = geometry(N, E);
     g.ctrl = ctrl;
     // far agents matter when a z row carries (v, l) of a tie-ordered agent (c = 5) or
     // when a clipped distance can pass a Delta mask (Delta_j >= dhat_i possible)
-    const bool far = (p->c == 5) || !(p->delta_max < p->d_hat_min);
+    a.far_inm = !(p->delta_max < p->d_hat_min) ? 1 : 0;
+    g.far = (p->c == 5 || a.far_inm) ? 1 : 0;
+    g.epi = (a.acc != nullptr || a.auto_reset != 0 || a.rand_act != 0) ? 1 : 0;   // DroneEpisodeCtl in use
     a.uniform = (p->d_hat_min == p->d_hat_max && p->delta_min == p->delta_max && p->radius_min == p->radius_max) ? 1 : 0;
+    const bool wide_rows = ((reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.nbr_idx)) & 15u) == 0;
     // one env per wave, uniform (d_hat, Delta, radius) only; its fixed-shape copy-out of c = 2 rows stores 16 bytes per lane.
     // Round 4: also the FAR variant -- the reference's DEFAULT construction (deltas=None, simplify_zstate=False) at N = 64
-    if (p->N == 64 && a.uniform && ((reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.nbr_idx)) & 15u) == 0)
-        g.geo = kSym64;
+    if (N == 64 && a.uniform && wide_rows) g.geo = kSym64;
     // N = 256 with uniform constants (BASELINE configs[4]), fused rollouts: the workgroup-per-env kernel with four full waves known at compile time
-    if (mode == kRollout && g.geo == kBlock256 && p->N == 256 && !far && a.uniform &&
-        ((reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.nbr_idx)) & 15u) == 0)
-        g.geo = kBlockU256;
+    if (rollout && g.geo == kBlock256 && N == 256 && !g.far && a.uniform && wide_rows) g.geo = kBlockU256;
     // the episode layer's regions: only when in use (dronesim_reset_observe: the sampling table of its draw, kept in the tail)
-    const bool epi_regions = a.acc != nullptr || a.auto_reset != 0 || a.rand_act != 0 || a.do_reset != 0;
-    const size_t tail = epi_regions ? drone_lds_tail_bytes(g, p->N, mode != kRollout && !a.do_reset) : 0;
-    // kSym64 has its own carve-up: one block per wave (positions, staging area, cell tables)
-    const bool share = g.P == 0 && mode != kRollout;                                    // the sampling table shares the cell tables' region
-    const size_t samp = (share && a.auto_reset) ? drone_samp_bytes(g, p->N) : 0;
-    g.lds = g.geo == kSym64 ? (size_t)(g.threads / kWave) * sym_wave_bytes(p->k) : drone_lds_bytes(g, p->N, p->k, 2, mode == kRollout, samp);
-    a.stage5 = 0; a.lds_vel = 0;
-    if (p->c == 5 && g.geo == kSym64) {                 // per-wave blocks with 5-column rows, then the waves' velocities
-        a.stage5 = 1;
-        a.lds_vel = (int)((size_t)(g.threads / kWave) * sym_wave_bytes(p->k, 5));
-        g.lds = (size_t)a.lds_vel + sizeof(float2) * (size_t)g.epb * (size_t)p->N;
-    } else if (p->c == 5) {
-        // c = 5 rows: staged through LDS like the c = 2 ones, and the agents' velocities kept in LDS for the rows of the k
-        // nearest, when the env's tile still fits (it does up to N = 1024 at k <= 5; the rows leave as 4-byte stores at a
-        // 60-byte stride otherwise, as they all did through round 2)
-        const size_t lds5 = drone_lds_bytes(g, p->N, p->k, 5, mode == kRollout, samp), vel = sizeof(float2) * (size_t)g.epb * (size_t)p->N;
-        // (the velocity region is rounded up to 16 bytes: the episode layer reads its per-wave partial sums behind it as
-        // ds_read_b128 -- 8 N bytes with odd N left `lds_tail` 8-byte aligned)
-        const size_t vel16 = (vel + 15) & ~(size_t)15;
-        if (lds5 + vel16 + tail <= 160 * 1024) {
-            a.stage5 = 1; a.lds_vel = (int)lds5; g.lds = lds5 + vel16;
-        }
-    }
+    const bool epi_regions = g.epi || a.do_reset != 0;
+    const bool share = g.P == 0 && !rollout;               // workgroup-per-env, single step: the sampling table shares the cell tables' region
+    const StepLds l = step_lds(g.geo, g.P, g.epb, g.threads, N, p->k, p->c, rollout, epi_regions, !share || a.do_reset, share && a.auto_reset);
     // closed-loop rollout: the c = 5 rows of the k nearest carry the partners' velocities = their actions, which exist in LDS only
-    if (ctrl != 0 && p->c == 5 && !a.stage5)
+    if (ctrl != 0 && p->c == 5 && !l.stage5)
         return fail(DRONESIM_EUNSUPPORTED, "dronesim_rollout_control: c = 5 rows of this n_agents x k_closest do not fit the LDS tile");
-    g.lds = (g.lds + 15) & ~(size_t)15;                 // the tail's float4 reads (per-wave partial sums) need 16 bytes
-    a.lds_tail = (int)g.lds;
+    if (l.total > kLdsTile) return fail(DRONESIM_EUNSUPPORTED, "n_agents x k_closest too large for the 160 KiB LDS tile");
+    g.lds = l.total;
+    a.stage5 = l.stage5; a.lds_vel = l.lds_vel; a.lds_tail = l.lds_tail;
     if (epi_regions) {
-        g.lds += tail;
-        a.samp_tbl = samp_table_entries(p->N);
+        a.samp_tbl = samp_table_entries(N);
         a.samp_shift = 32 - __builtin_ctz((unsigned)a.samp_tbl);
     }
-    if (g.lds > 160 * 1024) return fail(DRONESIM_EUNSUPPORTED, "n_agents x k_closest too large for the 160 KiB LDS tile");
-    a.N = p->N; a.c = p->c; a.max_steps = p->max_steps; a.E = E;
-    a.P = g.P; a.epb = g.epb;
-    a.trace = ((kTrace || kTraceSpan) && (mode == kStep || (mode == kObserve && a.do_reset))) ? g_trace : nullptr;
+    a.N = N; a.c = p->c; a.max_steps = p->max_steps; a.E = E; a.P = g.P; a.epb = g.epb;
     a.dt = p->dt; a.q = p->q; a.b = p->b; a.done_radius = p->done_radius;
-    a.ghost_factor = p->ghost_factor; a.radius_max = p->radius_max;
-    a.reach_max = p->d_hat_max + 2.0f * p->radius_max;
+    a.ghost_factor = p->ghost_factor; a.radius_max = p->radius_max; a.reach_max = reach_max(p);
     a.dhat_u = p->d_hat_max; a.delta_u = p->delta_max; a.radius_u = p->radius_max;
     a.xF = p->xF; a.xF_lo = p->xF_lo; a.d_hat = p->d_hat; a.delta = p->delta; a.radius = p->radius;
-    a.bucket = (g.P > 0 && p->N >= kBucketMinN) ? 1 : 0;
-    a.far_inm = !(p->delta_max < p->d_hat_min) ? 1 : 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    a.bucket = (g.P > 0 && N >= kBucketMinN) ? 1 : 0;
+    return DRONESIM_OK;
+}
+
+int launch(int mode, const DroneParams *p, KArgs &a, int E, void *stream, int ctrl = 0)
+{
+    if (E == 0) return DRONESIM_OK;
+    Geometry g;
+    const int rc = plan_step_launch(mode, p, a, E, ctrl, g);
+    if (rc) return rc;
+    a.trace = ((kTrace || kTraceSpan) && (mode == kStep || (mode == kObserve && a.do_reset))) ? g_trace : nullptr;
     static_assert(DRONESIM_MAX_K == 8, "eight translation units, one k value each");
-    int le = 0;
-    switch (p->k) {
-    case 1: le = dronesim_launch_k1(mode, far, &a, &g, s); break;
-    case 2: le = dronesim_launch_k2(mode, far, &a, &g, s); break;
-    case 3: le = dronesim_launch_k3(mode, far, &a, &g, s); break;
-    case 4: le = dronesim_launch_k4(mode, far, &a, &g, s); break;
-    case 5: le = dronesim_launch_k5(mode, far, &a, &g, s); break;
-    case 6: le = dronesim_launch_k6(mode, far, &a, &g, s); break;
-    case 7: le = dronesim_launch_k7(mode, far, &a, &g, s); break;
-    case 8: le = dronesim_launch_k8(mode, far, &a, &g, s); break;
-    default: return fail(DRONESIM_EUNSUPPORTED, "k_closest > DRONESIM_MAX_K");
-    }
+#define DRONESIM_NAME_K(k) dronesim_launch_k##k,
+    static constexpr int (*launch_k[DRONESIM_MAX_K])(int, const void *, const void *, void *) = {DRONESIM_EACH_K(DRONESIM_NAME_K)};
+    const int le = launch_k[p->k - 1](mode, &a, &g, stream);            // (check_params: 1 <= k <= DRONESIM_MAX_K)
     if (le != 0) {
         char msg[200];
         snprintf(msg, sizeof(msg), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for %zu bytes of LDS: %s",
@@ -528,9 +566,7 @@ int dronesim_step_ex(const DroneParams *p, const DroneEpisodeCtl *ctl, float *po
     if (rc) return rc;
     if (!pos || !vel || !t || !act || !z || !nbr_idx || !done)
         return fail(DRONESIM_EINVAL, "dronesim_step: required buffer is NULL");
-    KArgs a{};
-    a.pos = pos; a.vel = vel; a.t = t; a.act = act; a.reward = reward; a.true_reward = true_reward;
-    a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll; a.done = done; a.T = 1;
+    KArgs a = step_args(pos, vel, t, act, reward, true_reward, z, nbr_idx, n_coll, done, 1);
     if ((rc = apply_ctl(p, ctl, false, a)) != 0) return rc;
     return launch(kStep, p, a, E, stream);
 }
@@ -556,10 +592,8 @@ int dronesim_observe(const DroneParams *p, const float *pos, const float *vel,
     const int rc = check_params(p, E);
     if (rc) return rc;
     if (!pos || !vel || !z || !nbr_idx) return fail(DRONESIM_EINVAL, "dronesim_observe: required buffer is NULL");
-    KArgs a{};
-    a.pos = const_cast<float *>(pos); a.vel = const_cast<float *>(vel);
-    a.reward = reward; a.true_reward = true_reward; a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll;
-    a.mask = mask; a.T = 1;
+    KArgs a = step_args(const_cast<float *>(pos), const_cast<float *>(vel), nullptr, nullptr, reward, true_reward, z, nbr_idx, n_coll, nullptr, 1);
+    a.mask = mask;
     return launch(kObserve, p, a, E, stream);
 }
 
@@ -570,18 +604,12 @@ int dronesim_reset_observe(const DroneParams *p, const DroneEpisodeCtl *ctl, con
     if (rc) return rc;
     if (!ctl || !ctl->episode) return fail(DRONESIM_EINVAL, "dronesim_reset_observe: ctl with the lattice, seed / env_base and episode is required");
     if (!pos || !vel || !t || !z || !nbr_idx) return fail(DRONESIM_EINVAL, "dronesim_reset_observe: required buffer is NULL");
-    if (ctl->div_x < 1 || ctl->div_y < 1) return fail(DRONESIM_EINVAL, "bad E / lattice size");
-    const uint64_t M = (uint64_t)ctl->div_x * (uint64_t)ctl->div_y;
-    if (M < (uint64_t)p->N) return fail(DRONESIM_EINVAL, "lattice has fewer nodes than agents (random.sample would raise)");
-    if (M > 0xFFFFFFFFull) return fail(DRONESIM_EUNSUPPORTED, "lattice larger than 2^32 nodes");
-    KArgs a{};
-    a.pos = pos; a.vel = vel; a.t = t; a.z = z; a.nbr_idx = nbr_idx; a.mask = mask; a.T = 1;
-    a.do_reset = 1; a.node_out = node_out;
+    KArgs a = step_args(pos, vel, t, nullptr, nullptr, nullptr, z, nbr_idx, nullptr, nullptr, 1);
+    if ((rc = check_lattice(ctl->div_x, ctl->div_y, p->N, "bad E / lattice size", &a.lat_M)) != 0) return rc;
+    a.mask = mask; a.do_reset = 1; a.node_out = node_out;
     a.acc = reinterpret_cast<double *>(ctl->acc);             // retire the episode in progress (as dronesim_reset_ex does)
-    a.episode = ctl->episode;
-    a.key0 = (uint32_t)ctl->seed; a.key1 = (uint32_t)(ctl->seed >> 32);
-    a.gid_base = (uint32_t)ctl->env_base;
-    a.lat_M = (uint32_t)M; a.div_y = ctl->div_y; a.pitch = ctl->pitch;
+    set_stream(ctl, a);
+    a.div_y = ctl->div_y; a.pitch = ctl->pitch;
     return launch(kObserve, p, a, E, stream);
 }
 
@@ -595,10 +623,8 @@ int dronesim_rollout_ex(const DroneParams *p, const DroneEpisodeCtl *ctl, float 
     if (!pos || !vel || !t || !act || !z || !nbr_idx || !done)
         return fail(DRONESIM_EINVAL, "dronesim_rollout: required buffer is NULL");
     if (T == 0) return DRONESIM_OK;
-    KArgs a{};
-    a.pos = pos; a.vel = vel; a.t = t; a.act = act; a.reward = reward; a.true_reward = true_reward;
-    a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll; a.done = done; a.T = T;
-    a.skin = kSkin * (p->d_hat_max + 2.0f * p->radius_max);
+    KArgs a = step_args(pos, vel, t, act, reward, true_reward, z, nbr_idx, n_coll, done, T);
+    a.skin = skin(p);
     if ((rc = apply_ctl(p, ctl, false, a)) != 0) return rc;
     return launch(kRollout, p, a, E, stream);
 }
@@ -621,10 +647,8 @@ int dronesim_rollout_random(const DroneParams *p, const DroneEpisodeCtl *ctl, fl
     if (!pos || !vel || !t || !z || !nbr_idx || !done)
         return fail(DRONESIM_EINVAL, "dronesim_rollout_random: required buffer is NULL");
     if (T == 0) return DRONESIM_OK;
-    KArgs a{};
-    a.pos = pos; a.vel = vel; a.t = t; a.act = nullptr; a.reward = reward; a.true_reward = true_reward;
-    a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll; a.done = done; a.T = T;
-    a.skin = kSkin * (p->d_hat_max + 2.0f * p->radius_max);
+    KArgs a = step_args(pos, vel, t, nullptr, reward, true_reward, z, nbr_idx, n_coll, done, T);
+    a.skin = skin(p);
     a.act_out = act_out;
     if ((rc = apply_ctl(p, ctl, true, a)) != 0) return rc;
     return launch(kRollout, p, a, E, stream);
@@ -643,10 +667,8 @@ int dronesim_rollout_control(const DroneParams *p, const DroneEpisodeCtl *ctl, i
     if (!pos || !vel || !t || !z || !nbr_idx || !done)
         return fail(DRONESIM_EINVAL, "dronesim_rollout_control: required buffer is NULL");
     if (T == 0) return DRONESIM_OK;
-    KArgs a{};
-    a.pos = pos; a.vel = vel; a.t = t; a.act = nullptr; a.reward = reward; a.true_reward = true_reward;
-    a.z = z; a.nbr_idx = nbr_idx; a.n_coll = n_coll; a.done = done; a.T = T;
-    a.skin = kSkin * (p->d_hat_max + 2.0f * p->radius_max);
+    KArgs a = step_args(pos, vel, t, nullptr, reward, true_reward, z, nbr_idx, n_coll, done, T);
+    a.skin = skin(p);
     a.act_out = act_out;
     a.u_max = u_max;
     if ((rc = apply_ctl(p, ctl, false, a)) != 0) return rc;
@@ -660,39 +682,6 @@ int dronesim_reset(const DroneParams *p, int div_x, int div_y, float pitch,
 {
     return reset_impl(p, div_x, div_y, pitch, seed, env_base, mask, pos, vel, t, episode, node_out, nullptr, E, stream);
 }
-
-}   // extern "C"
-
-namespace {
-int reset_impl(const DroneParams *p, int div_x, int div_y, float pitch, uint64_t seed, int64_t env_base,
-               const uint8_t *mask, float *pos, float *vel, int32_t *t, int32_t *episode, int32_t *node_out,
-               double *acc, int E, void *stream)
-{
-    if (!p) return fail(DRONESIM_EINVAL, "params is NULL");
-    if (p->N < 1 || p->N > DRONESIM_MAX_AGENTS) return fail(DRONESIM_EUNSUPPORTED, "N must be in 1..1024");
-    if (E < 0 || div_x < 1 || div_y < 1) return fail(DRONESIM_EINVAL, "bad E / lattice size");
-    if (!pos || !vel || !t || !episode) return fail(DRONESIM_EINVAL, "dronesim_reset: required buffer is NULL");
-    const uint64_t M = (uint64_t)div_x * (uint64_t)div_y;
-    if (M < (uint64_t)p->N) return fail(DRONESIM_EINVAL, "lattice has fewer nodes than agents (random.sample would raise)");
-    if (M > 0xFFFFFFFFull) return fail(DRONESIM_EUNSUPPORTED, "lattice larger than 2^32 nodes");
-    if (E == 0) return DRONESIM_OK;
-    const Geometry g = geometry(p->N, E);
-    RArgs a{};
-    a.N = p->N; a.E = E; a.P = g.P; a.epb = g.epb; a.div_y = div_y;
-    a.M = (uint32_t)M;
-    a.key0 = (uint32_t)seed;
-    a.key1 = (uint32_t)(seed >> 32);
-    a.env_base = env_base; a.pitch = pitch; a.mask = mask;
-    a.pos = pos; a.vel = vel; a.t = t; a.episode = episode; a.node_out = node_out; a.acc = acc;
-    a.nt = samp_table_entries(p->N);
-    a.shift = 32 - __builtin_ctz((unsigned)a.nt);
-    const size_t lds = sizeof(int2) * (size_t)g.epb * a.nt;
-    hipLaunchKernelGGL(reset_kernel, dim3(g.blocks), dim3(g.threads), lds, static_cast<hipStream_t>(stream), a);
-    return dronesim_launched();
-}
-}   // namespace
-
-extern "C" {
 
 int dronesim_reset_ex(const DroneParams *p, const DroneEpisodeCtl *ctl, const uint8_t *mask,
                       float *pos, float *vel, int32_t *t, int32_t *node_out, int E, void *stream)
@@ -728,7 +717,7 @@ int dronesim_control(const DroneParams *p, int kind, const float *pos, float *ac
     size_t lds = sizeof(float2) * (size_t)g.epb * p->N + sizeof(float) * (g.P > 0 ? nw : 1) * p->N;
     // gradient: the cell-mask far filter for envs of >= kBucketMinN agents (one env per wave, or one per workgroup)
     // (needs the bounds d_hat_max / radius_max of DroneParams: a caller that left them unset keeps the all-partner loop)
-    const float cell_w = (p->d_hat_max + 2.0f * p->radius_max) * 1.001f;
+    const float cell_w = reach_max(p) * 1.001f;
     a.bucket = (kind == DRONESIM_CONTROL_GRADIENT && p->N >= kBucketMinN && g.P <= 1 && p->d_hat_max > 0.0f && p->radius_max >= 0.0f &&
                 cell_w > 0.0f && cell_w < 3.0e38f) ? 1 : 0;
     if (a.bucket) {
@@ -757,6 +746,23 @@ int dronesim_episode_stats(const float *reward, const float *true_reward, const 
 // developer hook (tools/trace_*.py with a -DDRONESIM_TRACE build; not declared in include/dronesim.h): without that build
 // the buffer is never handed to a kernel
 void dronesim_debug_set_trace(long long *buf) { g_trace = buf; }
+
+// developer hook (tests/test_step_plan_host.py; not declared in include/dronesim.h): the plan of the launch an entry point of mode
+// `mode` (enum Mode) would make for these parameters, with the episode layer's parts in use as flagged and z / nbr_idx at
+// `z_addr` -> out[12] = (return code, geo, far, epi, threads, epb, LDS bytes, lds_tail, lds_vel, stage5, samp_tbl, bucket); a
+// refused launch reports its code only.  No HIP call is made.
+void dronesim_debug_step_plan(const DroneParams *p, int mode, int ctrl, int records, int auto_reset, int rand_act, int do_reset,
+                              uint64_t z_addr, int E, int64_t *out)
+{
+    KArgs a{};
+    a.acc = records ? reinterpret_cast<double *>(out) : nullptr;      // (never dereferenced: only tested)
+    a.auto_reset = auto_reset; a.rand_act = rand_act; a.do_reset = do_reset;
+    a.z = reinterpret_cast<float *>(z_addr); a.nbr_idx = reinterpret_cast<int *>(z_addr);
+    Geometry g;
+    const int rc = plan_step_launch(mode, p, a, E, ctrl, g);
+    const int64_t plan[12] = {rc, g.geo, g.far, g.epi, g.threads, g.epb, (int64_t)g.lds, a.lds_tail, a.lds_vel, a.stage5, a.samp_tbl, a.bucket};
+    for (int i = 0; i < 12; ++i) out[i] = (i == 0 || rc == 0) ? plan[i] : 0;
+}
 
 const char *dronesim_last_error(void) { return g_err; }
 
