@@ -20,9 +20,6 @@
 #include "policy_common.hpp"
 
 namespace {
-constexpr int kRowsB = 64, kTiles = 2;   // 64 env rows (2 row tiles) per workgroup
-constexpr int kLdx = 24;                 // bf16 per row of the x tile
-
 struct MArgsB {
     int E, N, d_in, h1, h2, nc1, nc2, ks1;
     const float *x, *b1, *b2, *b3;
@@ -62,7 +59,7 @@ __global__ void __launch_bounds__(256, NC1 <= 8 ? 4 : 3) mlp3_bf16_kernel(const 
     constexpr int KS2 = 2 * NC1;                         // k-steps (of 16) of layer 2
     constexpr int L1C = (NC1 + 3) / 4;                   // layer-1 chunks per wave (upper bound)
     constexpr int kMaxChunks = 4;                        // layer-2 chunks per wave: h2 <= 512
-    constexpr int ld1 = NC1 * 32 + 8;
+    constexpr int ld1 = bf16_h1_stride(NC1);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -71,8 +68,9 @@ __global__ void __launch_bounds__(256, NC1 <= 8 ? 4 : 3) mlp3_bf16_kernel(const 
     const int e0 = row_block * kRowsB;
     const int nb = (NC1 + a.nc2) * 32;
     __bf16 *sx = reinterpret_cast<__bf16 *>(smem);                 // [64][24]
-    float *sbias = reinterpret_cast<float *>(sx + kRowsB * kLdx);  // b1 | b2 (zero padded to chunks) | b3 (32)
+    float *sbias = reinterpret_cast<float *>(sx + bf16_x_elems());  // b1 | b2 (zero padded to chunks) | b3 (32)
     __bf16 *sh1 = reinterpret_cast<__bf16 *>(sbias + nb + 32);     // [64][ld1]; later f32 partials [4][64][33]
+    static_assert(bias_table_floats(0) == 32, "the bias table's b3 tail (a literal here: through bias_table_floats the address arithmetic is re-associated)");
     float *spart = reinterpret_cast<float *>(sh1);
     PT(0);
 
@@ -239,34 +237,15 @@ extern "C" int dronesim_mlp_forward_bf16(const DroneMlpBf16 *m, const float *x, 
                                          uint64_t seed, uint64_t counter, int64_t env_base,
                                          const int32_t *t, const int32_t *episode, int E, void *stream)
 {
-    if (!m || !x) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward_bf16: NULL argument");
-    const int rc = check_mlp(m->N, m->d_in, m->h1, m->h2, m->nout, m->out_kind, m->sample_kind, E);
-    if (rc) return rc;
-    if (m->d_in > 16) return dronesim_fail(DRONESIM_EUNSUPPORTED, "bf16 path: d_in <= 16");
-    if (!m->w1p || !m->w2p || !m->w3p || !m->b1 || !m->b2 || !m->b3)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward_bf16: NULL weight array");
-    if (E == 0) return DRONESIM_OK;
-    MArgsB a{};
-    a.trace = kTrace ? dronesim_policy_trace : nullptr;
-    a.E = E; a.N = m->N; a.d_in = m->d_in; a.h1 = m->h1; a.h2 = m->h2;
-    a.nc1 = (m->h1 + 31) / 32; a.nc2 = (m->h2 + 31) / 32; a.ks1 = 1;
-    a.x = x; a.b1 = m->b1; a.b2 = m->b2; a.b3 = m->b3;
-    a.w1p = reinterpret_cast<const bf16x8 *>(m->w1p); a.w2p = reinterpret_cast<const bf16x8 *>(m->w2p);
-    a.w3p = reinterpret_cast<const bf16x8 *>(m->w3p);
-    a.fin = make_finish(m->N, m->nout, m->out_kind, m->sample_kind, out, act, act_idx, seed, counter, env_base, t, episode);
-    const size_t sh1_bytes = sizeof(__bf16) * kRowsB * ((size_t)a.nc1 * 32 + 8);
-    const size_t part_bytes = sizeof(float) * 4 * kRowsB * 33;
-    const size_t lds = sizeof(__bf16) * kRowsB * kLdx + sizeof(float) * (32 * (a.nc1 + a.nc2) + 32) +
-                       (sh1_bytes > part_bytes ? sh1_bytes : part_bytes);
-    if (lds > 160 * 1024) return dronesim_fail(DRONESIM_EUNSUPPORTED, "hidden layer too wide for the LDS tile");
-    const dim3 grid(((E + kRowsB - 1) / kRowsB) * m->N);
-    switch (a.nc1) {                                     // the h1 tile's register residency is compile-time
-#define DRONESIM_BF16_CASE(n) case n: return launch_policy<mlp3_bf16_kernel<n>>("mlp3_bf16_kernel", 48 * 1024, grid, 256, lds, stream, a);
-        DRONESIM_BF16_CASE(1) DRONESIM_BF16_CASE(2) DRONESIM_BF16_CASE(3) DRONESIM_BF16_CASE(4)
-        DRONESIM_BF16_CASE(5) DRONESIM_BF16_CASE(6) DRONESIM_BF16_CASE(7) DRONESIM_BF16_CASE(8)
-        DRONESIM_BF16_CASE(9) DRONESIM_BF16_CASE(10) DRONESIM_BF16_CASE(11) DRONESIM_BF16_CASE(12)
-        DRONESIM_BF16_CASE(13) DRONESIM_BF16_CASE(14) DRONESIM_BF16_CASE(15) DRONESIM_BF16_CASE(16)
-#undef DRONESIM_BF16_CASE
-        default: return dronesim_fail(DRONESIM_EUNSUPPORTED, "bf16 path: h1 <= 512");
-    }
+#define K(n) launch_policy<mlp3_bf16_kernel<n>>,
+    static const PolicyLaunch<MArgsB> variants[512 / 32] = {K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8)           // [NC1 - 1]: the h1 tile's register residency
+                                                            K(9) K(10) K(11) K(12) K(13) K(14) K(15) K(16)};  // is compile-time (check_mlp: h1 <= 512)
+#undef K
+    return policy_forward("dronesim_mlp_forward_bf16", "mlp3_bf16_kernel", kFamBf16, variants, m, {x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream},
+                          0, 0, m && m->w1p && m->w2p && m->w3p && m->b1 && m->b2 && m->b3, nullptr, [m](MArgsB &a, const PolicyPlan &) {
+        a.nc1 = chunks32(m->h1); a.nc2 = chunks32(m->h2); a.ks1 = 1;
+        a.b1 = m->b1; a.b2 = m->b2; a.b3 = m->b3;
+        a.w1p = reinterpret_cast<const bf16x8 *>(m->w1p); a.w2p = reinterpret_cast<const bf16x8 *>(m->w2p);
+        a.w3p = reinterpret_cast<const bf16x8 *>(m->w3p);
+    });
 }

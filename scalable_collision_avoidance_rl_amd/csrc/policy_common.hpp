@@ -11,14 +11,24 @@
 // plus the sampling of sample_action (categorical over unit-circle actions utils.py:262-269,304-309;
 // Gaussian utils.py:110-117) from a counter-based Philox stream (finish_quad below, shared by every kernel).
 //
-// Five kernel generations sit behind the six entry points of include/dronesim.h, one file per family (DEFAULT = what the host class runs):
-//   policy_rowtile.hip  mlp3_rt_kernel     exact f32, a wave owns 32 rows and every output chunk (round 6): dronesim_mlp_forward, w2_layout = 2, DEFAULT
-//                       mlp3_rt16_kernel   f16x2 split, same ownership, one ring per workgroup (round 6): dronesim_mlp_forward_f16x2_rt, DEFAULT of "f16x2"
-//   policy_f32.hip      mlp3_kernel        exact f32, activations staged through LDS (rounds 2-5): dronesim_mlp_forward, w2_layout = 0 / 1
-//   policy_split.hip    mlp3_split_kernel  bf16x3 / f16x2 splits, a wave owns output chunks w, w + 4, ... (rounds 2-5): dronesim_mlp_forward_bf16x3, _f16x2
-//   policy_bf16.hip     mlp3_bf16_kernel   plain bf16, float32 accumulation (opt-in): dronesim_mlp_forward_bf16
-// The superseded generations stay: they are part of the C ABI and the tests drive them.  Everything here lives in an unnamed
-// namespace -- every translation unit gets its own copy, and the kernels keep the names they had in one file.
+// Which kernel serves which shape (h1, h2 <= 512 throughout; BatchedMLP: host class, policies.py; one file per kernel family).
+// plan_policy_launch below makes the choice; tests/test_policy_plan_host.py restates this table and checks it against the plan:
+//   precision  constructor switches           d_in    nout    entry point (include/dronesim.h)           kernel, variant
+//   "f32"      (default), d_in <= 14          1..14   1..4    dronesim_mlp_forward, w2_layout = 2        mlp3_rt_kernel<VL3 = true>         policy_rowtile.hip
+//                                             1..14   5..32     "                                        mlp3_rt_kernel<false>
+//   "f32"      pack_w2="fragments", or the    1..6    1..16   dronesim_mlp_forward, w2_layout = 1        mlp3_kernel<PACKED, NARROW, NU = 3>  policy_f32.hip
+//              default with d_in > 14         7..64   1..16     "                                        mlp3_kernel<true, true>
+//                                             1..64   17..32    "                                        mlp3_kernel<true, false>
+//   "f32"      pack_w2=False (the plain ABI)  1..64   1..16   dronesim_mlp_forward, w2_layout = 0        mlp3_kernel<false, true>
+//                                             1..64   17..32    "                                        mlp3_kernel<false, false>
+//   "f16x2"    (default)                      1..16   1..4    dronesim_mlp_forward_f16x2_rt              mlp3_rt16_kernel<VL3 = true>       policy_rowtile.hip
+//                                             1..16   5..32     "                                        mlp3_rt16_kernel<false>
+//   "f16x2"    split_kernel=True              1..16   1..32   dronesim_mlp_forward_f16x2                 mlp3_split_kernel<SchemeF16x2, 2>  policy_split.hip
+//   "bf16x3"                                  1..16   1..32   dronesim_mlp_forward_bf16x3                mlp3_split_kernel<SchemeBf16x3, 2>
+//   "bf16"                                    1..16   1..32   dronesim_mlp_forward_bf16                  mlp3_bf16_kernel<NC1 = ceil(h1 / 32)>  policy_bf16.hip
+// The row-tile kernels are the product for every shape they take; mlp3_kernel stays as the only exact-f32 path for d_in > 14 and for the
+// plain C ABI, the split f16x2 path because the C ABI has it and the tests drive it.  Everything here lives in an unnamed namespace --
+// every translation unit gets its own copy, and the kernels keep the names they had in one file.
 #pragma once
 #include <stdio.h>
 #include <mutex>
@@ -27,10 +37,12 @@
 
 // developer trace builds (kTrace, common.hpp) only: the stamps' buffer, set through dronesim_debug_set_policy_trace (policy_rowtile.hip)
 extern __attribute__((visibility("hidden"))) long long *dronesim_policy_trace;
-// w2_layout = 0 / 1 of dronesim_mlp_forward (policy_rowtile.hip) -> the LDS-staged kernel (policy_f32.hip); m, x, dimensions are checked
-extern "C" __attribute__((visibility("hidden"))) int dronesim_mlp_forward_staged(
-    const DroneMlp *m, const float *x, float *out, float *act, int32_t *act_idx, uint64_t seed, uint64_t counter, int64_t env_base,
-    const int32_t *t, const int32_t *episode, int E, void *stream);
+// what a policy call carries besides the network: the tail of every entry point's signature
+struct PolicyCall {
+    const float *x; float *out, *act; int32_t *act_idx; uint64_t seed, counter; int64_t env_base; const int32_t *t, *episode; int E; void *stream;
+};
+// w2_layout = 0 / 1 of dronesim_mlp_forward (policy_rowtile.hip) -> the LDS-staged kernel (policy_f32.hip); m is not NULL
+extern "C" __attribute__((visibility("hidden"))) int dronesim_mlp_forward_staged(const DroneMlp *m, const PolicyCall *c);
 
 namespace {
 
@@ -288,6 +300,8 @@ FinishArgs make_finish(int N, int nout, int out_kind, int sample_kind, float *ou
                       (uint32_t)counter, (uint32_t)(counter >> 32), env_base, t, episode};
 }
 
+int failf(int code, const char *fmt, const char *arg) { char msg[200]; snprintf(msg, sizeof(msg), fmt, arg); return dronesim_fail(code, msg); }
+
 int check_mlp(int N, int d_in, int h1, int h2, int nout, int out_kind, int sample_kind, int E)
 {
     if (N < 1 || d_in < 1 || d_in > 64 || h1 < 1 || h1 > 512 || h2 < 1 || h2 > 512 || nout < 1 || nout > kMaxOut)
@@ -300,22 +314,228 @@ int check_mlp(int N, int d_in, int h1, int h2, int nout, int out_kind, int sampl
     return DRONESIM_OK;
 }
 
-// THE launch sequence of every policy kernel: opt `Kernel` in for the big LDS on this device when `lds` exceeds `opt_in_above`
-// (0 = always; 48 KiB for the bf16 and split kernels), launch, report.  One instantiation per kernel: the opt-in state lives
-// here.  Every kernel takes (x, E, N, d_in, its argument block): the leading scalars are preloaded into SGPRs.
-template <auto Kernel, class Args>
-int launch_policy(const char *what, size_t opt_in_above, dim3 grid, unsigned threads, size_t lds, void *stream, const Args &a)
+// ---- The LDS layout of every kernel family: one function per region, next to the family's constants.  The kernel carves its dynamic
+//      LDS with them and the host's *_lds adds the same calls up -- no layout has a second definition.  Each function keeps the
+//      arithmetic in the spelling the kernel had as a literal: hipcc schedules `b + w` differently from `b * (vl3 ? 5 : 1)`.
+__host__ __device__ constexpr int chunks32(int h) { return (h + 31) / 32; }                  // 32-feature chunks of a layer
+constexpr size_t larger(size_t a, size_t b) { return a > b ? a : b; }                         // the size of a region two tenants share
+// b1 | b2 (zero padded to whole chunks: nb floats) | b3 (32): the bias table of the split and the bf16 kernel
+__host__ __device__ constexpr int bias_table_floats(int nb) { return nb + 32; }
+
+// mlp3_rt_kernel / mlp3_rt16_kernel (policy_rowtile.hip): kRtRows env rows per workgroup, a wave keeps kRtChunks output chunks per pass
+constexpr int kRtChunks = 7, kRtRing = 4, kRtPad = kRtRing, kRtRows = 128, kRtTileFloats = 32 * 33;    // (the [32 rows][33] output tile of a wave)
+__host__ __device__ constexpr int rt_passes(int nc2) { return (nc2 + kRtChunks - 1) / kRtChunks; }
+__host__ __device__ constexpr int rt_per_pass(int nc2) { return (nc2 + rt_passes(nc2) - 1) / rt_passes(nc2); }
+// blocks of one agent's stream that hold weights: per pass L1(c1) and L2(c1, c2 of the pass) for every c1, then (`l3`) L3(c2)
+__host__ __device__ constexpr int rt_weight_blocks(int nc1, int nc2, bool l3) { return rt_passes(nc2) * nc1 + nc1 * nc2 + (l3 ? nc2 : 0); }
+__host__ __device__ constexpr int rt_b2_bytes(int nc2) { return nc2 * 32 * 4; }                              // b2, zero padded to whole chunks
+__host__ __device__ constexpr int rt_tables_bytes(int nc2, bool vl3) { return nc2 * 32 * 4 * (vl3 ? 5 : 1); }   // b2, then (VL3) W3[f][0..3]
+__host__ __device__ constexpr int rt_ring_bytes() { return kRtRing * 4096; }                                 // per wave; later its output tile
+constexpr size_t rt_lds(int nc2, bool vl3) { return (size_t)rt_tables_bytes(nc2, vl3) + 4 * (size_t)rt_ring_bytes(); }
+constexpr int rt_blocks(int nc1, int nc2, int nout) { return rt_weight_blocks(nc1, nc2, nout > 4) + kRtPad; }
+
+constexpr int kR16Depth = 4, kR16PadSupers = 3;      // super-stages (four 4-KiB blocks) of the workgroup's ring; empty ones behind a stream
+__host__ __device__ constexpr int rt16_bias_floats(int nc) { return nc * 32; }                               // b1 * ws1, then b2 * ws2
+__host__ __device__ constexpr int rt16_w3_rows(int nc2, bool vl3) { return vl3 ? nc2 * 32 : 0; }             // VL3: W3[f][0..3], 16 bytes a row
+__host__ __device__ constexpr int rt16_ring_bytes() { return kR16Depth * 16384; }                            // later the four waves' output tiles
+constexpr size_t rt16_lds(int nc1, int nc2, bool vl3) { return sizeof(float) * (size_t)(rt16_bias_floats(nc1) + rt16_bias_floats(nc2)) + sizeof(f32x4) * (size_t)rt16_w3_rows(nc2, vl3) + rt16_ring_bytes(); }
+constexpr int rt16_blocks(int nc1, int nc2, int nout) { return ((rt_weight_blocks(nc1, nc2, nout > 4) + 3) / 4 + kR16PadSupers) * 4; }
+
+// mlp3_kernel (policy_f32.hip): kRows env rows per workgroup (32-row tiles x 4 feature waves each)
+constexpr int kRows = 32, kThreadsF = kRows * 8;
+constexpr int kStW = 33, kStN = 36;      // floats per row of the per-wave staging tile (wide / narrow layer 3)
+// LDS row stride (floats) of the h1 tile for the packed layer 2: whole 32-column chunks (the k padding is written as
+// zeros by layer 1), a multiple of 4 (16-byte aligned rows) whose quotient is odd (ds_read_b128 phases conflict-free)
+__host__ __device__ constexpr int packed_row_stride(int h1)
 {
-    if (lds > opt_in_above) {
+    const int w = ((h1 + 31) >> 5) * 32;
+    return ((w >> 2) & 1) ? w : w + 4;
+}
+__host__ __device__ constexpr int f32_tile_floats(int ld) { return kRows * ld; }                            // the x tile (ld = d_in + 1), the h1 tile
+__host__ __device__ constexpr int f32_stage_floats(int kst) { return 32 * kst; }                             // per wave; later the layer-3 partials
+constexpr size_t f32_lds(int d_in, int h1, bool packed, bool narrow)
+{
+    return sizeof(float) * ((size_t)f32_tile_floats(d_in + 1) + f32_tile_floats(packed ? packed_row_stride(h1) : h1 + 1) + (kThreadsF / 64) * f32_stage_floats(narrow ? kStN : kStW));
+}
+
+// mlp3_split_kernel<S, TILES> (policy_split.hip): 32 TILES env rows per workgroup, `parts` = S::kParts pieces of 1 KiB per stage
+constexpr int kStreamPadX = 8;             // zero stages behind every stream: the run-ahead requests of the deepest ring
+__host__ __device__ constexpr int split_ring_depth(int tiles) { return tiles <= 2 ? 4 : 8; }   // stages of the per-wave weight ring in LDS
+__host__ __device__ constexpr int split_parts(int scheme) { return scheme == 0 ? 3 : 2; }      // 0: SchemeBf16x3, 1: SchemeF16x2
+__host__ __device__ constexpr int split_x_bytes(int tiles, int parts) { return tiles * parts * 1024; }      // x operand [tile][part][lane] x 16 B
+__host__ __device__ constexpr int split_ring_bytes(int tiles, int parts) { return split_ring_depth(tiles) * parts * 1024; }   // per wave
+__host__ __device__ constexpr int split_part_bytes(int tiles) { return 4 * 32 * tiles * 33 * 4; }            // partials [4 waves][rows][33]: share the rings' LDS
+constexpr size_t split_lds(int nc1, int nc2, int tiles, int parts)
+{
+    return sizeof(float) * bias_table_floats((nc1 + nc2) * 32) + split_x_bytes(tiles, parts) + larger(split_part_bytes(tiles), 4 * split_ring_bytes(tiles, parts));
+}
+// stages per (agent, wave) stream: wave 0 owns the most chunks; + padding for the run-ahead requests
+constexpr int split_stages(int nc1, int nc2) { return nc1 * (1 + 2 * ((nc2 + 3) / 4)) + 2 * ((nc2 + 3) / 4) + kStreamPadX; }
+
+// mlp3_bf16_kernel<NC1> (policy_bf16.hip): 64 env rows (2 row tiles) per workgroup
+constexpr int kRowsB = 64, kTiles = 2;
+constexpr int kLdx = 24;                 // bf16 per row of the x tile
+__host__ __device__ constexpr int bf16_x_elems() { return kRowsB * kLdx; }
+__host__ __device__ constexpr int bf16_h1_stride(int nc1) { return nc1 * 32 + 8; }                           // bf16 per row of the h1 tile
+__host__ __device__ constexpr int bf16_part_bytes() { return 4 * kRowsB * 33 * 4; }                         // partials [4 waves][64][33]: share the h1 tile's LDS
+constexpr size_t bf16_lds(int nc1, int nc2)
+{
+    return sizeof(__bf16) * bf16_x_elems() + sizeof(float) * bias_table_floats((nc1 + nc2) * 32) + larger(sizeof(__bf16) * kRowsB * bf16_h1_stride(nc1), bf16_part_bytes());
+}
+
+// The layouts' promises over nc1, nc2 = 1..16 and every variant: a region that a 16-byte access or a DMA request lands in starts on a
+// 16-byte boundary; the rings are whole power-of-two slot counts where `& (depth - 1)` picks the slot, and hold the output tiles
+// that reuse them; regions that share LDS are sized by the larger tenant.
+constexpr bool policy_lds_regions_ok()
+{
+    bool ok = (kRtRing & (kRtRing - 1)) == 0 && (kR16Depth & (kR16Depth - 1)) == 0 && rt_ring_bytes() % 4096 == 0 && rt16_ring_bytes() % 16384 == 0 &&
+              sizeof(float) * kRtTileFloats <= (size_t)rt_ring_bytes() && 4 * sizeof(float) * kRtTileFloats <= (size_t)rt16_ring_bytes() &&
+              (split_ring_depth(2) & (split_ring_depth(2) - 1)) == 0 && bf16_x_elems() * sizeof(__bf16) % 16 == 0 && kStN % 4 == 0;
+    for (int nc1 = 1; nc1 <= 16; ++nc1) {
+        ok = ok && sizeof(__bf16) * bf16_h1_stride(nc1) % 16 == 0 && (sizeof(__bf16) * bf16_h1_stride(nc1) / 16) % 2 == 1;
+        for (int h1 = 32 * nc1 - 31; h1 <= 32 * nc1; ++h1)
+            ok = ok && packed_row_stride(h1) % 4 == 0 && (packed_row_stride(h1) / 4) % 2 == 1 && packed_row_stride(h1) >= 32 * nc1;
+        for (int nc2 = 1; nc2 <= 16; ++nc2) {
+            for (int vl3 = 0; vl3 < 2; ++vl3) {
+                ok = ok && rt_b2_bytes(nc2) % 16 == 0 && rt_tables_bytes(nc2, vl3) % 16 == 0 &&
+                     rt_tables_bytes(nc2, vl3) == rt_b2_bytes(nc2) + (vl3 ? 16 * nc2 * 32 : 0) && rt_lds(nc2, vl3) <= 160 * 1024;
+                ok = ok && sizeof(float) * (rt16_bias_floats(nc1) + rt16_bias_floats(nc2)) % 16 == 0 &&
+                     rt16_lds(nc1, nc2, vl3) == sizeof(float) * 32 * (nc1 + nc2) + (vl3 ? 16 * 32 * nc2 : 0) + rt16_ring_bytes() && rt16_lds(nc1, nc2, vl3) <= 160 * 1024;
+            }
+            for (int scheme = 0; scheme < 2; ++scheme) {
+                const int parts = split_parts(scheme), shared = (int)(split_lds(nc1, nc2, 2, parts) - sizeof(float) * bias_table_floats((nc1 + nc2) * 32) - split_x_bytes(2, parts));
+                ok = ok && sizeof(float) * bias_table_floats((nc1 + nc2) * 32) % 16 == 0 && split_x_bytes(2, parts) % 16 == 0 && split_ring_bytes(2, parts) % 1024 == 0 &&
+                     shared >= split_part_bytes(2) && shared >= 4 * split_ring_bytes(2, parts) && (shared == split_part_bytes(2) || shared == 4 * split_ring_bytes(2, parts)) &&
+                     split_lds(nc1, nc2, 2, parts) <= 160 * 1024;
+            }
+            const int shared = (int)(bf16_lds(nc1, nc2) - sizeof(__bf16) * bf16_x_elems() - sizeof(float) * bias_table_floats((nc1 + nc2) * 32));
+            ok = ok && shared >= bf16_part_bytes() && shared >= (int)sizeof(__bf16) * kRowsB * bf16_h1_stride(nc1) &&
+                 (shared == bf16_part_bytes() || shared == (int)sizeof(__bf16) * kRowsB * bf16_h1_stride(nc1));
+        }
+    }
+    return ok;
+}
+static_assert(policy_lds_regions_ok(), "an LDS region of a policy kernel is misaligned, a ring is no power-of-two slot count, or a shared region is not its larger tenant's size");
+
+// ---- The plan of a policy launch, without a HIP call: the refusals an entry point makes after check_mlp (in its own order, with its own
+//      texts), the instance that runs (`variant`: index into the family's table of launch_policy instantiations), its grid and LDS, and
+//      the stream length and division magic the kernel is told.  `layout`: DroneMlp.w2_layout (kFamRt, kFamStaged) or the scheme
+//      (kFamSplit: 0 bf16x3, 1 f16x2); `reserved`: DroneMlpBf16.reserved; `arrays`: the arrays the family reads are there;
+//      `stream_addr`: the array that must be 16-byte aligned.  E = 0 (nothing to launch) comes back accepted with grid = 0.
+enum PolicyFamily { kFamRt, kFamRt16, kFamStaged, kFamSplit, kFamBf16 };
+constexpr size_t kPolicyLdsMax = 160 * 1024;               // LDS of a CU: the most a workgroup can ask for
+// opt_in: the kernel must be opted in for this much dynamic LDS (enable_big_lds); stream: blocks / stages of one weight stream (0: the
+// family reads arrays); rb_magic: xcd_work_item's ceil(2^32 / row blocks), or 0
+struct PolicyPlan { int rc, variant; unsigned grid, threads; size_t lds; bool opt_in; int stream; unsigned rb_magic; };
+
+inline PolicyPlan plan_policy_launch(int family, int N, int d_in, int h1, int h2, int nout, int layout, int reserved, bool arrays,
+                                     uintptr_t stream_addr, int E)
+{
+    PolicyPlan p{};
+    const int nc1 = chunks32(h1), nc2 = chunks32(h2);
+    const bool aligned = (stream_addr & 15u) == 0, vl3 = nout <= 4;          // vl3: the row-tile kernels run layer 3 on the vector ALU
+    const char *const scheme = layout == 0 ? "bf16x3" : "f16x2";
+    auto refuse = [&p, scheme](int code, const char *fmt) { p.rc = failf(code, fmt, scheme); return p; };
+    // env rows per workgroup; LDS above which the kernel is opted in (0: always -- the opt-in is remembered per kernel and device); rb_magic in use
+    static constexpr struct { int rows; size_t opt_in_above; bool magic; } kFam[5] = {{kRtRows, 0, true}, {kRtRows, 0, true}, {kRows, 0, true},
+                                                                                      {32 * 2, 48 * 1024, false}, {kRowsB, 48 * 1024, false}};
+    static_assert(kThreadsF == 256, "every policy kernel runs four waves");
+    p.threads = 256;
+    switch (family) {
+    case kFamRt:
+        if (!arrays) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward: NULL weight array");
+        if (d_in > 14) return refuse(DRONESIM_EUNSUPPORTED, "dronesim_mlp_forward: w2_layout = 2 needs d_in <= 14");
+        if (!aligned) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward: the row-tile stream (w2_layout = 2) must be 16-byte aligned");
+        if (E == 0) return p;
+        p.variant = vl3; p.lds = rt_lds(nc2, vl3); p.stream = rt_blocks(nc1, nc2, nout);
+        break;
+    case kFamRt16:
+        if (d_in > 16) return refuse(DRONESIM_EUNSUPPORTED, "dronesim_mlp_forward_f16x2_rt: d_in <= 16");
+        if (!arrays) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: NULL weight array");
+        if (reserved != rt16_blocks(nc1, nc2, nout))
+            return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: DroneMlpBf16.reserved must hold dronesim_mlp_rt16_blocks(h1, h2, nout)");
+        if (!aligned) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: the stream must be 16-byte aligned");
+        if (E == 0) return p;
+        p.variant = vl3; p.lds = rt16_lds(nc1, nc2, vl3); p.stream = reserved;
+        break;
+    case kFamStaged: {
+        if (!arrays) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward: NULL weight array");
+        if (layout != 0 && layout != 1) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward: w2_layout must be 0, 1 or 2");
+        if (layout == 1 && !aligned)                                         // read with 16-byte vector loads
+            return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward: fragment-packed w2 (w2_layout = 1) must be 16-byte aligned");
+        if (E == 0) return p;
+        const bool packed = layout == 1, narrow = nout <= 16;               // narrow: layer 3 on the 16-column matrix instruction
+        p.lds = f32_lds(d_in, h1, packed, narrow);
+        // mlp3_kernel<PACKED, NARROW>: 0 .. 3 = 2 PACKED + NARROW; 4 = <true, true, NU = 3> (d_in <= 6: three k-steps of layer 1)
+        p.variant = (packed && narrow && d_in <= 6) ? 4 : (packed ? 2 : 0) + (narrow ? 1 : 0);
+        break;
+    }
+    case kFamSplit:
+        if (d_in > 16) return refuse(DRONESIM_EUNSUPPORTED, "%s path: d_in <= 16");
+        if (!arrays) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward_%s: NULL weight array");
+        if (E == 0) return p;
+        if (reserved != split_stages(nc1, nc2))
+            return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward_%s: DroneMlpBf16.reserved must hold dronesim_mlp_bf16x3_stages(h1, h2), "
+                                           "the stages per stream of w1p");
+        p.variant = layout; p.lds = split_lds(nc1, nc2, 2, split_parts(layout)); p.stream = reserved;      // TILES = 2
+        break;
+    case kFamBf16:
+        if (d_in > 16) return refuse(DRONESIM_EUNSUPPORTED, "bf16 path: d_in <= 16");
+        if (!arrays) return refuse(DRONESIM_EINVAL, "dronesim_mlp_forward_bf16: NULL weight array");
+        if (E == 0) return p;
+        p.lds = bf16_lds(nc1, nc2);
+        p.variant = nc1 - 1;                                                 // mlp3_bf16_kernel<NC1>: the h1 tile's register residency is compile-time
+        break;
+    }
+    // (mlp3_kernel's and bf16's tiles grow with h1; check_mlp's caps keep them at 92800 and 73856 bytes, the other families' are asserted above)
+    if (p.lds > kPolicyLdsMax) return refuse(DRONESIM_EUNSUPPORTED, "hidden layer too wide for the LDS tile");
+    const unsigned rb = (unsigned)((E + kFam[family].rows - 1) / kFam[family].rows);
+    p.grid = rb * N;
+    p.rb_magic = kFam[family].magic ? div_magic(p.grid, rb) : 0u;
+    p.opt_in = p.lds > kFam[family].opt_in_above;
+    return p;
+}
+
+// THE launch sequence of every policy kernel: opt `Kernel` in for the big LDS on this device where the plan says so, launch,
+// report.  One instantiation per kernel: the opt-in state lives here.  Every kernel takes (x, E, N, d_in, its argument block): the
+// leading scalars are preloaded into SGPRs.  A family's variants are one table of these, indexed by PolicyPlan.variant.
+template <auto Kernel, class Args>
+int launch_policy(const char *what, const PolicyPlan &p, void *stream, const Args &a)
+{
+    if (p.opt_in) {
         static std::mutex mu;
         static unsigned long long opted[4] = {0ull, 0ull, 0ull, 0ull};
         const int rc = enable_big_lds(reinterpret_cast<const void *>(Kernel), opted, mu, what);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, static_cast<hipStream_t>(stream), a.x, a.E, a.N, a.d_in, a);
+    hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(p.threads), p.lds, static_cast<hipStream_t>(stream), a.x, a.E, a.N, a.d_in, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
     return DRONESIM_OK;
+}
+
+// The front door of the five entry points: the NULL m / x check, check_mlp and the plan's refusals, E = 0, the fields every argument
+// block has, make_finish and the trace pointer; `fill(a, plan)` then sets what is the family's own, and the plan's variant of the
+// family's table is launched.  `entry`: the entry point's name for the NULL message; `aligned16`: the plan's `stream_addr`.
+template <class A> auto set_trace(A &a, int) -> decltype((void)a.trace) { a.trace = kTrace ? dronesim_policy_trace : nullptr; }
+template <class A> void set_trace(A &, long) {}                                // (mlp3_rt_kernel's block carries none)
+template <class Args> using PolicyLaunch = int (*)(const char *, const PolicyPlan &, void *, const Args &);
+
+template <class Args, size_t V, class M, class Fill>
+int policy_forward(const char *entry, const char *kernel, int family, const PolicyLaunch<Args> (&variants)[V], const M *m, const PolicyCall &c,
+                   int layout, int reserved, bool arrays, const void *aligned16, Fill fill)
+{
+    if (!m || !c.x) return failf(DRONESIM_EINVAL, "%s: NULL argument", entry);
+    const int rc = check_mlp(m->N, m->d_in, m->h1, m->h2, m->nout, m->out_kind, m->sample_kind, c.E);
+    if (rc) return rc;
+    const PolicyPlan p = plan_policy_launch(family, m->N, m->d_in, m->h1, m->h2, m->nout, layout, reserved, arrays, reinterpret_cast<uintptr_t>(aligned16), c.E);
+    if (p.rc || c.E == 0) return p.rc;
+    Args a{};
+    a.E = c.E; a.N = m->N; a.d_in = m->d_in; a.h1 = m->h1; a.h2 = m->h2; a.x = c.x;
+    a.fin = make_finish(m->N, m->nout, m->out_kind, m->sample_kind, c.out, c.act, c.act_idx, c.seed, c.counter, c.env_base, c.t, c.episode);
+    set_trace(a, 0);
+    fill(a, p);
+    return variants[p.variant](kernel, p, c.stream, a);
 }
 
 }   // namespace

@@ -1,5 +1,5 @@
 // policy_f32.hip -- the exact-float32 policy forward of rounds 2-5: mlp3_kernel, activations staged through LDS (dronesim_mlp_forward
-// with DroneMlp.w2_layout = 0 / 1; the default is mlp3_rt_kernel in policy_rowtile.hip; overview of the generations: policy_common.hpp).
+// with DroneMlp.w2_layout = 0 / 1; the default is mlp3_rt_kernel in policy_rowtile.hip; which kernel serves which shape: policy_common.hpp).
 // Arithmetic: exact float32 on the matrix cores -- v_mfma_f32_32x32x2_f32 is a k-ordered fmaf chain
 // (no reduced precision), so results match a float32 torch reference to round-off.
 // Decomposition: ceil(E/32) x N workgroups (XCD-aware order, see xcd_work_item): one workgroup = 32 env rows of ONE agent, 4 waves.
@@ -17,9 +17,6 @@
 #include "policy_common.hpp"
 
 namespace {
-constexpr int kRows = 32;                // env rows per workgroup (32-row tiles x 4 feature waves each)
-constexpr int kThreadsF = kRows * 8;
-
 struct MArgs {
     int E, N, d_in, h1, h2, nout;
     const float *x, *w1, *b1, *w2, *b2, *w3, *b3;
@@ -27,14 +24,6 @@ struct MArgs {
     long long *trace;                    // developer trace builds only (NULL otherwise)
     unsigned rb_magic;                   // xcd_work_item: ceil(2^32 / row blocks), or 0
 };
-
-// LDS row stride (floats) of the h1 tile for the packed layer 2: whole 32-column chunks (the k padding is written as
-// zeros by layer 1), a multiple of 4 (16-byte aligned rows) whose quotient is odd (ds_read_b128 phases conflict-free)
-__host__ __device__ __forceinline__ int packed_row_stride(int h1)
-{
-    const int w = ((h1 + 31) >> 5) * 32;
-    return ((w >> 2) & 1) ? w : w + 4;
-}
 
 // acc += A[32 x K] * B[K x 32].  A row-major in LDS (lda floats per row, odd stride -> conflict-free), B row-major
 // in global / L2 (ldb floats per row); B columns >= ncols_valid read a clamped column (never stored), k >= K reads
@@ -191,8 +180,6 @@ __device__ __forceinline__ void tile_gemm_packed(f32x16 &acc, const float *Arow,
 // CONSECUTIVE floats of its staged row: two ds_read_b128 per tile instead of eight ds_read_b32; kStN = 36 floats per
 // row = a multiple of 4 with an odd quotient, so the 8 lanes of a read phase hit different bank quads) and reads its
 // eight W3 values once for both tiles.  D: reg r of lane l = (row 4 (l >> 4) + r, col l & 15).
-constexpr int kStW = 33, kStN = 36;      // floats per row of the per-wave staging tile (wide / narrow layer 3)
-
 __device__ __forceinline__ void layer3_narrow(f32x4 (&y)[2], const float *st, const float *__restrict__ w3c, int nout, int kvalid, int lane)
 {
     const int g = lane >> 4, i = lane & 15, c = min(i, nout - 1);
@@ -235,10 +222,10 @@ __global__ void __launch_bounds__(kThreadsF, 2) mlp3_kernel(const float *x, int 
     const int e0 = row_block * kRows;
     const int ldx = a.d_in + 1, ld1 = PACKED ? packed_row_stride(a.h1) : a.h1 + 1;
     float *sx = reinterpret_cast<float *>(smem);                 // [rows][d_in+1]
-    float *sh1 = sx + kRows * ldx;                               // [rows][h1+1]
+    float *sh1 = sx + f32_tile_floats(ldx);                      // [rows][h1+1]
     constexpr int kSt = NARROW ? kStN : kStW;
     constexpr bool TR = PACKED && NARROW;                        // transposed tiles (see store_tile_tr)
-    float *sst = sh1 + kRows * ld1;                              // [waves][32][kSt] layer-2 chunk staging,
+    float *sst = sh1 + f32_tile_floats(ld1);                     // [waves][32][kSt] layer-2 chunk staging,
                                                                  // reused for the layer-3 partials
     const float *w1 = a.w1 + (size_t)agent * a.d_in * a.h1, *b1 = a.b1 + (size_t)agent * a.h1;
     const int nst = (a.h1 + 15) >> 4;                            // PACKED: 16-k stages of layer 2
@@ -362,7 +349,7 @@ __global__ void __launch_bounds__(kThreadsF, 2) mlp3_kernel(const float *x, int 
     // waves (half the range each); the partial tiles meet in LDS and one wave per chunk finishes it.
     f32x16 y = {0};
     f32x4 yn[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
-    float *st = sst + wave * 32 * kSt;
+    float *st = sst + wave * f32_stage_floats(kSt);
     const int nch = (a.h2 + 31) >> 5;
     // Measured at the C5 shard: one leftover (13 chunks at h = 400) -5.5 %, -4.3 % at C3; two leftovers (10 chunks at h = 300)
     // as pairs -8.7 % (round 4; as two quarter-split trips, i.e. four barriers, +1.5 %); three leftovers (7 chunks at
@@ -531,33 +518,14 @@ __global__ void __launch_bounds__(kThreadsF, 2) mlp3_kernel(const float *x, int 
 
 }   // namespace
 
-extern "C" int dronesim_mlp_forward_staged(const DroneMlp *m, const float *x, float *out, float *act, int32_t *act_idx,
-                                           uint64_t seed, uint64_t counter, int64_t env_base,
-                                           const int32_t *t, const int32_t *episode, int E, void *stream)
+extern "C" int dronesim_mlp_forward_staged(const DroneMlp *m, const PolicyCall *c)
 {
-    if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward: NULL weight array");
-    if (m->w2_layout != 0 && m->w2_layout != 1) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward: w2_layout must be 0, 1 or 2");
-    if (m->w2_layout == 1 && (reinterpret_cast<uintptr_t>(m->w2) & 15u) != 0)     // read with 16-byte vector loads
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward: fragment-packed w2 (w2_layout = 1) must be 16-byte aligned");
-    if (E == 0) return DRONESIM_OK;
-    MArgs a{};
-    a.trace = kTrace ? dronesim_policy_trace : nullptr;
-    a.E = E; a.N = m->N; a.d_in = m->d_in; a.h1 = m->h1; a.h2 = m->h2; a.nout = m->nout;
-    a.x = x; a.w1 = m->w1; a.b1 = m->b1; a.w2 = m->w2; a.b2 = m->b2; a.w3 = m->w3; a.b3 = m->b3;
-    a.fin = make_finish(m->N, m->nout, m->out_kind, m->sample_kind, out, act, act_idx, seed, counter, env_base, t, episode);
-    const bool packed = m->w2_layout == 1;
-    const size_t ld1 = packed ? (size_t)packed_row_stride(m->h1) : (size_t)m->h1 + 1;
-    // (x rows: d_in + 1 floats; the h1 tile follows on a 16-byte boundary)
-    const bool narrow = m->nout <= 16;                           // layer 3 on the 16-column matrix instruction
-    const size_t lds = sizeof(float) * ((size_t)kRows * (m->d_in + 1) + (size_t)kRows * ld1 + (kThreadsF / 64) * 32 * (narrow ? kStN : kStW));
-    if (lds > 160 * 1024) return dronesim_fail(DRONESIM_EUNSUPPORTED, "hidden layer too wide for the LDS tile");
-    typedef int (*Launch)(const char *, size_t, dim3, unsigned, size_t, void *, const MArgs &);
-    static const Launch launchers[5] = {launch_policy<mlp3_kernel<false, false>>, launch_policy<mlp3_kernel<false, true>>,
-                                        launch_policy<mlp3_kernel<true, false>>, launch_policy<mlp3_kernel<true, true>>,
-                                        launch_policy<mlp3_kernel<true, true, 3>>};
-    const int which = (packed && narrow && m->d_in <= 6) ? 4 : (packed ? 2 : 0) + (narrow ? 1 : 0);
-    const dim3 grid(((E + kRows - 1) / kRows) * m->N);
-    a.rb_magic = div_magic(grid.x, (unsigned)((E + kRows - 1) / kRows));
-    return launchers[which]("mlp3_kernel", 0, grid, kThreadsF, lds, stream, a);
+    static const PolicyLaunch<MArgs> variants[5] = {launch_policy<mlp3_kernel<false, false>>, launch_policy<mlp3_kernel<false, true>>,    // [2 PACKED + NARROW]
+                                                    launch_policy<mlp3_kernel<true, false>>, launch_policy<mlp3_kernel<true, true>>,
+                                                    launch_policy<mlp3_kernel<true, true, 3>>};                                          // d_in <= 6
+    return policy_forward("dronesim_mlp_forward", "mlp3_kernel", kFamStaged, variants, m, *c, m->w2_layout, 0,
+                          m->w1 && m->b1 && m->w2 && m->b2 && m->w3 && m->b3, m->w2, [m](MArgs &a, const PolicyPlan &p) {
+        a.nout = m->nout; a.rb_magic = p.rb_magic;
+        a.w1 = m->w1; a.b1 = m->b1; a.w2 = m->w2; a.b2 = m->b2; a.w3 = m->w3; a.b3 = m->b3;
+    });
 }

@@ -1,6 +1,6 @@
 // policy_rowtile.hip -- the ROW-TILE policy forward of round 6, the default of the host class: mlp3_rt_kernel (exact float32,
 // dronesim_mlp_forward with DroneMlp.w2_layout = 2) and, further down, mlp3_rt16_kernel (f16x2, dronesim_mlp_forward_f16x2_rt).
-// The two share the ownership (kRtChunks, rt_passes, rt_per_pass) and dma_to_lds; overview of the generations: policy_common.hpp.
+// The two share the ownership (kRtChunks, rt_passes, rt_per_pass) and dma_to_lds; which kernel serves which shape, the LDS layouts and the launch plan: policy_common.hpp.
 // mlp3_rt_kernel, exact float32: the register-fused formulation of the split kernels on
 // v_mfma_f32_32x32x2_f32, with the work split the other way round.  A wave owns 32 env rows of one agent and ALL output chunks
 // of layer 2 for them (up to kRtChunks = 7 accumulator tiles = 112 registers per pass; h2 > 224 takes two passes and recomputes
@@ -24,10 +24,6 @@
 #include "policy_common.hpp"
 
 namespace {
-constexpr int kRtChunks = 7, kRtRing = 4, kRtPad = kRtRing, kRtRows = 128;
-__host__ __device__ constexpr int rt_passes(int nc2) { return (nc2 + kRtChunks - 1) / kRtChunks; }
-__host__ __device__ constexpr int rt_per_pass(int nc2) { return (nc2 + rt_passes(nc2) - 1) / rt_passes(nc2); }
-
 struct MArgsR {
     int E, N, d_in, h1, h2, nout, nc1, nc2, blocks;
     const float *x, *ws, *b2, *b3;
@@ -57,8 +53,8 @@ __global__ void __launch_bounds__(256, 2) mlp3_rt_kernel(const float *x, int E, 
     const int half = lane >> 5;
     const int nc1 = a.nc1, nc2 = a.nc2, ks1 = (a.d_in + 1) >> 1;
     float *sb2 = reinterpret_cast<float *>(smem);                  // b2, zero padded to whole chunks
-    f32x4 *sw3 = reinterpret_cast<f32x4 *>(smem + nc2 * 32 * 4);   // VL3: W3[f][0..3] (zero beyond h2 / nout)
-    char *ring = smem + nc2 * 32 * 4 * (VL3 ? 5 : 1) + wave * (kRtRing * 4096);
+    f32x4 *sw3 = reinterpret_cast<f32x4 *>(smem + rt_b2_bytes(nc2));   // VL3: W3[f][0..3] (zero beyond h2 / nout)
+    char *ring = smem + rt_tables_bytes(nc2, VL3) + wave * rt_ring_bytes();
 
     // ---- the weight stream.  Everything about it is scalar except the lane's 16-byte slot: the float32 matrix instructions run
     // on the vector ALUs, so every vector instruction in the loop is matrix time lost -- the DMA requests are issued by name with a
@@ -315,8 +311,6 @@ __global__ void __launch_bounds__(256, 2) mlp3_rt_kernel(const float *x, int E, 
 //                                    nout > 4 (layer 3 on the matrix cores), after the pass's in-chunks:  L3(c2) = (hi, lo of k-step 2 c2),
 //                                             (hi, lo of k-step 2 c2 + 1) of W3^T, outputs zero-padded to 32, for c2 in S_p;
 //   padded to whole super-stages, then three empty super-stages (the requests run two super-stages ahead, the reads one block).  Weights carry DroneMlpBf16.wscale like the split kernel's.
-constexpr int kR16Depth = 4;
-
 struct MArgsR16 {
     int E, N, d_in, h1, h2, nout, nc1, nc2, blocks;
     const float *x, *b1, *b2, *b3, *w3, *wscale;
@@ -355,9 +349,9 @@ __global__ void __launch_bounds__(256, 2) mlp3_rt16_kernel(const float *x, int E
         if constexpr (!VL3) wi3 = __builtin_amdgcn_rcpf(a.wscale[3 * (size_t)agent + 2]);
     }
     float *sb1 = reinterpret_cast<float *>(smem);                  // b1 * ws1 | b2 * ws2, zero padded to whole chunks
-    float *sb2 = sb1 + nc1 * 32;
-    f32x4 *sw3 = reinterpret_cast<f32x4 *>(sb2 + nc2 * 32);        // VL3: W3[f][0..3] / layer 2's weight factor (zero beyond h2 / nout)
-    char *ring = reinterpret_cast<char *>(sw3 + (VL3 ? nc2 * 32 : 0));   // [kR16Depth][4 blocks][4 pieces][1 KiB], shared by the workgroup
+    float *sb2 = sb1 + rt16_bias_floats(nc1);
+    f32x4 *sw3 = reinterpret_cast<f32x4 *>(sb2 + rt16_bias_floats(nc2));   // VL3: W3[f][0..3] / layer 2's weight factor (zero beyond h2 / nout)
+    char *ring = reinterpret_cast<char *>(sw3 + rt16_w3_rows(nc2, VL3));   // [kR16Depth][4 blocks][4 pieces][1 KiB], shared by the workgroup
 
     // ---- the weight stream: wave w requests piece w of every block (scalar base + this lane's 16-byte slot, by name)
     const unsigned long long sbase0 = reinterpret_cast<unsigned long long>(a.ws) + (unsigned long long)agent * a.blocks * 4096ull +
@@ -594,7 +588,7 @@ __global__ void __launch_bounds__(256, 2) mlp3_rt16_kernel(const float *x, int E
     __syncthreads();                                               // ... and no wave may still be reading it
     PT64(30);
 
-    float *st = reinterpret_cast<float *>(ring) + wave * (32 * 33);
+    float *st = reinterpret_cast<float *>(ring) + wave * kRtTileFloats;
     if constexpr (VL3) {
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
@@ -633,84 +627,59 @@ long long *dronesim_policy_trace = nullptr;
 // developer hook (tools/trace_policy.py / trace_x3.py with a -DDRONESIM_TRACE build; not declared in include/dronesim.h)
 extern "C" void dronesim_debug_set_policy_trace(long long *p) { dronesim_policy_trace = p; }
 
-// blocks (4 KiB each) of one agent's row-tile weight stream, zero padding included (DroneMlp.w2_layout = 2; see mlp3_rt_kernel)
-// (nout <= 4: layer 3 runs on the vector ALU from the plain w3 array and the stream holds no L3 blocks)
-extern "C" int dronesim_mlp_rt_blocks(int h1, int h2, int nout)
+// developer hook (tests/test_policy_plan_host.py; not declared in include/dronesim.h): the plan of the launch that entry point `entry`
+// (0 dronesim_mlp_forward with w2_layout = `layout`, 1 _f16x2_rt, 2 _bf16x3, 3 _f16x2, 4 _bf16) would make for a network of these
+// dimensions with DroneMlpBf16.reserved = `reserved`, its arrays there or not (`arrays`) and its stream at `stream_addr` ->
+// out[9] = (return code, PolicyFamily, variant, grid, threads, LDS bytes, opt-in, stream length, rb_magic); a refused launch and E = 0
+// report the code only.  No HIP call is made.
+extern "C" void dronesim_debug_policy_plan(int entry, int N, int d_in, int h1, int h2, int nout, int layout, int reserved, int arrays,
+                                           uint64_t stream_addr, int E, int64_t *out)
 {
-    if (h1 < 1 || h2 < 1 || nout < 1) return 0;
-    const int nc1 = (h1 + 31) / 32, nc2 = (h2 + 31) / 32;
-    return rt_passes(nc2) * nc1 + nc1 * nc2 + (nout <= 4 ? 0 : nc2) + kRtPad;
+    const int family = entry == 0 ? (layout == 2 ? kFamRt : kFamStaged) : entry == 1 ? kFamRt16 : entry == 4 ? kFamBf16 : kFamSplit;
+    PolicyPlan p{};
+    if ((p.rc = check_mlp(N, d_in, h1, h2, nout, 0, 0, E)) == 0)
+        p = plan_policy_launch(family, N, d_in, h1, h2, nout, family == kFamSplit ? entry - 2 : layout, reserved, arrays != 0, (uintptr_t)stream_addr, E);
+    const int64_t plan[9] = {p.rc, family, p.variant, p.grid, p.threads, (int64_t)p.lds, p.opt_in, p.stream, p.rb_magic};
+    for (int i = 0; i < 9; ++i) out[i] = (i == 0 || (p.rc == 0 && E != 0)) ? plan[i] : 0;
 }
 
+// blocks (4 KiB each) of one agent's row-tile weight stream, zero padding included (DroneMlp.w2_layout = 2; see mlp3_rt_kernel)
+// (nout <= 4: layer 3 runs on the vector ALU from the plain w3 array and the stream holds no L3 blocks)
+extern "C" int dronesim_mlp_rt_blocks(int h1, int h2, int nout) { return (h1 < 1 || h2 < 1 || nout < 1) ? 0 : rt_blocks(chunks32(h1), chunks32(h2), nout); }
+
 // blocks (4 KiB) of one agent's float16 row-tile stream (dronesim_mlp_forward_f16x2_rt): the real blocks rounded up to whole
-// super-stages of four, plus three super-stages of padding for the run-ahead of the DMA requests
-extern "C" int dronesim_mlp_rt16_blocks(int h1, int h2, int nout)
-{
-    if (h1 < 1 || h2 < 1 || nout < 1) return 0;
-    const int nc1 = (h1 + 31) / 32, nc2 = (h2 + 31) / 32;
-    const int real = rt_passes(nc2) * nc1 + nc1 * nc2 + (nout > 4 ? nc2 : 0);
-    return ((real + 3) / 4 + 3) * 4;
-}
+// super-stages of four, plus kR16PadSupers super-stages of padding for the run-ahead of the DMA requests
+extern "C" int dronesim_mlp_rt16_blocks(int h1, int h2, int nout) { return (h1 < 1 || h2 < 1 || nout < 1) ? 0 : rt16_blocks(chunks32(h1), chunks32(h2), nout); }
 
 extern "C" int dronesim_mlp_forward_f16x2_rt(const DroneMlpBf16 *m, const float *x, float *out, float *act, int32_t *act_idx,
                                              uint64_t seed, uint64_t counter, int64_t env_base,
                                              const int32_t *t, const int32_t *episode, int E, void *stream)
 {
-    if (!m || !x) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: NULL argument");
-    const int rc = check_mlp(m->N, m->d_in, m->h1, m->h2, m->nout, m->out_kind, m->sample_kind, E);
-    if (rc) return rc;
-    if (m->d_in > 16) return dronesim_fail(DRONESIM_EUNSUPPORTED, "dronesim_mlp_forward_f16x2_rt: d_in <= 16");
-    const bool vl3 = m->nout <= 4;                                // layer 3 on the vector ALU, from the plain float32 array
-    if (!m->w1p || (vl3 && !m->w3p) || !m->b1 || !m->b2 || !m->b3)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: NULL weight array");
-    if (m->reserved != dronesim_mlp_rt16_blocks(m->h1, m->h2, m->nout))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: DroneMlpBf16.reserved must hold dronesim_mlp_rt16_blocks(h1, h2, nout)");
-    if ((reinterpret_cast<uintptr_t>(m->w1p) & 15u) != 0)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward_f16x2_rt: the stream must be 16-byte aligned");
-    if (E == 0) return DRONESIM_OK;
-    MArgsR16 r{};
-    r.E = E; r.N = m->N; r.d_in = m->d_in; r.h1 = m->h1; r.h2 = m->h2; r.nout = m->nout;
-    r.nc1 = (m->h1 + 31) / 32; r.nc2 = (m->h2 + 31) / 32;
-    r.blocks = m->reserved;
-    r.x = x; r.b1 = m->b1; r.b2 = m->b2; r.b3 = m->b3; r.w3 = reinterpret_cast<const float *>(m->w3p); r.wscale = m->wscale;
-    r.ws = reinterpret_cast<const char *>(m->w1p);
-    r.fin = make_finish(m->N, m->nout, m->out_kind, m->sample_kind, out, act, act_idx, seed, counter, env_base, t, episode);
-    r.trace = kTrace ? dronesim_policy_trace : nullptr;
-    const size_t lds = (size_t)(r.nc1 + r.nc2) * 32 * 4 + (vl3 ? (size_t)r.nc2 * 32 * 16 : 0) + (size_t)kR16Depth * 16384;
-    const unsigned rb = (unsigned)((E + kRtRows - 1) / kRtRows);
-    const dim3 grid(rb * m->N);
-    r.rb_magic = div_magic(grid.x, rb);
-    return vl3 ? launch_policy<mlp3_rt16_kernel<true>>("mlp3_rt16_kernel", 0, grid, 256, lds, stream, r)
-               : launch_policy<mlp3_rt16_kernel<false>>("mlp3_rt16_kernel", 0, grid, 256, lds, stream, r);
+    static const PolicyLaunch<MArgsR16> variants[2] = {launch_policy<mlp3_rt16_kernel<false>>, launch_policy<mlp3_rt16_kernel<true>>};   // [VL3]
+    // VL3 (nout <= 4): layer 3 on the vector ALU, from the plain float32 array in w3p
+    return policy_forward("dronesim_mlp_forward_f16x2_rt", "mlp3_rt16_kernel", kFamRt16, variants, m, {x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream},
+                          0, m ? m->reserved : 0, m && m->w1p && (m->nout > 4 || m->w3p) && m->b1 && m->b2 && m->b3, m ? m->w1p : nullptr,
+                          [m](MArgsR16 &r, const PolicyPlan &p) {
+        r.nout = m->nout; r.nc1 = chunks32(m->h1); r.nc2 = chunks32(m->h2);
+        r.blocks = p.stream; r.rb_magic = p.rb_magic;
+        r.b1 = m->b1; r.b2 = m->b2; r.b3 = m->b3; r.w3 = reinterpret_cast<const float *>(m->w3p); r.wscale = m->wscale;
+        r.ws = reinterpret_cast<const char *>(m->w1p);
+    });
 }
 
 extern "C" int dronesim_mlp_forward(const DroneMlp *m, const float *x, float *out, float *act, int32_t *act_idx,
                                     uint64_t seed, uint64_t counter, int64_t env_base,
                                     const int32_t *t, const int32_t *episode, int E, void *stream)
 {
-    if (!m || !x) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward: NULL argument");
-    const int rc = check_mlp(m->N, m->d_in, m->h1, m->h2, m->nout, m->out_kind, m->sample_kind, E);
-    if (rc) return rc;
-    // w2_layout = 0 / 1: the LDS-staged kernel of rounds 2-5 (policy_f32.hip)
-    if (m->w2_layout != 2) return dronesim_mlp_forward_staged(m, x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream);
-    // the row-tile stream (round 6): w2 = [N][dronesim_mlp_rt_blocks(h1, h2)][4][64][4] float32 holding W1, b1, W2 and W3 in the
-    // kernel's consumption order; w1 / b1 / w3 are not read
-    const bool vl3 = m->nout <= 4;                            // layer 3 on the vector ALU, from the plain w3 array
-    if (!m->w2 || !m->b2 || !m->b3 || (vl3 && !m->w3)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward: NULL weight array");
-    if (m->d_in > 14) return dronesim_fail(DRONESIM_EUNSUPPORTED, "dronesim_mlp_forward: w2_layout = 2 needs d_in <= 14");
-    if ((reinterpret_cast<uintptr_t>(m->w2) & 15u) != 0)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_mlp_forward: the row-tile stream (w2_layout = 2) must be 16-byte aligned");
-    if (E == 0) return DRONESIM_OK;
-    MArgsR r{};
-    r.E = E; r.N = m->N; r.d_in = m->d_in; r.h1 = m->h1; r.h2 = m->h2; r.nout = m->nout;
-    r.nc1 = (m->h1 + 31) / 32; r.nc2 = (m->h2 + 31) / 32;
-    r.blocks = dronesim_mlp_rt_blocks(m->h1, m->h2, m->nout);
-    r.x = x; r.ws = m->w2; r.b2 = m->b2; r.b3 = m->b3; r.w3 = m->w3;
-    r.fin = make_finish(m->N, m->nout, m->out_kind, m->sample_kind, out, act, act_idx, seed, counter, env_base, t, episode);
-    const size_t lds = (size_t)r.nc2 * 32 * 4 * (vl3 ? 5 : 1) + 4 * (size_t)kRtRing * 4096;
-    const unsigned rb = (unsigned)((E + kRtRows - 1) / kRtRows);
-    const dim3 grid(rb * m->N);
-    r.rb_magic = div_magic(grid.x, rb);
-    return vl3 ? launch_policy<mlp3_rt_kernel<true>>("mlp3_rt_kernel", 0, grid, 256, lds, stream, r)
-               : launch_policy<mlp3_rt_kernel<false>>("mlp3_rt_kernel", 0, grid, 256, lds, stream, r);
+    const PolicyCall c{x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream};
+    if (m && m->w2_layout != 2) return dronesim_mlp_forward_staged(m, &c);     // w2_layout = 0 / 1: the LDS-staged kernel (policy_f32.hip)
+    // the row-tile stream: w2 = [N][dronesim_mlp_rt_blocks(h1, h2, nout)][4][64][4] float32 holding W1, b1, W2 and W3 in the
+    // kernel's consumption order; w1 / b1 are not read, w3 (the plain array) only by VL3 (nout <= 4: layer 3 on the vector ALU)
+    static const PolicyLaunch<MArgsR> variants[2] = {launch_policy<mlp3_rt_kernel<false>>, launch_policy<mlp3_rt_kernel<true>>};         // [VL3]
+    return policy_forward("dronesim_mlp_forward", "mlp3_rt_kernel", kFamRt, variants, m, c, 2, 0, m && m->w2 && m->b2 && m->b3 && (m->nout > 4 || m->w3),
+                          m ? m->w2 : nullptr, [m](MArgsR &r, const PolicyPlan &p) {
+        r.nout = m->nout; r.nc1 = chunks32(m->h1); r.nc2 = chunks32(m->h2);
+        r.blocks = p.stream; r.rb_magic = p.rb_magic;
+        r.ws = m->w2; r.b2 = m->b2; r.b3 = m->b3; r.w3 = m->w3;
+    });
 }

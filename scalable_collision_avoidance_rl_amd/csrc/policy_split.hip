@@ -31,8 +31,6 @@
 #include "policy_common.hpp"
 
 namespace {
-constexpr int kStreamPadX = 8;             // zero stages behind every stream: the run-ahead requests of the deepest ring
-__host__ __device__ constexpr int split_ring_depth(int tiles) { return tiles <= 2 ? 4 : 8; }   // stages of the per-wave weight ring in LDS
 template <int N, int I = 0, class F> __device__ __forceinline__ void for_each_slot(F &f)
 {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); for_each_slot<N, I + 1>(f); }
@@ -132,8 +130,8 @@ __global__ void __launch_bounds__(256, TILES <= 2 ? 2 : 1) mlp3_split_kernel(con
         a.trace[((size_t)blockIdx.x * 4 + wave) * 8 + 1] = __builtin_amdgcn_s_memrealtime();
     }
     float *sbias = reinterpret_cast<float *>(smem);                // b1 | b2 (zero padded to chunks) | b3 (32)
-    char *sxb = reinterpret_cast<char *>(sbias + nb + 32);         // x operand [tile][part][lane] x 16 B
-    float *spart = reinterpret_cast<float *>(sxb + kTilesX * kStageBytes);   // [4 waves][kRowsX rows][33], shares LDS with the rings
+    char *sxb = reinterpret_cast<char *>(sbias + bias_table_floats(nb));   // x operand [tile][part][lane] x 16 B
+    float *spart = reinterpret_cast<float *>(sxb + split_x_bytes(kTilesX, P));   // [4 waves][kRowsX rows][33], shares LDS with the rings
 
     // ---- the x operand: row 32 t + (lane & 31), inputs 8 (lane >> 5) .. + 7, split once, kept in LDS (every wave uses it)
     if (wave < kTilesX) {
@@ -213,7 +211,7 @@ __global__ void __launch_bounds__(256, TILES <= 2 ? 2 : 1) mlp3_split_kernel(con
     //      the registers that stage has just finished with: no copies, no exposed LDS or L2 latency.  The ring needs no
     //      barrier (one wave writes and reads it); a read is ordered behind its DMA by the counted s_waitcnt vmcnt.
     //      The stream is padded by kRingX stages, so the producer never needs to know where it ends.
-    char *ring = reinterpret_cast<char *>(spart) + (size_t)wave * kRingX * kStageBytes;
+    char *ring = reinterpret_cast<char *>(spart) + (size_t)wave * split_ring_bytes(kTilesX, P);
     const char *gp = a.ws + (((size_t)agent * 4 + wave) * a.stages * P * 64 + lane) * 16;
     int pslot = 0;
     auto request_part = [&](int p) {                               // 1 KiB of the stage kRingX ahead
@@ -364,65 +362,40 @@ __global__ void __launch_bounds__(256, TILES <= 2 ? 2 : 1) mlp3_split_kernel(con
 #undef X3_PIN
 #undef X3_RING_READ
 
-template <class S, int TILES>
-int launch_split(const MArgsX &a, int N, void *stream)
-{
-    constexpr size_t stage_bytes = S::kParts * 1024, rows = 32 * TILES;
-    const size_t part_bytes = sizeof(float) * 4 * rows * 33, ring_bytes = (size_t)4 * split_ring_depth(TILES) * stage_bytes;   // share LDS
-    const size_t lds = sizeof(float) * (32 * (size_t)(a.nc1 + a.nc2) + 32) + TILES * stage_bytes +
-                       (part_bytes > ring_bytes ? part_bytes : ring_bytes);
-    return launch_policy<mlp3_split_kernel<S, TILES>>("mlp3_split_kernel", 48 * 1024, dim3(((a.E + rows - 1) / rows) * N), 256, lds, stream, a);
-}
+static_assert(SchemeBf16x3::kParts == split_parts(0) && SchemeF16x2::kParts == split_parts(1) && !SchemeBf16x3::kScaled && SchemeF16x2::kScaled,
+              "the plan sizes a scheme's stages, and the entry point hands wscale on, by the scheme's number");
 
-template <class S>
-int mlp_forward_split(const char *what, const DroneMlpBf16 *m, const float *x, float *out, float *act, int32_t *act_idx,
-                      uint64_t seed, uint64_t counter, int64_t env_base, const int32_t *t, const int32_t *episode, int E,
-                      void *stream)
+// `scheme`: 0 bf16x3, 1 f16x2 (the plan's `layout`, and the variant it picks)
+int mlp_forward_split(int scheme, const DroneMlpBf16 *m, const PolicyCall &c)
 {
-    auto fail = [what](int code, const char *fmt) { char msg[200]; snprintf(msg, sizeof(msg), fmt, what); return dronesim_fail(code, msg); };
-    if (!m || !x) return fail(DRONESIM_EINVAL, "dronesim_mlp_forward_%s: NULL argument");
-    const int rc = check_mlp(m->N, m->d_in, m->h1, m->h2, m->nout, m->out_kind, m->sample_kind, E);
-    if (rc) return rc;
-    if (m->d_in > 16) return fail(DRONESIM_EUNSUPPORTED, "%s path: d_in <= 16");
-    if (!m->w1p || !m->b1 || !m->b2 || !m->b3) return fail(DRONESIM_EINVAL, "dronesim_mlp_forward_%s: NULL weight array");
-    if (E == 0) return DRONESIM_OK;
-    MArgsX a{};
-    a.E = E; a.N = m->N; a.d_in = m->d_in; a.h1 = m->h1; a.h2 = m->h2;
-    a.nc1 = (m->h1 + 31) / 32; a.nc2 = (m->h2 + 31) / 32;
-    a.stages = dronesim_mlp_bf16x3_stages(m->h1, m->h2);
-    if (m->reserved != a.stages)
-        return fail(DRONESIM_EINVAL, "dronesim_mlp_forward_%s: DroneMlpBf16.reserved must hold dronesim_mlp_bf16x3_stages(h1, h2), "
-                                     "the stages per stream of w1p");
-    a.x = x; a.b1 = m->b1; a.b2 = m->b2; a.b3 = m->b3;
-    a.wscale = S::kScaled ? m->wscale : nullptr;
-    a.ws = reinterpret_cast<const char *>(m->w1p);
-    a.trace = kTrace ? dronesim_policy_trace : nullptr;
-    a.fin = make_finish(m->N, m->nout, m->out_kind, m->sample_kind, out, act, act_idx, seed, counter, env_base, t, episode);
     // TILES = 4 (128-row workgroups, one per CU, accumulators in the AGPR half of a 512-register wave) builds and is
     // correct, but hipcc 7.2 places the accumulators badly (1100 v_accvgpr copies, scratch spills whose waits drain the
     // DMA ring): 561 vs 301 us at C3 Gaussian f16x2.  Not instantiated; it needs hand-placed AGPR accumulators.
-    return launch_split<S, 2>(a, m->N, stream);
+    static const PolicyLaunch<MArgsX> variants[2] = {launch_policy<mlp3_split_kernel<SchemeBf16x3, 2>>, launch_policy<mlp3_split_kernel<SchemeF16x2, 2>>};
+    return policy_forward(scheme ? "dronesim_mlp_forward_f16x2" : "dronesim_mlp_forward_bf16x3", "mlp3_split_kernel", kFamSplit, variants, m, c, scheme,
+                          m ? m->reserved : 0, m && m->w1p && m->b1 && m->b2 && m->b3, nullptr, [m, scheme](MArgsX &a, const PolicyPlan &p) {
+        a.nc1 = chunks32(m->h1); a.nc2 = chunks32(m->h2);
+        a.stages = p.stream;
+        a.b1 = m->b1; a.b2 = m->b2; a.b3 = m->b3;
+        a.wscale = scheme ? m->wscale : nullptr;                   // SchemeF16x2::kScaled
+        a.ws = reinterpret_cast<const char *>(m->w1p);
+    });
 }
 
 }   // namespace
 
-// stages per (agent, wave) stream: wave 0 owns the most chunks; + padding for the run-ahead requests
-extern "C" int dronesim_mlp_bf16x3_stages(int h1, int h2)
-{
-    const int nc1 = (h1 + 31) / 32, nc2 = (h2 + 31) / 32, nm = (nc2 + 3) / 4;
-    return nc1 * (1 + 2 * nm) + 2 * nm + kStreamPadX;
-}
+extern "C" int dronesim_mlp_bf16x3_stages(int h1, int h2) { return split_stages(chunks32(h1), chunks32(h2)); }
 
 extern "C" int dronesim_mlp_forward_bf16x3(const DroneMlpBf16 *m, const float *x, float *out, float *act, int32_t *act_idx,
                                            uint64_t seed, uint64_t counter, int64_t env_base,
                                            const int32_t *t, const int32_t *episode, int E, void *stream)
 {
-    return mlp_forward_split<SchemeBf16x3>("bf16x3", m, x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream);
+    return mlp_forward_split(0, m, {x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream});
 }
 
 extern "C" int dronesim_mlp_forward_f16x2(const DroneMlpBf16 *m, const float *x, float *out, float *act, int32_t *act_idx,
                                           uint64_t seed, uint64_t counter, int64_t env_base,
                                           const int32_t *t, const int32_t *episode, int E, void *stream)
 {
-    return mlp_forward_split<SchemeF16x2>("f16x2", m, x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream);
+    return mlp_forward_split(1, m, {x, out, act, act_idx, seed, counter, env_base, t, episode, E, stream});
 }

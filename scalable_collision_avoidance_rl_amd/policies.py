@@ -181,7 +181,8 @@ def pack_f32_fragments(w):
     return frag.reshape(n, nc, ns, 2, 64, 4).contiguous()
 
 
-RT_CHUNKS, RT_PAD = 7, 4          # csrc/policy_rowtile.hip: kRtChunks (output chunks a wave keeps per pass), kRtPad (zero blocks behind a stream)
+RT_CHUNKS, RT_PAD = 7, 4          # csrc/policy_common.hpp: kRtChunks (output chunks a wave keeps per pass), kRtPad (zero blocks behind a stream)
+RT16_PAD = 3 * 4                  # ... kR16PadSupers: the three empty super-stages (of four blocks) `dronesim_mlp_rt16_blocks` adds behind a stream
 
 
 def pack_f32_rowtile_stream(w1, b1, w2, w3):
@@ -256,7 +257,7 @@ def pack_f16_rowtile_stream(w1, w2, blocks, w3=None):
                 seq.append(torch.stack([f2[:, c2, 2 * c1, 0], f2[:, c2, 2 * c1, 1], f2[:, c2, 2 * c1 + 1, 0], f2[:, c2, 2 * c1 + 1, 1]], dim=1))
         for c2 in (chunks if f3 is not None else ()):
             seq.append(torch.stack([f3[:, 0, 2 * c2, 0], f3[:, 0, 2 * c2, 1], f3[:, 0, 2 * c2 + 1, 0], f3[:, 0, 2 * c2 + 1, 1]], dim=1))
-    assert len(seq) <= blocks - 12
+    assert len(seq) <= blocks - RT16_PAD
     pad = torch.zeros_like(seq[0])
     seq += [pad] * (blocks - len(seq))
     return torch.stack(seq, dim=1).contiguous()

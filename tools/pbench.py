@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Developer benchmark: batched policy forward (csrc/policy_*.hip; default: policy_rowtile.hip) alone and inside the rollout loop
-obs -> sample_action -> env.step (hipGraph replay)."""
+obs -> sample_action -> env.step (hipGraph replay).  The spec `host` instead times the entry points' host side: eager
+`BatchedMLP.forward` at E = 1, us per call."""
+import time
 import os
 import sys
 
@@ -21,6 +23,8 @@ def rnd_policy(kind, N, d, dev, precision="f32"):
         h1 = h2 = 300; nout = 16; ok, sk = 1, 1
     elif kind == "gaussian":
         h1 = h2 = 400; nout = 4; ok, sk = 2, 2
+    elif kind == "small":                     # (host_time: a kernel of a few us)
+        h1 = h2 = 32; nout = 4; ok, sk = 2, 2
     else:
         h1 = h2 = 200; nout = 1; ok, sk = 0, 0
     return BatchedMLP(r(N, d, h1), r(N, h1), r(N, h1, h2), r(N, h2), r(N, h2, nout), r(N, nout), ok, sk, device=dev, precision=precision,
@@ -44,7 +48,29 @@ def timeit(fn, steps=20, reps=5):
     return float(np.median(ts))
 
 
+def host_time(calls=2000, batches=7):
+    """Eager per-call time of `forward` at E = 1 on 4 agents with h1 = h2 = 32 (the kernel is a few us, shorter than the host path -- the
+    entry point's checks, its plan and the launch -- so the calls queue up behind the host): median over `batches` of (`calls` calls, one
+    sync at the end) / calls, per precision."""
+    for prec in os.environ.get("PB_PREC", "f32,bf16x3,f16x2,bf16").split(","):
+        pol, _ = rnd_policy("small", 4, 6, torch.device("cuda", torch.cuda.current_device()), prec)
+        z = torch.rand(1, 4, 6, device=pol.device)
+        out = torch.empty(1, 4, 4, device=pol.device)
+        ts = []
+        for _ in range(batches + 1):                                # (the first batch warms up)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                pol.forward(z, out=out)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / calls * 1e6)
+        print(f"host     small {prec:>6}: forward at E = 1 {float(np.median(ts[1:])):8.2f} us/call (eager, {batches} x {calls} calls)", flush=True)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["host"]:
+        host_time()
+        sys.exit(0)
     for spec in (sys.argv[1:] or ["c3", "c2", "c5"]):
         N, E, G, delta = PRESETS[spec]
         env = drones(N, 0, [G, G], "O", deltas=np.ones(N) * delta, simplify_zstate=True, n_envs=E, batched=True, seed=1)
