@@ -614,13 +614,6 @@ Layout layout_of(const DroneMlp *m, int rows_per_chunk, unsigned form)
     return y;
 }
 
-int launch_status()
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
-}
-
 // The chunked chain of the header comment over all R rows; the job validated by the entry points.
 int run_chain(const ChainJob &j)
 {
@@ -696,7 +689,7 @@ int run_chain(const ChainJob &j)
         if (gate) hipLaunchKernelGGL(kl_sum_kernel, agents, block, 0, st, Kp, Rc, rc, first, last, (double)R, Kacc, kl, active);
         if (vclip) hipLaunchKernelGGL(row_sum_kernel, agents, block, 0, st, S, Rc, rc, first, last, (float)R, j.clip_fraction, active);
     }
-    return launch_status();
+    return dronesim_launched();
 }
 
 int fail_at(const char *where, const char *what)
@@ -785,7 +778,7 @@ int adam_step(const char *where, const DroneMlp *m, float *grad, float *m1, floa
     hipLaunchKernelGGL(grad_norm_kernel, dim3(m->N), dim3(kThreads), 0, st, grad, t, step, grad_norm, active);
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((t.per_agent + kThreads - 1) / kThreads), m->N), dim3(kThreads), 0, st,
                        grad, m1, m2, p, t, step, grad_norm, lr, beta1, beta2, eps, max_norm, active);
-    return launch_status();
+    return dronesim_launched();
 }
 
 }  // namespace
@@ -932,5 +925,5 @@ extern "C" int dronesim_kl_gate(const float *kl, float target_kl, int32_t *activ
     if (!(target_kl > 0.f) || isinf(target_kl)) return fail_at(where, "target_kl must be finite and > 0");
     hipLaunchKernelGGL(kl_gate_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, kl,
                        target_kl, active, taken, N, reset);
-    return launch_status();
+    return dronesim_launched();
 }

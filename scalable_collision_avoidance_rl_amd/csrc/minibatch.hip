@@ -128,9 +128,7 @@ int dronesim_row_permutation(int R, uint64_t seed, const int32_t *counter, int32
     const int h = bits <= 2 ? 1 : (bits + 1) / 2;                 // max(1, ceil(bits / 2))
     hipLaunchKernelGGL(row_permutation_kernel, dim3((unsigned)(((uint32_t)R + 255u) / 256u)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        (uint32_t)R, h, (uint32_t)seed, (uint32_t)(seed >> 32), counter, perm);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(err));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 int dronesim_gather_rows(const int32_t *perm, int R, int M, int n_arrays, const void *const *src, void *const *dst,
@@ -157,9 +155,7 @@ int dronesim_gather_rows(const int32_t *perm, int R, int M, int n_arrays, const 
     }
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((int64_t)R + kTilePos - 1) / kTilePos)), dim3(kGatherThreads), 0,
                        static_cast<hipStream_t>(stream), a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(err));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 }   // extern "C"

@@ -509,9 +509,7 @@ int launch_policy(const char *what, const PolicyPlan &p, void *stream, const Arg
         if (rc) return rc;
     }
     hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(p.threads), p.lds, static_cast<hipStream_t>(stream), a.x, a.E, a.N, a.d_in, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dronesim_fail(DRONESIM_ELAUNCH, hipGetErrorString(e));
-    return DRONESIM_OK;
+    return dronesim_launched();
 }
 
 // The front door of the five entry points: the NULL m / x check, check_mlp and the plan's refusals, E = 0, the fields every argument

@@ -16,8 +16,9 @@ from tests import ppo_ref as P
 
 ZERO_MARGIN = 1e-4          # rows whose standardised advantage is this close to 0 may take either side of the clip test in float32
 
-# (R, N) of the standardisation tests: one row, less than a wave, several slabs, a ragged last slab, column tiles, N % 4 != 0
-STANDARDIZE_SHAPES = [(1, 5), (63, 5), (600, 5), (8193, 64), (1000, 70), (257, 256), (4099, 3)]
+# (R, N) of the standardisation tests: one row, less than a wave, several slabs, a ragged last slab, column tiles, N % 4 != 0,
+# and 257 lane groups of four (the tile is capped at 256: a second column tile with one live group)
+STANDARDIZE_SHAPES = [(1, 5), (63, 5), (600, 5), (8193, 64), (1000, 70), (257, 256), (4099, 3), (257, 1028)]
 HARD_COLUMN, CONSTANT_COLUMN = 0, 1
 
 

@@ -3,7 +3,7 @@ dronesim_obsnorm_apply): the two-pass moments over the finite values, Chan's mer
 the GPU tests, made here once so that the host tier can check that they do their job."""
 import torch
 
-SHAPES = [(5, 6), (6, 6), (64, 6), (70, 15), (256, 6)]      # (N, d): C = 30, 36, 384, 1050, 1536
+SHAPES = [(5, 6), (6, 6), (64, 6), (70, 15), (256, 6), (257, 4)]      # (N, d): C = 30, 36, 384, 1050, 1536, 1028
 WINDOW_ROWS = (4099, 64, 1, 777)
 HARD, CONSTANT, SMALL, WIDE, INF_COLUMN, NAN_COLUMN = 0, 1, 2, 3, 4, 5
 CONSTANT_VALUE = 3.25

@@ -1,7 +1,8 @@
 """GPU tests of the observation normaliser's kernels (csrc/obsnorm.hip) through `ObsNormalizer`: the running statistics against
 the float64 restatement (tests/obsnorm_ref.py) over four successive windows, the exact cases, determinism (run to run, and
 16-byte against 4-byte aligned inputs) and the map.  Shapes: C = N d = 30 (4-byte path), 36 (C % 4 == 0 but not % 64), 384
-(% 64), 1050 (two column tiles, odd) and 1536; windows of 4099, 64, 1 and 777 rows."""
+(% 64), 1050 (two column tiles, odd), 1536 and 1028 (257 lane groups of four: the tile capped at 256, a second tile with one live
+group); windows of 4099, 64, 1 and 777 rows."""
 import pytest
 
 from tests import obsnorm_ref as OR

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Bit-for-bit A/B of the learner-side native entry points between two builds of libdronesim.so, for refactorings of
-csrc/learner.hip / csrc/standardize.hip / csrc/scans.hip / csrc/evaluate.hip (scan_common.hpp) that claim "same results".
+csrc/learner.hip / csrc/standardize.hip / csrc/obsnorm.hip (colstats_common.hpp) / csrc/scans.hip / csrc/evaluate.hip
+(scan_common.hpp) that claim "same results".
 Two runs, two processes, the library chosen by DRONESIM_LIB:
 
     DRONESIM_LIB=before.so python tools/learner_ab.py --dump ab.npz
@@ -16,9 +17,17 @@ The scans (`run_scans`): windows of T = 1, 8, 9, 17 steps (a partial stage, one 
 E x N = 333 x 2 (one column per thread, ragged last wave, a wave spans 32 envs: per-thread flags) and 5 x 64 (cooperative
 flags), and T = 9 over 65536 x 4 and 1025 x 256 (column quadruples without and with cooperative flags, ragged last
 workgroup); `done` set at t = 0, t = T - 1 and in between, or NULL; ends of M = 2 slots with 0 .. 3 truncated ends per env;
-G only, A only and both; the evaluation with and without V; the advantages with K1 = 3 and 2 and a -1 neighbour."""
+G only, A only and both; the evaluation with and without V; the advantages with K1 = 3 and 2 and a -1 neighbour.
+The column statistics (`run_colstats`): `dronesim_standardize` on tests/entropy_ref.STANDARDIZE_SHAPES -- one row; tw = 5 with
+q = 204, no power of two; 129 slabs in 16 runs; V = 1 on a wide row; and (257, 1028), 257 lane groups of four, where the tile is
+capped at 256 and a second column tile has one live group --, each out of place, in place and from a base that is 4-byte but not
+16-byte aligned, with and without `stats`; `dronesim_obsnorm_update` over the four windows (4099, 64, 1 and 777 rows, with their NaN
+and inf entries) of tests/obsnorm_ref.SHAPES, aligned and offset, `state` and `table` kept after every window;
+`dronesim_obsnorm_apply` on the same windows, clamped at 10 and unclamped, in place and out of place, aligned and offset, and on
+one matrix of exactly the 32 MiB from which the map streams (8192 x 1024) and one a row short of it."""
 import argparse
 import ctypes as C
+import hashlib
 import os
 import sys
 import types
@@ -82,15 +91,78 @@ def run_all():
         _native.check(lib.dronesim_kl_gate(kl.data_ptr(), 0.01, active.data_ptr(), taken.data_ptr(), N, reset, None), "dronesim_kl_gate")
         keep(f"kl_gate.reset{reset}", active, taken)
 
-    for rows, cols in ((200, 3), (128, 64)):
-        v, n = rnd(rows, cols) * 3 - 500, C.c_size_t(0)
-        _native.check(lib.dronesim_standardize_workspace(rows, cols, C.byref(n)), "dronesim_standardize_workspace")
-        ws, y, stats = torch.empty(n.value // 8, dtype=torch.float64, device=DEV), torch.empty_like(v), torch.zeros(2, cols, device=DEV)
-        _native.check(lib.dronesim_standardize(v.data_ptr(), y.data_ptr(), stats.data_ptr(), rows, cols, 1e-8, ws.data_ptr(), n.value,
-                                               None), "dronesim_standardize")
-        keep(f"standardize.{rows}x{cols}", y, stats)
+    run_colstats(out)
     run_scans(out)
     return out
+
+
+def run_colstats(out):
+    """`dronesim_standardize` and the observation normaliser's two entry points (csrc/colstats_common.hpp) on the shapes of their
+    tests; a buffer above 1 MiB is kept as its SHA-256."""
+    from tests import entropy_ref as ER
+    from tests import obsnorm_ref as OR
+    lib = _native.lib()
+
+    def keep(name, *tensors):
+        torch.cuda.synchronize()
+        for k, t in enumerate(tensors):
+            a = t.detach().contiguous().view(torch.int32).cpu().numpy()
+            out[f"{name}.{k}"] = np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8) if a.nbytes > 1 << 20 else a.copy()
+
+    def offset(t):
+        """The same values at a base that is 4-byte but not 16-byte aligned."""
+        v = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)[1:].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4
+        return v
+
+    def workspace(query, rows, cols):
+        n = C.c_size_t(0)
+        _native.check(query(rows, cols, C.byref(n)), "workspace")
+        return torch.empty(n.value // 8, dtype=torch.float64, device=DEV), n.value
+
+    for rows, cols in dict.fromkeys(list(ER.STANDARDIZE_SHAPES) + [(257, 1028)]):
+        x = ER.standardize_case(rows, cols).to(DEV)
+        ws, nb = workspace(lib.dronesim_standardize_workspace, rows, cols)
+        for place, (src, dst) in (("out", (x, torch.empty_like(x))), ("in", (x.clone(), None)), ("offset", (offset(x), offset(x)))):
+            for with_stats in (True, False):
+                a, stats = src.clone() if dst is None else src, torch.zeros(2, cols, device=DEV)
+                y = a if dst is None else dst
+                _native.check(lib.dronesim_standardize(a.data_ptr(), y.data_ptr(), stats.data_ptr() if with_stats else None, rows, cols,
+                                                       1e-8, ws.data_ptr(), nb, None), "dronesim_standardize")
+                keep(f"standardize.{rows}x{cols}.{place}.stats{int(with_stats)}", y, stats)
+
+    for N, d in dict.fromkeys(list(OR.SHAPES) + [(257, 4)]):
+        cols = N * d
+        state = torch.zeros(3, cols, dtype=torch.float64, device=DEV)
+        table = torch.stack([torch.zeros(cols, dtype=torch.float64), torch.ones(cols, dtype=torch.float64)]).to(DEV)
+        windows = [w.to(DEV) for w in OR.windows(N, d)]
+        for k, w in enumerate(windows):
+            ws, nb = workspace(lib.dronesim_obsnorm_workspace, w.shape[0], cols)
+            for place, src in (("aligned", w), ("offset", offset(w))):
+                st, tb = state.clone(), table.clone()
+                _native.check(lib.dronesim_obsnorm_update(src.data_ptr(), w.shape[0], cols, st.data_ptr(), tb.data_ptr(), 1e-8, ws.data_ptr(),
+                                                          nb, None), "dronesim_obsnorm_update")
+                keep(f"obsnorm.{N}x{d}.update{k}.{place}", st, tb)
+            state, table = st, tb
+        for k, w in enumerate(windows):
+            for clip in (10.0, 0.0):
+                for place, (src, dst) in (("out", (w, torch.empty_like(w))), ("in", (w, None)), ("offset", (offset(w), offset(w))),
+                                          ("offset_in", (offset(w), None))):
+                    a = src.clone() if dst is None and place == "in" else src
+                    y = a if dst is None else dst
+                    _native.check(lib.dronesim_obsnorm_apply(a.data_ptr(), y.data_ptr(), w.shape[0], cols, table.data_ptr(), clip, None),
+                                  "dronesim_obsnorm_apply")
+                    keep(f"obsnorm.{N}x{d}.apply{k}.clip{clip:g}.{place}", y)
+
+    # the map's two instances: a matrix of exactly the 32 MiB from which it streams (non-temporal accesses), and one a row short
+    cols, gen = 1024, torch.Generator().manual_seed(20251020)
+    x = (torch.randn(8192, cols, generator=gen) * 3 + 1).to(DEV)
+    table = torch.stack([torch.randn(cols, generator=gen, dtype=torch.float64), torch.rand(cols, generator=gen, dtype=torch.float64) + 0.5]).to(DEV)
+    for rows in (8192, 8191):
+        y = torch.empty(rows, cols, device=DEV)
+        _native.check(lib.dronesim_obsnorm_apply(x.data_ptr(), y.data_ptr(), rows, cols, table.data_ptr(), 10.0, None), "dronesim_obsnorm_apply")
+        keep(f"obsnorm.apply.{rows}x{cols}", y)
 
 
 SCAN_SHAPES = ((333, 2, (1, 8, 9, 17)), (5, 64, (1, 8, 9, 17)), (65536, 4, (9,)), (1025, 256, (9,)))
