@@ -129,6 +129,21 @@ def pack_split_streams(w1, w2, w3, stages, scheme="bf16x3"):
     f2 = pack_split_fragments(w2, 2 * nc1, nc2, "accumulator", scheme).reshape(n, nc2 * 2 * nc1, P, 64, 8)  # [c2 * KS2 + s]
     f3 = pack_split_fragments(w3, 2 * nc2, 1, "accumulator", scheme).reshape(n, 2 * nc2, P, 64, 8)         # [s]
     table = torch.cat([f1, f2, f3, torch.zeros_like(f1[:, :1])], dim=1)
+    return table[:, _split_stream_order(nc1, nc2, stages, table.device)].contiguous()
+
+
+_SPLIT_STREAM_ORDER = {}          # (nc1, nc2, stages, device) -> `_split_stream_order`'s index tensor
+
+
+def _split_stream_order(nc1, nc2, stages, device):
+    """``[4, stages]`` (int64, on `device`): per wave the entries of `pack_split_streams`' table -- L1 chunks, then L2 (c2, k-step)
+    fragments, then L3 k-steps, then one zero stage -- in the kernel's consumption order.  It depends on the shape alone and is made
+    ONCE per (shape, device): building it copies a host list to the device, which a stream capture does not permit, and the first
+    packing of a network is its constructor's while every later one (`BatchedMLP.refresh_weights`) may run inside a captured graph."""
+    import torch
+    key = (nc1, nc2, stages, str(device))
+    if key in _SPLIT_STREAM_ORDER:
+        return _SPLIT_STREAM_ORDER[key]
     o2, o3, zero = nc1, nc1 + nc2 * 2 * nc1, nc1 + nc2 * 2 * nc1 + 2 * nc2
     streams = []
     for w in range(4):
@@ -144,8 +159,8 @@ def pack_split_streams(w1, w2, w3, stages, scheme="bf16x3"):
             seq += [o3 + 2 * c2, o3 + 2 * c2 + 1]
         assert len(seq) <= stages
         streams.append(seq + [zero] * (stages - len(seq)))
-    idx = torch.tensor(streams, device=table.device)                                             # [4, stages]
-    return table[:, idx].contiguous()
+    _SPLIT_STREAM_ORDER[key] = torch.tensor(streams, device=device)                              # [4, stages]
+    return _SPLIT_STREAM_ORDER[key]
 
 
 def f16_weight_scales(w1, w2, w3, target_exp=14):
@@ -357,7 +372,8 @@ class BatchedMLP:
         taken when the object was built: an in-place update
         of ``self.w2`` alone (optimizer step) would otherwise leave the kernel on a mix of new and stale weights.
         Optional arguments are copied into the live tensors first; every packed image is then re-made IN PLACE (same
-        device addresses), so a captured hipGraph that holds them stays valid."""
+        device addresses), so a captured hipGraph that holds them stays valid.  The re-packing is device work only (no copy
+        from the host, no synchronisation), so the call itself may be captured: the learners' ``train()`` relies on it."""
         for name, val in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("w3", w3), ("b3", b3)):
             if val is not None:
                 getattr(self, name).copy_(self._torch.as_tensor(val, dtype=self._torch.float32))

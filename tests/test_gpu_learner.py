@@ -266,23 +266,43 @@ def test_clip_and_adam_match_torch_over_five_steps(torch, kind):
 N_RS, G_RS, E_RS, T_RS = 16, 10.0, 32, 12
 
 
-def storage_setup(torch, seed_env=5):
-    """A batched env whose episodes end inside the first window, a softmax-16 actor, a critic, a real RolloutStorage."""
-    from scalable_collision_avoidance_rl_amd import drones
-    from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
-    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
-    from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
-    N, G, E, T = N_RS, G_RS, E_RS, T_RS
+def storage_weights(torch, N=N_RS, actor_hidden=(48, 48), critic_hidden=(32, 32), actor_kind="softmax"):
+    """The seeded networks of `storage_parts` (CPU tensors; needs no GPU): ``(wa, wc)``, a softmax-16 actor -- or, with
+    ``actor_kind="gaussian"``, a four-output actor with the block-diagonal layer 3 -- and a critic, on 6 inputs."""
     gp = torch.Generator().manual_seed(0)
     rw = lambda *s: (torch.rand(*s, generator=gp) * 2 - 1) * 0.2
-    wa = [rw(N, 6, 48), rw(N, 48), rw(N, 48, 48), rw(N, 48), rw(N, 48, 16), rw(N, 16)]
-    wc = [rw(N, 6, 32), rw(N, 32), rw(N, 32, 32), rw(N, 32), rw(N, 32, 1), rw(N, 1)]
-    env = drones(N, 0, [G, G], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
+    (a1, a2), (c1, c2), nout = actor_hidden, critic_hidden, {"softmax": 16, "gaussian": 4}[actor_kind]
+    wa = [rw(N, 6, a1), rw(N, a1), rw(N, a1, a2), rw(N, a2), rw(N, a2, nout), rw(N, nout)]
+    wc = [rw(N, 6, c1), rw(N, c1), rw(N, c1, c2), rw(N, c2), rw(N, c2, 1), rw(N, 1)]
+    if actor_kind == "gaussian":
+        wa[4] = wa[4] * R.structural_mask(2, wa)
+    return wa, wc
+
+
+def storage_parts(torch, seed_env=5, N=N_RS, E=E_RS, T=T_RS, t0=193, config="f32", actor_kind="softmax", actor_hidden=(48, 48),
+                  critic_hidden=(32, 32)):
+    """``(env, actor, critic, storage)``: a batched env (k_closest 2, auto_reset) whose clock starts at ``t0`` -- the time limit
+    fires ``199 - t0`` steps into the first window --, the networks of `storage_weights` built with the policy configuration
+    ``config`` (tests/helpers.py: POLICY_CONFIGS; actor AND critic), a real RolloutStorage of T steps."""
+    from scalable_collision_avoidance_rl_amd import drones
+    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+    from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
+    wa, wc = storage_weights(torch, N, actor_hidden, critic_hidden, actor_kind)
+    env = drones(N, 0, [G_RS, G_RS], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=DEV, seed=seed_env, auto_reset=True)
-    env.t.fill_(193)                                       # the time limit fires inside the first window
-    actor, critic = BatchedMLP(*wa, 1, 1, device=DEV, seed=7), BatchedMLP(*wc, 0, 0, device=DEV)
-    st = RolloutStorage(env, T, actions=True)
-    return env, actor, critic, st, SA2CLearner(actor, critic, 0.99)
+    env.t.fill_(t0)                                        # the time limit fires inside the first window
+    k = {"softmax": 1, "gaussian": 2}[actor_kind]
+    kw = H.policy_kw(config)
+    actor, critic = BatchedMLP(*wa, k, k, device=DEV, seed=7, **kw), BatchedMLP(*wc, 0, 0, device=DEV, **kw)
+    return env, actor, critic, RolloutStorage(env, T, actions=True)
+
+
+def storage_setup(torch, seed_env=5, setup=None, **learner_kw):
+    """A batched env whose episodes end inside the first window, a softmax-16 actor, a critic, a real RolloutStorage
+    (``setup``: other keywords of `storage_parts`) and an `SA2CLearner` (``learner_kw``: its keywords)."""
+    from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
+    env, actor, critic, st = storage_parts(torch, seed_env, **(setup or {}))
+    return env, actor, critic, st, SA2CLearner(actor, critic, 0.99, **learner_kw)
 
 
 def rollout_window(env, actor, st):

@@ -1613,32 +1613,63 @@ def test_episode_statistic_kernel(torch):
 
 
 # ------------------------------------------------------------------------------- round 4: ADVICE r3 items on the policies
-@pytest.mark.parametrize("prec", ["f32", "bf16x3", "f16x2", "f16x2-split", "bf16"])
+@pytest.mark.parametrize("prec", H.POLICY_CONFIGS)
 def test_policy_weight_updates_reach_the_kernel_after_refresh(torch, prec):
-    """The kernels read PACKED images of the weights (snapshots).  After an in-place update of the live tensors the
-    outputs are stale until `refresh_weights()` re-packs -- into the SAME device buffers (a captured graph stays valid) --
-    and then equal a freshly built network's (SAC_agents.py: the actors are re-evaluated after every optimiser step)."""
+    """The kernels read PACKED images of the weights (snapshots, `BatchedMLP._packed`).  After an in-place update of the live tensors
+    `refresh_weights()` re-packs -- into the SAME device buffers, so a captured graph that holds them stays valid: a graph captured
+    BEFORE the update replays the new network -- and the outputs then equal a freshly built network's (SAC_agents.py: the actors are
+    re-evaluated after every optimiser step).  Every configuration has an image except the plain [N, h1, h2] array of the C ABI."""
     from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
     N, E, d, h, nout = 6, 70, 6, 96, 4
     g = torch.Generator().manual_seed(3)
     r = lambda *s: (torch.rand(*s, generator=g) * 2 - 1) * 0.3
     w = [r(N, d, h), r(N, h), r(N, h, h), r(N, h), r(N, h, nout), r(N, nout)]
-    pol = BatchedMLP(*w, 2, 0, device="cuda", **_prec_kw(prec))                  # ("cuda" without an index is accepted)
+    kw = H.policy_kw(prec)
+    pol = BatchedMLP(*w, 2, 0, device="cuda", **kw)                             # ("cuda" without an index is accepted)
     x = torch.rand(E, N, d, device="cuda:0") * 2 - 1
     out0 = pol.forward(x).clone()
-    ptrs = [getattr(pol, n).data_ptr() for n in ("_w1p", "_w2p", "_w3p") if getattr(pol, n, None) is not None]
+    ptrs = {name: image.data_ptr() for name, image in pol._packed.items()}
+    if prec == "f32-w2-unpacked":
+        assert pol._packed == {}
+    else:
+        assert ptrs and all(ptrs.values())
+    # the forward alone in a graph (one kernel, no parallel branches), captured on the weights as built
+    buf = torch.empty_like(out0)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        pol.forward(x, out=buf)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        pol.forward(x, out=buf)
+    buf.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(buf, out0)
     w2 = [t * 1.5 + 0.01 for t in w]
     for name, t in zip(("w1", "b1", "w2", "b2", "w3", "b3"), w2):
         getattr(pol, name).copy_(t.to("cuda:0"))                                # an in-place update of the live tensors
     graph_out = torch.empty_like(out0)
     pol.refresh_weights()
-    assert ptrs == [getattr(pol, n).data_ptr() for n in ("_w1p", "_w2p", "_w3p") if getattr(pol, n, None) is not None]
+    assert ptrs == {name: image.data_ptr() for name, image in pol._packed.items()}
+    for name, image in pol._pack().items():
+        assert torch.equal(pol._packed[name], image), name
     out1 = pol.forward(x, out=graph_out)                                        # out= on device "cuda:0" with a "cuda" policy
-    ref = BatchedMLP(*w2, 2, 0, device="cuda:0", **_prec_kw(prec)).forward(x)
+    ref = BatchedMLP(*w2, 2, 0, device="cuda:0", **kw).forward(x)
     assert torch.equal(out1, ref) and not torch.equal(out1, out0)
+    buf.zero_()
+    graph.replay()                                                              # the graph holds the images' addresses
+    torch.cuda.synchronize()
+    assert torch.equal(buf, ref) and not torch.equal(buf, out0)
     pol.refresh_weights(w2=w[2])                                                # the keyword form copies, then re-packs
     w3 = list(w2); w3[2] = w[2]
-    assert torch.equal(pol.forward(x), BatchedMLP(*w3, 2, 0, device="cuda:0", **_prec_kw(prec)).forward(x))
+    ref3 = BatchedMLP(*w3, 2, 0, device="cuda:0", **kw).forward(x)
+    assert torch.equal(pol.forward(x), ref3)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(buf, ref3)
 
 
 def test_packed_w2_must_be_aligned(torch):

@@ -136,23 +136,11 @@ def test_logp_pass_matches_float64_and_the_head_bit_for_bit(torch):
 N_RS, G_RS, E_RS, T_RS = TG.N_RS, TG.G_RS, TG.E_RS, TG.T_RS
 
 
-def storage_setup(torch, seed_env=5, **kw):
-    """`test_gpu_learner.storage_setup` with a `PPOLearner`: a batched env whose episodes end inside the first window, a
-    softmax-16 actor, a critic, a real RolloutStorage."""
-    from scalable_collision_avoidance_rl_amd import drones
+def storage_setup(torch, seed_env=5, setup=None, **kw):
+    """`test_gpu_learner.storage_setup` with a `PPOLearner` (``kw``: its keywords): a batched env whose episodes end inside the
+    first window, a softmax-16 actor, a critic, a real RolloutStorage (``setup``: keywords of `test_gpu_learner.storage_parts`)."""
     from scalable_collision_avoidance_rl_amd.learner import PPOLearner
-    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
-    from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
-    N, G, E, T = N_RS, G_RS, E_RS, T_RS
-    gp = torch.Generator().manual_seed(0)
-    rw = lambda *s: (torch.rand(*s, generator=gp) * 2 - 1) * 0.2
-    wa = [rw(N, 6, 48), rw(N, 48), rw(N, 48, 48), rw(N, 48), rw(N, 48, 16), rw(N, 16)]
-    wc = [rw(N, 6, 32), rw(N, 32), rw(N, 32, 32), rw(N, 32), rw(N, 32, 1), rw(N, 1)]
-    env = drones(N, 0, [G, G], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
-                 device=DEV, seed=seed_env, auto_reset=True)
-    env.t.fill_(193)                                       # the time limit fires inside the first window
-    actor, critic = BatchedMLP(*wa, 1, 1, device=DEV, seed=7), BatchedMLP(*wc, 0, 0, device=DEV)
-    st = RolloutStorage(env, T, actions=True)
+    env, actor, critic, st = TG.storage_parts(torch, seed_env, **(setup or {}))
     return env, actor, critic, st, PPOLearner(actor, critic, 0.99, **kw)
 
 
