@@ -8,6 +8,7 @@ each (E x rounds >= --episodes), every step of every env in one launch, and the 
     python examples/benchmark_agent.py --critics discrete-A2Ccritics.pth --actors discrete-A2Cactors.pth [--models models]
     python examples/benchmark_agent.py --controller proportional            # the commented alternatives of :76-77
     python examples/benchmark_agent.py ... --obs-norm stats.pt             # the observation statistics the networks were trained with
+    python examples/benchmark_agent.py ... --safety                        # closest approach, arrival and formation error per episode
 
 ``--obs-norm FILE``: an `ObsNormalizer.state_dict()` saved with ``torch.save``; the actor and the critic then read the normalised
 observation (the reference's files carry no statistics, so there is none by default).
@@ -35,6 +36,7 @@ def main():
     ap.add_argument("--envs", type=int, default=512)
     ap.add_argument("--precision", default="f32")
     ap.add_argument("--obs-norm", default=None, help="a torch.save'd ObsNormalizer.state_dict() (network actors only)")
+    ap.add_argument("--safety", action="store_true", help="also reduce and print the per-episode safety tables")
     a = ap.parse_args()
 
     if a.controller:
@@ -57,7 +59,7 @@ def main():
     if a.obs_norm:
         import torch
         obs_norm = ObsNormalizer(n_agents, env.local_state_space, env.device).load_state_dict(torch.load(a.obs_norm))
-    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm)
+    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety)
     ev.run(rounds)
     s = ev.summary()
     print(f"Episodes {s['episodes']} - Average Reward/Collisions/Steps: {s['mean_return']:.1f}/{s['mean_collisions']:.2f}/"
@@ -70,6 +72,13 @@ def main():
     pair = lambda j: hist[lo + 2 * j:lo + 2 * j + 2].sum() / max(hist.sum(), 1.0)
     print(f"Runs with 0 coll. = {pair(0) * 100:.2f}%. 2 coll. = {pair(1) * 100:.2f}%")             # :151
     print(f"(episodes without any collision: {s['zero_collision_share'] * 100:.2f}%)")
+    if a.safety:                                             # (no reference line: the reference logs none of these)
+        f = ev.safety_summary()
+        fmt = lambda x, spec: "-" if x is None else format(x, spec)
+        print(f"Arrived = {f['arrived_share'] * 100:.2f}%. Arrived without a collision = {f['success_share'] * 100:.2f}%. "
+              f"Mean step of an agent's arrival = {fmt(f['mean_arrive_step'], '.1f')}")
+        print(f"Smallest clearance per episode: mean {f['mean_min_clearance']:.3f} m, minimum {fmt(f['min_clearance'], '.3f')} m. "
+              f"Largest final goal distance per episode: mean {f['mean_goal_dist_max']:.3f} m")
 
 
 if __name__ == "__main__":

@@ -370,6 +370,31 @@ int dronesim_episode_eval(const float *reward, const float *true_reward, const i
                           double *agent_return, double *agent_true_return, double *ep_return, double *ep_true_return,
                           float *G, double *mean_adv, int T, int E, int N, void *stream);
 
+/* Per-episode safety tables of the same FIRST episode (L_e as above), from the stored post-step observations: z [T][E][N][k1 c]
+ * float32 (row 0 of a record = x_i - xF_i, row 1 = x_j - x_i of the closest neighbour), nbr [T][E][N][k1] int32 (slot 1 = j, or
+ * -1 for a ghost row), done [T][E] uint8; radius, delta [N] float32.  z_final / nbr_final (same shapes; both or neither): the
+ * terminal observations of an auto_reset window -- the observation of step t is z_final[t] / nbr_final[t] where t = L - 1 and
+ * they are given, z[t] / nbr[t] otherwise.  With |v| = sqrtf(fmaf(vy, vy, vx vx)) and j = nbr[t][e][i][1]:
+ *   clearance(t,e,i) = min(|row 1| - radius[i] - radius[j], delta[i])  where 0 <= j < N,  delta[i] otherwise (a ghost row or
+ *                      any id outside [0, N): radius is never indexed with it)
+ *   min_clearance [E][N] float32     min_{t < L} clearance(t,e,i)
+ *   goal_dist_final [E][N] float32   |row 0| of the observation of step L - 1
+ *   arrive_step [E][N] int32         the smallest t + 1 <= L with |row 0| <= done_radius after step t, -1 if there is none
+ *   ep_min_clearance [E] float32     min_i min_clearance[e][i], agents in ascending order  (needs min_clearance)
+ *   ep_goal_dist_max [E] float32     max_i goal_dist_final[e][i], agents in ascending order  (needs goal_dist_final)
+ *   ep_arrived [E] uint8             1 when no agent has !(goal_dist_final <= done_radius): dronesim_episode_ends' own test, a
+ *                                    non-finite offset counts as outside -- equal to (ends[L-1][e] == 1)  (needs goal_dist_final)
+ * min / max keep a NaN (numpy.minimum / maximum).  Envs with L_e = 0: NaN in the float tables (0 is a meaningful clearance),
+ * arrive_step -1, ep_arrived 0.  Every output but ep_len may be NULL.  EINVAL for a NULL z / nbr / done / radius / delta /
+ * ep_len, exactly one of z_final / nbr_final, T < 0, E < 0, N < 1, N > 1024, k1 < 2, c not in {2, 5}, a NaN done_radius, a
+ * per-env output without the per-agent table it needs.  E = 0 enqueues nothing; T = 0 writes the L = 0 values.  Loads are as
+ * wide as c, k1 and the alignment of z / z_final allow (16, 8 or 4 bytes), never misaligned.  Two launches on `stream` (the
+ * column scan, then one thread per env and table); no atomics, no memset nodes: graph-capturable, bit-identical run to run. */
+int dronesim_episode_safety(const float *z, const int32_t *nbr, const float *z_final, const int32_t *nbr_final, const uint8_t *done,
+                            const float *radius, const float *delta, float done_radius, int T, int E, int N, int k1, int c,
+                            int32_t *ep_len, float *min_clearance, float *goal_dist_final, int32_t *arrive_step,
+                            float *ep_min_clearance, float *ep_goal_dist_max, uint8_t *ep_arrived, void *stream);
+
 /* counts[min(v, n_bins)] += 1 for every e < E with values[e] = v >= 0 and (valid == NULL or valid[e] != 0): counts
  * [n_bins + 1] int64, the last bin takes the overflow (the collision histogram of benchmark_agent.py:148-156).
  * accumulate == 0: the kernel writes the counts itself (no memset); != 0: it adds to what is there.  One launch.    */

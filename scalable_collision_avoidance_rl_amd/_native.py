@@ -36,7 +36,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent",
            "dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
            "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip",
-           "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
+           "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_episode_safety", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
            "dronesim_row_permutation", "dronesim_gather_rows",
            "dronesim_obsnorm_workspace", "dronesim_obsnorm_update", "dronesim_obsnorm_apply",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
@@ -183,7 +183,8 @@ def lib():
         getattr(L, name).restype = C.c_int
     L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
     L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    L.dronesim_episode_eval.restype = L.dronesim_histogram_i32.restype = C.c_int
+    L.dronesim_episode_safety.argtypes = [vp] * 7 + [f32] + [i32] * 5 + [vp] * 7 + [vp]
+    L.dronesim_episode_eval.restype = L.dronesim_histogram_i32.restype = L.dronesim_episode_safety.restype = C.c_int
     # (the four host arrays of dronesim_gather_rows are ctypes arrays: c_void_p / c_int64 times n_arrays)
     L.dronesim_row_permutation.argtypes = [i32, u64, vp, vp, vp]
     L.dronesim_gather_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]

@@ -506,7 +506,7 @@ class drones:
         reproduce every output bit for bit).  With ``auto_reset`` an env that finishes at step s acts at step s + 1 on
         its new episode's positions.  Results do not depend on how T is split into calls.  ``into`` (a
         `rollout_buffer.RolloutStorage` of exactly T steps): the launch fills the storage's own tensors -- the whole window, with
-        the env's current observation as ``z_pre[0]`` -- instead of new ones, and the dict returned holds views of them."""
+        the env's current observation as ``z_pre[0]``, the terminal observations of an auto_reset env in its ``z_final`` / ``nbr_final`` -- instead of new ones, and the dict returned holds views of them."""
         codes = {"proportional": self._native.CONTROL_PROPORTIONAL, "gradient": self._native.CONTROL_GRADIENT}
         if kind not in codes:
             raise ValueError(f"kind must be 'proportional' or 'gradient', got {kind!r}")
@@ -564,7 +564,11 @@ class drones:
             out["z_final"] = torch.zeros(T, E, N, K1 * c, **f32)
             out["nbr_final"] = torch.full((T, E, N, K1), -1, dtype=torch.int32, device=self.device)
             out["pos_final"] = torch.zeros(T, E, N, 2, **f32)
-        ctl = self._make_ctl(out.get("z_final"), out.get("nbr_final"), out.get("pos_final"))
+        zf, nf = out.get("z_final"), out.get("nbr_final")
+        into_final = _into is not None and _into.z_final is not None
+        if into_final and zf is None:                     # the storage's own [T, ...] terminal observations, as step(into=) fills them
+            zf, nf = _into.z_final, _into.nbr_final
+        ctl = self._make_ctl(zf, nf, out.get("pos_final"))
         with torch.cuda.device(self.device):
             if random_actions:
                 rc = self._lib.dronesim_rollout_random(
@@ -586,6 +590,8 @@ class drones:
                     out["true_reward"].data_ptr(), out["z"].data_ptr(), out["nbr_idx"].data_ptr(),
                     out["n_coll"].data_ptr(), out["done"].data_ptr(), E, T, self._stream())
         self._native.check(rc, "dronesim_rollout")
+        if into_final and zf is not _into.z_final:        # (keep_final_obs: the launch wrote this call's own buffers)
+            _into.z_final.copy_(zf); _into.nbr_final.copy_(nf)
         if in_kernel is not None and act is not None:
             out["actions"] = act
         if with_pre and T > 0:

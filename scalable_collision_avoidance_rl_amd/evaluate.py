@@ -17,8 +17,12 @@ import ctypes as C
 import os
 from collections import deque
 
+from ._native import MAX_AGENTS as _MAX_AGENTS
+from .drone_env import DONE_RADIUS
+
 CONTROLLERS = ("proportional", "gradient")       # the commented alternatives of benchmark_agent.py:76-77
 TABLES = ("ep_len", "ep_collisions", "ep_return", "ep_true_return", "agent_return", "agent_true_return", "mean_adv")
+SAFETY_TABLES = ("min_clearance", "goal_dist_final", "arrive_step", "ep_min_clearance", "ep_goal_dist_max", "ep_arrived")
 
 
 def episode_eval(reward, true_reward, n_coll, done, V=None, gamma=0.99, out=None, want_G=True):
@@ -65,6 +69,77 @@ def episode_eval(reward, true_reward, n_coll, done, V=None, gamma=0.99, out=None
     return out
 
 
+def _safety_shapes(z, nbr, done, radius, delta, z_final, nbr_final, done_radius):
+    """(T, E, N, k1, c) of `episode_safety`'s arguments, or ValueError -- shapes only, nothing here touches a device."""
+    import torch
+    if (z_final is None) != (nbr_final is None):
+        raise ValueError("z_final and nbr_final go together: the terminal observations and their neighbour lists; got only one")
+    if isinstance(done_radius, bool) or not float(done_radius) == float(done_radius):
+        raise ValueError(f"done_radius must be a number, got {done_radius!r}")
+    if not all(torch.is_tensor(x) for x in (z, nbr, done, radius, delta)) or z.dim() != 4 or nbr.dim() != 4 or \
+            tuple(nbr.shape[:3]) != tuple(z.shape[:3]):
+        raise ValueError(f"z must be [T,E,N,(k+1)c] and nbr [T,E,N,k+1], got {tuple(getattr(z, 'shape', ()))} and "
+                         f"{tuple(getattr(nbr, 'shape', ()))}")
+    T, E, N, k1 = (int(x) for x in nbr.shape)
+    if k1 < 2:
+        raise ValueError(f"the neighbour lists need slot 1 (the closest neighbour): k+1 = {k1} < 2")
+    c, rest = divmod(int(z.shape[3]), k1)
+    if rest or c not in (2, 5):
+        raise ValueError(f"z holds {int(z.shape[3])} floats per agent for {k1} rows: c must be 2 or 5")
+    if not 1 <= N <= _MAX_AGENTS:
+        raise ValueError(f"N must be in 1..{_MAX_AGENTS}, got {N}")
+    if tuple(done.shape) != (T, E):
+        raise ValueError(f"done must be [T,E] = {(T, E)}, got {tuple(done.shape)}")
+    for name, x in (("radius", radius), ("delta", delta)):
+        if tuple(x.shape) != (N,):
+            raise ValueError(f"{name} must be [N] = ({N},), got {tuple(x.shape)}")
+    if z_final is not None and not (torch.is_tensor(z_final) and torch.is_tensor(nbr_final) and tuple(z_final.shape) == tuple(z.shape)
+                                    and tuple(nbr_final.shape) == tuple(nbr.shape)):
+        raise ValueError(f"z_final / nbr_final must have the shapes of z / nbr, got {tuple(getattr(z_final, 'shape', ()))} and "
+                         f"{tuple(getattr(nbr_final, 'shape', ()))}")
+    return T, E, N, k1, c
+
+
+def episode_safety(z, nbr, done, radius, delta, z_final=None, nbr_final=None, done_radius=DONE_RADIUS, out=None):
+    """`dronesim_episode_safety` on device tensors: the post-step observations ``z [T,E,N,(k+1)c]`` float32 and their
+    neighbour lists ``nbr [T,E,N,k+1]`` int32 (`RolloutStorage.z` / ``.nbr_idx``), ``done [T,E]`` uint8, ``radius, delta [N]``
+    float32, and -- both or neither -- the terminal observations ``z_final`` / ``nbr_final`` of an auto_reset window.  The
+    safety table of the FIRST episode of every env (`episode_eval`'s episode): ``ep_len [E]`` int32; ``min_clearance [E,N]``
+    float32, the smallest gap to the closest neighbour, clipped at the agent's Delta; ``goal_dist_final [E,N]`` float32;
+    ``arrive_step [E,N]`` int32, the first step count at which the agent stood inside its goal disk, -1 if never;
+    ``ep_min_clearance``, ``ep_goal_dist_max [E]`` float32 and ``ep_arrived [E]`` uint8 over the agents.  Envs without an
+    episode get NaN, -1 and 0; min / max keep a NaN.  ``out``: a dict of tensors to write into (the entries it lacks are not
+    computed, except ``ep_len``; a per-env table needs the per-agent one it reduces)."""
+    import torch
+    from . import _native
+    from .rollout_buffer import _prep
+    T, E, N, k1, c = _safety_shapes(z, nbr, done, radius, delta, z_final, nbr_final, done_radius)
+    z, nbr, done = _prep(z, torch.float32), _prep(nbr, torch.int32), _prep(done, torch.uint8)
+    radius, delta = _prep(radius, torch.float32), _prep(delta, torch.float32)
+    if z_final is not None:
+        z_final, nbr_final = _prep(z_final, torch.float32), _prep(nbr_final, torch.int32)
+    lib = _native.lib()
+    dev = z.device
+    shapes = dict(ep_len=(torch.int32, (E,)), min_clearance=(torch.float32, (E, N)), goal_dist_final=(torch.float32, (E, N)),
+                  arrive_step=(torch.int32, (E, N)), ep_min_clearance=(torch.float32, (E,)), ep_goal_dist_max=(torch.float32, (E,)),
+                  ep_arrived=(torch.uint8, (E,)))
+    if out is None:
+        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, (dtype, shape) in shapes.items()}
+    for name, t in out.items():
+        dtype, shape = shapes[name]
+        if not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+    ptr = lambda name: out[name].data_ptr() if name in out else None
+    with torch.cuda.device(dev):
+        rc = lib.dronesim_episode_safety(z.data_ptr(), nbr.data_ptr(), None if z_final is None else z_final.data_ptr(),
+                                         None if nbr_final is None else nbr_final.data_ptr(), done.data_ptr(), radius.data_ptr(),
+                                         delta.data_ptr(), float(done_radius), T, E, N, k1, c, out["ep_len"].data_ptr(),
+                                         ptr("min_clearance"), ptr("goal_dist_final"), ptr("arrive_step"), ptr("ep_min_clearance"),
+                                         ptr("ep_goal_dist_max"), ptr("ep_arrived"), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_episode_safety")
+    return out
+
+
 def histogram_i32(values, n_bins, valid=None, out=None, accumulate=False):
     """`dronesim_histogram_i32`: ``counts[min(v, n_bins)] += 1`` over the entries of ``values`` (int32 device tensor) with
     ``v >= 0`` and ``valid != 0``; ``counts [n_bins + 1]`` int64, the last bin takes the overflow.  ``out`` / ``accumulate``:
@@ -102,7 +177,8 @@ class Evaluator:
     ``actor``: a `BatchedMLP` with a sampling head, or "proportional" / "gradient" (the classical baselines, one
     `rollout_control` launch per round).  ``critic``: a `BatchedMLP` value network (adds ``mean_adv``), network actors only.
     ``obs_norm``: the `ObsNormalizer` the networks were trained with -- both read ``obs_norm(env.z)``; its statistics are never
-    updated here; network actors only.
+    updated here; network actors only.  ``safety=True``: a round also reduces the stored observations to the per-episode
+    safety tables (`episode_safety`: closest approach, final goal distance, arrival); `safety_summary` reports them.
 
     A round is ``env.reset()``, ``T = max_time_steps`` steps into an owned `RolloutStorage`, then the two reductions.  Every env
     contributes exactly one episode per round -- its first one: a fresh episode always ends inside ``max_time_steps``
@@ -113,7 +189,7 @@ class Evaluator:
     Buffers are allocated by the first ``run`` (and again only when ``rounds`` changes); one round can be captured in a
     ``torch.cuda.graph`` after an eager warm-up call."""
 
-    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None):
+    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False):
         from .drone_env import max_time_steps
         if not getattr(env, "batched", False):
             raise ValueError("Evaluator needs the batched (tensor) API of `drones`")
@@ -140,9 +216,11 @@ class Evaluator:
             if obs_norm is not None:
                 obs_norm.check_networks(actor, critic)
         self.actor, self.critic, self.obs_norm = actor, critic, obs_norm
+        self.safety = bool(safety)
         self.T = int(max_time_steps)
         self.storage = None
         self.tables = None
+        self.safety_tables = None
 
     def _alloc(self, rounds):
         import torch
@@ -161,6 +239,13 @@ class Evaluator:
             t["mean_adv"] = torch.zeros(rounds, E, N, **f64)
         self.tables = t
         self._views = [{name: x[r] for name, x in t.items()} for r in range(rounds)]
+        if self.safety:                                     # (ep_len: the same length, written by both reductions)
+            f32 = dict(dtype=torch.float32, device=dev)
+            s = dict(min_clearance=torch.zeros(rounds, E, N, **f32), goal_dist_final=torch.zeros(rounds, E, N, **f32),
+                     arrive_step=torch.zeros(rounds, E, N, **i32), ep_min_clearance=torch.zeros(rounds, E, **f32),
+                     ep_goal_dist_max=torch.zeros(rounds, E, **f32), ep_arrived=torch.zeros(rounds, E, dtype=torch.uint8, device=dev))
+            self.safety_tables = s
+            self._safety_views = [dict({name: x[r] for name, x in s.items()}, ep_len=t["ep_len"][r]) for r in range(rounds)]
 
     def rollout(self):
         """One round's experience: ``env.reset()`` and ``T`` steps into ``self.storage`` (no reduction)."""
@@ -184,7 +269,8 @@ class Evaluator:
         ``ep_collisions`` int32 and ``ep_return``, ``ep_true_return`` float64 ``[rounds, E]`` (benchmark_agent.py:98-101),
         ``agent_return``, ``agent_true_return`` and -- with a critic -- ``mean_adv`` float64 ``[rounds, E, N]`` (:104-106),
         ``collision_hist`` int64 ``[n_bins + 1]`` over all rounds of this call (:148-156; the last bin holds the episodes with
-        ``n_bins`` collisions or more).  No host synchronisation."""
+        ``n_bins`` collisions or more).  With ``safety=True`` also the tables of `episode_safety` (`SAFETY_TABLES`) as
+        ``[rounds, E(, N)]`` tensors, one more call per round.  No host synchronisation."""
         import torch
         rounds = int(rounds)
         if rounds < 1:
@@ -198,6 +284,10 @@ class Evaluator:
                          self.gamma, out=out)
             torch.ne(out["ep_len"], 0, out=self._valid)
             histogram_i32(out["ep_collisions"], self.n_bins, valid=self._valid, out=self.collision_hist, accumulate=r > 0)
+            if self.safety:
+                st.safety(out=self._safety_views[r])
+        if self.safety:
+            return dict(self.tables, collision_hist=self.collision_hist, **self.safety_tables)
         return dict(self.tables, collision_hist=self.collision_hist)
 
     # fixed-length float64 vector of one rank: [episodes, sum return, sum true return, sum collisions, sum length,
@@ -221,6 +311,46 @@ class Evaluator:
         (`sharding.all_gather_stats`) makes the figures global, the same on every rank."""
         from .sharding import all_gather_stats
         return summarize_evaluation(all_gather_stats(self._vector(), group), self.n_bins, self.critic is not None)
+
+
+    # fixed-length float64 vector of one rank: [episodes, arrived, successes, sum ep_min_clearance, min ep_min_clearance (+inf
+    # without an episode), sum ep_goal_dist_max, agents that arrived, sum of their arrive_step]
+    def _safety_vector(self):
+        import torch
+        t, s = self.tables, self.safety_tables
+        if not self.safety:
+            raise RuntimeError("safety_summary needs Evaluator(..., safety=True)")
+        if t is None or s is None:
+            raise RuntimeError("run() first")
+        ok = t["ep_len"] > 0
+        zero, inf = torch.zeros((), dtype=torch.float64, device=ok.device), torch.full((), float("inf"), dtype=torch.float64, device=ok.device)
+        arrived = ok & (s["ep_arrived"] != 0)
+        clr, goal = s["ep_min_clearance"].double(), s["ep_goal_dist_max"].double()
+        there = ok[..., None] & (s["arrive_step"] > 0)
+        cnt = lambda m: m.sum().double().view(1)
+        return torch.cat([cnt(ok), cnt(arrived), cnt(arrived & (t["ep_collisions"] == 0)), torch.where(ok, clr, zero).sum().view(1),
+                          torch.where(ok, clr, inf).min().view(1), torch.where(ok, goal, zero).sum().view(1), cnt(there),
+                          torch.where(there, s["arrive_step"].double(), zero).sum().view(1)])
+
+    def safety_summary(self, group=None):
+        """Host-side safety figures of the last ``run`` of an ``Evaluator(..., safety=True)``: episodes, the share that arrived
+        (every agent inside its goal disk at the end), the share of successes (arrived without a collision), mean and minimum
+        of the episodes' smallest clearance, the mean of their largest final goal distance, the mean step count at which an
+        agent that arrived first stood inside its goal disk.  ONE all-gather of a fixed-length vector, as `summary`."""
+        from .sharding import all_gather_stats
+        return summarize_safety(all_gather_stats(self._safety_vector(), group))
+
+
+def summarize_safety(gathered):
+    """`Evaluator.safety_summary` from the gathered ``[world, 8]`` vectors (host side): sums over the ranks, except the
+    smallest clearance, which is the minimum over them."""
+    g = gathered.double().cpu()
+    tot = g.sum(0)
+    n, eps, agents = int(tot[0]), max(float(tot[0]), 1.0), float(tot[6])
+    return {"episodes": n, "arrived_share": float(tot[1]) / eps, "success_share": float(tot[2]) / eps,
+            "mean_min_clearance": float(tot[3]) / eps, "min_clearance": float(g[:, 4].min()) if n else None,
+            "mean_goal_dist_max": float(tot[5]) / eps, "mean_arrive_step": float(tot[7]) / agents if agents else None,
+            "world_size": int(gathered.shape[0])}
 
 
 def summarize_evaluation(gathered, n_bins, has_critic=True):

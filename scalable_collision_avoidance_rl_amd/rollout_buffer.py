@@ -173,6 +173,15 @@ class RolloutStorage:
         _episode_ends(self.done, self.z_final, drone_env.DONE_RADIUS, M, *self._ends, self.z_trunc)
         return self._ends
 
+    def safety(self, out=None):
+        """The per-episode safety tables of the stored window (`evaluate.episode_safety`): closest approach, final goal
+        distance and arrival step of every agent of every env's first episode, from the stored post-step observations (the
+        terminal ones under auto_reset) and the env's live ``drone_radius`` / ``deltas``."""
+        from .drone_env import DONE_RADIUS
+        from .evaluate import episode_safety
+        return episode_safety(self.z, self.nbr_idx, self.done, self.env._radius, self.env._delta, self.z_final, self.nbr_final,
+                              DONE_RADIUS, out=out)
+
     def advantage(self, V, gamma, G=None):
         """Actor-loss weights from the stored pre-step neighbour lists (`neighbour_advantage`)."""
         G = self.returns(gamma) if G is None else G

@@ -3,10 +3,12 @@
 
   1. `dronesim_episode_eval` on a stored window (with and without V; G written) next to its yardstick, `dronesim_returns` on
      the same rewards in the same session: the scan moves 16 B per element (12 B without V) against the yardstick's 8 B;
-  2. one `Evaluator` round (softmax-16 actor + critic, f16x2) next to the bare loop of examples/rollout_loop.py part 2 (b)
-     without the evaluation.
+  2. `dronesim_episode_safety` on a stored window of observations next to `dronesim_episode_eval, G = NULL` on the same
+     storage: expected = that line scaled by the bytes fetched, counted as whole 64-byte segments touched per record;
+  3. one `Evaluator` round (softmax-16 actor + critic, f16x2) next to the bare loop of examples/rollout_loop.py part 2 (b)
+     without the evaluation, and the same round with safety=True.
 
-    python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
+    python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
 Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
 import argparse
 import ctypes as C
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from scalable_collision_avoidance_rl_amd import _native, drones
-from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, episode_eval
+from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, episode_eval, episode_safety
 from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
 
 
@@ -62,6 +64,33 @@ def kernels(T, E, N, emit):
     us, lo = gtime(lambda: episode_eval(r, tr, n_coll, done, V, 0.99, out=tables))
     emit(dict(what="dronesim_episode_eval, G = NULL", T=T, E=E, N=N, us=us, us_min=lo, bytes_per_element=12, tb_s=r.numel() * 12 / 1e6 / us,
               yardstick_us=us_ret))
+    return done, us
+
+
+def segment_bytes(stride, ranges, records=4096):
+    """Bytes fetched per record when consecutive records of `stride` bytes are read at the byte `ranges` [(lo, hi), ...] and
+    memory moves in whole 64-byte-aligned segments."""
+    touched = set()
+    for i in range(records):
+        for lo, hi in ranges:
+            touched.update(range((i * stride + lo) // 64, (i * stride + hi - 1) // 64 + 1))
+    return len(touched) * 64 / records
+
+
+def safety(T, E, N, k, c, done, us_eval, emit):
+    """`dronesim_episode_safety` with and without terminal observations; yardstick: `dronesim_episode_eval, G = NULL` (12 B per
+    element) measured just before on the same `done`."""
+    dev, k1 = "cuda:0", k + 1
+    z, zf = (torch.randn(T, E, N, k1 * c, device=dev) * 0.3 for _ in range(2))
+    nbr, nf = (torch.randint(-1, N, (T, E, N, k1), device=dev, dtype=torch.int32) for _ in range(2))
+    radius, delta = torch.full((N,), 0.1, device=dev), torch.ones(N, device=dev)
+    nbytes = segment_bytes(4 * k1 * c, [(0, 8), (4 * c, 4 * c + 8)]) + segment_bytes(4 * k1, [(4, 8)])
+    for name, fin in (("dronesim_episode_safety", (None, None)), ("dronesim_episode_safety, z_final", (zf, nf))):
+        out = episode_safety(z, nbr, done, radius, delta, *fin)
+        us, lo = gtime(lambda: episode_safety(z, nbr, done, radius, delta, *fin, out=out))
+        emit(dict(what=name, T=T, E=E, N=N, k=k, c=c, us=us, us_min=lo, bytes_per_element=nbytes, useful_bytes_per_element=20,
+                  tb_s=T * E * N * nbytes / 1e6 / us, yardstick_us=us_eval, expected_us=us_eval * nbytes / 12,
+                  allowed_us=us_eval * nbytes / 12 * 1.25, within_allowance=bool(us <= us_eval * nbytes / 12 * 1.25)))
 
 
 def one_round(E, N, emit):
@@ -81,6 +110,13 @@ def one_round(E, N, emit):
     emit(dict(what="Evaluator round (softmax-16 + critic, f16x2)", T=ev.T, E=E, N=N, us=us_round, us_min=lo_round, bare_loop_us=us_loop,
               bare_loop_us_min=lo_loop, evaluation_us=us_round - us_loop, agent_steps_per_s=E * N * ev.T / (us_round * 1e-6),
               mean_return=s["mean_return"], mean_length=s["mean_length"], zero_collision_share=s["zero_collision_share"]))
+    env2 = drones(N, 0, [G, G], "O", deltas=np.ones(N), simplify_zstate=True, n_envs=E, seed=0, auto_reset=True)
+    ev2 = Evaluator(env2, actor, critic, safety=True)
+    ev2.run(1)
+    us_safe, lo_safe = gtime(lambda: ev2.run(1), calls=1, reps=5)
+    s2 = ev2.safety_summary()
+    emit(dict(what="Evaluator round, safety=True (softmax-16 + critic, f16x2)", T=ev2.T, E=E, N=N, us=us_safe, us_min=lo_safe,
+              plain_round_us=us_round, safety_us=us_safe - us_round, **{k: v for k, v in s2.items() if k != "world_size"}))
 
 
 def main():
@@ -88,6 +124,8 @@ def main():
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--agents", type=int, default=64)
+    ap.add_argument("--k", type=int, default=2, help="k_closest of the safety window's records")
+    ap.add_argument("--c", type=int, default=2, choices=(2, 5), help="floats per row of the safety window's records")
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-round", action="store_true")
     ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
@@ -101,7 +139,8 @@ def main():
         if a.out:
             with open(a.out, "a") as f:
                 f.write(line + "\n")
-    kernels(a.T, a.envs, a.agents, emit)
+    done, us_eval = kernels(a.T, a.envs, a.agents, emit)
+    safety(a.T, a.envs, a.agents, a.k, a.c, done, us_eval, emit)
     if not a.skip_round:
         one_round(a.envs, a.agents, emit)
 
