@@ -7,7 +7,7 @@ actor loss + clip + Adam, for all N agents' networks at once in HIP.
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
                                   [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
                                   [--normalize-advantage] [--minibatches K] [--shuffle-seed S] [--target-kl X] [--vf-clip X]
-                                  [--obs-norm] [--obs-clip X]
+                                  [--obs-norm] [--obs-clip X] [--share all]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -39,6 +39,11 @@ the device.  The rollout feeds the networks ``norm(env.z)``, ``train()`` normali
 window into the statistics as its last work.  One warm-up window of `update` only runs before the first ``train``, so that
 window 0 is not trained on the identity map.  Every episode line then shows the largest ``|mean|`` and the range of the
 columns' standard deviations.  ``--obs-clip X`` clamps the normalised observation to [-X, X] (default 10).
+
+``--share all`` trains ONE actor and ONE critic for the whole team (parameter sharing): the networks are tied
+(`BatchedMLP.tie_weights`) and every update pools the agents' gradients (`dronesim_adam_step_shared`); with ``--target-kl`` the
+team stops together, on the mean of the agents' KL estimates.  After the loop the script prints that agent 0's and agent N-1's
+weights are identical.
 """
 import argparse
 import os
@@ -89,6 +94,7 @@ def main():
     ap.add_argument("--vf-clip", type=float, default=None, help="clipped value loss with this range (--learner ppo; default: off)")
     ap.add_argument("--obs-norm", action="store_true", help="normalise observations with running per-agent statistics on the device")
     ap.add_argument("--obs-clip", type=float, default=10.0, help="clamp of the normalised observation (--obs-norm; default 10)")
+    ap.add_argument("--share", choices=("all",), default=None, help="parameter sharing: one actor and one critic for all agents (default: off)")
     args = ap.parse_args()
     if args.minibatches != 1 and args.learner != "ppo":
         ap.error("--minibatches needs --learner ppo (one update per window is what A2C is)")
@@ -103,6 +109,9 @@ def main():
     gen = torch.Generator().manual_seed(0)
     actor = BatchedMLP(*network(gen, N, [d_in, 300, 300, 16]), 1, 1, device=dev, seed=3)     # DiscreteSoftmaxNN x N
     critic = BatchedMLP(*network(gen, N, [d_in, 200, 200, 1]), 0, 0, device=dev)            # CriticNN x N
+    if args.share:            # one network for the team: every agent starts from agent 0's weights
+        actor.tie_weights(args.share)
+        critic.tie_weights(args.share)
     storage = RolloutStorage(env, T, actions=True)
     norm = ObsNormalizer(N, d_in, dev, clip=args.obs_clip) if args.obs_norm else None
     see = (lambda z: z) if norm is None else norm           # what the networks read of an observation
@@ -111,10 +120,10 @@ def main():
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                              lam=args.lam, time_limit=args.time_limit, ent_coef=args.ent_coef,
                              normalize_advantage=args.normalize_advantage, minibatches=args.minibatches, shuffle_seed=args.shuffle_seed,
-                             target_kl=args.target_kl, vf_clip=args.vf_clip, obs_norm=norm)
+                             target_kl=args.target_kl, vf_clip=args.vf_clip, obs_norm=norm, share=args.share)
     else:
         learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
-                              time_limit=args.time_limit, ent_coef=args.ent_coef, obs_norm=norm)
+                              time_limit=args.time_limit, ent_coef=args.ent_coef, obs_norm=norm, share=args.share)
     if norm is not None:      # one warm-up window of statistics only: window 0 is not trained on the identity map
         storage.begin()
         for t in range(T):
@@ -160,6 +169,9 @@ def main():
     finished = int(storage.done.sum())
     print(f"last window: {finished} finished episodes, {int(n_trunc.sum())} of them truncated by the time limit"
           + (f" ({int(n_trunc.sum()) / finished:.1%})" if finished else ""))
+    if args.share:
+        same = all(torch.equal(getattr(m, n)[0], getattr(m, n)[N - 1]) for m in (actor, critic) for n in ("w1", "b1", "w2", "b2", "w3", "b3"))
+        print(f"share {args.share}: agent 0's and agent {N - 1}'s actor and critic weights are {'identical' if same else 'DIFFERENT'}")
 
 
 if __name__ == "__main__":

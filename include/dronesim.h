@@ -674,6 +674,40 @@ int dronesim_mlp_grad_vclip(const DroneMlp *m, const float *x, int R, float row_
                             float vf_clip, float *grad, float *loss, float *clip_fraction, int rows_per_chunk, void *ws,
                             size_t ws_bytes, void *stream);
 
+/* Parameter sharing across agent groups (tied networks; csrc/learner.hip).  A sharing map ties the weights of the agents of a
+ * group: they are bit-identical before and after every update.  It reaches the device in CSR form, two int32 arrays in DEVICE
+ * memory that the caller builds once: group_ptr [n_groups + 1] and members [N]; the members of group g are
+ * members[group_ptr[g] .. group_ptr[g + 1]), ascending, so the first is the group's LEADER (its lowest-numbered agent), and the
+ * groups are ordered by leader.  Same contract as the entry points above: kernels only (no memset node), no allocation, no host
+ * synchronisation, no atomics, bit-identical run to run, capturable in a graph.  EINVAL before any launch: a NULL pointer,
+ * n_groups outside [1, N], and what the unshared sibling rejects.  The host cannot read the arrays without a synchronisation,
+ * so every kernel skips a map entry outside [0, N): a bad map is never an out-of-bounds access.
+ *
+ * dronesim_adam_step_shared: dronesim_adam_step (active == NULL) or dronesim_adam_step_gated (active set) per GROUP:
+ *   1. the group's gradient is the MEAN of its members' slices of grad, per element: float64 partial sums in ascending member
+ *      order starting from the first member's value, divided by (double)|G|, rounded once to float32, written into the leader's
+ *      slice of grad.  (The gradient of ONE network on the members' pooled rows with row scale 1 / (|G| rows): lr and max_norm
+ *      keep their meaning.)
+ *   2. the pre-clip norm, the clip and the Adam step of dronesim_adam_step on the LEADERS only, by the same kernels and hence
+ *      the same instructions: the leader ends up bit for bit where dronesim_adam_step would put an agent holding that mean
+ *      gradient.  Only the leader's slices of m1, m2 and grad are live -- after the call the leader's slice of grad holds the
+ *      clipped group gradient; the other members' slices of the three buffers are left untouched.
+ *   3. the leader's six weight tensors and its step counter are copied to every other member, and the group's pre-clip norm
+ *      into every member's grad_norm[i].
+ *   With active set a group's flag is its leader's: a stopped group changes nothing and all its members report NaN norms.
+ *   A map of singletons is dronesim_adam_step(_gated) bit for bit.  Traffic per element of a group: 8 |G| + 44 bytes (each
+ *   member's gradient read, each member's weight written, one 40-byte leader pass, one broadcast read) against 36 |G| unshared.
+ * dronesim_kl_gate_shared: dronesim_kl_gate with one change -- the tested estimate of a group is the mean of its members' kl,
+ *   float64 partial sums in ascending member order, compared in float64 -- and active / taken written identically for all
+ *   members.  reset and the NaN rule are unchanged (a NaN member stops the group).
+ * dronesim_mlp_tie: step 3 for the weights alone -- every member's six tensors become its leader's.                           */
+int dronesim_adam_step_shared(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
+                              float beta2, float eps, float max_norm, float *grad_norm, const int32_t *active /* or NULL */,
+                              const int32_t *group_ptr, const int32_t *members, int n_groups, void *stream);
+int dronesim_kl_gate_shared(const float *kl, float target_kl, int32_t *active, int32_t *taken, int N, int reset,
+                            const int32_t *group_ptr, const int32_t *members, int n_groups, void *stream);
+int dronesim_mlp_tie(const DroneMlp *m, const int32_t *group_ptr, const int32_t *members, int n_groups, void *stream);
+
 /* Shuffled minibatches (csrc/minibatch.hip).  Both entry points only enqueue one kernel on `stream`: no memset node, no
  * allocation, no host synchronisation, no atomics; deterministic, and capturable in a graph.
  *

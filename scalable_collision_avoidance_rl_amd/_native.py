@@ -36,6 +36,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent",
            "dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
            "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip",
+           "dronesim_adam_step_shared", "dronesim_kl_gate_shared", "dronesim_mlp_tie",
            "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_episode_safety", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
            "dronesim_row_permutation", "dronesim_gather_rows",
            "dronesim_obsnorm_workspace", "dronesim_obsnorm_update", "dronesim_obsnorm_apply",
@@ -181,6 +182,11 @@ def lib():
     for name in ("dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
                  "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip"):
         getattr(L, name).restype = C.c_int
+    # parameter sharing: the siblings' arguments, then active (or NULL) where it is new, group_ptr, members, n_groups, stream
+    L.dronesim_adam_step_shared.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, i32, vp]
+    L.dronesim_kl_gate_shared.argtypes = [vp, f32, vp, vp, i32, i32, vp, vp, i32, vp]
+    L.dronesim_mlp_tie.argtypes = [PM, vp, vp, i32, vp]
+    L.dronesim_adam_step_shared.restype = L.dronesim_kl_gate_shared.restype = L.dronesim_mlp_tie.restype = C.c_int
     L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
     L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]
     L.dronesim_episode_safety.argtypes = [vp] * 7 + [f32] + [i32] * 5 + [vp] * 7 + [vp]

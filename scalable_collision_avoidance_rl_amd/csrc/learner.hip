@@ -30,6 +30,14 @@
 // per-agent gate `active` (int32 [N], device memory; NULL for every form but the gated one) -- gemm_kernel's batch index is the
 // agent, so a workgroup of a gated agent returns at entry, before any barrier, uniformly; the head skips its rows and the
 // per-agent results are NaN for it.  dronesim_kl_gate decides the stop on the device; dronesim_adam_step_gated obeys it.
+//
+// Parameter sharing (dronesim_adam_step_shared, dronesim_kl_gate_shared, dronesim_mlp_tie): a sharing map in CSR form (group_ptr
+// [n_groups + 1], members [N], ascending inside a group, so a group's first member is its leader) ties the weights of a group's
+// members.  The step is three launches around the two of the unshared step: group_mean_kernel leaves the float64 mean of the
+// members' gradients in the leader's slice, grad_norm_kernel and adam_kernel -- the SAME kernels, one workgroup row per group
+// instead of per agent (agent_of) -- update the leader, group_broadcast_kernel copies the leader's weights, counter and norm to
+// the other members.  Every kernel skips a map entry outside [0, N) (group_range, agent_ok): the device arrays cannot be checked
+// by the host without a synchronisation.
 #include "common.hpp"
 #include "../../include/dronesim.h"
 
@@ -466,6 +474,63 @@ __global__ __launch_bounds__(kThreads) void kl_gate_kernel(const float *kl, floa
     if (a) taken[i] = taken[i] + 1;
 }
 
+// The sharing map's guards.  The members [beg, end) of group g, clamped to the N entries of `members`; false for an empty range.
+__device__ __forceinline__ bool group_range(const int32_t *group_ptr, int g, int N, int &beg, int &end)
+{
+    beg = group_ptr[g];
+    end = group_ptr[g + 1];
+    if (beg < 0) beg = 0;
+    if (end > N) end = N;
+    return beg < end;
+}
+
+__device__ __forceinline__ bool agent_ok(int i, int N) { return (unsigned)i < (unsigned)N; }
+
+// The agent that workgroup row b of the norm / Adam kernels serves: b itself, or under a sharing map (group_ptr set) the leader
+// of group b; -1 for a map entry outside [0, N).
+__device__ __forceinline__ int agent_of(int b, int N, const int32_t *group_ptr, const int32_t *members)
+{
+    if (!group_ptr) return b;
+    const int at = group_ptr[b];
+    if (!agent_ok(at, N)) return -1;
+    const int i = members[at];
+    return agent_ok(i, N) ? i : -1;
+}
+
+// dronesim_kl_gate_shared: one thread per group, kl_gate_kernel's rule on the group's estimate -- the mean of the members' kl,
+// float64 partial sums in ascending member order from the leader's value -- with the verdict written to every member.  A
+// singleton's mean is its own kl: kl_gate_kernel's test.
+__global__ __launch_bounds__(kThreads) void kl_gate_shared_kernel(const float *kl, float target_kl, int32_t *active, int32_t *taken,
+                                                                  int N, int reset, const int32_t *group_ptr, const int32_t *members,
+                                                                  int n_groups)
+{
+    const int g = blockIdx.x * kThreads + threadIdx.x;
+    int beg, end;
+    if (g >= n_groups || !group_range(group_ptr, g, N, beg, end)) return;
+    const int lead = members[beg];
+    if (!agent_ok(lead, N)) return;
+    int a = 1, tk = 0;
+    if (!reset) {
+        a = active[lead];
+        tk = taken[lead];
+        if (a) {
+            double s = (double)kl[lead];
+            for (int k = beg + 1; k < end; ++k) {
+                const int i = members[k];
+                if (agent_ok(i, N)) s += (double)kl[i];
+            }
+            if (!(s / (double)(end - beg) <= (double)target_kl)) a = 0;
+        }
+        if (a) tk += 1;
+    }
+    for (int k = beg; k < end; ++k) {
+        const int i = members[k];
+        if (!agent_ok(i, N)) continue;
+        active[i] = a;
+        taken[i] = tk;
+    }
+}
+
 struct Tensors {
     long long size[6];      // per agent: w1, b1, w2, b2, w3, b3
     long long off[6];       // of the [N, ...] tensor in the flat buffer
@@ -485,20 +550,36 @@ Tensors tensors_of(const DroneMlp *m)
 struct Params { float *p[6]; };
 
 // the pre-clip gradient norm of agent i over its six tensors (double partial sums, block_sum's order); advances the step counter
-// (dronesim_adam_step_gated: an agent with active[i] == 0 keeps its counter and reports NaN)
+// (dronesim_adam_step_gated: an agent with active[i] == 0 keeps its counter and reports NaN).  Under a sharing map the agents
+// are the groups' leaders (agent_of).
 __global__ __launch_bounds__(kThreads) void grad_norm_kernel(const float *grad, Tensors t, int32_t *step, float *grad_norm,
-                                                             const int32_t *active)
+                                                             const int32_t *active, int N, const int32_t *group_ptr,
+                                                             const int32_t *members)
 {
     __shared__ double part[kThreads];
-    const int i = blockIdx.x;
+    const int i = agent_of(blockIdx.x, N, group_ptr, members);
+    if (i < 0) return;                           // (the whole workgroup, before any barrier)
     if (active && active[i] == 0) {
         if (threadIdx.x == 0) grad_norm[i] = __builtin_nanf("");
         return;
     }
+    // Each lane adds the squares of its strided elements in element order.  The loads of kNormUnroll of them are issued before
+    // the first is added: under a sharing map ONE workgroup walks a whole network, and the walk is bound by memory latency.
+    // The order of the additions, and with it every bit of the sum, is that of the plain loop (a float's square is exact in
+    // float64, so neither the batching nor a fused multiply-add can change a rounding).
+    constexpr int kNormUnroll = 16;
     double s = 0.0;
     for (int j = 0; j < 6; ++j) {
         const float *g = grad + t.off[j] + (long long)i * t.size[j];
-        for (long long e = threadIdx.x; e < t.size[j]; e += kThreads) s += (double)g[e] * (double)g[e];
+        long long e = threadIdx.x;
+        for (; e + (kNormUnroll - 1) * kThreads < t.size[j]; e += kNormUnroll * kThreads) {
+            float v[kNormUnroll];
+#pragma unroll
+            for (int u = 0; u < kNormUnroll; ++u) v[u] = g[e + u * kThreads];
+#pragma unroll
+            for (int u = 0; u < kNormUnroll; ++u) s += (double)v[u] * (double)v[u];
+        }
+        for (; e < t.size[j]; e += kThreads) s += (double)g[e] * (double)g[e];
     }
     block_sum(part, s);
     if (threadIdx.x == 0) {
@@ -507,12 +588,15 @@ __global__ __launch_bounds__(kThreads) void grad_norm_kernel(const float *grad, 
     }
 }
 
-// clip (coef = min(1, max_norm / (norm + 1e-6)), the clipped gradient is written back) and one Adam step, torch's formulas
+// clip (coef = min(1, max_norm / (norm + 1e-6)), the clipped gradient is written back) and one Adam step, torch's formulas;
+// the shared step's leaders go through this same kernel (agent_of): one set of instructions for both
 __global__ __launch_bounds__(kThreads) void adam_kernel(float *grad, float *m1, float *m2, Params prm, Tensors t,
                                                         const int32_t *step, const float *grad_norm, float lr, float beta1,
-                                                        float beta2, float eps, float max_norm, const int32_t *active)
+                                                        float beta2, float eps, float max_norm, const int32_t *active, int N,
+                                                        const int32_t *group_ptr, const int32_t *members)
 {
-    const int i = blockIdx.y;
+    const int i = agent_of(blockIdx.y, N, group_ptr, members);
+    if (i < 0) return;                           // (the whole workgroup, before the barrier)
     if (active && active[i] == 0) return;        // weights, moments and the gradient slice stay as they are
     // the agent's bias corrections (torch: step_size = lr / (1 - beta1^step), sqrt(1 - beta2^step)), once per workgroup
     __shared__ float corr[2];
@@ -538,6 +622,172 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(float *grad, float *m1, 
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     float *p = prm.p[j] + (long long)i * t.size[j] + e;
     *p = *p - step_size * (m / denom);
+}
+
+// The element quads of the per-agent layout, the work items of the two group kernels: tensor j has ceil(size[j] / 4) of them,
+// the last one possibly short.  quad q -> tensor j, first element e, cnt elements.
+__host__ __device__ __forceinline__ long long quads_of(const Tensors &t)
+{
+    long long n = 0;
+    for (int j = 0; j < 6; ++j) n += (t.size[j] + 3) >> 2;
+    return n;
+}
+
+__device__ __forceinline__ void quad_at(const Tensors &t, long long q, int &j, long long &e, int &cnt)
+{
+    for (j = 0; j < 5; ++j) {
+        const long long nq = (t.size[j] + 3) >> 2;
+        if (q < nq) break;
+        q -= nq;
+    }
+    e = 4 * q;
+    const long long left = t.size[j] - e;
+    cnt = left < 4 ? (int)left : 4;
+}
+
+// One quad from / to an agent's slice: <true> one 16-byte access (a whole quad at an aligned address), <false> element by
+// element (a tensor's short last quad; slices that do not start on a 16-byte boundary).
+template <bool kVec>
+__device__ __forceinline__ float4 load_quad(const float *p, int cnt)
+{
+    if (kVec) return *reinterpret_cast<const float4 *>(p);
+    float4 v = {0.f, 0.f, 0.f, 0.f};
+    if (cnt == 4) {
+        v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3];
+        return v;
+    }
+    v.x = p[0];
+    if (cnt > 1) v.y = p[1];
+    if (cnt > 2) v.z = p[2];
+    return v;
+}
+
+template <bool kVec>
+__device__ __forceinline__ void store_quad(float *p, int cnt, float4 v)
+{
+    if (kVec) {
+        *reinterpret_cast<float4 *>(p) = v;
+        return;
+    }
+    p[0] = v.x;
+    if (cnt > 1) p[1] = v.y;
+    if (cnt > 2) p[2] = v.z;
+    if (cnt > 3) p[3] = v.w;
+}
+
+// Whether the quad at `p` of EVERY agent's slice is one aligned 16-byte access: the quad is whole, this one is aligned, and the
+// slices are a multiple of four floats apart.
+__device__ __forceinline__ bool quad_is_vector(const float *p, long long stride, int cnt)
+{
+    return cnt == 4 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
+constexpr int kGroupThreads = 64;       // small workgroups: one large group's quads still reach every compute unit
+constexpr int kGroupUnroll = 8;         // members whose loads are in flight together (the sum itself stays in member order)
+
+// The sum of one quad over the members [beg + 1, end) of a group on top of the leader's: float64 partial sums in ascending member
+// order.  The loads of kGroupUnroll members are issued before the first of them is added -- the walk is bound by memory
+// latency, the order of the additions is untouched.  A member outside [0, N) is read at the leader's address and not added.
+template <bool kVec>
+__device__ __forceinline__ void sum_quad(const float *base, long long stride, int cnt, int N, const int32_t *members, int beg, int end,
+                                         int lead, double (&s)[4])
+{
+    const float4 v0 = load_quad<kVec>(base + (long long)lead * stride, cnt);
+    s[0] = (double)v0.x; s[1] = (double)v0.y; s[2] = (double)v0.z; s[3] = (double)v0.w;
+    int k = beg + 1;
+    for (; k + kGroupUnroll <= end; k += kGroupUnroll) {
+        float4 v[kGroupUnroll];
+        bool ok[kGroupUnroll];
+#pragma unroll
+        for (int u = 0; u < kGroupUnroll; ++u) {
+            const int i = members[k + u];
+            ok[u] = agent_ok(i, N);
+            v[u] = load_quad<kVec>(base + (long long)(ok[u] ? i : lead) * stride, cnt);
+        }
+#pragma unroll
+        for (int u = 0; u < kGroupUnroll; ++u) {
+            if (!ok[u]) continue;
+            s[0] += (double)v[u].x; s[1] += (double)v[u].y; s[2] += (double)v[u].z; s[3] += (double)v[u].w;
+        }
+    }
+    for (; k < end; ++k) {
+        const int i = members[k];
+        if (!agent_ok(i, N)) continue;
+        const float4 v = load_quad<kVec>(base + (long long)i * stride, cnt);
+        s[0] += (double)v.x; s[1] += (double)v.y; s[2] += (double)v.z; s[3] += (double)v.w;
+    }
+}
+
+// The group mean of the shared step.  Grid (quad blocks, group): a thread owns one quad of the per-agent layout at a time
+// (grid-stride over the quads) and walks the group's members for it -- consecutive lanes read consecutive quads of one member's
+// slice --, so a group of any size is spread over the whole grid.  Per element: float64 partial sums in ascending member order
+// from the first member's value, divided by (double)|G|, rounded once to float32, written into the LEADER's slice; the other
+// members' slices are only read.  No atomics: one owner per element.  A singleton's mean is its own value (nothing to do); a
+// stopped group (active[leader] == 0) is skipped.
+__global__ __launch_bounds__(kGroupThreads) void group_mean_kernel(float *grad, Tensors t, int N, const int32_t *active,
+                                                                   const int32_t *group_ptr, const int32_t *members)
+{
+    int beg, end;
+    if (!group_range(group_ptr, blockIdx.y, N, beg, end)) return;
+    const int lead = members[beg];
+    if (end - beg == 1 || !agent_ok(lead, N)) return;
+    if (active && active[lead] == 0) return;
+    const double n = (double)(end - beg);
+    const long long quads = quads_of(t);
+    for (long long q = (long long)blockIdx.x * kGroupThreads + threadIdx.x; q < quads; q += (long long)gridDim.x * kGroupThreads) {
+        int j, cnt;
+        long long e;
+        quad_at(t, q, j, e, cnt);
+        float *base = grad + t.off[j] + e;
+        float *out = base + (long long)lead * t.size[j];
+        const bool vec = quad_is_vector(out, t.size[j], cnt);
+        double s[4];
+        if (vec) sum_quad<true>(base, t.size[j], cnt, N, members, beg, end, lead, s);
+        else sum_quad<false>(base, t.size[j], cnt, N, members, beg, end, lead, s);
+        const float4 mean = {(float)(s[0] / n), (float)(s[1] / n), (float)(s[2] / n), (float)(s[3] / n)};
+        if (vec) store_quad<true>(out, cnt, mean);
+        else store_quad<false>(out, cnt, mean);
+    }
+}
+
+// The broadcast of the shared step and dronesim_mlp_tie: the leader's six weight tensors to every other member of its group, on
+// group_mean_kernel's grid and quads; the group's first workgroup also mirrors the leader's pre-clip norm and step counter
+// (either may be NULL: dronesim_mlp_tie).  A stopped group keeps its weights and counters, and all its members report the
+// leader's NaN norm.
+__global__ __launch_bounds__(kGroupThreads) void group_broadcast_kernel(Params prm, Tensors t, int N, int32_t *step, float *grad_norm,
+                                                                        const int32_t *active, const int32_t *group_ptr,
+                                                                        const int32_t *members)
+{
+    int beg, end;
+    if (!group_range(group_ptr, blockIdx.y, N, beg, end)) return;
+    const int lead = members[beg];
+    if (end - beg == 1 || !agent_ok(lead, N)) return;
+    const bool stopped = active && active[lead] == 0;
+    if (blockIdx.x == 0) {
+        for (int k = beg + 1 + (int)threadIdx.x; k < end; k += kGroupThreads) {
+            const int i = members[k];
+            if (!agent_ok(i, N)) continue;
+            if (grad_norm) grad_norm[i] = grad_norm[lead];
+            if (step && !stopped) step[i] = step[lead];
+        }
+    }
+    if (stopped) return;
+    const long long quads = quads_of(t);
+    for (long long q = (long long)blockIdx.x * kGroupThreads + threadIdx.x; q < quads; q += (long long)gridDim.x * kGroupThreads) {
+        int j, cnt;
+        long long e;
+        quad_at(t, q, j, e, cnt);
+        float *base = prm.p[j] + e;
+        const float *from = base + (long long)lead * t.size[j];
+        const bool vec = quad_is_vector(from, t.size[j], cnt);
+        const float4 v = vec ? load_quad<true>(from, cnt) : load_quad<false>(from, cnt);
+        for (int k = beg + 1; k < end; ++k) {
+            const int i = members[k];
+            if (!agent_ok(i, N)) continue;
+            if (vec) store_quad<true>(base + (long long)i * t.size[j], cnt, v);
+            else store_quad<false>(base + (long long)i * t.size[j], cnt, v);
+        }
+    }
 }
 
 int launch_gemm(GemmArgs g, int batch, hipStream_t st, const int32_t *active)
@@ -762,8 +1012,34 @@ int ppo_grad(const char *where, unsigned form, const DroneMlp *m, const float *x
     return run_chain(j);
 }
 
+Params params_of(const DroneMlp *m)
+{
+    Params p;
+    const float *w[6] = {m->w1, m->b1, m->w2, m->b2, m->w3, m->b3};
+    for (int j = 0; j < 6; ++j) p.p[j] = const_cast<float *>(w[j]);
+    return p;
+}
+
+// the grid of the two group kernels: x over the quads of the per-agent layout in workgroups of kGroupThreads -- capped so that
+// all groups together stay near 8192 of them, the kernels stride over the rest --, y the group
+dim3 group_grid(const Tensors &t, int n_groups)
+{
+    const long long want = (quads_of(t) + kGroupThreads - 1) / kGroupThreads, cap = (8192 + n_groups - 1) / n_groups;
+    return dim3((unsigned)(want < cap ? want : cap), (unsigned)n_groups);
+}
+
+int check_groups(const char *where, int N, const int32_t *group_ptr, const int32_t *members, int n_groups)
+{
+    if (!group_ptr || !members) return fail_at(where, "NULL group_ptr / members");
+    if (n_groups < 1 || n_groups > N) return fail_at(where, "n_groups must be in [1, N]");
+    return DRONESIM_OK;
+}
+
+// The three Adam entry points.  group_ptr NULL: one norm and one Adam workgroup row per agent; else one per group (its leader),
+// between the group mean and the broadcast.
 int adam_step(const char *where, const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
-              float beta2, float eps, float max_norm, float *grad_norm, const int32_t *active, void *stream)
+              float beta2, float eps, float max_norm, float *grad_norm, const int32_t *active, const int32_t *group_ptr,
+              const int32_t *members, int n_groups, void *stream)
 {
     int rc = check_mlp(m, where);
     if (rc != DRONESIM_OK) return rc;
@@ -772,12 +1048,16 @@ int adam_step(const char *where, const DroneMlp *m, float *grad, float *m1, floa
         return fail_at(where, "need lr >= 0, 0 <= beta < 1, eps > 0, max_norm > 0");
     hipStream_t st = (hipStream_t)stream;
     const Tensors t = tensors_of(m);
-    Params p;
-    const float *w[6] = {m->w1, m->b1, m->w2, m->b2, m->w3, m->b3};
-    for (int j = 0; j < 6; ++j) p.p[j] = const_cast<float *>(w[j]);
-    hipLaunchKernelGGL(grad_norm_kernel, dim3(m->N), dim3(kThreads), 0, st, grad, t, step, grad_norm, active);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((t.per_agent + kThreads - 1) / kThreads), m->N), dim3(kThreads), 0, st,
-                       grad, m1, m2, p, t, step, grad_norm, lr, beta1, beta2, eps, max_norm, active);
+    const Params p = params_of(m);
+    const int rows = group_ptr ? n_groups : m->N;
+    if (group_ptr)
+        hipLaunchKernelGGL(group_mean_kernel, group_grid(t, n_groups), dim3(kGroupThreads), 0, st, grad, t, m->N, active, group_ptr, members);
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(rows), dim3(kThreads), 0, st, grad, t, step, grad_norm, active, m->N, group_ptr, members);
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((t.per_agent + kThreads - 1) / kThreads), rows), dim3(kThreads), 0, st,
+                       grad, m1, m2, p, t, step, grad_norm, lr, beta1, beta2, eps, max_norm, active, m->N, group_ptr, members);
+    if (group_ptr)
+        hipLaunchKernelGGL(group_broadcast_kernel, group_grid(t, n_groups), dim3(kGroupThreads), 0, st, p, t, m->N, step, grad_norm, active,
+                           group_ptr, members);
     return dronesim_launched();
 }
 
@@ -904,7 +1184,8 @@ extern "C" int dronesim_mlp_grad_ppo_gated(const DroneMlp *m, const float *x, in
 extern "C" int dronesim_adam_step(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
                                   float beta2, float eps, float max_norm, float *grad_norm, void *stream)
 {
-    return adam_step("dronesim_adam_step", m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, nullptr, stream);
+    return adam_step("dronesim_adam_step", m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, nullptr, nullptr, nullptr,
+                     0, stream);
 }
 
 extern "C" int dronesim_adam_step_gated(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
@@ -913,7 +1194,31 @@ extern "C" int dronesim_adam_step_gated(const DroneMlp *m, float *grad, float *m
 {
     const char *where = "dronesim_adam_step_gated";
     if (!active) return fail_at(where, "NULL active");
-    return adam_step(where, m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, active, stream);
+    return adam_step(where, m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, active, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int dronesim_adam_step_shared(const DroneMlp *m, float *grad, float *m1, float *m2, int32_t *step, float lr, float beta1,
+                                         float beta2, float eps, float max_norm, float *grad_norm, const int32_t *active,
+                                         const int32_t *group_ptr, const int32_t *members, int n_groups, void *stream)
+{
+    const char *where = "dronesim_adam_step_shared";
+    int rc = check_mlp(m, where);
+    if (rc == DRONESIM_OK) rc = check_groups(where, m->N, group_ptr, members, n_groups);
+    if (rc != DRONESIM_OK) return rc;
+    return adam_step(where, m, grad, m1, m2, step, lr, beta1, beta2, eps, max_norm, grad_norm, active, group_ptr, members, n_groups,
+                     stream);
+}
+
+extern "C" int dronesim_mlp_tie(const DroneMlp *m, const int32_t *group_ptr, const int32_t *members, int n_groups, void *stream)
+{
+    const char *where = "dronesim_mlp_tie";
+    int rc = check_mlp(m, where);
+    if (rc == DRONESIM_OK) rc = check_groups(where, m->N, group_ptr, members, n_groups);
+    if (rc != DRONESIM_OK) return rc;
+    const Tensors t = tensors_of(m);
+    hipLaunchKernelGGL(group_broadcast_kernel, group_grid(t, n_groups), dim3(kGroupThreads), 0, (hipStream_t)stream, params_of(m), t, m->N,
+                       (int32_t *)nullptr, (float *)nullptr, (const int32_t *)nullptr, group_ptr, members);
+    return dronesim_launched();
 }
 
 extern "C" int dronesim_kl_gate(const float *kl, float target_kl, int32_t *active, int32_t *taken, int N, int reset, void *stream)
@@ -925,5 +1230,20 @@ extern "C" int dronesim_kl_gate(const float *kl, float target_kl, int32_t *activ
     if (!(target_kl > 0.f) || isinf(target_kl)) return fail_at(where, "target_kl must be finite and > 0");
     hipLaunchKernelGGL(kl_gate_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, kl,
                        target_kl, active, taken, N, reset);
+    return dronesim_launched();
+}
+
+extern "C" int dronesim_kl_gate_shared(const float *kl, float target_kl, int32_t *active, int32_t *taken, int N, int reset,
+                                       const int32_t *group_ptr, const int32_t *members, int n_groups, void *stream)
+{
+    const char *where = "dronesim_kl_gate_shared";
+    if (N < 1) return fail_at(where, "N < 1");
+    if (!active || !taken) return fail_at(where, "NULL active / taken");
+    if (!reset && !kl) return fail_at(where, "NULL kl (only reset may omit it)");
+    if (!(target_kl > 0.f) || isinf(target_kl)) return fail_at(where, "target_kl must be finite and > 0");
+    const int rc = check_groups(where, N, group_ptr, members, n_groups);
+    if (rc != DRONESIM_OK) return rc;
+    hipLaunchKernelGGL(kl_gate_shared_kernel, dim3((unsigned)((n_groups + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, kl, target_kl, active, taken, N, reset, group_ptr, members, n_groups);
     return dronesim_launched();
 }

@@ -32,6 +32,11 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
   obs_norm= of both    dronesim_obsnorm_apply, dronesim_obsnorm_update   an `ObsNormalizer`: everything a network reads is
                                        normalised first, with the table as it stands, into learner-owned buffers; the window's
                                        T E pre-step rows are merged into the statistics as ``train()``'s last work (default None)
+  share= of BatchedAdam and both   dronesim_adam_step_shared, dronesim_kl_gate_shared, dronesim_mlp_tie   parameter sharing: a
+                                       sharing map (`agent_groups`: None, ``"all"`` or a group id per agent) ties the networks of
+                                       a group -- one set of weights, the gradient the mean of the members' per-agent gradients,
+                                       one Adam state and one norm per group, the PPO gate decided on the group's mean KL;
+                                       `BatchedMLP.tie_weights` / `BatchedMLP.take` tie and re-lay-out networks (default None: off)
 
 Flat gradient layout (and Adam's moments): one buffer per network, the six tensors ``w1 | b1 | w2 | b2 | w3 | b3`` each
 ``[N, ...]`` like `BatchedMLP`'s weights (`flat_layout`).  The learner reads and writes the plain weight arrays
@@ -255,19 +260,92 @@ def mlp_gradients(mlp, x, target=None, act=None, weight=None, row_scale=None, ro
     return g, l
 
 
+def agent_groups(share, n_agents):
+    """The sharing map ``share`` of ``n_agents`` agents, normalised: ``(group_of, group_ptr, members)``, three lists of ints.
+
+      ``share``      None (nobody shares: N singletons), ``"all"`` (one group) or a length-N sequence of non-negative ints, agent
+                     i's group id.  The ids are labels: they need not be contiguous (`evaluate.network_index`'s output is a map).
+      ``group_of``   ``[N]``: agent i's group, numbered 0 .. n_groups-1 in the order of the groups' LEADERS, a group's
+                     lowest-numbered member.
+      ``group_ptr``, ``members``   the same in CSR form (``[n_groups + 1]``, ``[N]``), what the ``dronesim_*_shared`` entry points
+                     read: group g's members are ``members[group_ptr[g]:group_ptr[g + 1]]``, ascending, leader first.
+
+    Anything else (another string, a wrong length, a negative, non-integer or bool id) raises ValueError."""
+    import numbers
+    n = int(n_agents)
+    if n < 1:
+        raise ValueError(f"n_agents must be >= 1, got {n_agents!r}")
+    if share is None:
+        ids = list(range(n))
+    elif isinstance(share, str):
+        if share != "all":
+            raise ValueError(f'share must be None, "all" or a sequence of {n} group ids, got {share!r}')
+        ids = [0] * n
+    else:
+        try:
+            ids = list(share)
+        except TypeError:
+            raise ValueError(f'share must be None, "all" or a sequence of {n} group ids, got {share!r}') from None
+        if len(ids) != n:
+            raise ValueError(f"share has {len(ids)} entries, the network {n} agents")
+        for v in ids:
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0:
+                raise ValueError(f"share must hold non-negative integers, got {v!r}")
+        ids = [int(v) for v in ids]
+    number, groups = {}, []
+    for i, v in enumerate(ids):                  # agents ascending: a group is first met at its leader
+        if v not in number:
+            number[v] = len(groups)
+            groups.append([])
+        groups[number[v]].append(i)
+    group_ptr = [0]
+    for g in groups:
+        group_ptr.append(group_ptr[-1] + len(g))
+    return [number[v] for v in ids], group_ptr, [i for g in groups for i in g]
+
+
+class SharingMap:
+    """`agent_groups` of ``share`` uploaded once: ``group_ptr`` / ``members`` as int32 device tensors, ``leader_of`` (a long
+    ``[N]`` device tensor, each agent's leader) and ``n_groups``."""
+
+    def __init__(self, share, n_agents, device):
+        import torch
+        self.group_of, ptr, members = agent_groups(share, n_agents)
+        self.n_groups = len(ptr) - 1
+        self.group_ptr = torch.tensor(ptr, dtype=torch.int32, device=device)
+        self.members = torch.tensor(members, dtype=torch.int32, device=device)
+        self.leader_of = torch.tensor([members[ptr[g]] for g in self.group_of], dtype=torch.long, device=device)
+
+    def tied(self, mlp):
+        """Whether every member's six plain tensors equal its leader's (synchronises the host)."""
+        import torch
+        return all(torch.equal(w, w[self.leader_of]) for w in (getattr(mlp, name) for name in TENSOR_NAMES))
+
+
 class BatchedAdam:
     """clip_grad_norm_(max_norm) + torch.optim.Adam (torch defaults: no weight decay, no amsgrad) for the N networks of
     one `BatchedMLP`, one optimiser state per agent: flat moments ``m1`` / ``m2`` and a per-agent step counter in device
     memory (a captured graph advances it on every replay).  ``step(grad)`` returns the pre-clip norms ``[N]``.
     ``step(grad, active=a)`` (int32 ``[N]`` on the device) is `dronesim_adam_step_gated`: an agent with ``a[i] == 0`` keeps its
-    weights, moments, counter and gradient slice, and its norm is NaN."""
+    weights, moments, counter and gradient slice, and its norm is NaN.
 
-    def __init__(self, mlp, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=10.0):
+    ``share`` (default None: exactly the calls above, nothing more allocated) is a sharing map (`agent_groups`), fixed for the
+    life of the object: the members of a group hold ONE network.  The CSR arrays are uploaded once, and every member's six
+    tensors must already equal its leader's (checked here with ``torch.equal``; `BatchedMLP.tie_weights` makes them so).
+    ``step`` is then `dronesim_adam_step_shared`, gated or not: the group's gradient is the mean of its members' slices
+    (float64, into the leader's slice), one norm, clip and Adam step on the leader -- its slices of ``m1`` / ``m2`` / ``grad``
+    are the only live ones --, then the leader's weights and counter are copied to the members and the group's norm to every
+    member's slot.  A gated group's flag is its leader's."""
+
+    def __init__(self, mlp, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=10.0, share=None):
         import torch
         self.mlp = mlp
         self.lr, self.betas, self.eps, self.max_norm = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(max_norm)
         _, total = flat_layout(mlp.n_agents, mlp.d_in, mlp.h1, mlp.h2, mlp.nout)
         self.numel = total
+        self.share = None if share is None else SharingMap(share, mlp.n_agents, mlp.device)
+        if self.share is not None and not self.share.tied(mlp):
+            raise ValueError("share: a member's weights differ from its leader's; call mlp.tie_weights(share) first")
         self.m1 = torch.zeros(total, device=mlp.device)
         self.m2 = torch.zeros(total, device=mlp.device)
         self.steps = torch.zeros(mlp.n_agents, dtype=torch.int32, device=mlp.device)
@@ -286,6 +364,18 @@ class BatchedAdam:
         if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != self.mlp.n_agents
                                    or active.device != self.m1.device):
             raise ValueError(f"active must be a contiguous int32 tensor [{self.mlp.n_agents}] on {self.m1.device}")
+        if self.share is not None:
+            with torch.cuda.device(self.mlp.device):
+                rc = _native.lib().dronesim_adam_step_shared(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
+                                                             self.steps.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                                                             self.max_norm, norm.data_ptr(),
+                                                             None if active is None else active.data_ptr(),
+                                                             self.share.group_ptr.data_ptr(), self.share.members.data_ptr(),
+                                                             self.share.n_groups, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _native.check(rc, "dronesim_adam_step_shared")
+            if refresh:
+                self.mlp.refresh_weights()
+            return norm
         with torch.cuda.device(self.mlp.device):
             if active is None:
                 rc = _native.lib().dronesim_adam_step(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
@@ -523,10 +613,18 @@ class SA2CLearner:
     gathered ``z_trunc`` (the kinds of the ends are still decided on the RAW ``z_final``: that is geometry) -- and the table is
     not touched until the last step has been enqueued: the rollout that collected the window and every step of the update see
     one map.  Its last enqueued work, unless ``update_obs_norm=False``, is ``obs_norm.update(storage.z_pre)``: the T E pre-step
-    rows only, ring slot T is the next window's slot 0.  A normaliser of another shape raises ValueError."""
+    rows only, ring slot T is the next window's slot 0.  A normaliser of another shape raises ValueError.
+
+    ``share`` (default None: exactly the calls above, nothing more allocated) is a sharing map (`agent_groups`) applied to BOTH
+    the actor and the critic: the agents of a group train ONE network.  Nothing upstream of the optimiser changes -- every agent
+    still gets its own gradient from its own rows, and all per-agent outputs keep their shapes and meaning --; both steps become
+    `dronesim_adam_step_shared` (`BatchedAdam`): the group's gradient is the mean of its members', i.e. the gradient of one
+    network on the members' pooled rows with row scale ``1 / (|G| rows)``, so ``lr`` and ``max_norm`` keep their meaning.  The
+    members' weights must be tied beforehand (`BatchedMLP.tie_weights`; ValueError otherwise) and stay bit-identical after every
+    update; the two grad-norm outputs carry the group's norm in every member's slot."""
 
     def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None,
-                 time_limit="terminal", ent_coef=0.0, obs_norm=None, update_obs_norm=True):
+                 time_limit="terminal", ent_coef=0.0, obs_norm=None, update_obs_norm=True, share=None):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -538,8 +636,8 @@ class SA2CLearner:
         self.ent_coef = _check_ent_coef(ent_coef)
         self.obs_norm, self.update_obs_norm = _check_obs_norm(obs_norm, actor, critic), bool(update_obs_norm)
         self.rows_per_chunk = rows_per_chunk
-        self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
-        self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
+        self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm, share=share)
+        self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm, share=share)
         self._shape = None
 
     def _prepare(self, storage):
@@ -721,13 +819,23 @@ class PPOLearner:
     ``obs_norm`` / ``update_obs_norm`` as for `SA2CLearner` (default None: nothing above changes): the window (or ring, and
     ``z_trunc``) is normalised once at the start of ``train()`` with the table as it stands, ``logp_old``, every epoch and the
     minibatch gather read that normalised x -- the first epoch's ratio stays exactly 1 -- and the T E pre-step rows are merged
-    into the statistics as the call's last enqueued work."""
+    into the statistics as the call's last enqueued work.
+
+    ``share`` as for `SA2CLearner` (default None: nothing above changes, nothing more allocated): a sharing map for both
+    networks, every Adam step `dronesim_adam_step_shared`.  It composes with every option above.  All per-agent outputs keep
+    their shapes and meaning (losses, the PPO diagnostics, ``kl``, ``entropy``, ``adv_*`` are each agent's own, from its own
+    rows); the two grad-norm outputs carry the group's norm in every member's slot.  ``normalize_advantage`` STAYS PER AGENT:
+    each member's advantages are standardised over its own T E rows before the gradients are pooled, so every member
+    contributes at the same scale.  With ``target_kl`` the gate is `dronesim_kl_gate_shared`: a group stops when the MEAN of its
+    members' ``kl`` (float64) passes the threshold, all its members together -- ``actor_steps`` is equal within a group.  The
+    row permutation still reads ``critic_opt.steps[0]``: the counters are mirrored into every member, so it advances."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                  baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
-                 adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None, obs_norm=None, update_obs_norm=True):
+                 adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None, obs_norm=None, update_obs_norm=True,
+                 share=None):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -754,8 +862,8 @@ class PPOLearner:
         self._ent = self.ent_coef > 0 or self.normalize_advantage or self.target_kl is not None
         self._stat_rows = 6 if self.target_kl is not None else (5 if self._ent else 4)
         self.rows_per_chunk = rows_per_chunk
-        self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm)
-        self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm)
+        self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm, share=share)
+        self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm, share=share)
         self._shape = None
 
     def _prepare(self, storage):
@@ -867,10 +975,16 @@ class PPOLearner:
     def _kl_gate(self, kl, reset, lib, stream):
         import torch
         from . import _native
+        share = self.actor_opt.share
         with torch.cuda.device(self.critic.device):
-            rc = lib.dronesim_kl_gate(None if kl is None else kl.data_ptr(), self.target_kl, self.active.data_ptr(),
-                                      self.actor_steps.data_ptr(), self.actor.n_agents, int(reset), stream)
-        _native.check(rc, "dronesim_kl_gate")
+            if share is None:
+                rc = lib.dronesim_kl_gate(None if kl is None else kl.data_ptr(), self.target_kl, self.active.data_ptr(),
+                                          self.actor_steps.data_ptr(), self.actor.n_agents, int(reset), stream)
+            else:       # the group's verdict, from the mean of its members' estimates, for all its members
+                rc = lib.dronesim_kl_gate_shared(None if kl is None else kl.data_ptr(), self.target_kl, self.active.data_ptr(),
+                                                 self.actor_steps.data_ptr(), self.actor.n_agents, int(reset),
+                                                 share.group_ptr.data_ptr(), share.members.data_ptr(), share.n_groups, stream)
+        _native.check(rc, "dronesim_kl_gate" if share is None else "dronesim_kl_gate_shared")
 
     def _step(self, critic_grad, actor_grad, rows, x, act, logp_old, adv, G, V=None, *, at, last, lib, stream):
         """One critic step, then one actor step, on these ``rows`` rows (the window, or one minibatch's block of every gathered

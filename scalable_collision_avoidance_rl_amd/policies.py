@@ -316,6 +316,7 @@ class BatchedMLP:
         if precision != "f32" and self.d_in > 16:
             raise ValueError(f"the {precision} path supports d_in <= 16")
         self.precision = precision
+        self._pack_kw = dict(precision=precision, pack_w2=pack_w2, split_kernel=split_kernel)      # (`take` builds its like)
         lib, dims = self._lib, (self.h1, self.h2)
         # the mode: which kernel runs and which packed image it reads (`_pack`); `_stages`: the length `DroneMlpBf16.reserved` carries
         if precision == "f32":
@@ -381,6 +382,34 @@ class BatchedMLP:
             self._packed[name].copy_(image)
 
     load_weights = refresh_weights
+
+    # ------------------------------------------------------------------ tied networks
+    def tie_weights(self, share):
+        """Parameter sharing: copy each group leader's six plain tensors to the other members of its group, on the device
+        (`dronesim_mlp_tie`), and re-pack the forward images.  ``share``: a sharing map (`learner.agent_groups`: ``"all"``, or a
+        group id per agent; None ties nothing); the leader of a group is its lowest-numbered member.  A `BatchedAdam` /
+        learner built with the same ``share`` then keeps the members bit-identical.  Returns ``self``."""
+        from .learner import SharingMap, plain_struct
+        torch = self._torch
+        groups = SharingMap(share, self.n_agents, self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.dronesim_mlp_tie(C.byref(plain_struct(self)), groups.group_ptr.data_ptr(), groups.members.data_ptr(),
+                                            groups.n_groups, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        self._native.check(rc, "dronesim_mlp_tie")
+        self.refresh_weights()
+        return self
+
+    def take(self, index):
+        """A NEW `BatchedMLP` of ``len(index)`` agents whose agent i holds this object's network ``index[i]`` (copies of the
+        plain tensors, packed afresh): the same kinds, precision and packing arguments, device and seed.  E.g. a tied team
+        trained on 5 agents laid out for 64: ``actor.take(evaluate.network_index(1, 64))``."""
+        import numbers
+        index = list(index)
+        if not index or any(isinstance(i, bool) or not isinstance(i, numbers.Integral) or not 0 <= i < self.n_agents for i in index):
+            raise ValueError(f"index must be a non-empty sequence of integers in [0, {self.n_agents})")
+        at = self._torch.tensor([int(i) for i in index], dtype=self._torch.long, device=self.device)
+        return BatchedMLP(*(getattr(self, name)[at] for name in ("w1", "b1", "w2", "b2", "w3", "b3")), self.out_kind,
+                          self.sample_kind, device=self.device, seed=self.seed, **self._pack_kw)
 
     # ------------------------------------------------------------------ constructors
     @classmethod

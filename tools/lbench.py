@@ -14,6 +14,8 @@ or, with ``--learner ppo``, one `PPOLearner.train` of ``--epochs M`` epochs --, 
     python tools/lbench.py --gate-compare [--configs c3,c5] [--reps 3] [--out profiles/target_kl_lbench.jsonl]
     python tools/lbench.py --scans --obsnorm [--configs c3,c5] [--reps 9] [--out profiles/obsnorm_lbench.jsonl]
     python tools/lbench.py [--learner ppo --epochs M] --obs-norm [--out profiles/obsnorm_lbench.jsonl]
+    python tools/lbench.py [--learner ppo --epochs M] --share all [--out profiles/share_lbench.jsonl]
+    python tools/lbench.py --adam-step [--share all] [--configs c3,c5] [--reps 9] [--calls 20] [--out profiles/share_lbench.jsonl]
 
 ``--lam X`` times the learner with bootstrapped lambda-returns (one more ring slot of observations; off by default).
 ``--time-limit bootstrap`` (with ``--lam``) times it with time-limit ends bootstrapped from their terminal observations: the
@@ -43,6 +45,10 @@ reads 4 bytes per x element (expected: the yardstick x d / 2), `dronesim_obsnorm
 allowed = expected + 15 %.  For c3 it then times the captured rollout loop (softmax-16 actor ``precision="f16x2"`` + step) with and
 without `norm(env.z)` in front of the policy: required <= 1.05 x the loop without it.  ``--obs-norm`` times a whole update with
 an `ObsNormalizer` (normalise first, update last).
+``--share all`` times the learner with parameter sharing: both networks tied over all agents (`BatchedMLP.tie_weights`), every
+Adam step `dronesim_adam_step_shared`.  ``--adam-step`` times `BatchedAdam.step` alone, actor + critic on fixed gradients
+(``refresh=False``; device events around ``--calls`` back-to-back step pairs, median / min / max over ``--reps``), unshared or
+with ``--share all``, next to the bytes each form has to move (36 |G| against 8 |G| + 44 per element of a group).
 ``--scans`` times the learner-side scans alone instead: `dronesim_returns` (the yardstick) and `dronesim_lambda_returns`
 with G only and with G + A, on the same buffers in the same process, device events around ``--calls`` back-to-back calls
 after a warm-up, median and minimum over ``--reps`` repetitions, one JSON line each (appended to ``--out`` when given).
@@ -455,11 +461,10 @@ def scans_time_limit(args):
                 f.write(json.dumps(line) + "\n")
 
 
-def window_of(torch, name, dev="cuda:0", lam=None, boot=False):
-    """The seeded networks and the storage-like window of one shape: (actor weights, actor kind, critic weights, storage, widths)."""
+def networks_of(torch, name, dev, g):
+    """The seeded networks of one shape, drawn from the generator ``g``: (actor weights, actor kind, critic weights, widths)."""
     N, E, T, kind = CONFIGS[name]
     d_in = 6
-    g = torch.Generator(device=dev).manual_seed(0)
     u = lambda *s, fan: (torch.rand(*s, device=dev, generator=g) * 2 - 1) / math.sqrt(fan)
     net = lambda h1, h2, no: [u(N, d_in, h1, fan=d_in), u(N, h1, fan=d_in), u(N, h1, h2, fan=h1), u(N, h2, fan=h1),
                               u(N, h2, no, fan=h2), u(N, no, fan=h2)]
@@ -468,7 +473,15 @@ def window_of(torch, name, dev="cuda:0", lam=None, boot=False):
     else:
         aw, ak, widths = net(400, 400, 4), 2, (400, 400, 4)
         aw[4][:, :200, 2:] = 0; aw[4][:, 200:, :2] = 0
-    cw = net(200, 200, 1)
+    return aw, ak, net(200, 200, 1), widths
+
+
+def window_of(torch, name, dev="cuda:0", lam=None, boot=False):
+    """The seeded networks and the storage-like window of one shape: (actor weights, actor kind, critic weights, storage, widths)."""
+    N, E, T, kind = CONFIGS[name]
+    d_in = 6
+    g = torch.Generator(device=dev).manual_seed(0)
+    aw, ak, cw, widths = networks_of(torch, name, dev, g)
     ring = (torch.rand(T + (lam is not None), E, N, d_in, device=dev, generator=g) * 2 - 1) * 3
     a = torch.randint(0, 16, (T, E, N), device=dev, generator=g).float() * (2 * math.pi / 16)
     st = SimpleNamespace(z_pre=ring[:T], reward=torch.randn(T, E, N, device=dev, generator=g),
@@ -549,6 +562,69 @@ def gate_compare(args):
                 f.write(json.dumps(line) + "\n")
 
 
+def adam_step_bench(args):
+    """`BatchedAdam.step` alone (no gradient chain, ``refresh=False``): per repetition ``--calls`` back-to-back steps of the actor's
+    and the critic's optimiser on fixed random gradients, between two device events.  ``--share all`` ties each network first
+    and times the shared step.  The byte counts per element of a group of |G| members: unshared 36 |G| (the norm reads g; Adam
+    reads and writes g, m1, m2, p), shared 8 |G| + 44 (every member's g read and p written, one 40-byte leader pass, one
+    broadcast read); the line carries both and the bandwidth the measured time amounts to."""
+    import statistics
+
+    import torch
+    from scalable_collision_avoidance_rl_amd.learner import BatchedAdam
+    from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+    dev = "cuda:0"
+    lines = []
+    for name in args.configs.split(","):
+        N, E, T, kind = CONFIGS[name]
+        g = torch.Generator(device=dev).manual_seed(0)
+        aw, ak, cw, _ = networks_of(torch, name, dev, g)
+        nets = [BatchedMLP(*aw, ak, ak, device=dev), BatchedMLP(*cw, 0, 0, device=dev)]
+        kw = {}
+        if args.share:
+            kw["share"] = args.share
+            for mlp in nets:
+                mlp.tie_weights(args.share)
+        opts = [BatchedAdam(mlp, **kw) for mlp in nets]
+        grads = [torch.randn(o.numel, device=dev, generator=g) * 1e-3 for o in opts]
+        keep = [t.clone() for t in grads]
+
+        def steps(n):
+            for _ in range(n):
+                for o, t in zip(opts, grads):
+                    o.step(t, refresh=False)
+        steps(max(1, args.warmup))
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        times = []
+        for _ in range(args.reps):
+            for t, k in zip(grads, keep):          # (the step clips in place: every repetition starts from the same gradients)
+                t.copy_(k)
+            torch.cuda.synchronize()
+            ev[0].record(); steps(args.calls); ev[1].record()
+            torch.cuda.synchronize()
+            times.append(ev[0].elapsed_time(ev[1]) / args.calls)
+        elements = sum(o.numel for o in opts)        # all agents, both networks
+        groups = 1 if args.share == "all" else N
+        unshared_bytes, shared_bytes = 36 * elements, 8 * elements + 44 * elements // N * groups
+        ms = statistics.median(times)
+        moved = shared_bytes if args.share else unshared_bytes
+        line = dict(what="BatchedAdam.step, actor + critic", config=name, N=N, actor=kind, share=args.share, elements=elements,
+                    ms_per_step=round(ms, 4), ms_min=round(min(times), 4), ms_max=round(max(times), 4),
+                    ms_all=[round(t, 4) for t in times], calls=args.calls, unshared_bytes=unshared_bytes,
+                    expected_bytes=moved, expected_share_of_unshared=round(moved / unshared_bytes, 4),
+                    tb_per_s=round(moved / ms / 1e9, 3))
+        if args.tag:
+            line["tag"] = args.tag
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="c1,c3,c5")
@@ -573,6 +649,9 @@ def main():
     ap.add_argument("--vf-clip", type=float, default=None, help="clipped value loss with this range (--learner ppo; default: off)")
     ap.add_argument("--gate-compare", action="store_true",
                     help="gated against ungated PPOLearner.train at 2 and 6 epochs and the critic-only epoch, in one process")
+    ap.add_argument("--share", choices=("all",), default=None,
+                    help="parameter sharing: all agents train ONE actor and ONE critic (tied weights; default: off)")
+    ap.add_argument("--adam-step", action="store_true", help="time BatchedAdam.step alone (actor + critic), unshared or with --share")
     ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per timed repetition (--scans)")
     ap.add_argument("--out", help="append the JSON lines to this file")
@@ -595,6 +674,8 @@ def main():
         return
     if (args.target_kl is not None or args.vf_clip is not None) and args.learner != "ppo":
         ap.error("--target-kl and --vf-clip need --learner ppo")
+    if args.adam_step:
+        return adam_step_bench(args)
     if args.gate_compare:
         return gate_compare(args)
     if args.gather:
@@ -633,6 +714,9 @@ def main():
         if args.obs_norm:
             from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
             lam_kw["obs_norm"] = ObsNormalizer(N, d_in, dev)
+        if args.share:
+            lam_kw["share"] = args.share
+            actor.tie_weights(args.share); critic.tie_weights(args.share)
         learner = PPOLearner(actor, critic, 0.99, epochs=args.epochs, **lam_kw) if ppo else SA2CLearner(actor, critic, 0.99, **lam_kw)
         for _ in range(args.warmup):
             learner.train(st)
@@ -669,6 +753,8 @@ def main():
             tag["vf_clip"] = args.vf_clip
         if args.obs_norm:
             tag["obs_norm"] = True
+        if args.share:
+            tag["share"] = args.share
         if (args.target_kl is not None or args.vf_clip is not None) and args.minibatches == 1:
             tag["critic_epoch_ms"] = round(critic_epoch_ms(torch, learner, st, args.reps), 3)
         if args.tag:
