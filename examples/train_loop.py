@@ -7,7 +7,7 @@ actor loss + clip + Adam, for all N agents' networks at once in HIP.
     python examples/train_loop.py [--envs 256] [--agents 5] [--episodes 5] [--learner {sa2c,ppo}] [--epochs 10]
                                   [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
                                   [--normalize-advantage] [--minibatches K] [--shuffle-seed S] [--target-kl X] [--vf-clip X]
-                                  [--obs-norm] [--obs-clip X] [--share all]
+                                  [--obs-norm] [--obs-clip X] [--share all] [--grid G] [--reward-norm] [--reward-clip X]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -40,6 +40,13 @@ window into the statistics as its last work.  One warm-up window of `update` onl
 window 0 is not trained on the identity map.  Every episode line then shows the largest ``|mean|`` and the range of the
 columns' standard deviations.  ``--obs-clip X`` clamps the normalised observation to [-X, X] (default 10).
 
+``--grid G`` sets the side length of the square the goals lie in (default 5, the reference's).  The reward grows with its
+square and the return with 200 such terms, which is what ``--reward-norm`` is for: a `RewardNormalizer` (team scope) keeps the
+running discounted return of every (env, agent) on the device, ``train()`` merges the window into its statistics and trains on
+the rewards times ``1 / std(return)``; ``storage.reward`` and the printed mean reward stay in raw units.  Every episode line then
+shows the scale and the returns' standard deviation.  ``--reward-clip X`` clamps the scaled reward to [-X, X] (default 10).
+Try ``--grid 28 --reward-norm --obs-norm``.
+
 ``--share all`` trains ONE actor and ONE critic for the whole team (parameter sharing): the networks are tied
 (`BatchedMLP.tie_weights`) and every update pools the agents' gradients (`dronesim_adam_step_shared`); with ``--target-kl`` the
 team stops together, on the mean of the agents' KL estimates.  After the loop the script prints that agent 0's and agent N-1's
@@ -58,6 +65,7 @@ from scalable_collision_avoidance_rl_amd import drones
 from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
 from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
+from scalable_collision_avoidance_rl_amd.reward_norm import RewardNormalizer
 from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
 
 
@@ -95,6 +103,9 @@ def main():
     ap.add_argument("--obs-norm", action="store_true", help="normalise observations with running per-agent statistics on the device")
     ap.add_argument("--obs-clip", type=float, default=10.0, help="clamp of the normalised observation (--obs-norm; default 10)")
     ap.add_argument("--share", choices=("all",), default=None, help="parameter sharing: one actor and one critic for all agents (default: off)")
+    ap.add_argument("--grid", type=float, default=5.0, help="side length of the goals' square (default 5)")
+    ap.add_argument("--reward-norm", action="store_true", help="scale rewards by the running std of the discounted return, on the device")
+    ap.add_argument("--reward-clip", type=float, default=10.0, help="clamp of the scaled reward (--reward-norm; default 10)")
     args = ap.parse_args()
     if args.minibatches != 1 and args.learner != "ppo":
         ap.error("--minibatches needs --learner ppo (one update per window is what A2C is)")
@@ -103,7 +114,7 @@ def main():
     if (args.target_kl is not None or args.vf_clip is not None) and args.learner != "ppo":
         ap.error("--target-kl and --vf-clip need --learner ppo")
     N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
-    env = drones(N, 0, [5, 5], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
+    env = drones(N, 0, [args.grid, args.grid], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=dev, seed=1, auto_reset=True)
     d_in = env.local_state_space
     gen = torch.Generator().manual_seed(0)
@@ -115,15 +126,16 @@ def main():
     storage = RolloutStorage(env, T, actions=True)
     norm = ObsNormalizer(N, d_in, dev, clip=args.obs_clip) if args.obs_norm else None
     see = (lambda z: z) if norm is None else norm           # what the networks read of an observation
+    rnorm = RewardNormalizer(N, 0.99, dev, clip=args.reward_clip) if args.reward_norm else None
     # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
     if args.learner == "ppo":
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                              lam=args.lam, time_limit=args.time_limit, ent_coef=args.ent_coef,
                              normalize_advantage=args.normalize_advantage, minibatches=args.minibatches, shuffle_seed=args.shuffle_seed,
-                             target_kl=args.target_kl, vf_clip=args.vf_clip, obs_norm=norm, share=args.share)
+                             target_kl=args.target_kl, vf_clip=args.vf_clip, obs_norm=norm, share=args.share, reward_norm=rnorm)
     else:
         learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
-                              time_limit=args.time_limit, ent_coef=args.ent_coef, obs_norm=norm, share=args.share)
+                              time_limit=args.time_limit, ent_coef=args.ent_coef, obs_norm=norm, share=args.share, reward_norm=rnorm)
     if norm is not None:      # one warm-up window of statistics only: window 0 is not trained on the identity map
         storage.begin()
         for t in range(T):
@@ -161,6 +173,8 @@ def main():
         if norm is not None:
             std = norm.var.sqrt()
             ppo += f"  obs |mean| <= {float(norm.mean.abs().max()):.2f}  std [{float(std.min()):.3g}, {float(std.max()):.3g}]"
+        if rnorm is not None:
+            ppo += f"  reward scale {float(out['reward_scale'][0]):.3g}  return std {float(rnorm.std[0]):.4g}"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(mean(out['actor_loss'])):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
               f"{float(mean(out['actor_grad_norm'])):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")

@@ -40,6 +40,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_episode_safety", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
            "dronesim_row_permutation", "dronesim_gather_rows",
            "dronesim_obsnorm_workspace", "dronesim_obsnorm_update", "dronesim_obsnorm_apply",
+           "dronesim_rewnorm_workspace", "dronesim_rewnorm_update", "dronesim_rewnorm_apply",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -199,6 +200,10 @@ def lib():
     L.dronesim_obsnorm_update.argtypes = [vp, i32, i32, vp, vp, C.c_double, vp, C.c_size_t, vp]
     L.dronesim_obsnorm_apply.argtypes = [vp, vp, i32, i32, vp, f32, vp]
     L.dronesim_obsnorm_workspace.restype = L.dronesim_obsnorm_update.restype = L.dronesim_obsnorm_apply.restype = C.c_int
+    L.dronesim_rewnorm_workspace.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
+    L.dronesim_rewnorm_update.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, i32, vp, vp, vp, C.c_double, vp, C.c_size_t, vp]
+    L.dronesim_rewnorm_apply.argtypes = [vp, vp, i32, i32, i32, vp, f32, vp]
+    L.dronesim_rewnorm_workspace.restype = L.dronesim_rewnorm_update.restype = L.dronesim_rewnorm_apply.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

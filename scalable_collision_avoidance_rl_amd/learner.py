@@ -32,6 +32,9 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
   obs_norm= of both    dronesim_obsnorm_apply, dronesim_obsnorm_update   an `ObsNormalizer`: everything a network reads is
                                        normalised first, with the table as it stands, into learner-owned buffers; the window's
                                        T E pre-step rows are merged into the statistics as ``train()``'s last work (default None)
+  reward_norm= of both dronesim_rewnorm_update, dronesim_rewnorm_apply   a `RewardNormalizer` (reward_norm.py): the window is merged
+                                       into the running discounted-return statistics, then the return scans read the rewards
+                                       times ``1 / std(return)`` from a learner-owned buffer (default None)
   share= of BatchedAdam and both   dronesim_adam_step_shared, dronesim_kl_gate_shared, dronesim_mlp_tie   parameter sharing: a
                                        sharing map (`agent_groups`: None, ``"all"`` or a group id per agent) ties the networks of
                                        a group -- one set of weights, the gradient the mean of the members' per-agent gradients,
@@ -431,13 +434,14 @@ def _ring(storage, T):
     return ring
 
 
-def _lambda_returns(learner, storage, Vall, G):
-    """`dronesim_lambda_returns` of the stored rewards with the values of all T+1 ring slots, into ``G``."""
+def _lambda_returns(learner, storage, Vall, G, reward):
+    """`dronesim_lambda_returns` of ``reward`` (the stored rewards, or their normalised image) with the values of all T+1 ring
+    slots, into ``G``."""
     import torch
     from . import _native
     T, E, N = learner._shape
     with torch.cuda.device(learner.critic.device):
-        rc = _native.lib().dronesim_lambda_returns(storage.reward.data_ptr(), storage.done.data_ptr(), Vall.data_ptr(),
+        rc = _native.lib().dronesim_lambda_returns(reward.data_ptr(), storage.done.data_ptr(), Vall.data_ptr(),
                                                    learner.gamma, learner.lam, G.data_ptr(), None, T, E, N,
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
     _native.check(rc, "dronesim_lambda_returns")
@@ -477,7 +481,7 @@ def _prepare_ends(learner, storage, T, E, N):
     learner.V_trunc = torch.empty(M * E, N, 1, device=dev)
 
 
-def _lambda_returns_ends(learner, storage, Vall, G):
+def _lambda_returns_ends(learner, storage, Vall, G, reward):
     """``time_limit="bootstrap"``: the kinds of the window's episode ends and the terminal observations of the truncated ones
     (`dronesim_episode_ends`), the PRE-update critic over those into ``V_trunc``, then `dronesim_lambda_returns_ends` into ``G``."""
     import torch
@@ -492,7 +496,7 @@ def _lambda_returns_ends(learner, storage, Vall, G):
         z_trunc = learner.obs_norm.norm(z_trunc, out=learner._xn_trunc)
     learner.critic.forward(z_trunc.view(M * E, N, -1), out=learner.V_trunc)
     with torch.cuda.device(learner.critic.device):
-        rc = _native.lib().dronesim_lambda_returns_ends(storage.reward.data_ptr(), learner.ends.data_ptr(), Vall.data_ptr(),
+        rc = _native.lib().dronesim_lambda_returns_ends(reward.data_ptr(), learner.ends.data_ptr(), Vall.data_ptr(),
                                                         learner.V_trunc.data_ptr(), M, learner.gamma, learner.lam, G.data_ptr(),
                                                         None, T, E, N, C.c_void_p(torch.cuda.current_stream().cuda_stream))
     _native.check(rc, "dronesim_lambda_returns_ends")
@@ -524,6 +528,32 @@ def _normalised(learner, storage, T):
         return learner.obs_norm.norm(storage.z_pre, out=learner._xn), None
     ring = learner.obs_norm.norm(storage.z_all, out=learner._xn)
     return ring[:T], ring
+
+
+def _check_reward_norm(reward_norm, actor, share):
+    """None, or a `RewardNormalizer` for the networks' N whose statistics groups respect the sharing map ``share`` (a
+    `SharingMap` or None): the members of a tied group must share one statistics group -- one critic cannot fit two units."""
+    if reward_norm is None:
+        return None
+    reward_norm.check_agents(actor.n_agents)
+    if share is not None:
+        unit = {}
+        for i, g in enumerate(share.group_of):
+            if unit.setdefault(g, reward_norm.group_of[i]) != reward_norm.group_of[i]:
+                raise ValueError(f"reward_norm puts the tied agents of sharing group {g} into different statistics groups: one "
+                                 'network cannot fit two units (use scope="team" or a map that keeps tied agents together)')
+    return reward_norm
+
+
+def _normalised_reward(learner, storage):
+    """What the return scans read: ``storage.reward`` itself without a ``reward_norm``; else the window is first merged into the
+    running return statistics (unless ``update_reward_norm=False``) and then scaled into the learner's own ``_rn [T,E,N]`` --
+    ``storage.reward`` is never written."""
+    if learner.reward_norm is None:
+        return storage.reward
+    if learner.update_reward_norm:
+        learner.reward_norm.update(storage.reward, storage.done)
+    return learner.reward_norm.norm(storage.reward, out=learner._rn)
 
 
 MINIBATCH_ALIGN = 256               # every minibatch's block of a gathered buffer starts on this boundary (bytes)
@@ -621,10 +651,22 @@ class SA2CLearner:
     `dronesim_adam_step_shared` (`BatchedAdam`): the group's gradient is the mean of its members', i.e. the gradient of one
     network on the members' pooled rows with row scale ``1 / (|G| rows)``, so ``lr`` and ``max_norm`` keep their meaning.  The
     members' weights must be tied beforehand (`BatchedMLP.tie_weights`; ValueError otherwise) and stay bit-identical after every
-    update; the two grad-norm outputs carry the group's norm in every member's slot."""
+    update; the two grad-norm outputs carry the group's norm in every member's slot.
+
+    ``reward_norm`` (default None: exactly the calls above, nothing more allocated) is a `RewardNormalizer` for the networks' N.
+    ``train()`` then starts with ``reward_norm.update(storage.reward, storage.done)`` (unless ``update_reward_norm=False``) and
+    writes ``reward_norm.norm(storage.reward)`` into a buffer of its own, ``_rn [T,E,N]``; that buffer is what `dronesim_returns`,
+    `dronesim_lambda_returns` and `dronesim_lambda_returns_ends` read.  UPDATE FIRST, THEN APPLY -- the other way round than
+    ``obs_norm``: no acting kernel has to agree with the reward scale, so nothing forbids changing it ahead of the update, and
+    a fresh normaliser (scale 1) would otherwise train its first window on raw rewards.  ``storage.reward`` is never written: the
+    `Evaluator` and every logged statistic stay in raw units.  The critic's values (and G, and the advantage) are then in
+    NORMALISED units.  ``train()`` also returns ``reward_scale [N]`` (float64, the scale this window was trained with).  A
+    normaliser for another N raises ValueError, and so does, with ``share``, one whose statistics groups split a tied group
+    (``scope="team"`` always fits)."""
 
     def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None,
-                 time_limit="terminal", ent_coef=0.0, obs_norm=None, update_obs_norm=True, share=None):
+                 time_limit="terminal", ent_coef=0.0, obs_norm=None, update_obs_norm=True, share=None, reward_norm=None,
+                 update_reward_norm=True):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -638,6 +680,8 @@ class SA2CLearner:
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm, share=share)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm, share=share)
+        self.reward_norm = _check_reward_norm(reward_norm, actor, self.critic_opt.share)
+        self.update_reward_norm = bool(update_reward_norm)
         self._shape = None
 
     def _prepare(self, storage):
@@ -665,6 +709,8 @@ class SA2CLearner:
             self._actor_grad._workspace("grad_ent")
         if self.obs_norm is not None:
             _prepare_obs_norm(self, storage)
+        if self.reward_norm is not None:
+            self._rn = torch.empty(T, E, N, device=dev)
         self._shape = (T, E, N)
 
     def train(self, storage):
@@ -674,14 +720,15 @@ class SA2CLearner:
         T, E, N = self._shape
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         x, ring = _normalised(self, storage, T)
+        reward = _normalised_reward(self, storage)
         if self.lam is None:
             with torch.cuda.device(self.critic.device):
-                rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
+                rc = lib.dronesim_returns(reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
                                           T, E, N, stream)
             _native.check(rc, "dronesim_returns")
         else:       # bootstrapped lambda-returns from the pre-update critic over all T+1 ring slots
             self.critic.forward(ring.view((T + 1) * E, N, -1), out=self.V_all)
-            (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G)
+            (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G, reward)
         # critic (SAC_agents.py:304-324)
         cg, closs = self._critic_grad.run(x, 1.0 / (T * E), target=self.G)
         cnorm = self.critic_opt.step(cg)
@@ -697,11 +744,16 @@ class SA2CLearner:
             ag, aloss, ent = self._actor_grad.run_ent(x, 1.0 / E, storage.actions, self.w, self.ent_coef / (T * E))
             anorm = self.actor_opt.step(ag)
             self._update_obs_norm(storage)
-            return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm, entropy=ent)
+            return self._with_scale(dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm, entropy=ent))
         ag, aloss = self._actor_grad.run(x, 1.0 / E, act=storage.actions, weight=self.w)
         anorm = self.actor_opt.step(ag)
         self._update_obs_norm(storage)
-        return dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm)
+        return self._with_scale(dict(critic_loss=closs, actor_loss=aloss, critic_grad_norm=cnorm, actor_grad_norm=anorm))
+
+    def _with_scale(self, out):
+        if self.reward_norm is not None:
+            out["reward_scale"] = self.reward_norm.scale
+        return out
 
     def _update_obs_norm(self, storage):
         """``train()``'s last enqueued work: the window's T E pre-step rows into the statistics (ring slot T is the next window's
@@ -828,14 +880,20 @@ class PPOLearner:
     each member's advantages are standardised over its own T E rows before the gradients are pooled, so every member
     contributes at the same scale.  With ``target_kl`` the gate is `dronesim_kl_gate_shared`: a group stops when the MEAN of its
     members' ``kl`` (float64) passes the threshold, all its members together -- ``actor_steps`` is equal within a group.  The
-    row permutation still reads ``critic_opt.steps[0]``: the counters are mirrored into every member, so it advances."""
+    row permutation still reads ``critic_opt.steps[0]``: the counters are mirrored into every member, so it advances.
+
+    ``reward_norm`` / ``update_reward_norm`` as for `SA2CLearner` (default None: nothing above changes, nothing more allocated):
+    the window is merged into the running return statistics first, then scaled into the learner's ``_rn``, which step 1's scan
+    reads in ``storage.reward``'s place (update first, then apply; ``storage.reward`` is never written).  G, the critic's values,
+    the advantages and therefore ``vf_clip`` are then in NORMALISED units.  New output ``reward_scale [N]``.  With ``share`` the
+    statistics groups must keep tied agents together (ValueError otherwise)."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                  baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
                  adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None, obs_norm=None, update_obs_norm=True,
-                 share=None):
+                 share=None, reward_norm=None, update_reward_norm=True):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -864,6 +922,8 @@ class PPOLearner:
         self.rows_per_chunk = rows_per_chunk
         self.actor_opt = BatchedAdam(actor, lr=lr_actor, max_norm=max_norm, share=share)
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm, share=share)
+        self.reward_norm = _check_reward_norm(reward_norm, actor, self.critic_opt.share)
+        self.update_reward_norm = bool(update_reward_norm)
         self._shape = None
 
     def _prepare(self, storage):
@@ -916,6 +976,8 @@ class PPOLearner:
             self.actor_steps = torch.zeros(N, dtype=torch.int32, device=dev)
         if self.obs_norm is not None:
             _prepare_obs_norm(self, storage)
+        if self.reward_norm is not None:
+            self._rn = torch.empty(T, E, N, device=dev)
         self._shape = (T, E, N)
 
     def _prepare_forms(self, critic_grad, actor_grad):
@@ -1030,11 +1092,12 @@ class PPOLearner:
         lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         act, nbr = storage.actions, storage.nbr_pre
         x, ring = _normalised(self, storage, T)
+        reward = _normalised_reward(self, storage)
         if self.target_kl is not None:
             self._kl_gate(None, True, lib, stream)
         if self.lam is None:
             with torch.cuda.device(self.critic.device):
-                rc = lib.dronesim_returns(storage.reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
+                rc = lib.dronesim_returns(reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
                                           T, E, N, stream)
             _native.check(rc, "dronesim_returns")
         # the old policy's log-probabilities and the advantage from the pre-update critic, once per window (:484-501, :512-513)
@@ -1043,7 +1106,7 @@ class PPOLearner:
             self.critic.forward(x.view(T * E, N, -1), out=self.V)
         else:       # the same forward over all T+1 ring slots; the bootstrapped lambda-returns of it
             self.critic.forward(ring.view((T + 1) * E, N, -1), out=self.V_all)
-            (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G)
+            (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G, reward)
         with torch.cuda.device(self.critic.device):
             rc = lib.dronesim_neighbour_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(),
                                                   int(self.baseline == "per_neighbour"), self.adv.data_ptr(), T, E, N,
@@ -1064,4 +1127,6 @@ class PPOLearner:
         if self.obs_norm is not None and self.update_obs_norm:
             # the last enqueued work: the T E pre-step rows only (ring slot T is the next window's slot 0 and is counted there)
             self.obs_norm.update(storage.z_pre)
+        if self.reward_norm is not None:
+            out["reward_scale"] = self.reward_norm.scale
         return out
