@@ -9,9 +9,15 @@ each (E x rounds >= --episodes), every step of every env in one launch, and the 
     python examples/benchmark_agent.py --controller proportional            # the commented alternatives of :76-77
     python examples/benchmark_agent.py ... --obs-norm stats.pt             # the observation statistics the networks were trained with
     python examples/benchmark_agent.py ... --safety                        # closest approach, arrival and formation error per episode
+    python examples/benchmark_agent.py ... --shield [--shield-rate X --shield-margin X]   # the same episodes again through an ActionShield
 
 ``--obs-norm FILE``: an `ObsNormalizer.state_dict()` saved with ``torch.save``; the actor and the critic then read the normalised
 observation (the reference's files carry no statistics, so there is none by default).
+
+``--shield``: after the plain evaluation the same number of episodes runs again with every action projected by an `ActionShield`
+(box 1, the clip of the controllers and the norm of the discrete actions) before the step integrates it, and the collision-free
+share is printed next to the unshielded one, with the share of decisions the shield changed and what it cost in arrival
+(``--safety``).  With ``--controller`` the shielded rounds are three launches per step instead of one fused launch per round.
 """
 import argparse
 import os
@@ -23,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import scalable_collision_avoidance_rl_amd.drone_env as drone_env          # was: import drone_env
 from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, TrainedAgent    # was: from SAC_agents import *
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
+from scalable_collision_avoidance_rl_amd.shield import ActionShield
 
 
 def main():
@@ -37,6 +44,9 @@ def main():
     ap.add_argument("--precision", default="f32")
     ap.add_argument("--obs-norm", default=None, help="a torch.save'd ObsNormalizer.state_dict() (network actors only)")
     ap.add_argument("--safety", action="store_true", help="also reduce and print the per-episode safety tables")
+    ap.add_argument("--shield", action="store_true", help="run the episodes again through an ActionShield and compare")
+    ap.add_argument("--shield-rate", type=float, default=0.25, help="share of a gap an agent may close per step, in (0, 0.5]")
+    ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
     a = ap.parse_args()
 
     if a.controller:
@@ -79,6 +89,23 @@ def main():
               f"Mean step of an agent's arrival = {fmt(f['mean_arrive_step'], '.1f')}")
         print(f"Smallest clearance per episode: mean {f['mean_min_clearance']:.3f} m, minimum {fmt(f['min_clearance'], '.3f')} m. "
               f"Largest final goal distance per episode: mean {f['mean_goal_dist_max']:.3f} m")
+    if a.shield:                                             # (no reference line: the reference has no safety layer)
+        shield = ActionShield(env, rate=a.shield_rate, margin=a.shield_margin, u_max=1.0, stats=True)
+        evs = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, shield=shield)
+        evs.run(rounds)
+        t = evs.summary()
+        print(f"### Shielded (rate = {shield.rate}, margin = {shield.margin} m, box = {shield.u_max})")
+        print(f"Episodes {t['episodes']} - Average Reward/Collisions/Steps: {t['mean_return']:.1f}/{t['mean_collisions']:.2f}/"
+              f"{t['mean_length']:.1f}. True r={t['mean_true_return']:.1f}.")
+        print(f"(episodes without any collision: shielded {t['zero_collision_share'] * 100:.2f}%, unshielded "
+              f"{s['zero_collision_share'] * 100:.2f}%)")
+        print(f"The shield changed {t['shield_intervention_share'] * 100:.2f}% of the decisions; mean correction {t['shield_mean_correction']:.4f} m/s "
+              f"(over the changed ones {t['shield']['mean_correction_intervened']:.4f}, largest {t['shield']['max_correction']:.4f})")
+        if a.safety:
+            g = evs.safety_summary()
+            print(f"Arrived = {g['arrived_share'] * 100:.2f}% (unshielded {f['arrived_share'] * 100:.2f}%). Smallest clearance per episode: "
+                  f"mean {g['mean_min_clearance']:.3f} m, minimum {fmt(g['min_clearance'], '.3f')} m (unshielded "
+                  f"{fmt(f['min_clearance'], '.3f')} m)")
 
 
 if __name__ == "__main__":

@@ -801,6 +801,33 @@ int dronesim_rewnorm_update(const float *reward, const uint8_t *done, int T, int
                             double *ret, double *state, double *scale, double eps, void *ws, size_t ws_bytes, void *stream);
 int dronesim_rewnorm_apply(const float *reward, float *out, int T, int E, int N, const double *scale, float clip, void *stream);
 
+/* Action shield: a local collision-avoidance filter between the policy and the step (csrc/shield.hip; DESIGN.md has the guarantee
+ * and its conditions).  Per record (e, i): z [E][N][k1 c] float32 and nbr [E][N][k1] int32 are the observation the agent acts on
+ * (row 0 = x_i - xF_i, rows 1..k = x_j - x_i of the k closest agents inside Delta, nbr[s] = j, an id outside [0, N) a ghost row),
+ * act [E][N][2] the nominal action u, radius [N].  The half-planes a.x <= b, in this fixed order:
+ *   1. the box: (+1,0), (-1,0), (0,+1), (0,-1), each with b = u_max (+inf: they never bind);
+ *   2. for slot s = 1..k with j = nbr[s], p = floats 0, 1 of row s, d = |p|: skipped unless 0 <= j < N, j != i, d finite and
+ *      d > 0; otherwise a = p / d, g = d - radius[i] - radius[j] - margin, b = rate max(g, 0) / dt.
+ * act_out [E][N][2] = u*, the Euclidean projection of u onto the intersection (never empty: 0 satisfies every constraint);
+ * intervened [E][N] uint8 and correction [E][N] float32 = |u* - u| may be NULL.  Where u satisfies every constraint as the kernel
+ * evaluates it (float32: d = sqrt(fma(py, py, px px)), a = p (1 / d), g = ((d - radius[i]) - radius[j]) - margin,
+ * b = (rate / dt) max(g, 0), violated where fma(ax, ux, ay uy) > b), act_out is u bit for bit, intervened 0, correction 0.  Where
+ * a component of u is not finite, u is copied through, intervened 0, correction NaN.  act_out may alias act.
+ * One launch on `stream`, one thread per record, loads as wide as c, k1 and the alignment of z allow (16, 8 or 4 bytes), never
+ * misaligned; no atomics, no workspace, no host synchronisation: graph-capturable, bit-identical run to run.  E = 0 enqueues
+ * nothing.  EINVAL: NULL z / nbr / act / radius / act_out, E < 0, N outside 1..1024, k1 outside 2..DRONESIM_MAX_K + 1, c not in
+ * {2, 5}, rate outside (0, 0.5], margin negative or not finite, u_max <= 0 or NaN, dt <= 0 or not finite.
+ *
+ * dronesim_shield_totals adds one call's planes to per-agent running totals (the caller zeroes them): interventions [N] int64
+ * (intervened != 0), nonfinite [N] int64 (correction NaN), correction_sum [N] float64 and correction_max [N] float32 over the
+ * corrections that are not NaN.  One launch, fixed reduction order (per lane the envs ascending with stride 256, one LDS tree, one
+ * plain read-modify-write per agent), no float atomics: bit-identical run to run.  EINVAL: a NULL pointer, E < 0, N outside 1..1024. */
+int dronesim_action_shield(const float *z, const int32_t *nbr, const float *act, const float *radius, float rate, float margin,
+                           float u_max, float dt, int E, int N, int k1, int c, float *act_out, uint8_t *intervened,
+                           float *correction, void *stream);
+int dronesim_shield_totals(const uint8_t *intervened, const float *correction, int E, int N, int64_t *interventions,
+                           int64_t *nonfinite, double *correction_sum, float *correction_max, void *stream);
+
 const char *dronesim_last_error(void);
 const char *dronesim_error_string(int code);
 int dronesim_version(void);

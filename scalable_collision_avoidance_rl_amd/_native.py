@@ -41,6 +41,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_row_permutation", "dronesim_gather_rows",
            "dronesim_obsnorm_workspace", "dronesim_obsnorm_update", "dronesim_obsnorm_apply",
            "dronesim_rewnorm_workspace", "dronesim_rewnorm_update", "dronesim_rewnorm_apply",
+           "dronesim_action_shield", "dronesim_shield_totals",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -204,6 +205,9 @@ def lib():
     L.dronesim_rewnorm_update.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, i32, vp, vp, vp, C.c_double, vp, C.c_size_t, vp]
     L.dronesim_rewnorm_apply.argtypes = [vp, vp, i32, i32, i32, vp, f32, vp]
     L.dronesim_rewnorm_workspace.restype = L.dronesim_rewnorm_update.restype = L.dronesim_rewnorm_apply.restype = C.c_int
+    L.dronesim_action_shield.argtypes = [vp] * 4 + [f32] * 4 + [i32] * 4 + [vp] * 4
+    L.dronesim_shield_totals.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.dronesim_action_shield.restype = L.dronesim_shield_totals.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

@@ -87,6 +87,22 @@ def shard_range(n_envs: int, rank: int, world_size: int):
 StepResult = namedtuple("StepResult", "state z_states rewards n_collisions finished true_rewards")
 
 
+def check_execute(execute, shape, device, batched=True):
+    """``step(execute=)``'s argument: the ``[E,N,2]`` float32 tensor the launch integrates in place of ``actions``.  It is
+    handed to the kernel as it is (no conversion, no copy), so anything else is a ValueError -- raised before any launch."""
+    import torch
+    if not batched:
+        raise ValueError("step(execute=...) needs the batched (tensor) API")
+    if not torch.is_tensor(execute):
+        raise ValueError(f"execute must be a tensor, got {type(execute).__name__}")
+    if execute.dtype != torch.float32 or tuple(execute.shape) != tuple(shape) or not execute.is_contiguous():
+        raise ValueError(f"execute must be a contiguous float32 tensor of shape {tuple(shape)}, got {execute.dtype} "
+                         f"{tuple(execute.shape)}{'' if execute.is_contiguous() else ' (not contiguous)'}")
+    if execute.device != torch.device(device):
+        raise ValueError(f"execute must live on the env's device {device}, got {execute.device}")
+    return execute
+
+
 class DroneState:
     """Batched state view: ``pos``/``vel`` ``[E,N,2]`` device tensors (live), ``radius`` ``[N]``."""
     __slots__ = ("pos", "vel", "radius")
@@ -410,8 +426,12 @@ class drones:
                                         None if mask is None else mask.data_ptr(), self.n_envs, self._stream())
         self._native.check(rc, "dronesim_observe")
 
-    def step(self, actions, copy=False, into=None):
+    def step(self, actions, copy=False, into=None, execute=None):
         """One env.step() for every env (drone_env.py:214-258).
+
+        ``execute`` (batched mode; ``[E,N,2]`` float32 on this env's device): the launch integrates ``execute`` instead of
+        ``actions`` -- e.g. the output of an `ActionShield` -- while ``actions`` remains what ``into=`` records in
+        ``storage.actions[t]``: the learners keep reading the policy's own sample.  ``None``: the launch integrates ``actions``.
 
         ``into=(storage, t)`` (batched mode; a `rollout_buffer.RolloutStorage`): the launch writes every per-step
         output STRAIGHT into slot ``t`` of the storage -- reward / true_reward / n_coll / done at ``[t]``, the new
@@ -445,6 +465,7 @@ class drones:
                            np.float32)
             self._act.copy_(torch.from_numpy(a).view(1, self.n_agents, 2), non_blocking=False)
             act = self._act
+        run = act if execute is None else check_execute(execute, self._act_shape, self.device, self.batched)
         self._params()                                   # (collision_weight is live: refreshes self._p_addr when it changed)
         # host fast path: the buffer addresses never change, so dronesim_step_ex's arguments are marshalled once per output
         # binding (per storage slot when stepping into a RolloutStorage) into a DroneStepCall; a step is a 3-argument
@@ -475,10 +496,10 @@ class drones:
         if call[0].p != self._p_addr:
             call[0].p = self._p_addr
         if self._cur_device() == self._dev_index:
-            rc = self._step_call(call[1], act.data_ptr(), self._raw_stream(self._dev_index))
+            rc = self._step_call(call[1], run.data_ptr(), self._raw_stream(self._dev_index))
         else:
             with torch.cuda.device(self.device):
-                rc = self._step_call(call[1], act.data_ptr(), self._raw_stream(self._dev_index))
+                rc = self._step_call(call[1], run.data_ptr(), self._raw_stream(self._dev_index))
         if rc:
             self._native.check(rc, "dronesim_step")
         if self.batched:
@@ -609,11 +630,13 @@ class drones:
             self._sync_host_views()
         return out
 
-    def control(self, kind: str, u_max: float = 1.0, state=None):
+    def control(self, kind: str, u_max: float = 1.0, state=None, out=None):
         """Batched classical controllers evaluated on the CURRENT state (drone_env.py:609-679):
         ``kind`` = "proportional" or "gradient".  Returns actions ``[E,N,2]`` (device tensor) in batched
         mode, a list of N float64 row vectors in compat mode -- directly usable as ``step()`` input.
-        ``state`` (compat mode, ``[N,5]``): evaluate on that state instead, leaving the env untouched."""
+        ``state`` (compat mode, ``[N,5]``): evaluate on that state instead, leaving the env untouched.
+        ``out`` (batched mode): a contiguous float32 ``[E,N,2]`` tensor on this env's device to write into, e.g.
+        ``storage.actions[t]``."""
         torch = self._torch
         code = {"proportional": self._native.CONTROL_PROPORTIONAL, "gradient": self._native.CONTROL_GRADIENT}[kind]
         pos = self.pos
@@ -623,7 +646,15 @@ class drones:
             else:                                    # a hypothetical state: temporary device copy, env.state untouched
                 pos = torch.as_tensor(np.asarray(state, np.float64)[None, :, 0:2].astype(np.float32),
                                       device=self.device).contiguous()
-        act = torch.empty_like(self._act)
+        if out is None:
+            act = torch.empty_like(self._act)
+        else:
+            if not self.batched:
+                raise ValueError("control(out=...) needs the batched (tensor) API")
+            if not (torch.is_tensor(out) and out.dtype is torch.float32 and out.shape == self._act_shape and out.is_contiguous()
+                    and out.device == self.device):
+                raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(self._act_shape)} on {self.device}")
+            act = out
         p = self._params()
         with torch.cuda.device(self.device):
             rc = self._lib.dronesim_control(C.byref(p), code, pos.data_ptr(), act.data_ptr(), float(u_max),

@@ -179,6 +179,11 @@ class Evaluator:
     ``obs_norm``: the `ObsNormalizer` the networks were trained with -- both read ``obs_norm(env.z)``; its statistics are never
     updated here; network actors only.  ``safety=True``: a round also reduces the stored observations to the per-episode
     safety tables (`episode_safety`: closest approach, final goal distance, arrival); `safety_summary` reports them.
+    ``shield``: an `ActionShield` of this env -- every action passes through it before the step integrates it, while the
+    storage keeps the nominal action (``step(actions, into=, execute=safe)``).  With a controller name the round is then the
+    un-fused loop ``env.control(kind)``, shield, ``step(into=, execute=)``: THREE launches per step (four with the shield's
+    ``stats``); the fused `rollout_control` launch serves only without a shield.  A shield with ``stats=True`` has its
+    totals cleared at the start of every ``run``, and `summary` reports its intervention share and mean correction.
 
     A round is ``env.reset()``, ``T = max_time_steps`` steps into an owned `RolloutStorage`, then the two reductions.  Every env
     contributes exactly one episode per round -- its first one: a fresh episode always ends inside ``max_time_steps``
@@ -189,7 +194,7 @@ class Evaluator:
     Buffers are allocated by the first ``run`` (and again only when ``rounds`` changes); one round can be captured in a
     ``torch.cuda.graph`` after an eager warm-up call."""
 
-    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False):
+    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False, shield=None):
         from .drone_env import max_time_steps
         if not getattr(env, "batched", False):
             raise ValueError("Evaluator needs the batched (tensor) API of `drones`")
@@ -216,11 +221,16 @@ class Evaluator:
             if obs_norm is not None:
                 obs_norm.check_networks(actor, critic)
         self.actor, self.critic, self.obs_norm = actor, critic, obs_norm
+        if shield is not None and getattr(shield, "env", None) is not env:
+            raise ValueError("shield must be an ActionShield of this env")
+        self.shield = shield
         self.safety = bool(safety)
         self.T = int(max_time_steps)
+        self._rounds_run = 0
         self.storage = None
         self.tables = None
         self.safety_tables = None
+        self._safe = None                                   # the shielded action of the step in flight
 
     def _alloc(self, rounds):
         import torch
@@ -251,8 +261,17 @@ class Evaluator:
         """One round's experience: ``env.reset()`` and ``T`` steps into ``self.storage`` (no reduction)."""
         env, st = self.env, self.storage
         env.reset(renew_obstacles=False)                                        # benchmark_agent.py:112
+        shield = self.shield
         if self.controller is not None:
-            env.rollout_control(self.controller, self.T, record_actions=True, into=st)
+            if shield is None:
+                env.rollout_control(self.controller, self.T, record_actions=True, into=st)
+                return st
+            if self._safe is None:
+                self._safe = st.actions[0].clone()
+            st.begin()
+            for t in range(self.T):                                             # control, shield, step: three launches per step
+                env.control(self.controller, out=st.actions[t])
+                env.step(st.actions[t], into=(st, t), execute=shield(st.actions[t], out=self._safe))
             return st
         actor, critic, norm = self.actor, self.critic, self.obs_norm
         st.begin()
@@ -261,7 +280,12 @@ class Evaluator:
             if critic is not None:
                 critic.forward(z, out=st.values[t])
             actor.sample_action(z, env=env, act_out=st.actions[t])              # :78
-            env.step(st.actions[t], into=(st, t))                               # :81-83
+            if shield is None:
+                env.step(st.actions[t], into=(st, t))                           # :81-83
+            else:                                                               # the storage keeps the policy's own sample
+                if self._safe is None:
+                    self._safe = st.actions[0].clone()
+                env.step(st.actions[t], into=(st, t), execute=shield(st.actions[t], out=self._safe))
         return st
 
     def run(self, rounds=1):
@@ -277,6 +301,9 @@ class Evaluator:
             raise ValueError("rounds < 1")
         if self.tables is None or self.tables["ep_len"].shape[0] != rounds:
             self._alloc(rounds)
+        self._rounds_run = rounds
+        if self.shield is not None and self.shield.stats:
+            self.shield.reset_totals()
         for r in range(rounds):
             st = self.rollout()
             out = self._views[r]
@@ -307,10 +334,16 @@ class Evaluator:
     def summary(self, group=None):
         """Host-side figures of the last ``run`` (benchmark_agent.py:115-120, :151): episodes, mean return / true return /
         collisions / length per episode, the share of episodes with 0 collisions, the histogram and the per-agent mean
-        advantage.  With ``torch.distributed`` initialised, ONE all-gather of this rank's fixed-length float64 vector
+        advantage; with a shield that keeps ``stats``, also ``shield_intervention_share`` and ``shield_mean_correction`` (and the
+        shield's whole `ActionShield.summary` under ``shield``).  With ``torch.distributed`` initialised, ONE all-gather of this rank's fixed-length float64 vector
         (`sharding.all_gather_stats`) makes the figures global, the same on every rank."""
         from .sharding import all_gather_stats
-        return summarize_evaluation(all_gather_stats(self._vector(), group), self.n_bins, self.critic is not None)
+        out = summarize_evaluation(all_gather_stats(self._vector(), group), self.n_bins, self.critic is not None)
+        if self.shield is not None and self.shield.stats:   # (this rank's shield: its totals are not gathered)
+            s = self.shield.summary(calls=self._rounds_run * self.T)
+            out["shield_intervention_share"], out["shield_mean_correction"] = s["intervention_share"], s["mean_correction"]
+            out["shield"] = s
+        return out
 
 
     # fixed-length float64 vector of one rank: [episodes, arrived, successes, sum ep_min_clearance, min ep_min_clearance (+inf

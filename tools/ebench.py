@@ -6,9 +6,12 @@
   2. `dronesim_episode_safety` on a stored window of observations next to `dronesim_episode_eval, G = NULL` on the same
      storage: expected = that line scaled by the bytes fetched, counted as whole 64-byte segments touched per record;
   3. one `Evaluator` round (softmax-16 actor + critic, f16x2) next to the bare loop of examples/rollout_loop.py part 2 (b)
-     without the evaluation, and the same round with safety=True.
+     without the evaluation, and the same round with safety=True;
+  4. `--shield` (alone: nothing of 1-3 runs): `dronesim_action_shield` on the env's own observation next to the step launch,
+     `dronesim_control` and `dronesim_shield_totals` in the same session, and the control -> shield -> step(execute=) chain.
 
     python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
+    python tools/ebench.py --shield [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/shield_ebench.jsonl]
 Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
 import argparse
 import ctypes as C
@@ -119,6 +122,41 @@ def one_round(E, N, emit):
               plain_round_us=us_round, safety_us=us_safe - us_round, **{k: v for k, v in s2.items() if k != "world_size"}))
 
 
+def shield(E, N, k, c, emit):
+    """`dronesim_action_shield` (rate 0.25, margin 0.05, box 1) on the observation of an env 20 proportional steps off the
+    lattice, with the controller's action as the nominal one and with a random action in 1.5 x the box (most lanes solve);
+    the step launch, the controller and the totals launch in the same session; then the three launches of a shielded step."""
+    from scalable_collision_avoidance_rl_amd.shield import ActionShield
+    G = 28.0 if N == 64 else max(6.0, 0.45 * N)
+    env = drones(N, 0, [G, G], "O", k_closest=k, deltas=np.ones(N), simplify_zstate=c == 2, n_envs=E, seed=0, auto_reset=True)
+    act, safe = env.control("proportional"), torch.empty(E, N, 2, device=env.device)
+    for _ in range(20):
+        env.step(env.control("proportional", out=act))
+    wild = torch.rand(E, N, 2, device=env.device) * 3 - 1.5
+    sh, shs = ActionShield(env, 0.25, 0.05, 1.0), ActionShield(env, 0.25, 0.05, 1.0, stats=True)
+    k1 = k + 1
+    nbytes = 4 * k1 * c + 4 * k1 + 8 + 8 + 1 + 4
+    base = dict(E=E, N=N, k=k, c=c)
+    for name, u in (("dronesim_action_shield, controller's action", act), ("dronesim_action_shield, random action in 1.5 x the box", wild)):
+        us, lo = gtime(lambda: sh(u, out=safe))
+        emit(dict(what=name, us=us, us_min=lo, bytes_per_record=nbytes, tb_s=E * N * nbytes / 1e6 / us,
+                  intervention_share=float(sh.intervened.float().mean()), **base))
+    us_both, lo_both = gtime(lambda: shs(act, out=safe))
+    emit(dict(what="dronesim_action_shield + dronesim_shield_totals", us=us_both, us_min=lo_both, **base))
+    us_ctl, lo_ctl = gtime(lambda: env.control("proportional", out=act))
+    emit(dict(what="dronesim_control (proportional)", us=us_ctl, us_min=lo_ctl, **base))
+    us_step, lo_step = gtime(lambda: env.step(wild))
+    emit(dict(what="step launch (env.step, episode layer, auto_reset)", us=us_step, us_min=lo_step, **base))
+
+    def chain():
+        env.control("proportional", out=act)
+        env.step(act, execute=sh(act, out=safe))
+    us, lo = gtime(chain)
+    emit(dict(what="control -> shield -> step(execute=)", us=us, us_min=lo, **base))
+    us, lo = gtime(lambda: env.step(env.control("proportional", out=act)))
+    emit(dict(what="control -> step", us=us, us_min=lo, **base))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=200)
@@ -128,6 +166,7 @@ def main():
     ap.add_argument("--c", type=int, default=2, choices=(2, 5), help="floats per row of the safety window's records")
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-round", action="store_true")
+    ap.add_argument("--shield", action="store_true", help="only the action shield next to the step launch")
     ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     a = ap.parse_args()
 
@@ -139,6 +178,9 @@ def main():
         if a.out:
             with open(a.out, "a") as f:
                 f.write(line + "\n")
+    if a.shield:
+        shield(a.envs, a.agents, a.k, a.c, emit)
+        return
     done, us_eval = kernels(a.T, a.envs, a.agents, emit)
     safety(a.T, a.envs, a.agents, a.k, a.c, done, us_eval, emit)
     if not a.skip_round:
