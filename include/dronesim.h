@@ -812,7 +812,9 @@ int dronesim_rewnorm_apply(const float *reward, float *out, int T, int E, int N,
  * intervened [E][N] uint8 and correction [E][N] float32 = |u* - u| may be NULL.  Where u satisfies every constraint as the kernel
  * evaluates it (float32: d = sqrt(fma(py, py, px px)), a = p (1 / d), g = ((d - radius[i]) - radius[j]) - margin,
  * b = (rate / dt) max(g, 0), violated where fma(ax, ux, ay uy) > b), act_out is u bit for bit, intervened 0, correction 0.  Where
- * a component of u is not finite, u is copied through, intervened 0, correction NaN.  act_out may alias act.
+ * a component of u is not finite, u is copied through, intervened 0, correction NaN.  act_out may alias act.  The correction
+ * of a finite u is finite wherever |u* - u| is a float32 (the norm is taken of the components scaled by a power of two, so their
+ * squares do not overflow for |u* - u| > 2^64).
  * One launch on `stream`, one thread per record, loads as wide as c, k1 and the alignment of z allow (16, 8 or 4 bytes), never
  * misaligned; no atomics, no workspace, no host synchronisation: graph-capturable, bit-identical run to run.  E = 0 enqueues
  * nothing.  EINVAL: NULL z / nbr / act / radius / act_out, E < 0, N outside 1..1024, k1 outside 2..DRONESIM_MAX_K + 1, c not in

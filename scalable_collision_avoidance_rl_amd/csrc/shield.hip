@@ -29,6 +29,10 @@ constexpr int kShieldM = kShieldBox + kShieldSlots;
 // |a_j . t_i| at or below this counts as parallel (2^-21): such a line bounds nothing on line i that it did not bound before
 // (both b >= 0: see DESIGN.md), and dividing by it would turn rounding noise into an interval end
 constexpr float kShieldParallel = 4.76837158203125e-07f;
+// Every earlier neighbour half-plane is relaxed on line m by kShieldNoise (4 b_m + min(|ux| + |uy|, 2 u_max)) -- 2 eps32 of the terms that num
+// and s den are computed from at the ends that can clip s0 wrongly or be the answer inside the box: a violation of that size is
+// rounding, not geometry, and at a small angle its end num / den lies anywhere on the line
+constexpr float kShieldNoise = 1.1920928955078125e-07f;
 
 typedef float sh_f4 __attribute__((ext_vector_type(4)));
 typedef float sh_f2 __attribute__((ext_vector_type(2)));
@@ -127,17 +131,20 @@ __global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
         if (m < M) violated |= fmaf(ax[m], ux, ay[m] * uy) > b[m];
     float x = ux, y = uy, corr = finite ? 0.0f : __builtin_nanf("");
     if (finite && violated) {
+        // |s0| <= |ux| + |uy| + b_m on every line m; inside the box |s| <= 2 u_max + b_m (+inf: no box)
+        const float noise_u = kShieldNoise * fminf(__builtin_fabsf(ux) + __builtin_fabsf(uy), 2.0f * a.u_max);
 #pragma unroll
         for (int m = 0; m < kShieldM; ++m) {
             if (m < M && fmaf(ax[m], x, ay[m] * y) > b[m]) {
                 const float qx = b[m] * ax[m], qy = b[m] * ay[m];                      // the line's point closest to 0 (|a| = 1)
                 const float tx = -ay[m], ty = ax[m];
-                const float s0 = fmaf(tx, ux - qx, ty * (uy - qy));
+                const float s0 = fmaf(tx, ux, ty * uy);                                 // t . (u - q), and t . q = 0
+                const float slack = fmaf(4.0f * kShieldNoise, b[m], noise_u);
                 float lo = -inf, hi = inf;
 #pragma unroll
                 for (int n = 0; n < m; ++n) {
                     const float den = fmaf(ax[n], tx, ay[n] * ty);
-                    const float num = b[n] - fmaf(ax[n], qx, ay[n] * qy);
+                    const float num = fmaf(-ax[n], qx, fmaf(-ay[n], qy, b[n])) + (n < kShieldBox ? 0.0f : slack);   // (the box stays exact)
                     const float at = num * __builtin_amdgcn_rcpf(den);
                     hi = den > kShieldParallel ? fminf(hi, at) : hi;
                     lo = den < -kShieldParallel ? fmaxf(lo, at) : lo;
@@ -146,8 +153,13 @@ __global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
                 x = fmaf(s, tx, qx); y = fmaf(s, ty, qy);
             }
         }
+        // |u* - u|; where the squares overflow (|u* - u| > 2^64), of the components scaled by 2^-64: the value is a float32
         const float dx = x - ux, dy = y - uy;
         corr = __builtin_sqrtf(fmaf(dy, dy, dx * dx));
+        if (corr == inf) {
+            const float sx = dx * 0x1p-64f, sy = dy * 0x1p-64f;
+            corr = __builtin_sqrtf(fmaf(sy, sy, sx * sx)) * 0x1p+64f;
+        }
     }
     if (a.act8) {
         sh_f2 o; o.x = x; o.y = y;

@@ -212,3 +212,178 @@ def test_shield_totals_entry_point_refuses_bad_arguments():
                 dict(correction_max=None), dict(E=-1), dict(N=0), dict(N=_native.MAX_AGENTS + 1)]:
         assert call(**bad) == _native.EINVAL, bad
         assert b"dronesim_shield_totals" in lib.dronesim_last_error()
+
+
+# ---- the inputs of tests/test_gpu_shield_geometry.py -------------------------------------------------------------------------------
+# sha256 over z, nbr, u, radius (bytes, in this order) of `synthetic` at its defaults: the recorded cases must not move
+SYNTHETIC_SHA256 = {
+    (2, 1, 2): "f972cf046a99801512ada3de419e92b1baf3257cff5a874aaa8e9d7a9fc5f535",
+    (5, 2, 2): "2e2ba53e99cb69a2f446ef4898e82e7a0f596b54a5da0ceb2b8bef189b810fa1",
+    (5, 2, 5): "86f438e28d45ea5b7930f8d86aac2b25c56b3299dba1553bf8d6becce3f63a08",
+    (9, 8, 2): "a78d709aee22651c7c3e200453b568f255372a422d0d6a0c15f4ecc941293794",
+    (1, 1, 2): "1b34f9364b1edea3d19cf3f2e53379ada624a25dd5dfd3e6fe903965e2f35016",
+}
+# (2, 1, 2): the first record of z and the last action, as a second witness that does not depend on a hash
+SYNTHETIC_FIRST = [-1.0487247705459595, -1.7071058750152588, 0.15000969171524048, 0.22014006972312927]
+SYNTHETIC_LAST = [-0.2521995007991791, -1.1860641241073608]
+# the smallest share of records (by the prefix of the figure's name) in which the named constraint must bind
+BINDING_MIN = {"axes neighbour and box": 0.08, "axes neighbour": 0.6, "axes b below": 0.5, "axes b above": 0.08,
+               "duplicates bind": 0.25, "duplicates triple": 0.25, "duplicates b1": 0.25,
+               "antipodal both b > 0 binds": 0.25, "antipodal one b = 0 binds": 0.5, "antipodal both b = 0 binds": 1.0,
+               "antipodal line": 1.0, "antipodal": 0.15,
+               "crowd point two": 1.0, "crowd point": 0.5, "crowd cone": 0.6,
+               "near_parallel": 0.0, "wedge 1 deg": 0.85, "wedge": 0.9, "magnitude box": 1.0, "magnitude no box": 0.6}
+
+
+def test_synthetic_defaults_still_give_the_recorded_arrays():
+    import hashlib
+    for case in S.CASES:
+        r = S.synthetic(*case)
+        h = hashlib.sha256(b"".join(np.ascontiguousarray(r[n]).tobytes() for n in ("z", "nbr", "u", "radius"))).hexdigest()
+        assert h == SYNTHETIC_SHA256[case], (case, h)
+        assert r["z"].dtype == np.float32 and r["nbr"].dtype == np.int32 and r["u"].dtype == np.float32 and r["radius"].dtype == np.float32
+    r = S.synthetic(2, 1, 2)
+    assert r["z"][0, 0].tolist() == SYNTHETIC_FIRST and r["u"][-1, -1].tolist() == SYNTHETIC_LAST
+
+
+@pytest.fixture(scope="module")
+def fams():
+    return S.families()
+
+
+@pytest.fixture(scope="module")
+def fam_refs(fams):
+    return {name: [(label, e0, e1, S.block_reference(fam, e0, e1)) for label, e0, e1 in fam["blocks"]] for name, fam in fams.items()}
+
+
+def test_families_are_what_the_gpu_test_expects(fams):
+    assert list(fams) == S.FAMILY_NAMES and list(S.families(0)) == S.FAMILY_NAMES
+    for name, fam in fams.items():
+        E, N, k1 = fam["nbr"].shape
+        assert N >= 3 and fam["c"] == 2 and fam["z"].shape == (E, N, 2 * k1) and fam["u"].shape == (E, N, 2), name
+        assert fam["z"].dtype == np.float32 and fam["u"].dtype == np.float32 and fam["nbr"].dtype == np.int32, name
+        rad = fam["radius"]
+        assert rad.dtype == np.float32 and rad.shape == (N,) and len(np.unique(rad)) == N and rad.min() >= 0.05 and rad.max() <= 0.2, name
+        assert (fam["nbr"][:, :, 0] == np.arange(N)).all() and np.isfinite(fam["u"]).all(), name
+        assert [b[1] for b in fam["blocks"]] == [0] + [b[2] for b in fam["blocks"]][:-1] and fam["blocks"][-1][2] == E, name
+    count = lambda prefix: sum(f["nbr"].shape[0] * f["nbr"].shape[1] for n, f in fams.items() if n.startswith(prefix))
+    for prefix in ("axes", "duplicates", "antipodal", "crowd", "near_parallel", "wedge", "magnitude"):
+        assert 2000 <= count(prefix) <= 4000, (prefix, count(prefix))
+    assert count("order") == 2 * (count("wedge") + count("crowd"))
+    again = S.families()
+    assert all(np.array_equal(fams[n][a], again[n][a]) for n in fams for a in ("z", "nbr", "u", "radius"))     # seeded
+
+
+@pytest.mark.parametrize("name", S.FAMILY_NAMES)
+def test_family_reference_is_feasible_idempotent_and_outside_the_flag_band(fams, fam_refs, name):
+    for label, e0, e1, r in fam_refs[name]:
+        what = f"{name} {label}"
+        assert (r["B"] >= 0).all(), what
+        slack = (r["A"] * r["ustar"][:, None, :]).sum(2) - r["B"]
+        # (`project` accepts a candidate within 1e-12 of the record's scale 1 + |u|inf + max b: the huge actions carry theirs)
+        scale = 1.0 + np.abs(r["u"]).max() + r["B"][np.isfinite(r["B"])].max(initial=0.0)
+        assert slack.max() <= 2e-12 * scale, what
+        again = S.project(r["ustar"], r["A"], r["B"], r["on"])
+        assert np.abs(again - r["ustar"]).max() <= 4e-12 * scale, what
+        band = (r["min_slack"] <= r["tol"]).mean()
+        print(f"{what}: tol {r['tol']:.3e}, flag band {band:.4f}, intervened {r['intervened'].mean():.3f}")
+        assert band <= 0.02, (what, band)
+        if name.startswith(S.ILL_CONDITIONED):
+            fin = np.isfinite(r["B"])
+            assert (r["B"][fin] >= 2 * r["tol"]).all(), what                       # C(B - tol) still contains 0
+            low = S.lowered(r, r["tol"])
+            u = r["u"].reshape(-1, 2).astype(np.float64)
+            assert (np.linalg.norm(low - u, axis=1) >= np.linalg.norm(r["ustar"] - u, axis=1) - 1e-11 * scale).all(), what
+
+
+def share(mask):
+    return float(np.mean(mask))
+
+
+def test_the_constraint_a_family_is_about_binds(fams, fam_refs):
+    """From the float64 answer: the share of records in which the constraints the family is named after hold with equality at
+    u* (`S.active`), against a stated minimum."""
+    one = lambda name: fam_refs[name][0][3]
+    nb = lambda act, *slots: np.any([act[:, S.M_BOX + s - 1] for s in slots], axis=0)
+    both = lambda act, *slots: np.all([act[:, S.M_BOX + s - 1] for s in slots], axis=0)
+    got = {}
+    # axes: an axis-aligned neighbour line binds; alone, with a box face, and b on both sides of u_max
+    r = one("axes"); act = S.active(r)
+    Bn, on = r["B"][:, S.M_BOX:], r["on"][:, S.M_BOX:]
+    got["axes neighbour"] = share(act[:, S.M_BOX:].any(1))
+    got["axes neighbour and box"] = share(act[:, S.M_BOX:].any(1) & act[:, :S.M_BOX].any(1))
+    got["axes b below u_max"], got["axes b above u_max"] = share((Bn < S.U_MAX)[on]), share((Bn > S.U_MAX)[on])
+    # duplicates: one of the lines with the same direction binds; both b orders of slots 1, 2 occur
+    r = one("duplicates"); act = S.active(r)
+    got["duplicates bind"] = share(nb(act, 1, 2))
+    got["duplicates triple bind"] = share(nb(act, 1, 2, 3)[fams["duplicates"]["triple"]])
+    B1, B2 = r["B"][:, S.M_BOX], r["B"][:, S.M_BOX + 1]
+    got["duplicates b1 < b2"], got["duplicates b1 > b2"] = share(B1 < B2), share(B1 > B2)
+    assert (r["A"][:, S.M_BOX] == r["A"][:, S.M_BOX + 1]).all()                  # the same direction bit for bit
+    # antipodal: the three kinds, and in each a line of the pair binds
+    r = one("antipodal"); act = S.active(r)
+    assert (r["A"][:, S.M_BOX] == -r["A"][:, S.M_BOX + 1]).all()
+    B1, B2 = r["B"][:, S.M_BOX], r["B"][:, S.M_BOX + 1]
+    kinds = {"both b > 0": (B1 > 0) & (B2 > 0), "one b = 0": (B1 > 0) != (B2 > 0), "both b = 0": (B1 == 0) & (B2 == 0)}
+    for kind, m in kinds.items():
+        got[f"antipodal {kind}"] = share(m)
+        got[f"antipodal {kind} binds"] = share(nb(act, 1, 2)[m])
+    got["antipodal line: both bind"] = share(both(act, 1, 2)[kinds["both b = 0"]])
+    # crowd: the set is {0} (at least two b = 0 lines bind at u* = 0) or a cone (a b = 0 line binds)
+    r = one("crowd"); act = S.active(r)
+    point = fams["crowd"]["point"]
+    zero = act[:, S.M_BOX:] & (r["B"][:, S.M_BOX:] == 0)
+    assert (r["ustar"][point] == 0).all()
+    got["crowd point"], got["crowd point two bind"] = share(point), share((zero.sum(1) >= 2)[point])
+    got["crowd cone binds"] = share(zero.any(1)[~point])
+    # near_parallel: a line of the pair binds; both do (the vertex) in some; every e on both sides of 2^-21
+    for name in S.FAMILY_NAMES:
+        if name.startswith("near_parallel"):
+            r = one(name); act = S.active(r, rel=1e-7)
+            got[f"{name} pair binds"] = share(nb(act, 1, 2))
+            got[f"{name} vertex"] = share(both(act, 1, 2))
+            assert set(fams[name]["e"]) == set(S.NEAR_PARALLEL_E) and fams[name]["third"].any() and not fams[name]["third"].all()
+    # wedge: the vertex of the two lines is the answer, at every angle
+    for label, _, _, r in fam_refs["wedge"]:
+        got[f"wedge {label} vertex"] = share(both(S.active(r), 1, 2))
+    # magnitude: the shield intervenes
+    for name in ("magnitude box", "magnitude no box"):
+        for label, _, _, r in fam_refs[name]:
+            got[f"{name} {label} intervened"] = share(r["intervened"])
+    for what, v in got.items():
+        print(f"{what}: {v:.3f}")
+    near = {"pair binds": 0.9, "vertex": 0.35}                                      # (vertex: both lines of the pair within 1e-7)
+    floor = {what: BINDING_MIN[next(p for p in BINDING_MIN if what.startswith(p))] for what in got}
+    floor.update({what: v for what in got if what.startswith("near_parallel") for end, v in near.items() if what.endswith(end)})
+    assert all(got[what] >= floor[what] for what in got), {w: (got[w], floor[w]) for w in got if got[w] < floor[w]}
+
+
+@pytest.mark.parametrize("shape", S.GEOMETRY_SHAPES + [S.WIDE_SHAPE] + S.PARAMETER_SHAPES, ids=lambda s: "N%dk%dc%d" % s)
+def test_new_shapes_and_parameter_sets_keep_the_flag_band_and_unequal_radii(shape):
+    N, k, c = shape
+    E = S.WIDE_E if shape == S.WIDE_SHAPE else S.E_CASE
+    for rate, margin, u_max in [(S.RATE, S.MARGIN, S.U_MAX)] + (S.PARAMETER_SETS if shape in S.PARAMETER_SHAPES else []):
+        rad = S.radii(N)
+        r = S.reference(S.synthetic(N, k, c, E=E, radius=rad, margin=margin, u_max=u_max), c, rate, margin, u_max)
+        assert rad.min() >= 0.05 and rad.max() <= 0.2 and len(np.unique(rad)) >= min(N, 8)
+        assert (r["min_slack"] <= r["tol"]).mean() <= 0.02
+        nb = r["on"][:, S.M_BOX:]
+        assert nb.any() and r["intervened"].any() and not r["intervened"].all()
+        assert (S.active(r)[:, S.M_BOX:].any(1)).mean() >= 0.2                      # neighbour lines bind at these parameters
+
+
+@pytest.mark.parametrize("N,E", [(2, 512), (4, 256), (9, 112)])
+def test_mutual_records_list_everyone_at_gaps_from_below_the_margin_to_half(N, E):
+    w = S.mutual(N, E)
+    rad, x = w["radius"].astype(np.float64), w["pos"].astype(np.float64)
+    assert w["pos"].dtype == np.float32 and len(np.unique(rad)) == N
+    z, nbr = w["z"].reshape(E, N, N, 2), w["nbr"]
+    for i in range(N):
+        others = [j for j in range(N) if j != i]
+        assert nbr[:, i].tolist() == [[i] + others] * E
+        assert np.array_equal(z[:, i, 1:], (x[:, others] - x[:, i:i + 1]).astype(np.float32))
+    iu, ju = np.triu_indices(N, 1)
+    clear = np.linalg.norm(x[:, iu] - x[:, ju], axis=2) - rad[iu] - rad[ju]
+    nearest = np.array([[clear[e][(iu == i) | (ju == i)].min() for i in range(N)] for e in range(E)])
+    assert clear.min() > 0 and nearest.min() < S.MARGIN and 0.3 < nearest.max() <= 0.5 + 1e-6
+    assert (clear < S.MARGIN).mean() >= 0.05
