@@ -356,12 +356,10 @@ def test_the_gate_resets_for_the_next_window(torch):
 
 
 # 11 -------------------------------------------------------------------------------------------------------------------
-def compare_guarded_with_float64(torch, learner, actor, critic, out, ref, epochs, K, M, what):
-    """`test_gpu_minibatch.compare_with_float64`'s assertions and bars on the steps the restatement computed; the steps it skipped
-    are NaN.  ``out`` entries ``[epochs, K, N]`` (a whole-window learner's are viewed so)."""
-    N = actor.n_agents
-    steps = epochs * K
-    taken = ref["actor_steps"]
+def compare_guarded_steps(torch, out, ref, epochs, K, M, what, skip_actor_loss=()):
+    """The per-step part of `compare_guarded_with_float64`: `test_gpu_minibatch.compare_with_float64`'s assertions and bars on the
+    steps the restatement computed; the steps it skipped are NaN.  ``out`` entries ``[epochs, K, N]``.  ``skip_actor_loss``: the steps
+    (``ep K + b``) whose ``actor_loss`` the caller compares itself."""
     for ep in range(epochs):
         for b in range(K):
             j = ep * K + b
@@ -379,9 +377,10 @@ def compare_guarded_with_float64(torch, learner, actor, critic, out, ref, epochs
             s = stepped.nonzero().flatten()
             np.testing.assert_allclose(got[s].numpy(), ref["actor_norm"][j][s].numpy(), rtol=1e-5)
             assert bool(torch.isnan(got[~stepped]).all()), j
-            aref = a["loss"].numpy()
-            al = out["actor_loss"][ep, b].cpu()
-            np.testing.assert_allclose(al[on].numpy(), aref[on.numpy()], rtol=1e-4, atol=1e-4 * np.abs(aref).max())
+            if j not in skip_actor_loss:
+                aref = a["loss"].numpy()
+                al = out["actor_loss"][ep, b].cpu()
+                np.testing.assert_allclose(al[on].numpy(), aref[on.numpy()], rtol=1e-4, atol=1e-4 * np.abs(aref).max())
             for k in ACTOR_KEYS:
                 if k in out:
                     assert bool(torch.isfinite(out[k][ep, b].cpu()[on]).all()) and bool(torch.isnan(out[k][ep, b].cpu()[~computed]).all()), (k, j)
@@ -393,15 +392,28 @@ def compare_guarded_with_float64(torch, learner, actor, critic, out, ref, epochs
                 vcount = torch.round(out["vf_clip_fraction"][ep, b].double().cpu() * M).long()
                 print(what, "step", j, "value rows clipped", vcount.tolist(), "ref", c["zero"].sum(0).tolist(), "near", c["near"].sum(0).tolist())
                 assert torch.all((vcount - c["zero"].sum(0)).abs() <= c["near"].sum(0)), (j, vcount, c["zero"].sum(0))
+
+
+def compare_guarded_weights(torch, mlp, lr, post, m2, n_steps, what=""):
+    """The weight part of `compare_guarded_with_float64`: the sharp / loose split on sqrt(m2), times the steps ``n_steps`` [N] each
+    agent took."""
+    for name, p, v in zip(NAMES, post, m2):
+        got = getattr(mlp, name).double().cpu()
+        sharp = v.sqrt() > 1e-3 * float(v.sqrt().max())
+        tol = torch.where(sharp, torch.full_like(p, 1e-6 + 1e-3 * lr), torch.full_like(p, 2 * lr))
+        tol = tol * n_steps.double().view(-1, *([1] * (v.dim() - 1)))
+        assert torch.all((got - p).abs() <= tol), (what, name, float(((got - p).abs() - tol).max()))
+
+
+def compare_guarded_with_float64(torch, learner, actor, critic, out, ref, epochs, K, M, what):
+    """One call from fresh optimisers: `compare_guarded_steps`, the two step counters, `compare_guarded_weights`."""
+    N = actor.n_agents
+    steps = epochs * K
+    taken = ref["actor_steps"]
+    compare_guarded_steps(torch, out, ref, epochs, K, M, what)
     assert learner.critic_opt.steps.cpu().tolist() == [steps] * N and learner.actor_opt.steps.cpu().tolist() == taken.tolist()
-    for opt, mlp, post, m2, n_steps in ((learner.critic_opt, critic, ref["critic_post"], ref["cm2"], torch.full((N,), steps)),
-                                        (learner.actor_opt, actor, ref["actor_post"], ref["am2"], taken)):
-        for name, p, v in zip(NAMES, post, m2):
-            got = getattr(mlp, name).double().cpu()
-            sharp = v.sqrt() > 1e-3 * float(v.sqrt().max())
-            tol = torch.where(sharp, torch.full_like(p, 1e-6 + 1e-3 * opt.lr), torch.full_like(p, 2 * opt.lr))
-            tol = tol * n_steps.double().view(-1, *([1] * (v.dim() - 1)))
-            assert torch.all((got - p).abs() <= tol), (name, float(((got - p).abs() - tol).max()))
+    compare_guarded_weights(torch, critic, learner.critic_opt.lr, ref["critic_post"], ref["cm2"], torch.full((N,), steps))
+    compare_guarded_weights(torch, actor, learner.actor_opt.lr, ref["actor_post"], ref["am2"], taken)
 
 
 def test_minibatches_with_both_guards_and_the_other_options_match_float64(torch):
