@@ -10,6 +10,7 @@ each (E x rounds >= --episodes), every step of every env in one launch, and the 
     python examples/benchmark_agent.py ... --obs-norm stats.pt             # the observation statistics the networks were trained with
     python examples/benchmark_agent.py ... --safety                        # closest approach, arrival and formation error per episode
     python examples/benchmark_agent.py ... --shield [--shield-rate X --shield-margin X]   # the same episodes again through an ActionShield
+    python examples/benchmark_agent.py ... --obstacles 8 [--shield --safety]              # static discs that matter
 
 ``--obs-norm FILE``: an `ObsNormalizer.state_dict()` saved with ``torch.save``; the actor and the critic then read the normalised
 observation (the reference's files carry no statistics, so there is none by default).
@@ -18,6 +19,11 @@ observation (the reference's files carry no statistics, so there is none by defa
 (box 1, the clip of the controllers and the norm of the discrete actions) before the step integrates it, and the collision-free
 share is printed next to the unshielded one, with the share of decisions the shield changed and what it cost in arrival
 (``--safety``).  With ``--controller`` the shielded rounds are three launches per step instead of one fused launch per round.
+
+``--obstacles N``: N discs of the reference's sizes off the goals (`place_obstacles`) in an `ObstacleField`; the evaluation (with
+``--safety`` implied) then reports the share of episodes in which no agent touched a disc, and with ``--shield`` the shield also
+projects onto one half-plane per listed disc, so the obstacle-free share is printed shielded next to unshielded.  The reward and
+the networks' input do not know the discs.
 """
 import argparse
 import os
@@ -29,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import scalable_collision_avoidance_rl_amd.drone_env as drone_env          # was: import drone_env
 from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, TrainedAgent    # was: from SAC_agents import *
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
+from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles
 from scalable_collision_avoidance_rl_amd.shield import ActionShield
 
 
@@ -47,7 +54,10 @@ def main():
     ap.add_argument("--shield", action="store_true", help="run the episodes again through an ActionShield and compare")
     ap.add_argument("--shield-rate", type=float, default=0.25, help="share of a gap an agent may close per step, in (0, 0.5]")
     ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
+    ap.add_argument("--obstacles", type=int, default=0, help="static discs off the goals, sensed, reported and (--shield) enforced")
+    ap.add_argument("--obstacle-rate", type=float, default=None, help="share of the gap to a disc an agent may close per step, in (0, 1]")
     a = ap.parse_args()
+    a.safety = a.safety or a.obstacles > 0
 
     if a.controller:
         n_agents, actor, critic = a.agents or 8, a.controller, None
@@ -69,7 +79,13 @@ def main():
     if a.obs_norm:
         import torch
         obs_norm = ObsNormalizer(n_agents, env.local_state_space, env.device).load_state_dict(torch.load(a.obs_norm))
-    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety)
+    field = None
+    if a.obstacles:
+        discs = place_obstacles(env.grid, a.obstacles, seed=0, keep_clear=env.end_points.reshape(n_agents, 2), clearance=0.3)
+        field = ObstacleField(env, discs, m=2)
+        print(f"Obstacles = {field.M} discs (of {a.obstacles} drawn; the rest covered a goal), radius {discs[:, 2].min():.2f} .. "
+              f"{discs[:, 2].max():.2f} m" if field.M else f"Obstacles = 0 (all {a.obstacles} drawn covered a goal)")
+    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, obstacles=field)
     ev.run(rounds)
     s = ev.summary()
     print(f"Episodes {s['episodes']} - Average Reward/Collisions/Steps: {s['mean_return']:.1f}/{s['mean_collisions']:.2f}/"
@@ -89,9 +105,14 @@ def main():
               f"Mean step of an agent's arrival = {fmt(f['mean_arrive_step'], '.1f')}")
         print(f"Smallest clearance per episode: mean {f['mean_min_clearance']:.3f} m, minimum {fmt(f['min_clearance'], '.3f')} m. "
               f"Largest final goal distance per episode: mean {f['mean_goal_dist_max']:.3f} m")
+        if field is not None:
+            print(f"Episodes without an obstacle hit = {f['obstacle_free_share'] * 100:.2f}%. Arrived with no collision and no hit = "
+                  f"{f['arrived_clear_share'] * 100:.2f}%. Smallest gap to a disc per episode: mean {f['mean_min_obstacle_gap']:.3f} m, "
+                  f"minimum {fmt(f['min_obstacle_gap'], '.3f')} m")
     if a.shield:                                             # (no reference line: the reference has no safety layer)
-        shield = ActionShield(env, rate=a.shield_rate, margin=a.shield_margin, u_max=1.0, stats=True)
-        evs = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, shield=shield)
+        shield = ActionShield(env, rate=a.shield_rate, margin=a.shield_margin, u_max=1.0, stats=True, obstacles=field,
+                              obstacle_rate=a.obstacle_rate if field is not None else None)
+        evs = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, shield=shield, obstacles=field)
         evs.run(rounds)
         t = evs.summary()
         print(f"### Shielded (rate = {shield.rate}, margin = {shield.margin} m, box = {shield.u_max})")
@@ -106,6 +127,10 @@ def main():
             print(f"Arrived = {g['arrived_share'] * 100:.2f}% (unshielded {f['arrived_share'] * 100:.2f}%). Smallest clearance per episode: "
                   f"mean {g['mean_min_clearance']:.3f} m, minimum {fmt(g['min_clearance'], '.3f')} m (unshielded "
                   f"{fmt(f['min_clearance'], '.3f')} m)")
+            if field is not None:
+                print(f"Episodes without an obstacle hit: shielded {g['obstacle_free_share'] * 100:.2f}%, unshielded "
+                      f"{f['obstacle_free_share'] * 100:.2f}%. Smallest gap to a disc: shielded {fmt(g['min_obstacle_gap'], '.3f')} m, "
+                      f"unshielded {fmt(f['min_obstacle_gap'], '.3f')} m")
 
 
 if __name__ == "__main__":

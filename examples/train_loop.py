@@ -8,7 +8,7 @@ actor loss + clip + Adam, for all N agents' networks at once in HIP.
                                   [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
                                   [--normalize-advantage] [--minibatches K] [--shuffle-seed S] [--target-kl X] [--vf-clip X]
                                   [--obs-norm] [--obs-clip X] [--share all] [--grid G] [--reward-norm] [--reward-clip X]
-                                  [--shield] [--shield-rate X] [--shield-margin X]
+                                  [--shield] [--shield-rate X] [--shield-margin X] [--obstacles N]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -51,7 +51,10 @@ Try ``--grid 28 --reward-norm --obs-norm``.
 ``--shield`` trains THROUGH an `ActionShield` (rate ``--shield-rate``, margin ``--shield-margin``, box 1): the env integrates
 the projected action, the projection counting as part of the environment, while the storage -- and with it the learner -- keeps
 the policy's own sample (the discrete actor's action index needs unit vectors).  Every episode line then shows the share of the
-window's decisions the shield changed and the mean correction.
+window's decisions the shield changed and the mean correction.  ``--obstacles N`` (with ``--shield``) puts N static discs of the
+reference's sizes off the goals (`place_obstacles`, an `ObstacleField`): the shield then also projects onto one half-plane per
+listed disc, and every episode line shows the share of the window's first episodes in which no agent touched a disc.  The reward
+and the networks' input do not know the discs: the policy meets them as part of the environment.
 
 ``--share all`` trains ONE actor and ONE critic for the whole team (parameter sharing): the networks are tied
 (`BatchedMLP.tie_weights`) and every update pools the agents' gradients (`dronesim_adam_step_shared`); with ``--target-kl`` the
@@ -70,6 +73,7 @@ import torch
 from scalable_collision_avoidance_rl_amd import drones
 from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
+from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles
 from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
 from scalable_collision_avoidance_rl_amd.reward_norm import RewardNormalizer
 from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
@@ -116,7 +120,10 @@ def main():
     ap.add_argument("--shield", action="store_true", help="train through an ActionShield: the env integrates the projected action")
     ap.add_argument("--shield-rate", type=float, default=0.25, help="share of a gap an agent may close per step, in (0, 0.5]")
     ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
+    ap.add_argument("--obstacles", type=int, default=0, help="static discs off the goals, enforced by the shield (needs --shield)")
     args = ap.parse_args()
+    if args.obstacles and not args.shield:
+        ap.error("--obstacles needs --shield (nothing else enforces the discs)")
     if args.minibatches != 1 and args.learner != "ppo":
         ap.error("--minibatches needs --learner ppo (one update per window is what A2C is)")
     if args.normalize_advantage and args.learner != "ppo":
@@ -134,7 +141,11 @@ def main():
         actor.tie_weights(args.share)
         critic.tie_weights(args.share)
     storage = RolloutStorage(env, T, actions=True)
-    shield = ActionShield(env, args.shield_rate, args.shield_margin, u_max=1.0, stats=True) if args.shield else None
+    field = None
+    if args.obstacles:
+        field = ObstacleField(env, place_obstacles(env.grid, args.obstacles, seed=0, keep_clear=env.end_points.reshape(N, 2),
+                                                   clearance=0.3), m=2)
+    shield = ActionShield(env, args.shield_rate, args.shield_margin, u_max=1.0, stats=True, obstacles=field) if args.shield else None
     safe = torch.empty(E, N, 2, device=dev) if shield is not None else None
 
     def step(t):              # the storage keeps the policy's own sample; with a shield the env integrates its projection
@@ -198,6 +209,11 @@ def main():
         if shield is not None:
             sh = shield.summary()
             ppo += f"  shield changed {sh['intervention_share']:.2%} of the decisions, mean correction {sh['mean_correction']:.4f}"
+        if field is not None:
+            tab = field.episode_safety(storage)
+            ok = tab["ep_len"] > 0
+            free = (ok & (tab["ep_obstacle_hit_steps"] == 0)).sum().item() / max(int(ok.sum().item()), 1)
+            ppo += f"  obstacle-free episodes {free:.2%} ({field.M} discs)"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(mean(out['actor_loss'])):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
               f"{float(mean(out['actor_grad_norm'])):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")

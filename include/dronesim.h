@@ -45,6 +45,8 @@ extern "C" {
                                           points moved to libdronesim_verify.so (dronesim_verify.h), DroneMlpBf16.wscale */
 #define DRONESIM_MAX_K 8               /* k_closest supported by the kernels */
 #define DRONESIM_MAX_AGENTS 1024       /* one workgroup holds one env */
+#define DRONESIM_MAX_OBSTACLES 1024    /* static discs of an obstacle list (12 KB staged per workgroup) */
+#define DRONESIM_MAX_SENSE 4           /* obstacle list slots per agent */
 
 #define DRONESIM_OK 0
 #define DRONESIM_EINVAL (-1)           /* null pointer / size out of range */
@@ -829,6 +831,56 @@ int dronesim_action_shield(const float *z, const int32_t *nbr, const float *act,
                            float *correction, void *stream);
 int dronesim_shield_totals(const uint8_t *intervened, const float *correction, int E, int N, int64_t *interventions,
                            int64_t *nonfinite, double *correction_sum, float *correction_max, void *stream);
+
+/* Static obstacle discs (csrc/obstacles.hip, csrc/shield.hip; DESIGN.md has the guarantee and its conditions).  The step kernel,
+ * the reward and the networks never read them: these entries work on stored observations, beside the step.
+ *
+ * Inputs: obstacles [M][3] float32 (x, y, r), one list shared by all envs, 0 <= M <= DRONESIM_MAX_OBSTACLES (may be NULL at
+ * M = 0); xF [N][2] the goals; radius [N]; sense [N] the range of every agent.
+ * Position, from the agent's OWN record (row 0 is x_i - xF_i; c = 2 or 5): x = fl32(z[0] + xF[i][0]), y = fl32(z[1] + xF[i][1]),
+ * z[0], z[1] floats 0, 1 of row 0.
+ * Gap to disc o: p = o.xy - (x, y), d = sqrtf(fmaf(p.y, p.y, p.x p.x)) (the correctly rounded square root),
+ * gap = (d - radius[i]) - o.r.
+ *
+ * The sense entry, per record (e, i) of z [E][N][k1 c]: among the discs with gap <= sense[i] (a NaN gap is not in
+ * range) the m smallest, 1 <= m <= DRONESIM_MAX_SENSE, ordered by gap ascending, then by id ascending.  Slot s of
+ * orow [E][N][m][3] = (p.x, p.y, o.r), oid [E][N][m] = the id; empty slots (0, 0, 0) and -1.  Optional planes over ALL M discs, in
+ * range or not: gap_min [E][N] (numpy.minimum: a NaN stays; +inf at M = 0) and hit [E][N] uint8 = gap_min <= 0.  One launch, one
+ * thread per record, row 0 loaded 16, 8 or 4 bytes wide by the shield's alignment rule, the list staged once per workgroup in
+ * LDS and read at wave-uniform addresses, the m best kept by sorted insertion in registers; no atomics, no workspace:
+ * graph-capturable, bit-identical run to run.  E = 0 enqueues nothing.  EINVAL: NULL z / xF / radius / sense / orow / oid, E < 0,
+ * N outside 1..1024, k1 outside 1..DRONESIM_MAX_K + 1, c not in {2, 5}, M outside 0..1024 (or NULL obstacles with M > 0), m
+ * outside 1..4.
+ *
+ * The obstacle shield takes the half-planes of the plain shield entry unchanged and in their order (box, then neighbour
+ * slots 1..k) and appends slot s = 0..m-1 of the record's list: skipped unless 0 <= oid < M and d = |row.xy| (as above, from the
+ * stored p) is finite and > 0; otherwise a = row.xy / d, g = ((d - radius[i]) - row.r) - margin, b = (obstacle_rate / dt)
+ * max(g, 0): at most 4 + 8 + 4 = 16 constraints, solved by the same incremental solve (one device function, instantiated for 12
+ * and for 16 constraints).  obstacle_rate in (0, 1]: the disc does not move, so the agent may spend the whole budget.  Every
+ * other argument, plane and property is the plain entry's; EINVAL also for NULL orow / oid, m outside 1..4, M outside 0..1024,
+ * obstacle_rate outside (0, 1].  With every slot empty the output is the plain entry's bit for bit.
+ *
+ * The episode tables cover the FIRST episode of every env of a stored window z [T][E][N][k1 c], done [T][E], with L_e (ep_len)
+ * exactly as the episode safety tables define it; the observation of step L - 1 comes from z_final where it is given (NULL: from
+ * z).  With gap_min(t) the sense entry's plane at step t:  min_obstacle_gap [E][N] float32 = min over t < L of gap_min(t)
+ * (a NaN stays);  obstacle_hit_steps [E][N] int32 = #{t < L : gap_min(t) <= 0};  ep_min_obstacle_gap [E] = the minimum over the
+ * agents in ascending order;  ep_obstacle_hit_steps [E] int32 = the sum over the agents;  ep_len [E].  L_e = 0: NaN in the float
+ * tables, 0 in the int tables.  Every table but ep_len may be NULL (a per-env table needs the per-agent one it reduces).  Two
+ * launches on `stream` (one without per-env tables): the backward column scan with the disc loop in its step, then one thread
+ * per (env, table); no atomics: graph-capturable, bit-identical run to run.  E = 0 enqueues nothing.  EINVAL: NULL z / done (with
+ * T > 0) / xF / radius / ep_len, T or E < 0, N outside 1..1024, k1 < 1, c not in {2, 5}, M outside 0..1024 (or NULL obstacles with M > 0), a
+ * per-env table without its per-agent one.                                                                                       */
+int dronesim_obstacle_sense(const float *z, const float *xF, const float *radius, const float *sense, const float *obstacles,
+                            int E, int N, int k1, int c, int M, int m, float *orow, int32_t *oid, float *gap_min, uint8_t *hit,
+                            void *stream);
+int dronesim_action_shield_obstacles(const float *z, const int32_t *nbr, const float *act, const float *radius, float rate, float margin,
+                                     float u_max, float dt, int E, int N, int k1, int c, float *act_out, uint8_t *intervened,
+                                     float *correction, const float *orow, const int32_t *oid, int m, int M, float obstacle_rate,
+                                     void *stream);
+int dronesim_episode_obstacle_safety(const float *z, const float *z_final, const uint8_t *done, const float *xF, const float *radius,
+                                     const float *obstacles, int T, int E, int N, int k1, int c, int M, int32_t *ep_len,
+                                     float *min_obstacle_gap, int32_t *obstacle_hit_steps, float *ep_min_obstacle_gap,
+                                     int32_t *ep_obstacle_hit_steps, void *stream);
 
 const char *dronesim_last_error(void);
 const char *dronesim_error_string(int code);

@@ -23,6 +23,8 @@ OK, EINVAL, EUNSUPPORTED, ELAUNCH = 0, -1, -2, -3
 CONTROL_PROPORTIONAL, CONTROL_GRADIENT = 0, 1
 MAX_K = 8
 MAX_AGENTS = 1024
+MAX_OBSTACLES = 1024                 # DRONESIM_MAX_OBSTACLES
+MAX_SENSE = 4                        # DRONESIM_MAX_SENSE
 
 # every symbol include/dronesim.h declares (tests check the .so exports all of them)
 STATS_SCRATCH_DOUBLES = 769          # DRONESIM_STATS_SCRATCH_DOUBLES (include/dronesim.h)
@@ -42,6 +44,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_obsnorm_workspace", "dronesim_obsnorm_update", "dronesim_obsnorm_apply",
            "dronesim_rewnorm_workspace", "dronesim_rewnorm_update", "dronesim_rewnorm_apply",
            "dronesim_action_shield", "dronesim_shield_totals",
+           "dronesim_obstacle_sense", "dronesim_action_shield_obstacles", "dronesim_episode_obstacle_safety",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -208,6 +211,10 @@ def lib():
     L.dronesim_action_shield.argtypes = [vp] * 4 + [f32] * 4 + [i32] * 4 + [vp] * 4
     L.dronesim_shield_totals.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.dronesim_action_shield.restype = L.dronesim_shield_totals.restype = C.c_int
+    L.dronesim_obstacle_sense.argtypes = [vp] * 5 + [i32] * 6 + [vp] * 4 + [vp]
+    L.dronesim_action_shield_obstacles.argtypes = [vp] * 4 + [f32] * 4 + [i32] * 4 + [vp] * 3 + [vp, vp, i32, i32, f32, vp]
+    L.dronesim_episode_obstacle_safety.argtypes = [vp] * 6 + [i32] * 6 + [vp] * 5 + [vp]
+    L.dronesim_obstacle_sense.restype = L.dronesim_action_shield_obstacles.restype = L.dronesim_episode_obstacle_safety.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

@@ -1,0 +1,300 @@
+// Static obstacle discs (include/dronesim.h states the rule): dronesim_obstacle_sense lists, per record (e, i), the m nearest of
+// the M discs within the agent's range from the agent's OWN observation -- the list the obstacle shield (shield.hip) turns into
+// half-planes --, dronesim_episode_obstacle_safety reduces a stored window to per-episode clearance and hit tables.
+//
+// Both need the agent's position, which its record holds: row 0 is x_i - xF_i, so x = z[0] + xF[i][0], y = z[1] + xF[i][1].  The
+// gap to disc o = (ox, oy, or):  p = o.xy - (x, y),  d = sqrtf(fmaf(p.y, p.y, p.x p.x)),  gap = (d - radius[i]) - or  (obstacle_gap
+// below: the ONE place that evaluates it; sqrtf is the correctly rounded one, so the sense planes and the tables agree bit for bit).
+//
+// One thread per record, consecutive threads on consecutive records.  The disc loop is wave-uniform: the workgroup stages the list
+// once in LDS (12 bytes a disc, 12 KB at M = 1024) and every lane then reads the same LDS address, which broadcasts -- no lane
+// gathers from global memory.  A thread past the end stays (the staging has a barrier, the scan's flag fetch is a wave operation).
+#include "scan_common.hpp"
+
+namespace {
+
+constexpr int kMaxObstacles = DRONESIM_MAX_OBSTACLES;
+constexpr int kMaxSense = DRONESIM_MAX_SENSE;                   // list slots per record
+
+typedef float ob_f4 __attribute__((ext_vector_type(4)));
+typedef float ob_f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float ob_nan_min(float a, float b) { return (a < b || a != a) ? a : b; }   // numpy.minimum: a NaN stays
+
+struct ObstacleGap { float px, py, gap; };
+
+__device__ __forceinline__ ObstacleGap obstacle_gap(float x, float y, float ri, float ox, float oy, float orad)
+{
+    ObstacleGap g;
+    g.px = ox - x; g.py = oy - y;
+    const float d = __builtin_sqrtf(fmaf(g.py, g.py, g.px * g.px));
+    g.gap = (d - ri) - orad;
+    return g;
+}
+
+// the workgroup's copy of the list: s[3 o + 0..2] = (x, y, r) of disc o
+__device__ __forceinline__ void stage_obstacles(float *s, const float *__restrict__ obstacles, int M)
+{
+    for (int q = threadIdx.x; q < 3 * M; q += blockDim.x) s[q] = obstacles[q];
+    __syncthreads();
+}
+
+// the smallest gap over ALL discs (+inf at M = 0)
+__device__ __forceinline__ float obstacle_gap_min(const float *s, int M, float x, float y, float ri)
+{
+    float gm = __builtin_inff();
+    for (int o = 0; o < M; ++o)                                // (wave-uniform; the three reads broadcast)
+        gm = ob_nan_min(obstacle_gap(x, y, ri, s[3 * o], s[3 * o + 1], s[3 * o + 2]).gap, gm);
+    return gm;
+}
+
+// ---- dronesim_obstacle_sense ------------------------------------------------------------------------------------------------------
+struct SenseArgs {
+    const float *z, *xF, *radius, *sense, *obstacles;
+    float *orow;
+    int32_t *oid;
+    float *gap_min;
+    uint8_t *hit;
+    int N, stride, M, W;                                       // stride: floats per record (k1 c); W: shield_load_width's rule
+    unsigned long long records;
+};
+
+// MS list slots kept sorted by (gap, id) in registers: the discs come in ascending id, so a new one goes in front of the first
+// slot with a LARGER gap (or an empty one) and everything behind moves down one -- arrays indexed by unrolled counters only.
+template <int MS>
+__global__ void __launch_bounds__(256) obstacle_sense_kernel(const SenseArgs a)
+{
+    __shared__ float s_obs[3 * kMaxObstacles];
+    stage_obstacles(s_obs, a.obstacles, a.M);
+    const unsigned long long r0 = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    const bool act = r0 < a.records;
+    const unsigned long long r = act ? r0 : a.records - 1;
+    const int i = (int)(r % (unsigned)a.N);
+    const float *rec = a.z + r * (unsigned long long)a.stride;
+    float zx, zy;
+    if (a.W == 4) {                                            // (wave-uniform) k1 even, c = 2, 16-byte aligned: row 0 with row 1
+        const ob_f4 v = *reinterpret_cast<const ob_f4 *>(rec);
+        zx = v.x; zy = v.y;
+    } else if (a.W == 2) {
+        const ob_f2 v = *reinterpret_cast<const ob_f2 *>(rec);
+        zx = v.x; zy = v.y;
+    } else {
+        zx = rec[0]; zy = rec[1];
+    }
+    const float x = zx + a.xF[2 * i], y = zy + a.xF[2 * i + 1];
+    const float ri = a.radius[i], range = a.sense[i];
+
+    const float inf = __builtin_inff();
+    float bg[MS], bx[MS], by[MS], br[MS];
+    int bi[MS];
+#pragma unroll
+    for (int s = 0; s < MS; ++s) { bg[s] = inf; bx[s] = by[s] = br[s] = 0.0f; bi[s] = -1; }
+    float gm = inf;
+    const int M = a.M;
+    for (int o = 0; o < M; ++o) {
+        const float orad = s_obs[3 * o + 2];
+        const ObstacleGap g = obstacle_gap(x, y, ri, s_obs[3 * o], s_obs[3 * o + 1], orad);
+        gm = ob_nan_min(g.gap, gm);
+        const bool in = g.gap <= range;                        // (a NaN gap is not in range)
+        if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;  // most discs are out of every lane's range: the wave skips the insertion
+        float cg = g.gap, cx = g.px, cy = g.py, cr = orad;
+        int ci = o;
+        bool moving = false;                                   // the carried entry has displaced a slot: every later slot moves down
+#pragma unroll
+        for (int s = 0; s < MS; ++s) {
+            moving = moving || (in && (cg < bg[s] || bi[s] < 0));
+            const float tg = bg[s], tx = bx[s], ty = by[s], tr = br[s];
+            const int ti = bi[s];
+            bg[s] = moving ? cg : tg; bx[s] = moving ? cx : tx; by[s] = moving ? cy : ty; br[s] = moving ? cr : tr; bi[s] = moving ? ci : ti;
+            cg = moving ? tg : cg; cx = moving ? tx : cx; cy = moving ? ty : cy; cr = moving ? tr : cr; ci = moving ? ti : ci;
+        }
+    }
+    if (!act) return;
+    float *orow = a.orow + r * (unsigned long long)(3 * MS);
+    int32_t *oid = a.oid + r * (unsigned long long)MS;
+#pragma unroll
+    for (int s = 0; s < MS; ++s) {
+        orow[3 * s] = bx[s]; orow[3 * s + 1] = by[s]; orow[3 * s + 2] = br[s];
+        oid[s] = bi[s];
+    }
+    if (a.gap_min) a.gap_min[r] = gm;
+    if (a.hit) a.hit[r] = gm <= 0.0f ? 1 : 0;
+}
+
+// Host: shield_load_width's rule (shield.hip) for row 0 of the records of z
+inline int sense_load_width(int k1, int c, uintptr_t z)
+{
+    if (c != 2) return 1;
+    if ((k1 % 2) == 0 && (z & 15u) == 0) return 4;
+    return (z & 7u) == 0 ? 2 : 1;
+}
+
+// ---- dronesim_episode_obstacle_safety ---------------------------------------------------------------------------------------------
+// SafetyScan's scan (evaluate.hip) with the disc loop in its step: the same backward driver, the same restart at `done`, the same
+// rare-path load of z_final.  A thread needs floats 0, 1 of record [t][e][i] only -- 8 bytes, so the staged load is 8 bytes wide
+// where c = 2 and the bases allow it (W = 2; a record starts at a multiple of 8 k1 bytes) and two dwords otherwise (W = 1): a
+// 16-byte load would fetch the same lines and hold twice the stage registers.  The launch sits between two bounds -- the z stream
+// (every line of the window once, as dronesim_episode_safety) and T M gap evaluations per thread --, so the rows of the next stage
+// are in flight while the disc loops of this one run (the driver's pipelining), and the loop body is the nine instructions of
+// obstacle_gap plus one minimum on LDS broadcasts.
+template <int W> struct ObstacleScan {
+    static constexpr bool kBeginFirst = false;
+    typedef bool Flag;
+    struct Rows { float zx[kStageT], zy[kStageT]; };
+    struct State { float gm, xf, yf, ri; int hits, L; };       // xf, yf, ri: the column's own goal and radius
+    const float *z, *z_final;
+    const uint8_t *flags;
+    const float *xF, *radius;
+    const float *s_obs;                                        // the workgroup's staged list
+    int N, stride, M;
+    __device__ __forceinline__ State begin(const ScanCols<1> &cols, int) const
+    {
+        const size_t i = cols.col - cols.e * (size_t)N;
+        return State{__builtin_inff(), xF[2 * i], xF[2 * i + 1], radius[i], 0, 0};
+    }
+    template <bool NT>
+    __device__ __forceinline__ void record(const float *__restrict__ p, float &zx, float &zy) const
+    {
+        if (W == 2) {
+            const ob_f2 v = NT ? __builtin_nontemporal_load(reinterpret_cast<const ob_f2 *>(p)) : *reinterpret_cast<const ob_f2 *>(p);
+            zx = v.x; zy = v.y;
+        } else {
+            zx = p[0]; zy = p[1];
+        }
+    }
+    __device__ __forceinline__ void load(Rows &st, int u, int t, const ScanCols<1> &cols) const
+    {
+        if (t >= 0) {
+            const size_t at = (size_t)t * cols.EN + cols.col;
+            record<true>(z + at * (size_t)stride, st.zx[u], st.zy[u]);
+        } else {
+            st.zx[u] = st.zy[u] = 0.0f;
+        }
+    }
+    __device__ __forceinline__ bool own(int t, const ScanCols<1> &cols) const
+    {
+        return t >= 0 && flags[(size_t)t * cols.E + cols.e] != 0;
+    }
+    template <bool COOP>
+    __device__ __forceinline__ void step(State &s, const ScanStage<ObstacleScan> &st, int u, int t, const ScanCols<1> &cols) const
+    {
+        const bool dn = COOP ? st.ds.get(cols.de, u) : st.flag[u];
+        float zx = st.rows.zx[u], zy = st.rows.zy[u];
+        if (dn && z_final)                                     // rare: the finished episode's terminal observation
+            record<false>(z_final + ((size_t)t * cols.EN + cols.col) * (size_t)stride, zx, zy);
+        const float gap = obstacle_gap_min(s_obs, M, zx + s.xf, zy + s.yf, s.ri);
+        const int h = gap <= 0.0f ? 1 : 0;
+        if (dn) {
+            s.gm = gap; s.hits = h; s.L = t + 1;
+        } else {
+            s.gm = ob_nan_min(gap, s.gm); s.hits += h;
+        }
+    }
+};
+
+template <int W>
+__global__ void __launch_bounds__(256) episode_obstacle_kernel(ObstacleScan<W> p, const float *__restrict__ obstacles, int32_t *ep_len,
+                                                               float *min_gap, int32_t *hit_steps, int T, int E)
+{
+    __shared__ float s_obs[3 * kMaxObstacles];
+    stage_obstacles(s_obs, obstacles, p.M);
+    p.s_obs = s_obs;
+    const ScanCols<1> c(E, p.N);
+    const bool coop = c.within_stage();
+    typename ObstacleScan<W>::State s;
+    if (coop) s = scan_backward<true, 1>(p, c, T);
+    else s = scan_backward<false, 1>(p, c, T);
+    if (!c.act) return;
+    const bool valid = s.L > 0;                                // no episode: NaN (0 is a meaningful gap), 0
+    if (min_gap) min_gap[c.col] = valid ? s.gm : __builtin_nanf("");
+    if (hit_steps) hit_steps[c.col] = valid ? s.hits : 0;
+    if (c.col == c.e * (size_t)p.N) ep_len[c.e] = s.L;         // the env's first column reports its length
+}
+
+// Per env, agents in ascending order: task 0 the smallest gap, task 1 the hit steps summed
+__global__ void __launch_bounds__(256) obstacle_env_kernel(const int32_t *__restrict__ ep_len, const float *__restrict__ min_gap,
+                                                           const int32_t *__restrict__ hit_steps, float *__restrict__ ep_min_gap,
+                                                           int32_t *__restrict__ ep_hit_steps, int E, int N)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 2 * (size_t)E) return;
+    const int task = (int)(idx / (size_t)E);
+    const size_t e = idx - (size_t)task * E;
+    const bool valid = ep_len[e] > 0;
+    if (task == 0) {
+        if (!ep_min_gap) return;
+        float m = __builtin_nanf("");
+        if (valid) {
+            m = min_gap[e * N];
+            for (int i = 1; i < N; ++i) m = ob_nan_min(min_gap[e * N + i], m);
+        }
+        ep_min_gap[e] = m;
+        return;
+    }
+    if (!ep_hit_steps) return;
+    int n = 0;
+    if (valid)
+        for (int i = 0; i < N; ++i) n += hit_steps[e * N + i];
+    ep_hit_steps[e] = n;
+}
+
+}   // namespace
+
+extern "C" {
+
+int dronesim_obstacle_sense(const float *z, const float *xF, const float *radius, const float *sense, const float *obstacles,
+                            int E, int N, int k1, int c, int M, int m, float *orow, int32_t *oid, float *gap_min, uint8_t *hit,
+                            void *stream)
+{
+    if (!z || !xF || !radius || !sense || !orow || !oid) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: NULL z / xF / radius / sense / orow / oid");
+    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: E < 0, N outside 1..1024, k1 outside 1..9 or c not in {2, 5}");
+    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: M outside 0..1024, or NULL obstacles with M > 0");
+    if (m < 1 || m > kMaxSense) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: m outside 1..4");
+    if (E == 0) return DRONESIM_OK;
+    SenseArgs a;
+    a.z = z; a.xF = xF; a.radius = radius; a.sense = sense; a.obstacles = obstacles; a.orow = orow; a.oid = oid; a.gap_min = gap_min; a.hit = hit;
+    a.N = N; a.stride = k1 * c; a.M = M; a.W = sense_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    a.records = (unsigned long long)E * (unsigned long long)N;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((a.records + 255) / 256));
+    if (m == 1) hipLaunchKernelGGL(obstacle_sense_kernel<1>, grid, dim3(256), 0, s, a);
+    else if (m == 2) hipLaunchKernelGGL(obstacle_sense_kernel<2>, grid, dim3(256), 0, s, a);
+    else if (m == 3) hipLaunchKernelGGL(obstacle_sense_kernel<3>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(obstacle_sense_kernel<4>, grid, dim3(256), 0, s, a);
+    return dronesim_launched();
+}
+
+int dronesim_episode_obstacle_safety(const float *z, const float *z_final, const uint8_t *done, const float *xF, const float *radius,
+                                     const float *obstacles, int T, int E, int N, int k1, int c, int M, int32_t *ep_len,
+                                     float *min_obstacle_gap, int32_t *obstacle_hit_steps, float *ep_min_obstacle_gap,
+                                     int32_t *ep_obstacle_hit_steps, void *stream)
+{
+    if (T < 0 || E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || (c != 2 && c != 5))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: T or E < 0, N outside 1..1024, k1 < 1 or c not in {2, 5}");
+    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: M outside 0..1024, or NULL obstacles with M > 0");
+    if ((ep_min_obstacle_gap && !min_obstacle_gap) || (ep_obstacle_hit_steps && !obstacle_hit_steps))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: a per-env table needs the per-agent one it reduces");
+    if (E == 0) return DRONESIM_OK;                            // (an empty window has no addresses: checked before the pointers)
+    if (!xF || !radius || !ep_len || (T > 0 && (!z || !done)))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: NULL z / done / xF / radius / ep_len");
+    const size_t cols = (size_t)E * N;
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(z_final);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((cols + 255) / 256));
+    if (c == 2 && (bases & 7u) == 0) {
+        const ObstacleScan<2> p{z, z_final, done, xF, radius, nullptr, N, k1 * c, M};
+        hipLaunchKernelGGL(episode_obstacle_kernel<2>, grid, dim3(256), 0, s, p, obstacles, ep_len, min_obstacle_gap, obstacle_hit_steps, T, E);
+    } else {
+        const ObstacleScan<1> p{z, z_final, done, xF, radius, nullptr, N, k1 * c, M};
+        hipLaunchKernelGGL(episode_obstacle_kernel<1>, grid, dim3(256), 0, s, p, obstacles, ep_len, min_obstacle_gap, obstacle_hit_steps, T, E);
+    }
+    const int rc = dronesim_launched();
+    if (rc != DRONESIM_OK || !(ep_min_obstacle_gap || ep_obstacle_hit_steps)) return rc;
+    hipLaunchKernelGGL(obstacle_env_kernel, dim3((unsigned)((2 * (size_t)E + 255) / 256)), dim3(256), 0, s, ep_len, min_obstacle_gap,
+                       obstacle_hit_steps, ep_min_obstacle_gap, ep_obstacle_hit_steps, E, N);
+    return dronesim_launched();
+}
+
+}   // extern "C"

@@ -18,6 +18,9 @@
 // a few instructions each, only in the lanes that violate, instead of 66 vertices x 12 tests in every lane of the wave.  A lane
 // whose u satisfies all constraints leaves before the solve with u's own bits.  Every array below is indexed by unrolled loop
 // counters only: registers, no scratch, no LDS.
+// dronesim_action_shield_obstacles appends up to four half-planes of static discs (slots of dronesim_obstacle_sense's list, csrc/
+// obstacles.hip) behind the neighbour slots: the set-up and the solve are device functions templated on the capacity of the
+// constraint set (12 and 16), so both entries run ONE solver and the plain entry keeps its bits.
 // dronesim_shield_totals folds the per-call planes into per-agent running totals in a fixed order, without float atomics.
 #include "common.hpp"
 
@@ -26,6 +29,8 @@ namespace {
 constexpr int kShieldSlots = DRONESIM_MAX_K;                   // neighbour constraints a record can hold
 constexpr int kShieldBox = 4;
 constexpr int kShieldM = kShieldBox + kShieldSlots;
+constexpr int kShieldObstacles = DRONESIM_MAX_SENSE;           // obstacle constraints a record can hold (dronesim_action_shield_obstacles)
+constexpr int kShieldAll = kShieldM + kShieldObstacles;
 // |a_j . t_i| at or below this counts as parallel (2^-21): such a line bounds nothing on line i that it did not bound before
 // (both b >= 0: see DESIGN.md), and dividing by it would turn rounding noise into an interval end
 constexpr float kShieldParallel = 4.76837158203125e-07f;
@@ -79,21 +84,14 @@ __device__ __forceinline__ void shield_rows(const float *__restrict__ rec, int k
     }
 }
 
-template <int W>
-__global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
+// The first 4 + kShieldSlots half-planes of a record -- the box, then slots 1..k of its observation -- into a set of capacity CAP;
+// a slot the record does not have is a = 0, b = +inf: never violated, never clips.  Returns radius[i].
+template <int W, int CAP>
+__device__ __forceinline__ float shield_constraints(const ShieldArgs &a, unsigned long long r, int i, float (&ax)[CAP],
+                                                    float (&ay)[CAP], float (&b)[CAP])
 {
-    const unsigned long long r = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (r >= a.records) return;
+    static_assert(CAP >= kShieldM, "the box and the neighbour slots come first");
     const int N = a.N, k1 = a.k1;
-    const int i = (int)(r % (unsigned)N);
-
-    float ux, uy;
-    if (a.act8) {
-        const sh_f2 u = *reinterpret_cast<const sh_f2 *>(a.act + 2 * r);
-        ux = u.x; uy = u.y;
-    } else {
-        ux = a.act[2 * r]; uy = a.act[2 * r + 1];
-    }
     float px[kShieldSlots], py[kShieldSlots];
     int nj[kShieldSlots];
     shield_rows<W>(a.z + r * (unsigned long long)(k1 * a.c), k1, a.c, px, py);
@@ -103,7 +101,6 @@ __global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
     const float ri = a.radius[i];
 
     const float inf = __builtin_inff();
-    float ax[kShieldM], ay[kShieldM], b[kShieldM];
     ax[0] = 1.0f; ay[0] = 0.0f; ax[1] = -1.0f; ay[1] = 0.0f; ax[2] = 0.0f; ay[2] = 1.0f; ax[3] = 0.0f; ay[3] = -1.0f;
     b[0] = b[1] = b[2] = b[3] = a.u_max;
 #pragma unroll
@@ -122,20 +119,63 @@ __global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
             b[kShieldBox + q] = on ? a.rate_dt * fmaxf(g, 0.0f) : inf;
         }
     }
+    return ri;
+}
 
-    const int M = kShieldBox + k1 - 1;                          // the record's constraints (wave-uniform)
+// Slots 0..m-1 of the record's obstacle list (dronesim_obstacle_sense: (p.x, p.y, r) and the disc's id) into entries kShieldM +
+// s: a disc is a neighbour that does not move, with a rate of its own.
+struct ShieldObstacles {
+    const float *orow;
+    const int32_t *oid;
+    float rate_dt;                                             // obstacle_rate / dt, rounded once on the host
+    int m, M;
+};
+
+template <int CAP>
+__device__ __forceinline__ void shield_obstacle_constraints(const ShieldObstacles &ob, unsigned long long r, float ri, float margin,
+                                                            float (&ax)[CAP], float (&ay)[CAP], float (&b)[CAP])
+{
+    static_assert(CAP == kShieldM + kShieldObstacles, "the obstacle slots come behind the neighbour slots");
+    const float inf = __builtin_inff();
+    const float *row = ob.orow + r * (unsigned long long)(3 * ob.m);
+    const int32_t *id = ob.oid + r * (unsigned long long)ob.m;
+#pragma unroll
+    for (int s = 0; s < kShieldObstacles; ++s) {
+        ax[kShieldM + s] = ay[kShieldM + s] = 0.0f;                                   // a = 0, b = +inf: never violated, never clips
+        b[kShieldM + s] = inf;
+        if (s < ob.m) {                                                               // (wave-uniform)
+            const float px = row[3 * s], py = row[3 * s + 1], ro = row[3 * s + 2];
+            const int o = id[s];
+            const float d = __builtin_sqrtf(fmaf(py, py, px * px));
+            const bool on = (unsigned)o < (unsigned)ob.M && d > 0.0f && d < inf;
+            const float inv = 1.0f / d;
+            const float g = ((d - ri) - ro) - margin;
+            ax[kShieldM + s] = on ? px * inv : 0.0f;
+            ay[kShieldM + s] = on ? py * inv : 0.0f;
+            b[kShieldM + s] = on ? ob.rate_dt * fmaxf(g, 0.0f) : inf;
+        }
+    }
+}
+
+// The projection of (ux, uy) onto the entries m < M and kShieldM <= m < kShieldM + MO of a set of capacity CAP (the entries in
+// between are rows the record does not have), and the stores of one record.
+template <int CAP>
+__device__ __forceinline__ void shield_solve_store(const ShieldArgs &a, unsigned long long r, float ux, float uy, const int M, const int MO,
+                                                   const float (&ax)[CAP], const float (&ay)[CAP], const float (&b)[CAP])
+{
+    const float inf = __builtin_inff();
     const bool finite = __builtin_fabsf(ux) < inf && __builtin_fabsf(uy) < inf;
     bool violated = false;
 #pragma unroll
-    for (int m = 0; m < kShieldM; ++m)
-        if (m < M) violated |= fmaf(ax[m], ux, ay[m] * uy) > b[m];
+    for (int m = 0; m < CAP; ++m)
+        if (m < M || (m >= kShieldM && m < kShieldM + MO)) violated |= fmaf(ax[m], ux, ay[m] * uy) > b[m];
     float x = ux, y = uy, corr = finite ? 0.0f : __builtin_nanf("");
     if (finite && violated) {
         // |s0| <= |ux| + |uy| + b_m on every line m; inside the box |s| <= 2 u_max + b_m (+inf: no box)
         const float noise_u = kShieldNoise * fminf(__builtin_fabsf(ux) + __builtin_fabsf(uy), 2.0f * a.u_max);
 #pragma unroll
-        for (int m = 0; m < kShieldM; ++m) {
-            if (m < M && fmaf(ax[m], x, ay[m] * y) > b[m]) {
+        for (int m = 0; m < CAP; ++m) {
+            if ((m < M || (m >= kShieldM && m < kShieldM + MO)) && fmaf(ax[m], x, ay[m] * y) > b[m]) {
                 const float qx = b[m] * ax[m], qy = b[m] * ay[m];                      // the line's point closest to 0 (|a| = 1)
                 const float tx = -ay[m], ty = ax[m];
                 const float s0 = fmaf(tx, ux, ty * uy);                                 // t . (u - q), and t . q = 0
@@ -169,6 +209,44 @@ __global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
     }
     if (a.intervened) a.intervened[r] = finite && violated ? 1 : 0;
     if (a.correction) a.correction[r] = corr;
+}
+
+__device__ __forceinline__ void shield_action(const ShieldArgs &a, unsigned long long r, float &ux, float &uy)
+{
+    if (a.act8) {
+        const sh_f2 u = *reinterpret_cast<const sh_f2 *>(a.act + 2 * r);
+        ux = u.x; uy = u.y;
+    } else {
+        ux = a.act[2 * r]; uy = a.act[2 * r + 1];
+    }
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) action_shield_kernel(const ShieldArgs a)
+{
+    const unsigned long long r = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (r >= a.records) return;
+    const int i = (int)(r % (unsigned)a.N);
+    float ux, uy;
+    shield_action(a, r, ux, uy);
+    float ax[kShieldM], ay[kShieldM], b[kShieldM];
+    shield_constraints<W>(a, r, i, ax, ay, b);
+    shield_solve_store(a, r, ux, uy, kShieldBox + a.k1 - 1, 0, ax, ay, b);
+}
+
+// dronesim_action_shield_obstacles: the same record, the same solve, up to four half-planes more
+template <int W>
+__global__ void __launch_bounds__(256) action_shield_obstacles_kernel(const ShieldArgs a, const ShieldObstacles ob)
+{
+    const unsigned long long r = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (r >= a.records) return;
+    const int i = (int)(r % (unsigned)a.N);
+    float ux, uy;
+    shield_action(a, r, ux, uy);
+    float ax[kShieldAll], ay[kShieldAll], b[kShieldAll];
+    const float ri = shield_constraints<W>(a, r, i, ax, ay, b);
+    shield_obstacle_constraints(ob, r, ri, a.margin, ax, ay, b);
+    shield_solve_store(a, r, ux, uy, kShieldBox + a.k1 - 1, ob.m, ax, ay, b);
 }
 
 // Host: episode_safety_kernel's width rule (evaluate.hip) for the records of z alone
@@ -268,6 +346,39 @@ int dronesim_action_shield(const float *z, const int32_t *nbr, const float *act,
     if (W == 4) hipLaunchKernelGGL(action_shield_kernel<4>, grid, dim3(256), 0, s, a);
     else if (W == 2) hipLaunchKernelGGL(action_shield_kernel<2>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(action_shield_kernel<1>, grid, dim3(256), 0, s, a);
+    return dronesim_launched();
+}
+
+int dronesim_action_shield_obstacles(const float *z, const int32_t *nbr, const float *act, const float *radius, float rate, float margin,
+                                     float u_max, float dt, int E, int N, int k1, int c, float *act_out, uint8_t *intervened,
+                                     float *correction, const float *orow, const int32_t *oid, int m, int M, float obstacle_rate,
+                                     void *stream)
+{
+    if (!z || !nbr || !act || !radius || !act_out || !orow || !oid)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: NULL z / nbr / act / radius / act_out / orow / oid");
+    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 2 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: E < 0, N outside 1..1024, k1 outside 2..9 or c not in {2, 5}");
+    if (m < 1 || m > DRONESIM_MAX_SENSE || M < 0 || M > DRONESIM_MAX_OBSTACLES)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: m outside 1..4 or M outside 0..1024");
+    if (!(rate > 0.0f && rate <= 0.5f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: rate must be in (0, 0.5]");
+    if (!(obstacle_rate > 0.0f && obstacle_rate <= 1.0f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: obstacle_rate must be in (0, 1]");
+    if (!(margin >= 0.0f) || !(margin < __builtin_inff())) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: margin must be finite and >= 0");
+    if (!(u_max > 0.0f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: u_max must be > 0 (+inf: no box; not NaN)");
+    if (!(dt > 0.0f) || !(dt < __builtin_inff())) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: dt must be finite and > 0");
+    if (E == 0) return DRONESIM_OK;
+    ShieldArgs a;
+    a.z = z; a.nbr = nbr; a.act = act; a.radius = radius; a.act_out = act_out; a.intervened = intervened; a.correction = correction;
+    a.rate_dt = rate / dt; a.margin = margin; a.u_max = u_max;
+    a.N = N; a.k1 = k1; a.c = c;
+    a.act8 = ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(act_out)) & 7u) == 0 ? 1 : 0;
+    a.records = (unsigned long long)E * (unsigned long long)N;
+    const ShieldObstacles ob{orow, oid, obstacle_rate / dt, m, M};
+    const int W = shield_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((a.records + 255) / 256));
+    if (W == 4) hipLaunchKernelGGL(action_shield_obstacles_kernel<4>, grid, dim3(256), 0, s, a, ob);
+    else if (W == 2) hipLaunchKernelGGL(action_shield_obstacles_kernel<2>, grid, dim3(256), 0, s, a, ob);
+    else hipLaunchKernelGGL(action_shield_obstacles_kernel<1>, grid, dim3(256), 0, s, a, ob);
     return dronesim_launched();
 }
 

@@ -184,6 +184,10 @@ class Evaluator:
     un-fused loop ``env.control(kind)``, shield, ``step(into=, execute=)``: THREE launches per step (four with the shield's
     ``stats``); the fused `rollout_control` launch serves only without a shield.  A shield with ``stats=True`` has its
     totals cleared at the start of every ``run``, and `summary` reports its intervention share and mean correction.
+    ``obstacles``: an `ObstacleField` of this env, with ``safety=True`` -- a round also reduces the stored observations to the
+    per-episode obstacle tables (`obstacles.episode_obstacle_safety`: smallest gap to a disc, steps in touch with one), two
+    launches more per round, and `safety_summary` gains ``obstacle_free_share``, ``arrived_clear_share``, ``min_obstacle_gap`` and
+    ``mean_min_obstacle_gap``.  (Whether the discs are ENFORCED is the shield's business: ``ActionShield(env, ..., obstacles=field)``.)
 
     A round is ``env.reset()``, ``T = max_time_steps`` steps into an owned `RolloutStorage`, then the two reductions.  Every env
     contributes exactly one episode per round -- its first one: a fresh episode always ends inside ``max_time_steps``
@@ -194,7 +198,7 @@ class Evaluator:
     Buffers are allocated by the first ``run`` (and again only when ``rounds`` changes); one round can be captured in a
     ``torch.cuda.graph`` after an eager warm-up call."""
 
-    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False, shield=None):
+    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False, shield=None, obstacles=None):
         from .drone_env import max_time_steps
         if not getattr(env, "batched", False):
             raise ValueError("Evaluator needs the batched (tensor) API of `drones`")
@@ -225,6 +229,13 @@ class Evaluator:
             raise ValueError("shield must be an ActionShield of this env")
         self.shield = shield
         self.safety = bool(safety)
+        if obstacles is not None:
+            if getattr(obstacles, "env", None) is not env:
+                raise ValueError("obstacles must be an ObstacleField of this env")
+            if not self.safety:
+                raise ValueError("the obstacle tables are part of the safety tables: obstacles= needs safety=True")
+        self.obstacles = obstacles
+        self.obstacle_tables = None
         self.T = int(max_time_steps)
         self._rounds_run = 0
         self.storage = None
@@ -256,6 +267,12 @@ class Evaluator:
                      ep_goal_dist_max=torch.zeros(rounds, E, **f32), ep_arrived=torch.zeros(rounds, E, dtype=torch.uint8, device=dev))
             self.safety_tables = s
             self._safety_views = [dict({name: x[r] for name, x in s.items()}, ep_len=t["ep_len"][r]) for r in range(rounds)]
+        if self.obstacles is not None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            o = dict(min_obstacle_gap=torch.zeros(rounds, E, N, **f32), obstacle_hit_steps=torch.zeros(rounds, E, N, **i32),
+                     ep_min_obstacle_gap=torch.zeros(rounds, E, **f32), ep_obstacle_hit_steps=torch.zeros(rounds, E, **i32))
+            self.obstacle_tables = o
+            self._obstacle_views = [dict({name: x[r] for name, x in o.items()}, ep_len=t["ep_len"][r]) for r in range(rounds)]
 
     def rollout(self):
         """One round's experience: ``env.reset()`` and ``T`` steps into ``self.storage`` (no reduction)."""
@@ -294,7 +311,8 @@ class Evaluator:
         ``agent_return``, ``agent_true_return`` and -- with a critic -- ``mean_adv`` float64 ``[rounds, E, N]`` (:104-106),
         ``collision_hist`` int64 ``[n_bins + 1]`` over all rounds of this call (:148-156; the last bin holds the episodes with
         ``n_bins`` collisions or more).  With ``safety=True`` also the tables of `episode_safety` (`SAFETY_TABLES`) as
-        ``[rounds, E(, N)]`` tensors, one more call per round.  No host synchronisation."""
+        ``[rounds, E(, N)]`` tensors, one more call per round, and with ``obstacles=`` the obstacle tables
+        (`obstacles.OBSTACLE_TABLES`) likewise.  No host synchronisation."""
         import torch
         rounds = int(rounds)
         if rounds < 1:
@@ -313,6 +331,10 @@ class Evaluator:
             histogram_i32(out["ep_collisions"], self.n_bins, valid=self._valid, out=self.collision_hist, accumulate=r > 0)
             if self.safety:
                 st.safety(out=self._safety_views[r])
+            if self.obstacles is not None:
+                self.obstacles.episode_safety(st, out=self._obstacle_views[r])
+        if self.obstacles is not None:
+            return dict(self.tables, collision_hist=self.collision_hist, **self.safety_tables, **self.obstacle_tables)
         if self.safety:
             return dict(self.tables, collision_hist=self.collision_hist, **self.safety_tables)
         return dict(self.tables, collision_hist=self.collision_hist)
@@ -347,7 +369,8 @@ class Evaluator:
 
 
     # fixed-length float64 vector of one rank: [episodes, arrived, successes, sum ep_min_clearance, min ep_min_clearance (+inf
-    # without an episode), sum ep_goal_dist_max, agents that arrived, sum of their arrive_step]
+    # without an episode), sum ep_goal_dist_max, agents that arrived, sum of their arrive_step]; with an obstacle field four more:
+    # [episodes without an obstacle hit, arrived with no collision and no hit, sum ep_min_obstacle_gap, min ep_min_obstacle_gap]
     def _safety_vector(self):
         import torch
         t, s = self.tables, self.safety_tables
@@ -361,29 +384,45 @@ class Evaluator:
         clr, goal = s["ep_min_clearance"].double(), s["ep_goal_dist_max"].double()
         there = ok[..., None] & (s["arrive_step"] > 0)
         cnt = lambda m: m.sum().double().view(1)
-        return torch.cat([cnt(ok), cnt(arrived), cnt(arrived & (t["ep_collisions"] == 0)), torch.where(ok, clr, zero).sum().view(1),
-                          torch.where(ok, clr, inf).min().view(1), torch.where(ok, goal, zero).sum().view(1), cnt(there),
-                          torch.where(there, s["arrive_step"].double(), zero).sum().view(1)])
+        v = [cnt(ok), cnt(arrived), cnt(arrived & (t["ep_collisions"] == 0)), torch.where(ok, clr, zero).sum().view(1),
+             torch.where(ok, clr, inf).min().view(1), torch.where(ok, goal, zero).sum().view(1), cnt(there),
+             torch.where(there, s["arrive_step"].double(), zero).sum().view(1)]
+        if self.obstacles is not None:                      # four more: see `summarize_safety`
+            o = self.obstacle_tables
+            free = ok & (o["ep_obstacle_hit_steps"] == 0)
+            gap = o["ep_min_obstacle_gap"].double()
+            v += [cnt(free), cnt(arrived & (t["ep_collisions"] == 0) & free), torch.where(ok, gap, zero).sum().view(1),
+                  torch.where(ok, gap, inf).min().view(1)]
+        return torch.cat(v)
 
     def safety_summary(self, group=None):
         """Host-side safety figures of the last ``run`` of an ``Evaluator(..., safety=True)``: episodes, the share that arrived
         (every agent inside its goal disk at the end), the share of successes (arrived without a collision), mean and minimum
         of the episodes' smallest clearance, the mean of their largest final goal distance, the mean step count at which an
-        agent that arrived first stood inside its goal disk.  ONE all-gather of a fixed-length vector, as `summary`."""
+        agent that arrived first stood inside its goal disk.  With ``obstacles=``: ``obstacle_free_share`` (episodes in which no
+        agent touched a disc), ``arrived_clear_share`` (arrived with no collision and no obstacle hit), ``min_obstacle_gap`` and
+        ``mean_min_obstacle_gap`` over the episodes' smallest gaps.  ONE all-gather of a fixed-length vector, as `summary`."""
         from .sharding import all_gather_stats
         return summarize_safety(all_gather_stats(self._safety_vector(), group))
 
 
 def summarize_safety(gathered):
-    """`Evaluator.safety_summary` from the gathered ``[world, 8]`` vectors (host side): sums over the ranks, except the
-    smallest clearance, which is the minimum over them."""
+    """`Evaluator.safety_summary` from the gathered ``[world, 8]`` vectors -- ``[world, 12]`` with an obstacle field: episodes
+    without an obstacle hit, arrived with no collision and no hit, sum and minimum of the episodes' smallest obstacle gap --
+    (host side): sums over the ranks, except the smallest clearance and the smallest obstacle gap, which are minima over them."""
     g = gathered.double().cpu()
+    if g.shape[1] not in (8, 12):
+        raise ValueError(f"the safety vectors hold 8 figures, 12 with an obstacle field, got {g.shape[1]}")
     tot = g.sum(0)
     n, eps, agents = int(tot[0]), max(float(tot[0]), 1.0), float(tot[6])
-    return {"episodes": n, "arrived_share": float(tot[1]) / eps, "success_share": float(tot[2]) / eps,
-            "mean_min_clearance": float(tot[3]) / eps, "min_clearance": float(g[:, 4].min()) if n else None,
-            "mean_goal_dist_max": float(tot[5]) / eps, "mean_arrive_step": float(tot[7]) / agents if agents else None,
-            "world_size": int(gathered.shape[0])}
+    out = {"episodes": n, "arrived_share": float(tot[1]) / eps, "success_share": float(tot[2]) / eps,
+           "mean_min_clearance": float(tot[3]) / eps, "min_clearance": float(g[:, 4].min()) if n else None,
+           "mean_goal_dist_max": float(tot[5]) / eps, "mean_arrive_step": float(tot[7]) / agents if agents else None,
+           "world_size": int(gathered.shape[0])}
+    if g.shape[1] == 12:
+        out.update(obstacle_free_share=float(tot[8]) / eps, arrived_clear_share=float(tot[9]) / eps,
+                   min_obstacle_gap=float(g[:, 11].min()) if n else None, mean_min_obstacle_gap=float(tot[10]) / eps)
+    return out
 
 
 def summarize_evaluation(gathered, n_bins, has_critic=True):

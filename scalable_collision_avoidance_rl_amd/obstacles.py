@@ -1,0 +1,266 @@
+"""Static obstacle discs that matter: sensing, and per-episode clearance / hit tables.
+
+The reference draws ``n_obstacles`` discs ``[x, y, r]`` and only paints them (drone_env.py:155-169: "never read by dynamics or
+reward"), and so does `drones`.  This module makes them real in the layers that handle safety, beside the step -- the step kernel,
+the reward and the networks' input do not change:
+
+  ObstacleField.sense            `dronesim_obstacle_sense` (csrc/obstacles.hip): per agent, the ``m`` nearest discs within its range,
+                                 from its OWN observation (row 0 is ``x_i - xF_i``, so the record holds the position)
+  ActionShield(obstacles=field)  one half-plane per listed disc in the projection (shield.py, csrc/shield.hip)
+  ObstacleField.episode_safety   `dronesim_episode_obstacle_safety`: clearance and hit tables of every env's first episode from a
+                                 stored window; ``Evaluator(..., safety=True, obstacles=field)`` reports them
+  place_obstacles                host numpy: discs of the reference's sizes that leave given points (the goals) free
+
+The rule (include/dronesim.h states it for the kernels, tests/obstacle_ref.py in float64): ``x = z[0] + xF[i][0]``,
+``y = z[1] + xF[i][1]``; to disc ``o``: ``p = o.xy - (x, y)``, ``d = |p|``, ``gap = d - radius[i] - o.r``.  A disc is in range where
+``gap <= sense[i]``; the list holds the ``m`` smallest gaps, ties to the lower id; ``gap_min`` / ``hit`` cover ALL discs.
+
+One list ``[M,3]`` serves all envs.  ``env.reset(renew_obstacles=True)`` (the reference's default) redraws ``env.obstacles``; a
+field follows only through ``field.set(env.obstacles)``.
+
+There is no CPU fallback; importing this module needs neither a GPU nor the library."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._native import MAX_AGENTS as _MAX_AGENTS, MAX_K as _MAX_K, MAX_OBSTACLES, MAX_SENSE
+
+OBSTACLE_TABLES = ("min_obstacle_gap", "obstacle_hit_steps", "ep_min_obstacle_gap", "ep_obstacle_hit_steps")
+
+
+def check_obstacles(obstacles, M=None):
+    """``obstacles`` as a float64 ``[M,3]`` array (x, y, r), or ValueError: wrong shape, non-finite entries, ``r < 0``, more than
+    `MAX_OBSTACLES` discs, or -- with ``M`` -- another count than ``M``."""
+    try:
+        obs = np.array(obstacles, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"obstacles must be an [M,3] array of (x, y, r), got {type(obstacles).__name__}") from None
+    if obs.ndim == 1 and obs.size == 0:                        # (an empty list)
+        obs = obs.reshape(0, 3)
+    if obs.ndim != 2 or obs.shape[1] != 3:
+        raise ValueError(f"obstacles must be an [M,3] array of (x, y, r), got shape {obs.shape}")
+    if obs.shape[0] > MAX_OBSTACLES:
+        raise ValueError(f"at most {MAX_OBSTACLES} obstacles (the list is staged per workgroup), got M = {obs.shape[0]}")
+    if not np.isfinite(obs).all():
+        raise ValueError("obstacles must be finite")
+    if (obs[:, 2] < 0).any():
+        raise ValueError("obstacle radii must be >= 0")
+    if M is not None and obs.shape[0] != M:
+        raise ValueError(f"M is fixed at construction: this field holds {M} obstacles, got {obs.shape[0]}")
+    return obs
+
+
+def check_m(m):
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= MAX_SENSE:
+        raise ValueError(f"m (list slots per agent) must be an integer in 1..{MAX_SENSE}, got {m!r}")
+    return int(m)
+
+
+def place_obstacles(grid, n, seed=0, keep_clear=None, clearance=0.0, centres=None):
+    """Host numpy: ``n`` discs of the reference's sizes (drone_env.py:155-169: radius uniform in ``[0.005, 0.1] max(grid)``) with
+    centres uniform in the grid -- or the given ``centres [n,2]`` --, minus the ones that come within ``clearance`` of a point of
+    ``keep_clear [P,2]`` (``|centre - point| - r <= clearance``): pass the goals (``env.end_points.reshape(N, 2)``) and e.g. the
+    starts -- under the shield a goal inside a disc cannot be reached.  Returns float64 ``[M,3]`` with ``M <= n``; the same ``seed``
+    gives the same discs."""
+    grid = np.asarray(grid, np.float64).reshape(-1)
+    if grid.shape[0] != 2 or not (grid > 0).all():
+        raise ValueError(f"grid must be two positive extents, got {grid!r}")
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"n must be an integer >= 0, got {n!r}")
+    n = int(n)
+    if not 0.0 <= float(clearance) < np.inf:
+        raise ValueError(f"clearance must be finite and >= 0, got {clearance!r}")
+    rng = np.random.default_rng(seed)
+    draw = rng.random((n, 3))
+    max_size = 0.1 * grid.max()
+    min_size = 0.05 * max_size
+    obs = np.empty((n, 3))
+    if centres is None:
+        obs[:, 0], obs[:, 1] = draw[:, 0] * grid[0], draw[:, 1] * grid[1]
+    else:
+        centres = np.asarray(centres, np.float64)
+        if centres.shape != (n, 2) or not np.isfinite(centres).all():
+            raise ValueError(f"centres must be a finite [n,2] = ({n}, 2) array, got shape {centres.shape}")
+        obs[:, :2] = centres
+    obs[:, 2] = draw[:, 2] * (max_size - min_size) + min_size
+    if keep_clear is not None and n:
+        pts = np.asarray(keep_clear, np.float64).reshape(-1, 2)
+        if not np.isfinite(pts).all():
+            raise ValueError("keep_clear must be finite")
+        if pts.shape[0]:
+            d = np.sqrt(((obs[:, None, :2] - pts[None]) ** 2).sum(2)) - obs[:, None, 2]
+            obs = obs[(d > float(clearance)).all(1)]
+    return obs
+
+
+def _tensor_check(name, x, dtype, shape, device):
+    import torch
+    if not torch.is_tensor(x):
+        raise ValueError(f"{name} must be a tensor, got {type(x).__name__}")
+    if x.dtype != dtype or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {x.dtype} {tuple(x.shape)}"
+                         f"{'' if x.is_contiguous() else ' (not contiguous)'}")
+    if x.device != device:
+        raise ValueError(f"{name} must live on the device {device}, got {x.device}")
+
+
+def _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final):
+    """(T, E, N, d) of `episode_obstacle_safety`'s arguments, or ValueError -- shapes, dtypes and devices only."""
+    import torch
+    if not all(torch.is_tensor(x) for x in (z, done, xF, radius, obstacles)) or z.dim() != 4:
+        raise ValueError(f"z must be a [T,E,N,(k+1)c] tensor and done, xF, radius, obstacles tensors, got z {tuple(getattr(z, 'shape', ()))}")
+    T, E, N, d = (int(x) for x in z.shape)
+    if not 1 <= N <= _MAX_AGENTS or d < 2:
+        raise ValueError(f"N must be in 1..{_MAX_AGENTS} and a record hold row 0 (2 floats or more), got N = {N}, {d} floats")
+    dev = z.device
+    if dev.type != "cuda":
+        raise ValueError(f"the obstacle tables work on ROCm device tensors only (no CPU fallback), got z on {dev}")
+    _tensor_check("z", z, torch.float32, (T, E, N, d), dev)
+    _tensor_check("done", done, torch.uint8, (T, E), dev)
+    _tensor_check("xF", xF, torch.float32, (N, 2), dev)
+    _tensor_check("radius", radius, torch.float32, (N,), dev)
+    if obstacles.dim() != 2 or obstacles.shape[1] != 3 or obstacles.shape[0] > MAX_OBSTACLES:
+        raise ValueError(f"obstacles must be [M,3] with M <= {MAX_OBSTACLES}, got {tuple(obstacles.shape)}")
+    _tensor_check("obstacles", obstacles, torch.float32, tuple(obstacles.shape), dev)
+    if z_final is not None:
+        _tensor_check("z_final", z_final, torch.float32, (T, E, N, d), dev)
+    return T, E, N, d
+
+
+def episode_obstacle_safety(z, done, xF, radius, obstacles, c, z_final=None, out=None):
+    """`dronesim_episode_obstacle_safety` on device tensors: the post-step observations ``z [T,E,N,(k+1)c]`` float32
+    (`RolloutStorage.z`), ``done [T,E]`` uint8, the goals ``xF [N,2]``, ``radius [N]`` and the discs ``obstacles [M,3]`` float32,
+    ``c`` (2 or 5) floats per row, and the terminal observations ``z_final`` of an auto_reset window.  The obstacle tables of the
+    FIRST episode of every env (`evaluate.episode_safety`'s episode, the same ``ep_len``): ``min_obstacle_gap [E,N]`` float32, the
+    smallest gap of the agent to any disc over the episode; ``obstacle_hit_steps [E,N]`` int32, the steps at which it touched or
+    overlapped one (``gap <= 0``); ``ep_min_obstacle_gap [E]`` float32 and ``ep_obstacle_hit_steps [E]`` int32 over the agents;
+    ``ep_len [E]`` int32.  Envs without an episode get NaN and 0; the minimum keeps a NaN; ``M = 0`` gives ``+inf`` and 0.  ``out``: a
+    dict of tensors to write into (the entries it lacks are not computed, except ``ep_len``; a per-env table needs the per-agent
+    one it reduces)."""
+    import torch
+    from . import _native
+    T, E, N, d = _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final)
+    if c not in (2, 5) or d % c:
+        raise ValueError(f"c must be 2 or 5 and divide the record's {d} floats, got {c!r}")
+    k1, M, dev = d // c, int(obstacles.shape[0]), z.device
+    shapes = dict(ep_len=(torch.int32, (E,)), min_obstacle_gap=(torch.float32, (E, N)), obstacle_hit_steps=(torch.int32, (E, N)),
+                  ep_min_obstacle_gap=(torch.float32, (E,)), ep_obstacle_hit_steps=(torch.int32, (E,)))
+    if out is not None:
+        for name, t in out.items():
+            if name not in shapes:
+                raise ValueError(f"out[{name!r}] is no obstacle table: {tuple(shapes)}")
+            _tensor_check(f"out[{name!r}]", t, shapes[name][0], shapes[name][1], dev)
+        if "ep_len" not in out:
+            raise ValueError("out needs ep_len")
+    lib = _native.lib()
+    if out is None:
+        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, (dtype, shape) in shapes.items()}
+    ptr = lambda name: out[name].data_ptr() if name in out else None
+    with torch.cuda.device(dev):
+        rc = lib.dronesim_episode_obstacle_safety(z.data_ptr(), None if z_final is None else z_final.data_ptr(), done.data_ptr(),
+                                                  xF.data_ptr(), radius.data_ptr(), obstacles.data_ptr() if M else None, T, E, N, k1, c, M,
+                                                  out["ep_len"].data_ptr(), ptr("min_obstacle_gap"), ptr("obstacle_hit_steps"),
+                                                  ptr("ep_min_obstacle_gap"), ptr("ep_obstacle_hit_steps"),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _native.check(rc, "dronesim_episode_obstacle_safety")
+    return out
+
+
+class ObstacleField:
+    """The static discs of a batched `drones` env, on its device.
+
+        field = ObstacleField(env, place_obstacles(env.grid, 8, seed=1, keep_clear=env.end_points.reshape(-1, 2)), m=2)
+        orow, oid = field.sense()                               # [E,N,m,3], [E,N,m] from env.z
+        shield = ActionShield(env, 0.25, 0.05, 1.0, obstacles=field)
+        tables = field.episode_safety(storage)
+
+    ``obstacles``: ``[M,3]`` (x, y, r), default ``env.obstacles``; ``M`` (0..1024) is fixed at construction, `set` re-uploads other
+    discs IN PLACE, so captured graphs see them.  ``env.reset(renew_obstacles=True)`` redraws ``env.obstacles``; the field follows
+    only through ``field.set(env.obstacles)``.  ``m``: list slots per agent, 1..4.  ``sense``: the range per agent ``[N]`` (a scalar
+    serves all), default the env's Delta (``env.deltas``, read live).  ValueError for a wrong shape, non-finite entries, ``r < 0``,
+    ``M > 1024`` or ``m`` outside 1..4 -- before anything touches a device.
+
+    ``sense(z=None, gap_min=False)`` returns ``(orow, oid)`` of the observation ``z`` (default ``env.z``; any observation of the
+    env's shape serves: a `RolloutStorage` ring slot, ``z_final``): slot ``s`` of ``orow [E,N,m,3]`` is ``(p.x, p.y, r)`` of the
+    ``s``-th nearest disc in range and ``oid [E,N,m]`` its id, empty slots ``(0, 0, 0)`` and -1.  With ``gap_min=True`` the
+    attributes ``gap_min [E,N]`` (over ALL discs, ``+inf`` at ``M = 0``) and ``hit [E,N]`` uint8 are written too.  The buffers are
+    allocated by the first call (the planes by the first call that asks for them) and reused: after an eager warm-up the calls
+    can be captured in a ``torch.cuda.graph``."""
+
+    def __init__(self, env, obstacles=None, m=2, sense=None):
+        if not getattr(env, "batched", False):
+            raise ValueError("ObstacleField needs the batched (tensor) API of `drones`")
+        self.m = check_m(m)
+        obs = check_obstacles(env.obstacles if obstacles is None else obstacles)
+        N = int(env.n_agents)
+        if sense is not None:
+            sense = np.array(sense, np.float64)
+            sense = np.full(N, float(sense)) if sense.ndim == 0 else sense
+            if sense.shape != (N,) or np.isnan(sense).any():
+                raise ValueError(f"sense must be a number or [N] = ({N},) numbers, got shape {sense.shape}")
+        import torch
+        self.env, self.M = env, int(obs.shape[0])
+        self.obstacles = obs
+        # (at least one row, so that the tensor has an address at M = 0; the kernels read M rows)
+        self._obs = torch.zeros(max(self.M, 1), 3, dtype=torch.float32, device=env.device)
+        self._obs_view = self._obs[:self.M]
+        self._sense = None if sense is None else torch.tensor(sense, dtype=torch.float32, device=env.device)
+        self.orow = self.oid = self.gap_min = self.hit = None
+        self.set(obs)
+
+    @property
+    def sense_range(self):
+        """The range per agent, float32 ``[N]`` on the device (the env's Delta unless the field was given its own)."""
+        return self.env._delta if self._sense is None else self._sense
+
+    @property
+    def device_obstacles(self):
+        """The discs as the kernels read them: float32 ``[M,3]`` on the env's device."""
+        return self._obs_view
+
+    def set(self, obstacles):
+        """Other discs, the same count: re-uploaded into the same device memory."""
+        import torch
+        obs = check_obstacles(obstacles, self.M)
+        self.obstacles = obs
+        if self.M:
+            self._obs_view.copy_(torch.as_tensor(obs.astype(np.float32)))
+        return self
+
+    def sense(self, z=None, gap_min=False):
+        import torch
+        from . import _native
+        env = self.env
+        E, N, k1, c = int(env.n_envs), int(env.n_agents), int(env.k_closest) + 1, int(env.c)
+        z = env.z if z is None else z
+        dev = torch.device(env.device)
+        if not 1 <= N <= _MAX_AGENTS or not 1 <= k1 <= _MAX_K + 1 or c not in (2, 5):
+            raise ValueError(f"sensing needs N in 1..{_MAX_AGENTS}, k + 1 in 1..{_MAX_K + 1} and c in (2, 5), got N = {N}, k + 1 = {k1}, c = {c}")
+        _tensor_check("z", z, torch.float32, (E, N, k1 * c), dev)
+        rng = self.sense_range
+        for name, x, shape in (("xF", env._xF, (N, 2)), ("radius", env._radius, (N,)), ("sense", rng, (N,))):
+            _tensor_check(name, x, torch.float32, shape, dev)
+        lib = _native.lib()
+        if self.orow is None:
+            self.orow = torch.zeros(E, N, self.m, 3, dtype=torch.float32, device=dev)
+            self.oid = torch.full((E, N, self.m), -1, dtype=torch.int32, device=dev)
+        if gap_min and self.gap_min is None:
+            self.gap_min = torch.zeros(E, N, dtype=torch.float32, device=dev)
+            self.hit = torch.zeros(E, N, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.dronesim_obstacle_sense(z.data_ptr(), env._xF.data_ptr(), env._radius.data_ptr(), rng.data_ptr(),
+                                             self._obs.data_ptr(), E, N, k1, c, self.M, self.m, self.orow.data_ptr(), self.oid.data_ptr(),
+                                             self.gap_min.data_ptr() if gap_min else None, self.hit.data_ptr() if gap_min else None,
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_obstacle_sense")
+        return self.orow, self.oid
+
+    def episode_safety(self, storage, out=None):
+        """The obstacle tables of a `RolloutStorage` window of this env (`episode_obstacle_safety`): from its stored post-step
+        observations (the terminal ones under auto_reset), the env's goals and live radii, and this field's discs."""
+        env = self.env
+        if getattr(storage, "env", None) is not env:
+            raise ValueError("storage must be a RolloutStorage of this field's env")
+        return episode_obstacle_safety(storage.z, storage.done, env._xF, env._radius, self._obs_view, int(env.c), storage.z_final, out=out)

@@ -17,7 +17,16 @@ least ``(1 - 2 rate) g`` where ``g >= 0`` and does not shrink where ``g < 0`` (D
 outside the list are unconstrained, so Delta must exceed ``2 sqrt(2) u_max dt + margin``, and with ``k`` below the local crowd the
 shield reduces collisions but does not exclude them).
 
-  ActionShield   one `dronesim_action_shield` launch per call (csrc/shield.hip), one `dronesim_shield_totals` more with ``stats``
+With ``obstacles=field`` (an `obstacles.ObstacleField` of the env) the set also holds one half-plane per disc of the agent's obstacle
+list, behind the neighbour slots: slot ``s`` of ``field.sense(z)``, skipped where empty; ``a = row.xy / d``,
+``g = d - radius[i] - row.r - margin``, ``b = obstacle_rate max(g, 0) / dt``.  A disc does not move, so the agent may spend the whole
+budget: ``obstacle_rate`` in (0, 1], default ``rate``.  For a listed disc the gap after the step is at least
+``(1 - obstacle_rate) g`` where ``g >= 0`` and does not shrink where ``g < 0`` (the range must exceed
+``sqrt(2) u_max dt + margin``; with more than ``m`` discs in range hits become rarer, not impossible).
+
+  ActionShield   one `dronesim_action_shield` launch per call (csrc/shield.hip), one `dronesim_shield_totals` more with ``stats``;
+                 with ``obstacles=``: `dronesim_obstacle_sense`, then `dronesim_action_shield_obstacles` (two launches, three with
+                 ``stats``)
 
 There is no CPU fallback; importing this module needs neither a GPU nor the library."""
 from __future__ import annotations
@@ -46,6 +55,16 @@ def check_shield_params(rate, margin, u_max):
     if not u_max > 0.0:
         raise ValueError(f"u_max must be > 0 (None or +inf: no box), got {u_max}")
     return rate, margin, u_max
+
+
+def check_obstacle_rate(obstacle_rate, rate):
+    """``obstacle_rate`` as a float in (0, 1] (``None`` -> ``rate``), or ValueError."""
+    if obstacle_rate is None:
+        return rate
+    obstacle_rate = _number("obstacle_rate", obstacle_rate)
+    if not 0.0 < obstacle_rate <= 1.0:
+        raise ValueError(f"obstacle_rate must be in (0, 1] (a disc does not move: the agent may take the whole gap), got {obstacle_rate}")
+    return obstacle_rate
 
 
 def _shield_shapes(actions, z, nbr, out, radius, E, N, k1, c, device):
@@ -80,12 +99,21 @@ class ActionShield:
     ``correction`` (float32, ``|u* - u|``; NaN where the action was not finite and went through unchanged) ``[E,N]`` hold the
     last call's planes.  ``stats=True`` adds one launch per call that folds them into per-agent running totals
     (`totals`, `reset_totals`).  Buffers are allocated by the first call; after an eager warm-up the calls can be captured in a
-    ``torch.cuda.graph``.  Shape, dtype and device mistakes raise ValueError before anything touches a device."""
+    ``torch.cuda.graph``.  Shape, dtype and device mistakes raise ValueError before anything touches a device.
 
-    def __init__(self, env, rate=0.25, margin=0.0, u_max=None, stats=False):
+    ``obstacles``: an `ObstacleField` of this env -- every call then senses the field from the same ``z`` and adds the listed
+    discs' half-planes with ``obstacle_rate`` (default ``rate``); ``None``: the plain launch, today's bits."""
+
+    def __init__(self, env, rate=0.25, margin=0.0, u_max=None, stats=False, obstacles=None, obstacle_rate=None):
         if not getattr(env, "batched", False):
             raise ValueError("ActionShield needs the batched (tensor) API of `drones`")
         self.rate, self.margin, self.u_max = check_shield_params(rate, margin, u_max)
+        if obstacles is None and obstacle_rate is not None:
+            raise ValueError("obstacle_rate needs obstacles= (an ObstacleField of this env)")
+        if obstacles is not None and getattr(obstacles, "env", None) is not env:
+            raise ValueError("obstacles must be an ObstacleField of this env")
+        self.obstacles = obstacles
+        self.obstacle_rate = None if obstacles is None else check_obstacle_rate(obstacle_rate, self.rate)
         self.env, self.stats = env, bool(stats)
         self.intervened = self.correction = None
         self._totals = None
@@ -119,12 +147,22 @@ class ActionShield:
             self._alloc()
         if out is None:
             out = torch.empty_like(actions)
+        field = self.obstacles
+        if field is not None:                               # the agent's obstacle list, from the observation it acts on
+            orow, oid = field.sense(z)
         with torch.cuda.device(env.device):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            rc = lib.dronesim_action_shield(z.data_ptr(), nbr.data_ptr(), actions.data_ptr(), radius.data_ptr(), self.rate, self.margin,
-                                            self.u_max, dt, E, N, k1, c, out.data_ptr(), self.intervened.data_ptr(),
-                                            self.correction.data_ptr(), stream)
-            _native.check(rc, "dronesim_action_shield")
+            if field is None:
+                rc = lib.dronesim_action_shield(z.data_ptr(), nbr.data_ptr(), actions.data_ptr(), radius.data_ptr(), self.rate, self.margin,
+                                                self.u_max, dt, E, N, k1, c, out.data_ptr(), self.intervened.data_ptr(),
+                                                self.correction.data_ptr(), stream)
+                _native.check(rc, "dronesim_action_shield")
+            else:
+                rc = lib.dronesim_action_shield_obstacles(z.data_ptr(), nbr.data_ptr(), actions.data_ptr(), radius.data_ptr(), self.rate,
+                                                          self.margin, self.u_max, dt, E, N, k1, c, out.data_ptr(),
+                                                          self.intervened.data_ptr(), self.correction.data_ptr(), orow.data_ptr(),
+                                                          oid.data_ptr(), field.m, field.M, self.obstacle_rate, stream)
+                _native.check(rc, "dronesim_action_shield_obstacles")
             if self.stats:
                 t = self._totals
                 rc = lib.dronesim_shield_totals(self.intervened.data_ptr(), self.correction.data_ptr(), E, N, t["interventions"].data_ptr(),

@@ -8,10 +8,14 @@
   3. one `Evaluator` round (softmax-16 actor + critic, f16x2) next to the bare loop of examples/rollout_loop.py part 2 (b)
      without the evaluation, and the same round with safety=True;
   4. `--shield` (alone: nothing of 1-3 runs): `dronesim_action_shield` on the env's own observation next to the step launch,
-     `dronesim_control` and `dronesim_shield_totals` in the same session, and the control -> shield -> step(execute=) chain.
+     `dronesim_control` and `dronesim_shield_totals` in the same session, and the control -> shield -> step(execute=) chain;
+  5. `--obstacles` (alone): for M in {16, 64} discs, m = 2: the sense launch; sense + `dronesim_action_shield_obstacles` next to the
+     plain `dronesim_action_shield` on the same observation; `dronesim_episode_obstacle_safety` next to `dronesim_episode_safety`
+     on the same window; and the control -> sense -> shield -> step(execute=) chain next to the plain chain.
 
     python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
     python tools/ebench.py --shield [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/shield_ebench.jsonl]
+    python tools/ebench.py --obstacles [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/obstacles_ebench.jsonl]
 Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
 import argparse
 import ctypes as C
@@ -157,6 +161,65 @@ def shield(E, N, k, c, emit):
     emit(dict(what="control -> step", us=us, us_min=lo, **base))
 
 
+def obstacles(T, E, N, k, c, emit, counts=(16, 64), m=2):
+    """The obstacle layer on an env 20 proportional steps off the lattice (the shield measurement's state), `place_obstacles`'
+    discs off the goals, the controller's action as the nominal one.  Every line carries its yardstick, measured in the same
+    session: the plain shield launch, `dronesim_episode_safety` on the same window, the plain chain."""
+    from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, episode_obstacle_safety, place_obstacles
+    from scalable_collision_avoidance_rl_amd.shield import ActionShield
+    G = 28.0 if N == 64 else max(6.0, 0.45 * N)
+    dev, k1 = "cuda:0", k + 1
+    env = drones(N, 0, [G, G], "O", k_closest=k, deltas=np.ones(N), simplify_zstate=c == 2, n_envs=E, seed=0, auto_reset=True)
+    act, safe = env.control("proportional"), torch.empty(E, N, 2, device=env.device)
+    for _ in range(20):
+        env.step(env.control("proportional", out=act))
+    plain = ActionShield(env, 0.25, 0.05, 1.0)
+    us_plain, lo_plain = gtime(lambda: plain(act, out=safe))
+    base = dict(E=E, N=N, k=k, c=c, m=m)
+    emit(dict(what="dronesim_action_shield (yardstick)", us=us_plain, us_min=lo_plain, **base))
+
+    def plain_chain():
+        env.control("proportional", out=act)
+        env.step(act, execute=plain(act, out=safe))
+    us_chain, lo_chain = gtime(plain_chain)
+    emit(dict(what="control -> shield -> step(execute=) (yardstick)", us=us_chain, us_min=lo_chain, **base))
+    # the window of the tables: observations around the goals (row 0 = x - xF), every env ends once
+    z = torch.randn(T, E, N, k1 * c, device=dev) * 3.0
+    nbr = torch.randint(-1, N, (T, E, N, k1), device=dev, dtype=torch.int32)
+    done = torch.zeros(T, E, dtype=torch.uint8, device=dev); done[-1] = 1
+    radius, delta = env._radius, env._delta
+    out_s = episode_safety(z, nbr, done, radius, delta)
+    us_safety, lo_safety = gtime(lambda: episode_safety(z, nbr, done, radius, delta, out=out_s), calls=4)
+    emit(dict(what="dronesim_episode_safety (yardstick)", T=T, us=us_safety, us_min=lo_safety, **base))
+    zbytes = segment_bytes(4 * k1 * c, [(0, 8)])
+    for M in counts:
+        discs = place_obstacles([G, G], 2 * M, seed=M, keep_clear=env.end_points.reshape(N, 2), clearance=0.3)[:M]
+        assert discs.shape[0] == M
+        field = ObstacleField(env, discs, m=m)
+        rec = dict(base, M=M)
+        us, lo = gtime(lambda: field.sense(gap_min=True))
+        emit(dict(what="dronesim_obstacle_sense (with gap_min, hit)", us=us, us_min=lo, slots_filled=float((field.oid >= 0).float().mean()),
+                  hit_share=float(field.hit.float().mean()), **rec))
+        field2 = ObstacleField(env, discs, m=m)
+        us, lo = gtime(lambda: field2.sense())
+        emit(dict(what="dronesim_obstacle_sense", us=us, us_min=lo, **rec))
+        sh = ActionShield(env, 0.25, 0.05, 1.0, obstacles=field2)
+        us, lo = gtime(lambda: sh(act, out=safe))
+        emit(dict(what="dronesim_obstacle_sense + dronesim_action_shield_obstacles", us=us, us_min=lo, yardstick_us=us_plain,
+                  ratio=us / us_plain, intervention_share=float(sh.intervened.float().mean()), **rec))
+        out_o = episode_obstacle_safety(z, done, env._xF, radius, field.device_obstacles, c)
+        us, lo = gtime(lambda: episode_obstacle_safety(z, done, env._xF, radius, field.device_obstacles, c, out=out_o), calls=4)
+        emit(dict(what="dronesim_episode_obstacle_safety", T=T, us=us, us_min=lo, yardstick_us=us_safety, ratio=us / us_safety,
+                  z_bytes_per_element=zbytes, z_tb_s=T * E * N * zbytes / 1e6 / us, gap_evaluations=T * E * N * M,
+                  gaps_per_ns=T * E * N * M / 1e3 / us, **rec))
+
+        def chain():
+            env.control("proportional", out=act)
+            env.step(act, execute=sh(act, out=safe))
+        us, lo = gtime(chain)
+        emit(dict(what="control -> sense -> shield -> step(execute=)", us=us, us_min=lo, yardstick_us=us_chain, ratio=us / us_chain, **rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=200)
@@ -167,6 +230,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-round", action="store_true")
     ap.add_argument("--shield", action="store_true", help="only the action shield next to the step launch")
+    ap.add_argument("--obstacles", action="store_true", help="only the obstacle layer next to its yardsticks")
     ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     a = ap.parse_args()
 
@@ -180,6 +244,9 @@ def main():
                 f.write(line + "\n")
     if a.shield:
         shield(a.envs, a.agents, a.k, a.c, emit)
+        return
+    if a.obstacles:
+        obstacles(a.T, a.envs, a.agents, a.k, a.c, emit)
         return
     done, us_eval = kernels(a.T, a.envs, a.agents, emit)
     safety(a.T, a.envs, a.agents, a.k, a.c, done, us_eval, emit)
