@@ -1,8 +1,10 @@
 """Float64 restatement of the obstacle rule (include/dronesim.h: the obstacle sense entry, the obstacle shield, the episode obstacle
 tables) by BRUTE FORCE -- test infrastructure, no GPU needed: positions, all gaps, the list by a full sort with the id as
 tie-break; the obstacle half-planes appended to `shield_ref.constraints`' arrays and solved by `shield_ref.project` (which takes
-any constraint count); the episode tables by a plain loop; the rule's closed loop (single integrator, proportional control);
-and the seeded generators the test files share."""
+any constraint count); the episode tables by a plain loop and, vectorised, bit for bit the same; the rule's closed loop (single
+integrator, proportional control); `ScanCols` of csrc/scan_common.hpp restated; and the seeded generators the test files share:
+records for the sense entry, windows for the tables at any shape, exact ties, the shield's geometry families with lines moved
+into the obstacle list, lists of slots that must be off."""
 import numpy as np
 
 from tests import shield_ref as S
@@ -10,6 +12,10 @@ from tests import shield_ref as S
 EPS32 = S.EPS32
 SEPARATION = 1e-4                                            # decisions of the generated inputs are at least this far apart
 SENSE_CASES = [(0, 2), (1, 1), (3, 2), (16, 4), (70, 4), (1024, 4)]             # (M, m)
+# (M, m) with more discs in range than slots in most records -- the sorted insertion of every list width evicts; the ranges the
+# M = 70 cases are drawn with are wider for that (`EVICT_REACH`), the M = 1024 one runs on shield_ref.CASES[1] and [3] only
+SENSE_CASES_EVICT = [(70, 1), (70, 2), (70, 3), (1024, 3)]
+EVICT_REACH = {70: (1.5, 2.5), 1024: (0.5, 1.5)}
 OBSTACLE_RATE = 0.5
 
 
@@ -166,14 +172,17 @@ def separated(G, reach, m):
     return (np.diff(v, axis=1) > SEPARATION).all(1)
 
 
-def sense_case(N, k, c, M, m, E=S.E_CASE, seed=0):
+def sense_case(N, k, c, M, m, E=S.E_CASE, seed=0, reach=(0.5, 1.5), order=None):
     """Seeded records for the sense entry, float32 as the kernel reads them: z of `shield_ref.synthetic` (row 0 uniform in
     [-2, 2]^2), goals, radii in [0.05, 0.2], ranges in [0.5, 1.5], M discs.  A record is REDRAWN (its row 0) until the decisions
-    the kernel takes on it are SEPARATION apart (`separated`); none is left out.  dict(z, nbr, u, radius, xF, sense, obstacles)."""
+    the kernel takes on it are SEPARATION apart (`separated`); none is left out.  `reach`: the interval the ranges are drawn from.
+    `order`: "descending" / "ascending" sorts the discs by their float64 gap to record 0's final position (the separation does
+    not depend on the order of the discs): record 0 then inserts every disc in range in front of the list / behind its last
+    entry.  dict(z, nbr, u, radius, xF, sense, obstacles)."""
     case = S.synthetic(N, k, c, E=E, seed=seed, radius=S.radii(N, seed))
     rng = np.random.default_rng(99991 * (seed + 1) + 1000 * N + 10 * M + m)
     xF, obs = goals(N, seed), discs(M, seed)
-    reach = rng.uniform(0.5, 1.5, N).astype(np.float32)
+    reach = rng.uniform(reach[0], reach[1], N).astype(np.float32)
     R, k1 = E * N, k + 1
     z = case["z"].reshape(R, k1 * c).copy()
     for _ in range(200):
@@ -184,6 +193,9 @@ def sense_case(N, k, c, M, m, E=S.E_CASE, seed=0):
         z[bad, :2] = rng.uniform(-2.0, 2.0, (int(bad.sum()), 2)).astype(np.float32)
     else:
         raise AssertionError("sense_case: records left that are not separated")
+    if order is not None:
+        g0 = gaps(z[:1], xF, case["radius"], obs)[1][0]
+        obs = obs[np.argsort(-g0 if order == "descending" else g0, kind="stable")]
     return dict(case, z=z.reshape(E, N, k1 * c), xF=xF, sense=reach, obstacles=obs)
 
 
@@ -213,11 +225,12 @@ def exact_case():
     return dict(z=z, xF=xF, radius=np.full(4, 0.125, np.float32), sense=np.ones(4, np.float32), obstacles=obs, want=want)
 
 
-def shield_case(N, k, c, M=48, m=4, reach=1.0, seed=0):
+def shield_case(N, k, c, M=48, m=4, reach=1.0, seed=0, **kw):
     """`shield_ref.synthetic` records (neighbour constraints, box faces and vertices bind) with goals, discs and one range for all:
     with 48 discs over the 9 x 9 square and a range of 1 about two discs are in range of a record, at gaps of both signs, so the
-    obstacle half-planes bind next to the others.  dict(z, nbr, u, radius, xF, sense, obstacles)."""
-    case = S.synthetic(N, k, c, seed=seed)
+    obstacle half-planes bind next to the others.  `kw`: `shield_ref.synthetic`'s radius / margin / u_max.  dict(z, nbr, u, radius, xF,
+    sense, obstacles)."""
+    case = S.synthetic(N, k, c, seed=seed, **kw)
     return dict(case, xF=goals(N, seed), sense=np.full(N, reach, np.float32), obstacles=discs(M, seed))
 
 
@@ -230,6 +243,7 @@ def shield_reference(case, c, orow, oid, rate=S.RATE, obstacle_rate=OBSTACLE_RAT
     orow, oid = np.asarray(orow).reshape(R, m, 3), np.asarray(oid).reshape(R, m)
     ref = shield(u, z, nbr, case["radius"], rate, margin, u_max, dt, c, orow, oid, M, obstacle_rate)
     ref["tol"] = tolerance(u, z, k1, c, case["radius"], rate, obstacle_rate, margin, u_max, dt, orow)
+    ref["u"] = u
     return ref
 
 
@@ -366,3 +380,348 @@ def closed_loop(setup, with_obstacles, steps=None):
         hit_steps += (after.min(2) <= 0).sum(1)
     arrived = (np.sqrt(((pos - xF[None]) ** 2).sum(2)) <= 0.2).all(1)
     return dict(min_gap=min_gap, hit_steps=hit_steps, shortfall=shortfall, arrived=arrived)
+
+
+# ---- episode tables on every scan path ---------------------------------------------------------------------------------------------
+STAGE_T = 8                                                  # scan_common.hpp's kStageT
+# (T, E, N): the window shapes of tests/test_gpu_obstacle_paths.py with the reason each one is there (tests/test_obstacles_host.py
+# restates `ScanCols` and asserts the reasons)
+WINDOW_SHAPES = [
+    ((12, 15, 5), "wave 0 spans 13 envs and reads its own flags; the ragged wave 1 is cooperative from env 12, envs 15..19 masked"),
+    ((17, 40, 8), "every wave spans exactly 8 envs (de reaches 7); two workgroups; two stages plus one step"),
+    ((8, 30, 12), "waves start mid-env; exactly one stage"),
+    ((9, 7, 64), "one env per wave; one stage plus one step"),
+    ((7, 70, 1), "N = 1: every column reports ep_len; wave 0 spans 64 envs; T under one stage"),
+    ((1, 3, 1), "the smallest window"),
+    ((3, 1, 1024), "four workgroups each stage the full 12 KB list (M = 1024)"),
+]
+WINDOW_M = {(3, 1, 1024): 1024, (12, 15, 5): 70, (9, 7, 64): 70}                  # the others: M = 3
+
+
+def scan_waves(E, N, block=256):
+    """`ScanCols<1>` (csrc/scan_common.hpp) restated: per wave of the launch dict(active, e_first, span, coop) -- lane l of wave
+    w owns column 64 w + l, clamped to E N - 1 where it is past the end; e = col // N; e_first is lane 0's env; span the largest
+    e - e_first of the wave; `within_stage` (the cooperative flag fetch) holds where span <= 7."""
+    EN = E * N
+    waves = []
+    for w in range(-(-EN // block) * (block // 64)):
+        col0 = 64 * w + np.arange(64)
+        e = np.where(col0 < EN, col0, EN - 1) // N
+        waves.append(dict(active=int((col0 < EN).sum()), e_first=int(e[0]), span=int((e - e[0]).max()), coop=bool(((e - e[0]) < 8).all())))
+    return waves
+
+
+def done_patterns(T):
+    """The ends of an env, as lists of steps, in the order the envs of `window_case` cycle through: t = T - 1 | none | t = 0 |
+    both sides of every stage seam counted backward from T - 1 (t = T - 1 - 8 s and t = T - 8 s, where they exist) | two adjacent
+    ends (t, t + 1) | an end at every step."""
+    pats = [[T - 1], [], [0]]
+    s = 1
+    while T - STAGE_T * s >= 0:
+        if T - 1 - STAGE_T * s >= 0:
+            pats.append([T - 1 - STAGE_T * s])
+        pats.append([T - STAGE_T * s])
+        s += 1
+    if T >= 2:
+        pats.append([T // 2 - 1 if T > 2 else 0, T // 2 if T > 2 else 1])
+    pats.append(list(range(T)))
+    return pats
+
+
+def first_ends(done):
+    """L [E]: one past the first end of every env, 0 without one."""
+    done = np.asarray(done) != 0
+    return np.where(done.any(0), done.argmax(0) + 1, 0)
+
+
+def window_case(T, E, N, c, M, seed=0, with_final=True, k=2):
+    """A seeded float32 window for the episode tables at any shape: radii `shield_ref.radii`, goals `goals`, discs `discs(M, lo=0,
+    hi=5)`, positions uniform in the 5 x 5 square, every record redrawn until its smallest gap is SEPARATION off 0.  `done` per env
+    cycles through `done_patterns(T)`.  Two records are placed by hand, in z and -- where that step ends the episode -- z_final:
+      touch  (step 0, env 0, agent 0): agent 0 has the dyadic goal (0.5, 0.5) and radius 0.125, disc 0 is (1.5, 1.5, 0.375), the
+             agent stands at (1.5, 1.0): d = 0.5 and the gap is 0 bit for bit -- a hit
+      nan    (step L // 2 of the last of the envs behind env 0 with the longest episode, agent N - 1): x is NaN -- the column's minimum is NaN, its hit count
+             leaves the step out, the env's minimum is NaN.  Absent where that record is the touch (E = N = 1).
+    dict(z, done, xF, radius, obstacles, c, z_final, touch, nan)."""
+    rng = np.random.default_rng(7103 + 1009 * seed + 101 * T + 11 * E + N + c + M)
+    xF, radius, obs = goals(N, seed).copy(), S.radii(N, seed).copy(), discs(M, seed, lo=0.0, hi=5.0)
+    xF[0], radius[0] = (0.5, 0.5), 0.125
+    if M:
+        obs[0] = (1.5, 1.5, 0.375)
+    d = (k + 1) * c
+    pats = done_patterns(T)
+    done = np.zeros((T, E), np.uint8)
+    for e in range(E):
+        done[pats[e % len(pats)], e] = 1
+    L = first_ends(done)
+
+    def place():
+        z = np.zeros((T, E, N, d), np.float32)
+        z[..., 2:] = (rng.standard_normal((T, E, N, d - 2)) * 0.3).astype(np.float32)
+        flat = z.reshape(-1, d)
+        flat[:, :2] = rng.uniform(0.0, 5.0, (flat.shape[0], 2)).astype(np.float32) - xF[np.arange(flat.shape[0]) % N]
+        return _separate(z, xF, radius, obs, rng, N, d)
+
+    z = place()
+    zf = place() if with_final else None
+    touch = (0, 0, 0)
+    rest = L[1:] if E > 1 else L                               # the last of the longest episodes besides env 0's
+    e_nan = int(np.flatnonzero(rest == rest.max()).max()) + (1 if E > 1 else 0)
+    nan = (int(L[e_nan]) // 2, e_nan, N - 1)
+    if nan == touch:
+        nan = None
+    for where, value in ((touch, np.array([1.5, 1.0], np.float32) - xF[0]), (nan, np.float32([np.nan, 0.25]))):
+        if where is not None:
+            z[where][:2] = value
+            if with_final:
+                zf[where][:2] = value
+    return dict(z=z, done=done, xF=xF, radius=radius, obstacles=obs, c=c, z_final=zf, touch=touch, nan=nan)
+
+
+def episode_tables_fast(z, done, xF, radius, obstacles, z_final=None):
+    """`episode_tables` without the Python loops: the same float64 operations in the same order (`gaps`, numpy.minimum), so the
+    tables are equal bit for bit (tests/test_obstacles_host.py)."""
+    z = np.asarray(z, np.float64)
+    T, E, N, d = z.shape
+    L = first_ends(np.asarray(done).reshape(T, E))
+    t = np.arange(T)[:, None]
+    if z_final is not None:
+        z = np.where((t == L[None] - 1)[:, :, None, None], np.asarray(z_final, np.float64), z)
+    obs = np.asarray(obstacles, np.float64).reshape(-1, 3)
+    G = gaps(z.reshape(T * E * N, d), xF, radius, obs)[1]
+    g = (np.minimum.reduce(G, axis=1, initial=np.inf) if obs.shape[0] else np.full(T * E * N, np.inf)).reshape(T, E, N)
+    inside = (t < L[None])[:, :, None]
+    valid = L > 0
+    with np.errstate(invalid="ignore"):
+        hits = ((g <= 0) & inside).sum(0)
+    gm = np.minimum.reduce(np.where(inside, g, np.inf), axis=0)
+    out = dict(ep_len=L.astype(np.int32), min_obstacle_gap=np.where(valid[:, None], gm, np.nan),
+               obstacle_hit_steps=np.where(valid[:, None], hits, 0).astype(np.int32))
+    out["ep_min_obstacle_gap"] = np.minimum.reduce(out["min_obstacle_gap"], axis=1)
+    out["ep_obstacle_hit_steps"] = out["obstacle_hit_steps"].sum(1).astype(np.int32)
+    return out
+
+
+# ---- sense: ties at the eviction boundary ------------------------------------------------------------------------------------------
+TIE_OFFSETS = [(3, 4), (-3, 4), (3, -4), (-3, -4), (4, 3), (-4, 3), (4, -3), (-4, -3), (5, 0), (-5, 0), (0, 5), (0, -5)]
+
+
+def tie_case():
+    """Hand-placed, exact like `exact_case`: N = 5, E = 1, k = 1, c = 2, every radius 0.125, dyadic goals and coordinates.  Agents
+    0..3 stand at (2, 2).  Twelve discs of radius 0.125 sit at (2, 2) + TIE_OFFSETS / 8: fmaf(py, py, px px) is exactly 25 / 64 for
+    every one of them, d = 0.625 and the gap is 0.375 bit for bit -- twelve ties.  Ids, in ascending order:
+      F0 T T F1 T T T T F2 T T T T T T N25 N125 F3      (T: tied; ids 1 2 4 5 6 7 9 10 11 12 13 14)
+    N25 (id 15) at (2.5, 2), gap 0.25, and N125 (id 16) at (2, 1.625), gap 0.125, are strictly nearer and come AFTER the tied
+    ones; F0 (3, 2), F1 (2, 3.5), F2 (0.5, 2), F3 (2, 0.25) are farther (gaps 0.75, 1.25, 1.25, 1.5).
+      agent 0  range 1: every tied disc and F0 in range -- the list is 16, 15, then the lowest tied ids 1, 2
+      agent 1  range 0.375, the tied gap itself: all twelve in range (gap <= range) -- the same list
+      agent 2  range the next float32 below 0.375: none of the tied -- 16, 15 and empty slots
+      agent 3  range +inf: agent 0's list
+      agent 4  stands at (3.0625, 2), inside F0 (d = 0.0625, gap -0.1875), range -0.0625: only the overlapping disc -- 0 and
+               empty slots; gap_min -0.1875 and a hit
+    dict(z, xF, radius, sense, obstacles, want): want[m] = (oid [5,m], orow [5,m,3]) for m = 1..4, gap_min [5], hit [5]."""
+    N = 5
+    P = np.array([2.0, 2.0])
+    xF = np.array([[0.5, 0.5], [3.0, 1.0], [2.0, 2.5], [1.0, 3.0], [4.0, 4.0]], np.float32)
+    pos = np.array([P, P, P, P, [3.0625, 2.0]], np.float32)
+    z = np.zeros((1, N, 4), np.float32)
+    z[0, :, :2] = pos - xF
+    z[0, :, 2:] = [3.0, 3.0]
+    r = 0.125
+    far = [(3.0, 2.0), (2.0, 3.5), (0.5, 2.0), (2.0, 0.25)]
+    tied = [tuple(P + np.array(o) / 8.0) for o in TIE_OFFSETS]
+    layout = "FTTFTTTTFTTTTTTabF"
+    obs, it, jf = [], iter(tied), iter(far)
+    for ch in layout:
+        obs.append({"F": lambda: next(jf), "T": lambda: next(it), "a": lambda: (2.5, 2.0), "b": lambda: (2.0, 1.625)}[ch]() + (r,))
+    obs = np.array(obs, np.float32)
+    below = float(np.nextafter(np.float32(0.375), np.float32(0.0)))
+    reach = np.array([1.0, 0.375, below, np.inf, -0.0625])
+    full = {0: [16, 15, 1, 2], 1: [16, 15, 1, 2], 2: [16, 15, -1, -1], 3: [16, 15, 1, 2], 4: [0, -1, -1, -1]}
+    want = {}
+    for m in (1, 2, 3, 4):
+        oid = np.array([full[i][:m] for i in range(N)], np.int64)
+        orow = np.zeros((N, m, 3))
+        for i in range(N):
+            for s, o in enumerate(oid[i]):
+                if o >= 0:
+                    orow[i, s] = (obs[o, 0] - pos[i, 0], obs[o, 1] - pos[i, 1], r)
+        want[m] = (oid, orow)
+    return dict(z=z, xF=xF, radius=np.full(N, r, np.float32), sense=reach, obstacles=obs, want=want,
+                gap_min=np.array([0.125, 0.125, 0.125, 0.125, -0.1875]), hit=np.array([0, 0, 0, 0, 1], np.uint8))
+
+
+# ---- the shield's families with their lines moved into the list --------------------------------------------------------------------
+LIST_M = 70                                                  # the M the converted sets are run with (ids are drawn below it)
+INT32_MIN = -2 ** 31
+
+
+def to_list(fam, moved, m, rng, r_o=None):
+    """A `shield_ref.families` record set with some neighbour lines moved into the obstacle list.  `moved` [R, n] (n <= m): the
+    neighbour slot (1..k) that list slot s of the record takes, 0 for none.  The float32 row p of a moved slot becomes the list
+    row (p.x, p.y, r_o), `r_o` [R, n] defaulting to radius[j] of the neighbour it replaces; its id any value in [0, LIST_M); the
+    neighbour's id becomes -1 and its row stays.  A moved slot whose neighbour was a ghost stays off: id -1, the row non-zero.
+    With obstacle_rate = rate and the default r_o the half-planes are the family's own, in another order.
+    dict(fam, nbr, orow [E,N,m,3] float32, oid [E,N,m] int32, moved)."""
+    E, N, k1 = fam["nbr"].shape
+    R = E * N
+    moved = np.asarray(moved).reshape(R, -1)
+    n = moved.shape[1]
+    assert n <= m and moved.min() >= 0 and moved.max() < k1
+    rows = fam["z"].reshape(R, k1, 2)
+    nbr = fam["nbr"].reshape(R, k1).copy()
+    radius = fam["radius"]
+    orow, oid = np.zeros((R, m, 3), np.float32), np.full((R, m), -1, np.int32)
+    ar = np.arange(R)
+    for s in range(n):
+        slot = moved[:, s]
+        take = slot > 0
+        j = nbr[ar, slot]
+        live = take & (j >= 0) & (j < N)
+        ro = radius[np.where(live, j, 0)] if r_o is None else np.asarray(r_o, np.float32).reshape(R, -1)[:, s]
+        orow[take, s, :2] = rows[ar, slot][take]
+        orow[take, s, 2] = ro[take]
+        oid[live, s] = rng.integers(0, LIST_M, R)[live]
+        nbr[ar[take], slot[take]] = -1
+    out = {name: v for name, v in fam.items()}
+    out.update(nbr=nbr.reshape(E, N, k1), orow=orow.reshape(E, N, m, 3), oid=oid.reshape(E, N, m), moved=moved)
+    return out
+
+
+def permute_list(conv, rng):
+    """The list slots of every record in a random order (ids with rows)."""
+    E, N, m = conv["oid"].shape
+    perm = np.argsort(rng.random((E, N, m)), axis=2)
+    return dict(conv, oid=np.take_along_axis(conv["oid"], perm, 2), orow=np.take_along_axis(conv["orow"], perm[..., None], 2))
+
+
+# name -> (family, the neighbour slots moved: a tuple for every record or "four of eight", m): the list widths vary on purpose
+LIST_FAMILIES = {
+    "duplicates": ("duplicates", (2,), 1),                                         # one of the equal directions
+    "antipodal": ("antipodal", (2,), 2),                                           # the opposite one
+    "crowd": ("crowd", "four of eight", 4),                                        # all 16 constraints listed
+    "near_parallel rate 0.25 box one": ("near_parallel rate 0.25 box", (2,), 3),
+    "near_parallel rate 0.25 box both": ("near_parallel rate 0.25 box", (1, 2), 2),
+    "near_parallel rate 0.25 no box one": ("near_parallel rate 0.25 no box", (2,), 1),
+    "near_parallel rate 0.25 no box both": ("near_parallel rate 0.25 no box", (1, 2), 4),
+    "wedge": ("wedge", (1,), 2),
+    "axes": ("axes", (3,), 3),                                                     # a list normal exactly along a box face
+    "crowd permuted": ("crowd", "four of eight", 4),
+}
+OWN_RADIUS = ("antipodal", "crowd")                          # repeated with obstacle_rate = 1 and an r_o of its own from [0, 0.3]
+LIST_FAMILY_NAMES = list(LIST_FAMILIES) + [n + " own radius" for n in OWN_RADIUS]
+
+
+def list_family(fams, name, seed=0):
+    """(converted record set, obstacle_rate) of one of LIST_FAMILY_NAMES from `shield_ref.families()`."""
+    own = name.endswith(" own radius")
+    base, slots, m = LIST_FAMILIES[name[:-len(" own radius")] if own else name]
+    fam = fams[base]
+    E, N, k1 = fam["nbr"].shape
+    R = E * N
+    rng = np.random.default_rng(60013 + 97 * LIST_FAMILY_NAMES.index(name) + seed)
+    if slots == "four of eight":
+        moved = 1 + np.sort(np.argsort(rng.random((R, k1 - 1)), axis=1)[:, :4], axis=1)
+    else:
+        moved = np.tile(np.array(slots), (R, 1))
+    r_o = rng.uniform(0.0, 0.3, moved.shape).astype(np.float32) if own else None
+    conv = to_list(fam, moved, m, rng, r_o)
+    if name == "crowd permuted":
+        conv = permute_list(conv, rng)
+    return conv, (1.0 if own else fam["rate"])
+
+
+def list_block_reference(conv, e0, e1, obstacle_rate):
+    """`shield_reference` of the envs e0 .. e1 of a converted record set at its own parameters (with `u`, for `shield_ref.lowered`)."""
+    part = dict(z=conv["z"][e0:e1], nbr=conv["nbr"][e0:e1], u=conv["u"][e0:e1], radius=conv["radius"], obstacles=np.zeros((LIST_M, 3)))
+    return shield_reference(part, conv["c"], conv["orow"][e0:e1], conv["oid"][e0:e1], conv["rate"], obstacle_rate, conv["margin"],
+                            conv["u_max"], conv["dt"])
+
+
+OFF_SLOTS = ("id -1, a row", "id M", "id INT32_MIN", "zero row", "inf coordinate", "nan coordinate")
+
+
+def off_slot(kind, row, M, rng):
+    """(row, id) of a list slot the `on` rule must skip, made from a live float32 row (p.x, p.y, r)."""
+    row = np.array(row, np.float32)
+    live = int(rng.integers(0, M))
+    if kind == "id -1, a row":
+        return row, -1
+    if kind == "id M":
+        return row, M
+    if kind == "id INT32_MIN":
+        return row, INT32_MIN
+    if kind == "zero row":
+        row[:2] = 0.0
+    elif kind == "inf coordinate":
+        row[int(rng.integers(0, 2))] = np.inf * rng.choice([-1.0, 1.0])
+    else:
+        row[int(rng.integers(0, 2))] = np.nan
+    return row, live
+
+
+def off_lists(case, m, live, seed=0):
+    """Lists [E,N,m,...] for a `shield_case` whose slots cycle through OFF_SLOTS, made from the case's own nearest discs
+    (`case_list` at m, empty slots filled with a row of their own so that every slot holds something); `live` of the m slots of
+    every record (the first ones after a per-record shuffle) keep a live row with a valid id."""
+    rng = np.random.default_rng(5501 + seed + 7 * live)
+    orow, oid = case_list(case, m)
+    E, N = oid.shape[:2]
+    M = case["obstacles"].shape[0]
+    q = 0
+    for e in range(E):
+        for i in range(N):
+            order = rng.permutation(m)
+            for n, s in enumerate(order):
+                if oid[e, i, s] < 0:                                               # an empty slot: a live row at a gap of 0.05 .. 0.4
+                    ang, dist = rng.uniform(0, 2 * np.pi), case["radius"][i] + 0.2 + S.MARGIN + rng.uniform(0.05, 0.4)
+                    orow[e, i, s], oid[e, i, s] = (dist * np.cos(ang), dist * np.sin(ang), 0.2), int(rng.integers(0, M))
+                if n >= live:
+                    orow[e, i, s], oid[e, i, s] = off_slot(OFF_SLOTS[q % len(OFF_SLOTS)], orow[e, i, s], M, rng)
+                    q += 1
+    return orow, oid
+
+
+def guarantee_shortfall(ustar, orow, oid, radius, M, obstacle_rate, margin, dt):
+    """The per-step guarantee on an answer: for every live list slot, g = |p| - l_i - r_o - margin from the float32 row in
+    float64, the largest (1 - obstacle_rate) max(g, 0) + min(g, 0) - (|p - dt u*| - l_i - r_o - margin), and the count of live slots."""
+    R = int(np.prod(oid.shape[:-1]))
+    m = oid.shape[-1]
+    orow, oid = np.asarray(orow, np.float64).reshape(R, m, 3), np.asarray(oid, np.int64).reshape(R, m)
+    u = np.asarray(ustar, np.float64).reshape(R, 2)
+    ri = np.asarray(radius, np.float64)[np.arange(R) % len(radius)][:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.sqrt((orow[..., :2] ** 2).sum(2))
+        live = (oid >= 0) & (oid < M) & np.isfinite(d) & (d > 0)
+        g = d - ri - orow[..., 2] - margin
+        after = np.sqrt(((orow[..., :2] - dt * u[:, None, :]) ** 2).sum(2)) - ri - orow[..., 2] - margin
+        short = (1 - obstacle_rate) * np.maximum(g, 0) + np.minimum(g, 0) - after
+    return float(short[live].max(initial=-np.inf)), int(live.sum())
+
+
+# ---- the obstacle shield at every list width and parameter ------------------------------------------------------------------------
+SWEEP_FIELD = dict(M=64, reach=3.0)                          # about twenty discs in range of a record: more than any m
+SWEEP_SHAPES = [(5, 2, 2), (9, 8, 2)]
+# (shape, m, obstacle_rate (None: the shield's rate), parameter set): every m at both shapes; the rates; margin 0 without a box
+SHIELD_SWEEP = ([(shape, m, OBSTACLE_RATE, "standard") for shape in SWEEP_SHAPES for m in (1, 2, 3, 4)]
+                + [((5, 2, 2), 2, None, "standard"), ((5, 2, 2), 2, 1.0, "standard"), ((9, 8, 2), 3, None, "standard"),
+                   ((9, 8, 2), 3, 1.0, "standard"), ((5, 2, 2), 3, OBSTACLE_RATE, "free"), ((9, 8, 2), 4, OBSTACLE_RATE, "free")])
+SWEEP_PARAMETERS = {"standard": (S.RATE, S.MARGIN, S.U_MAX), "free": (S.RATE, 0.0, np.inf)}   # (rate, margin, u_max)
+
+
+def sweep_case(shape, pset):
+    """The records of a SHIELD_SWEEP entry: `shield_case` in the wide field; "free" draws them with `shield_ref.radii` for a
+    margin of 0 and no box."""
+    N, k, c = shape
+    if pset == "free":
+        return shield_case(N, k, c, radius=S.radii(N), margin=0.0, u_max=np.inf, **SWEEP_FIELD)
+    return shield_case(N, k, c, **SWEEP_FIELD)
+
+
+def sweep_reference(case, shape, m, obstacle_rate, pset, orow=None, oid=None):
+    """The restatement's answer of a SHIELD_SWEEP entry for a list (default: the restatement's own), and that list."""
+    rate, margin, u_max = SWEEP_PARAMETERS[pset]
+    if oid is None:
+        orow, oid = case_list(case, m)
+    ref = shield_reference(case, shape[2], orow, oid, rate, rate if obstacle_rate is None else obstacle_rate, margin, u_max)
+    return ref, orow, oid

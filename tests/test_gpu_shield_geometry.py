@@ -56,8 +56,9 @@ def launch(torch, recs, c, rate, margin, u_max, offset=0, stats=False):
 
 
 def check(what, got, ref, lowered=False):
-    """The bars of tests/test_gpu_shield.check_against_ref on (u*, intervened, correction) against a `S.reference`; `lowered`:
-    the backward-stable optimality bar of the module docstring.  Returns the per-record residuals (feasibility, optimality
+    """The bars of tests/test_gpu_shield.check_against_ref on (u*, intervened, correction) against a `S.reference` -- or any `ref`
+    with the same entries over MORE constraint columns (`obstacle_ref.shield_reference`: the obstacle slots appended; nothing here
+    or in `S.lowered` depends on the count); `lowered`: the backward-stable optimality bar of the module docstring.  Returns the per-record residuals (feasibility, optimality
     excess) and tol."""
     o, iv, corr = got
     A, B, tol, ustar, riv, slack = (ref[n] for n in ("A", "B", "tol", "ustar", "intervened", "min_slack"))

@@ -1,6 +1,8 @@
 """Obstacles on the host (no GPU): parameter and shape errors of `obstacles.py` / `ActionShield(obstacles=)` / `Evaluator(obstacles=)`,
 `place_obstacles`, the exports with their argtypes, the float64 restatement tests/obstacle_ref.py against hand-computed cases,
-and the conditions the shared generators promise to the GPU tests -- asserted under the restatement alone."""
+and the conditions the shared generators promise to the GPU tests -- asserted under the restatement alone: separation, the scan
+path every window shape is there for (`ScanCols` restated), eviction shares, ties, the shares of records in which a list slot of a
+converted shield family is active, the `on` rule's slots."""
 import ctypes as C
 import types
 
@@ -249,3 +251,224 @@ def test_closed_loop_restatement_predicts_hits_without_and_none_with_the_obstacl
     assert predicted.sum() >= 1
     assert shielded["hit_steps"].sum() == 0 and shielded["min_gap"].min() >= O.LOOP["margin"] - 1e-9
     assert shielded["shortfall"] <= 1e-9
+
+
+# ---------------------------------------------------------------------------------------------- episode tables on every scan path
+def same_tables(a, b):
+    return all(a[n].dtype == b[n].dtype and np.array_equal(a[n], b[n], equal_nan=a[n].dtype.kind == "f") for n in O.TABLES)
+
+
+@pytest.mark.parametrize("with_final", [True, False], ids=["z_final", "no z_final"])
+@pytest.mark.parametrize("c", [2, 5])
+def test_vectorised_tables_equal_the_loop_restatement_exactly(c, with_final):
+    w = O.window(c=c, with_final=with_final)
+    args = (w["z"], w["done"], w["xF"], w["radius"], w["obstacles"], w["z_final"])
+    assert same_tables(O.episode_tables(*args), O.episode_tables_fast(*args))
+    w = O.window_case(12, 15, 5, c, 3, with_final=with_final)                      # (unequal radii, a NaN record, ends at every step)
+    args = (w["z"], w["done"], w["xF"], w["radius"], w["obstacles"], w["z_final"])
+    assert same_tables(O.episode_tables(*args), O.episode_tables_fast(*args))
+    none = (w["z"], w["done"], w["xF"], w["radius"], np.zeros((0, 3)), w["z_final"])
+    assert same_tables(O.episode_tables(*none), O.episode_tables_fast(*none))
+
+
+@pytest.mark.parametrize("shape,why", O.WINDOW_SHAPES, ids=["T%dE%dN%d" % s for s, _ in O.WINDOW_SHAPES])
+def test_window_shapes_take_the_scan_path_they_are_there_for(shape, why):
+    """`ScanCols` restated (`obstacle_ref.scan_waves`): a span of at most 7 envs means the cooperative flag fetch.  If someone
+    changes a shape, its reason must stay true."""
+    T, E, N = shape
+    waves = [w for w in O.scan_waves(E, N) if w["active"]]
+    stages, rest = divmod(T, O.STAGE_T)
+    if shape == (12, 15, 5):
+        assert [(w["active"], w["e_first"], w["span"], w["coop"]) for w in waves] == [(64, 0, 12, False), (11, 12, 2, True)]
+        assert waves[1]["e_first"] + 8 > E                                         # the fetch of wave 1 asks for envs 15..19: masked
+    elif shape == (17, 40, 8):
+        assert len(waves) == 5 and all(w["coop"] and w["span"] == 7 and w["active"] == 64 for w in waves)
+        assert E * N > 256 and (stages, rest) == (2, 1)
+    elif shape == (8, 30, 12):
+        assert all(w["coop"] for w in waves) and sum((64 * n) % N != 0 for n in range(len(waves))) >= 3 and (stages, rest) == (1, 0)
+    elif shape == (9, 7, 64):
+        assert [(w["e_first"], w["span"]) for w in waves] == [(e, 0) for e in range(7)] and (stages, rest) == (1, 1)
+    elif shape == (7, 70, 1):
+        assert (waves[0]["span"], waves[0]["coop"]) == (63, False) and waves[1]["coop"] and waves[1]["active"] == 6 and stages == 0
+    elif shape == (1, 3, 1):
+        assert len(waves) == 1 and waves[0]["active"] == 3
+    else:
+        assert shape == (3, 1, 1024) and O.WINDOW_M[shape] == OB.MAX_OBSTACLES and len(waves) == 16      # 4 workgroups of 4 waves
+
+
+@pytest.mark.parametrize("shape", [s for s, _ in O.WINDOW_SHAPES], ids=lambda s: "T%dE%dN%d" % s)
+def test_window_cases_hold_what_they_promise(shape):
+    """Separation (none left out but the touch and the NaN record), unequal radii, distinct goals, the ends of `done_patterns`
+    with both sides of every stage seam, and the touch / NaN records in the float64 tables."""
+    T, E, N = shape
+    M = O.WINDOW_M.get(shape, 3)
+    pats = O.done_patterns(T)
+    assert [T - 1] in pats and [] in pats and [0] in pats and list(range(T)) in pats
+    for s in range(1, T // O.STAGE_T + 1):
+        assert [T - O.STAGE_T * s] in pats and (T - 1 - O.STAGE_T * s < 0 or [T - 1 - O.STAGE_T * s] in pats)
+    if T >= 2:
+        assert any(len(p) == 2 and p[1] == p[0] + 1 for p in pats)
+    for c in (2, 5):
+        for with_final in (True, False):
+            w = O.window_case(T, E, N, c, M, with_final=with_final)
+            assert w["z"].shape == (T, E, N, 3 * c) and w["z"].dtype == np.float32 and w["obstacles"].shape == (M, 3)
+            assert len(np.unique(w["radius"])) == N and len(np.unique(w["xF"], axis=0)) == N
+            for e in range(E):
+                assert np.flatnonzero(w["done"][:, e]).tolist() == pats[e % len(pats)]
+            for z in [w["z"]] + ([w["z_final"]] if with_final else []):
+                g = O.gaps(z.reshape(-1, 3 * c), w["xF"], w["radius"], w["obstacles"])[1].min(1).reshape(T, E, N)
+                placed = np.zeros((T, E, N), bool)
+                placed[w["touch"]] = True
+                if w["nan"] is not None:
+                    placed[w["nan"]] = True
+                    assert np.isnan(g[w["nan"]])
+                assert (np.abs(g) > O.SEPARATION)[~placed].all()                   # none left out but the two placed by hand
+            t = O.episode_tables_fast(w["z"], w["done"], w["xF"], w["radius"], w["obstacles"], w["z_final"])
+            assert t["ep_len"][0] == T and t["obstacle_hit_steps"][0, 0] >= 1 and (T > 1 or M > 3 or t["min_obstacle_gap"][0, 0] == 0.0)
+            zt = (w["z_final"] if with_final and T == 1 else w["z"])[0, 0, 0]
+            touch = O.gaps(zt[None], w["xF"][:1], w["radius"][:1], w["obstacles"])[1][0]
+            assert touch[0] == 0.0 and (M > 3 or touch.min() == 0.0)               # the touch: exactly 0 (among many discs another may overlap)
+            if w["nan"] is not None:
+                tn, en, an = w["nan"]
+                assert tn < t["ep_len"][en] and np.isnan(t["min_obstacle_gap"][en, an]) and np.isnan(t["ep_min_obstacle_gap"][en])
+                other = dict(w, z=np.nan_to_num(w["z"], nan=100.0), z_final=None if not with_final else np.nan_to_num(w["z_final"], nan=100.0))
+                far = O.episode_tables_fast(other["z"], w["done"], w["xF"], w["radius"], w["obstacles"], other["z_final"])
+                assert t["obstacle_hit_steps"][en, an] == far["obstacle_hit_steps"][en, an]           # the NaN step counts no hit
+    if E >= 15:
+        assert (t["ep_obstacle_hit_steps"] > 0).sum() >= 3 and (t["ep_len"] == 0).any()
+
+
+# ---------------------------------------------------------------------------------------------- sense: eviction and ties
+@pytest.mark.parametrize("Mm", O.SENSE_CASES_EVICT, ids=lambda c: "M%dm%d" % c)
+def test_eviction_cases_have_more_discs_in_range_than_slots(Mm):
+    """From the restatement alone: the share of records with more discs in range than list slots.  Measured: 1.000 in every
+    case but (9, 8, 2) at (70, 3), 0.994 (ranges from [1.5, 2.5] at M = 70)."""
+    M, m = Mm
+    for N, k, c in (S.CASES if M == 70 else [S.CASES[1], S.CASES[3]]):
+        case = O.sense_case(N, k, c, M, m, reach=O.EVICT_REACH[M])
+        R = S.E_CASE * N
+        r = O.sense(case["z"].reshape(R, -1), case["xF"], case["radius"], case["sense"], case["obstacles"], m)
+        reach = case["sense"].astype(np.float64)[np.arange(R) % N]
+        assert O.separated(r["G"], reach, m).all()                                 # every record: none left out
+        share = (r["n_in"] > m).mean()
+        print(f"M={M} m={m} {(N, k, c)}: more discs in range than slots in {share:.3f} of the records")
+        assert share > 0.5
+
+
+@pytest.mark.parametrize("order", ["descending", "ascending"])
+def test_ordered_lists_make_record_0_insert_in_front_every_time_and_never(order):
+    N, k, c = S.CASES[1]
+    case = O.sense_case(N, k, c, 70, 4, reach=O.EVICT_REACH[70], order=order)
+    plain = O.sense_case(N, k, c, 70, 4, reach=O.EVICT_REACH[70])
+    assert np.array_equal(case["z"], plain["z"]) and not np.array_equal(case["obstacles"], plain["obstacles"])
+    assert np.array_equal(np.sort(case["obstacles"], axis=0), np.sort(plain["obstacles"], axis=0))
+    R = S.E_CASE * N
+    r = O.sense(case["z"].reshape(R, -1), case["xF"], case["radius"], case["sense"], case["obstacles"], 4)
+    step = np.diff(r["G"][0])
+    assert (step < 0).all() if order == "descending" else (step > 0).all()
+    assert r["n_in"][0] > 4 and (r["n_in"] > 4).mean() > 0.5
+    want = [69, 68, 67, 66] if order == "descending" else [0, 1, 2, 3]
+    assert r["oid"][0].tolist() == want
+    reach = case["sense"].astype(np.float64)[np.arange(R) % N]
+    assert O.separated(r["G"], reach, 4).all()
+
+
+def test_tie_case_by_hand_under_the_restatement():
+    t = O.tie_case()
+    tied = [o for o in range(18) if o not in (0, 3, 8, 15, 16, 17)]
+    z = t["z"].reshape(5, 4)
+    G = O.gaps(z, t["xF"], t["radius"], t["obstacles"])[1]
+    assert len(tied) == 12 and (G[:4][:, tied] == 0.375).all() and G[0, 15] == 0.25 and G[0, 16] == 0.125    # ties: bit for bit
+    p = (t["obstacles"][tied, :2] - np.float32([2.0, 2.0])).astype(np.float32)
+    assert (np.float32(p[:, 1] * p[:, 1]) + np.float32(p[:, 0] * p[:, 0]) == np.float32(25 / 64)).all()   # every product and sum exact
+    assert t["sense"][1] == 0.375 and t["sense"][2] < 0.375 and np.float32(t["sense"][2]) == t["sense"][2] and np.isposinf(t["sense"][3])
+    for m in (1, 2, 3, 4):
+        r = O.sense(z, t["xF"], t["radius"], t["sense"], t["obstacles"], m)
+        assert np.array_equal(r["oid"], t["want"][m][0]) and np.array_equal(r["orow"], t["want"][m][1]), m
+        assert np.array_equal(r["gap_min"], t["gap_min"]) and np.array_equal(r["hit"], t["hit"].astype(bool))
+    assert r["n_in"].tolist() == [15, 14, 2, 18, 1]
+    assert t["want"][4][0].tolist() == [[16, 15, 1, 2], [16, 15, 1, 2], [16, 15, -1, -1], [16, 15, 1, 2], [0, -1, -1, -1]]
+
+
+# ---------------------------------------------------------------------------------------------- shield: every m, families, the on rule
+def test_sweep_cases_evict_bind_list_slots_and_stay_under_the_band_cap():
+    """From the restatement alone.  Measured: every record has more discs in range than m; a list slot is active at u* in
+    0.065 .. 0.156 of the records (0.076 at (5, 2, 2) m = 1, 0.135 at (9, 8, 2) m = 1); the flag band is empty."""
+    for shape, m, orate, pset in O.SHIELD_SWEEP:
+        N, k, c = shape
+        case = O.sweep_case(shape, pset)
+        ref, orow, oid = O.sweep_reference(case, shape, m, orate, pset)
+        s = O.sense(case["z"].reshape(S.E_CASE * N, -1), case["xF"], case["radius"], case["sense"], case["obstacles"], m)
+        act = S.active(dict(A=ref["A"], B=ref["B"], on=ref["on"], ustar=ref["ustar"]))[:, 4 + k:].any(1).mean()
+        band = (ref["min_slack"] <= ref["tol"]).mean()
+        print(f"{shape} m={m} obstacle_rate={orate} {pset}: more in range than m {(s['n_in'] > m).mean():.3f}, a list slot active {act:.3f}, band {band:.4f}")
+        assert (s["n_in"] > m).mean() > 0.5 and act >= 0.05 and band <= BAND_CAP and ref["on"][:, 4 + k:].all()
+        if pset == "free":
+            assert len(np.unique(case["radius"])) == N and np.isinf(ref["B"][:, :4]).all()
+
+
+@pytest.fixture(scope="module")
+def fams():
+    return S.families()
+
+
+# the smallest share of records whose float64 answer has a LIST slot active, per converted family
+LIST_ACTIVE_FLOOR = {"duplicates": 0.1, "antipodal": 0.25, "crowd": 0.7, "near_parallel rate 0.25 box one": 0.35,
+                     "near_parallel rate 0.25 box both": 0.9, "near_parallel rate 0.25 no box one": 0.35,
+                     "near_parallel rate 0.25 no box both": 0.9, "wedge": 0.95, "axes": 0.2, "crowd permuted": 0.7,
+                     "antipodal own radius": 0.2, "crowd own radius": 0.6}
+
+
+@pytest.mark.parametrize("name", O.LIST_FAMILY_NAMES)
+def test_converted_families_keep_the_feasible_set_and_bind_list_slots(fams, name):
+    """A family with lines moved into the list (obstacle_rate = rate, r_o the neighbour's radius) has the family's own answer
+    (within 1e-12; measured: 0, the candidates are the same); per family, the share of records with a list slot active at u*
+    (`S.active` on the appended columns) and the flag band.  Measured shares: duplicates 0.160, antipodal 0.341, crowd 0.817,
+    near_parallel box one 0.458 / both 0.961, no box one 0.455 / both 1.000, wedge 0.992, axes 0.297, crowd permuted 0.828,
+    antipodal own radius 0.296, crowd own radius 0.726."""
+    conv, orate = O.list_family(fams, name)
+    own = name.endswith(" own radius")
+    base = fams[O.LIST_FAMILIES[name[:-len(" own radius")] if own else name][0]]
+    E, N, k1 = conv["nbr"].shape
+    m = conv["oid"].shape[2]
+    assert np.array_equal(conv["z"], base["z"]) and conv["orow"].dtype == np.float32 and conv["oid"].dtype == np.int32
+    assert conv["oid"].max() < O.LIST_M and (orate == 1.0) == own
+    act, band = [], []
+    for label, e0, e1 in conv["blocks"]:
+        ref = O.list_block_reference(conv, e0, e1, orate)
+        assert ref["A"].shape[1] == 4 + (k1 - 1) + m
+        if not own:
+            orig = S.block_reference(base, e0, e1)
+            assert np.abs(ref["ustar"] - orig["ustar"]).max() <= 1e-12 and np.array_equal(ref["intervened"], orig["intervened"])
+            assert np.array_equal(np.sort(ref["B"], axis=1)[:, :orig["B"].shape[1]], np.sort(orig["B"], axis=1))   # the same lines
+        act.append(S.active(dict(A=ref["A"], B=ref["B"], on=ref["on"], ustar=ref["ustar"]))[:, 4 + k1 - 1:].any(1))
+        band.append(ref["min_slack"] <= ref["tol"])
+    act, band = np.concatenate(act), np.concatenate(band)
+    print(f"{name}: a list slot active in {act.mean():.3f} of {act.size} records, flag band {band.mean():.4f}")
+    assert act.mean() >= LIST_ACTIVE_FLOOR[name] and band.mean() <= BAND_CAP
+    if name.startswith("crowd"):                                                   # 4 + 8 + 4: the whole capacity of the solve
+        assert ref["A"].shape[1] == 16 and (conv["oid"] >= 0).all(2).mean() >= 0.2
+        point = conv["point"]
+        assert (act & point).sum() >= 100                                          # where 0 is the only feasible action too
+    if own:
+        neighbour = base["radius"][np.maximum(base["nbr"].reshape(E * N, k1), 0)[np.arange(E * N)[:, None], conv["moved"]]]
+        live = conv["oid"].reshape(E * N, m)[:, :conv["moved"].shape[1]] >= 0
+        assert (conv["orow"].reshape(E * N, m, 3)[:, :conv["moved"].shape[1], 2] != neighbour)[live].all()
+
+
+def test_off_lists_are_off_and_the_mixed_ones_keep_three_live_slots():
+    case = O.shield_case(5, 2, 2)
+    M = case["obstacles"].shape[0]
+    for live in (0, 3):
+        orow, oid = O.off_lists(case, 4, live)
+        on = O.obstacle_constraints(orow.reshape(-1, 4, 3), oid.reshape(-1, 4), case["radius"], M, 0.5, S.MARGIN, S.DT)[2]
+        assert (on.sum(1) == live).all()
+        flat_id, flat_row = oid.reshape(-1), orow.reshape(-1, 3)
+        off = ~on.reshape(-1)
+        kinds = [(flat_id == -1) & (flat_row[:, :2] != 0).any(1), flat_id == M, flat_id == O.INT32_MIN,
+                 (flat_id >= 0) & (flat_id < M) & (flat_row[:, :2] == 0).all(1), np.isinf(flat_row[:, :2]).any(1), np.isnan(flat_row[:, :2]).any(1)]
+        assert all((kind & off).sum() >= 20 for kind in kinds) and (np.logical_or.reduce(kinds) == off).all()
+    ref = O.shield_reference(case, 2, orow, oid)
+    act = S.active(dict(A=ref["A"], B=ref["B"], on=ref["on"], ustar=ref["ustar"]))[:, 6:].any(1).mean()
+    print(f"mixed lists: a list slot active {act:.3f}, band {(ref['min_slack'] <= ref['tol']).mean():.4f}, tol {ref['tol']:.2e}")
+    assert act >= 0.05 and (ref["min_slack"] <= ref["tol"]).mean() <= BAND_CAP and np.isfinite(ref["tol"])
