@@ -22,8 +22,10 @@ share is printed next to the unshielded one, with the share of decisions the shi
 
 ``--obstacles N``: N discs of the reference's sizes off the goals (`place_obstacles`) in an `ObstacleField`; the evaluation (with
 ``--safety`` implied) then reports the share of episodes in which no agent touched a disc, and with ``--shield`` the shield also
-projects onto one half-plane per listed disc, so the obstacle-free share is printed shielded next to unshielded.  The reward and
-the networks' input do not know the discs.
+projects onto one half-plane per listed disc, so the obstacle-free share is printed shielded next to unshielded.  The reward does
+not know the discs, and neither do the networks' inputs unless ``--obstacle-inputs`` is given: the saved networks were then trained
+obstacle-aware (``train_loop.py --obstacle-inputs``: ``d_in = field.obs_width``) and read ``field.observe(env.z)``, ahead of
+``--obs-norm``.
 """
 import argparse
 import os
@@ -56,7 +58,11 @@ def main():
     ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
     ap.add_argument("--obstacles", type=int, default=0, help="static discs off the goals, sensed, reported and (--shield) enforced")
     ap.add_argument("--obstacle-rate", type=float, default=None, help="share of the gap to a disc an agent may close per step, in (0, 1]")
+    ap.add_argument("--obstacle-inputs", action="store_true",
+                    help="the saved networks were trained obstacle-aware: they read the record plus the field's obstacle columns")
     a = ap.parse_args()
+    if a.obstacle_inputs and (not a.obstacles or a.controller):
+        ap.error("--obstacle-inputs needs --obstacles N and saved networks (no --controller)")
     a.safety = a.safety or a.obstacles > 0
 
     if a.controller:
@@ -76,16 +82,18 @@ def main():
     print(f"N of agents = {env.n_agents}, collision weight b = {env.collision_weight}")
 
     obs_norm = None
-    if a.obs_norm:
-        import torch
-        obs_norm = ObsNormalizer(n_agents, env.local_state_space, env.device).load_state_dict(torch.load(a.obs_norm))
     field = None
     if a.obstacles:
         discs = place_obstacles(env.grid, a.obstacles, seed=0, keep_clear=env.end_points.reshape(n_agents, 2), clearance=0.3)
         field = ObstacleField(env, discs, m=2)
+    if a.obs_norm:
+        import torch
+        width = field.obs_width if a.obstacle_inputs else env.local_state_space
+        obs_norm = ObsNormalizer(n_agents, width, env.device).load_state_dict(torch.load(a.obs_norm))
+    if field is not None:
         print(f"Obstacles = {field.M} discs (of {a.obstacles} drawn; the rest covered a goal), radius {discs[:, 2].min():.2f} .. "
               f"{discs[:, 2].max():.2f} m" if field.M else f"Obstacles = 0 (all {a.obstacles} drawn covered a goal)")
-    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, obstacles=field)
+    ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, obstacles=field, obstacle_inputs=a.obstacle_inputs)
     ev.run(rounds)
     s = ev.summary()
     print(f"Episodes {s['episodes']} - Average Reward/Collisions/Steps: {s['mean_return']:.1f}/{s['mean_collisions']:.2f}/"
@@ -112,7 +120,8 @@ def main():
     if a.shield:                                             # (no reference line: the reference has no safety layer)
         shield = ActionShield(env, rate=a.shield_rate, margin=a.shield_margin, u_max=1.0, stats=True, obstacles=field,
                               obstacle_rate=a.obstacle_rate if field is not None else None)
-        evs = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, shield=shield, obstacles=field)
+        evs = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, shield=shield, obstacles=field,
+                        obstacle_inputs=a.obstacle_inputs)
         evs.run(rounds)
         t = evs.summary()
         print(f"### Shielded (rate = {shield.rate}, margin = {shield.margin} m, box = {shield.u_max})")

@@ -53,8 +53,14 @@ the projected action, the projection counting as part of the environment, while 
 the policy's own sample (the discrete actor's action index needs unit vectors).  Every episode line then shows the share of the
 window's decisions the shield changed and the mean correction.  ``--obstacles N`` (with ``--shield``) puts N static discs of the
 reference's sizes off the goals (`place_obstacles`, an `ObstacleField`): the shield then also projects onto one half-plane per
-listed disc, and every episode line shows the share of the window's first episodes in which no agent touched a disc.  The reward
-and the networks' input do not know the discs: the policy meets them as part of the environment.
+listed disc, and every episode line shows the share of the window's first episodes in which no agent touched a disc.  Without
+``--obstacle-inputs`` the reward and the networks' input do not know the discs: the policy meets them as part of the environment.
+
+``--obstacle-inputs`` makes the training obstacle-aware: the networks read `ObstacleField.observe` -- the record plus
+``(p.x, p.y, r)`` of the two nearest discs in range, 12 inputs at k = 2 -- in the rollout (ahead of ``--obs-norm``) and in the
+learner (``obstacles=field``), and the learner takes ``--obstacle-weight W`` times the obstacle cost (the reference's collision term
+with a disc in the neighbour's place) off every stored reward; the default W is the env's ``collision_weight x dt``.  With a weight
+> 0 the discs need no ``--shield``.  Every episode line then shows the window's mean obstacle cost next to the obstacle-free share.
 
 ``--share all`` trains ONE actor and ONE critic for the whole team (parameter sharing): the networks are tied
 (`BatchedMLP.tie_weights`) and every update pools the agents' gradients (`dronesim_adam_step_shared`); with ``--target-kl`` the
@@ -71,6 +77,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from scalable_collision_avoidance_rl_amd import drones
+from scalable_collision_avoidance_rl_amd.drone_env import dt
 from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
 from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles
@@ -120,10 +127,22 @@ def main():
     ap.add_argument("--shield", action="store_true", help="train through an ActionShield: the env integrates the projected action")
     ap.add_argument("--shield-rate", type=float, default=0.25, help="share of a gap an agent may close per step, in (0, 0.5]")
     ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
-    ap.add_argument("--obstacles", type=int, default=0, help="static discs off the goals, enforced by the shield (needs --shield)")
+    ap.add_argument("--obstacles", type=int, default=0,
+                    help="static discs off the goals, enforced by the shield (needs --shield or an --obstacle-weight > 0)")
+    ap.add_argument("--obstacle-inputs", action="store_true",
+                    help="obstacle-aware training: the networks read the record plus the nearest discs, the reward pays the obstacle cost")
+    ap.add_argument("--obstacle-weight", type=float, default=None,
+                    help="weight of the obstacle cost in the reward (--obstacle-inputs; default: the env's collision_weight x dt)")
     args = ap.parse_args()
-    if args.obstacles and not args.shield:
-        ap.error("--obstacles needs --shield (nothing else enforces the discs)")
+    if args.obstacle_inputs and not args.obstacles:
+        ap.error("--obstacle-inputs needs --obstacles N")
+    if args.obstacle_weight is not None and not args.obstacle_inputs:
+        ap.error("--obstacle-weight needs --obstacle-inputs (a cost the networks cannot see teaches nothing)")
+    if args.obstacle_weight is not None and not 0.0 <= args.obstacle_weight < float("inf"):
+        ap.error("--obstacle-weight must be finite and >= 0")
+    penalised = args.obstacle_inputs and (args.obstacle_weight is None or args.obstacle_weight > 0)
+    if args.obstacles and not args.shield and not penalised:
+        ap.error("--obstacles needs --shield or --obstacle-inputs with a weight > 0 (nothing else makes the discs matter)")
     if args.minibatches != 1 and args.learner != "ppo":
         ap.error("--minibatches needs --learner ppo (one update per window is what A2C is)")
     if args.normalize_advantage and args.learner != "ppo":
@@ -133,7 +152,15 @@ def main():
     N, E, T, dev = args.agents, args.envs, args.window, "cuda:0"
     env = drones(N, 0, [args.grid, args.grid], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=dev, seed=1, auto_reset=True)
-    d_in = env.local_state_space
+    field = None
+    if args.obstacles:
+        field = ObstacleField(env, place_obstacles(env.grid, args.obstacles, seed=0, keep_clear=env.end_points.reshape(N, 2),
+                                                   clearance=0.3), m=2)
+    seen_field = field if args.obstacle_inputs else None     # the field whose columns the networks read
+    obstacle_weight = 0.0
+    if seen_field is not None:                               # the reference's own collision weight, per step
+        obstacle_weight = float(env.collision_weight) * dt if args.obstacle_weight is None else args.obstacle_weight
+    d_in = env.local_state_space if seen_field is None else seen_field.obs_width
     gen = torch.Generator().manual_seed(0)
     actor = BatchedMLP(*network(gen, N, [d_in, 300, 300, 16]), 1, 1, device=dev, seed=3)     # DiscreteSoftmaxNN x N
     critic = BatchedMLP(*network(gen, N, [d_in, 200, 200, 1]), 0, 0, device=dev)            # CriticNN x N
@@ -141,10 +168,6 @@ def main():
         actor.tie_weights(args.share)
         critic.tie_weights(args.share)
     storage = RolloutStorage(env, T, actions=True)
-    field = None
-    if args.obstacles:
-        field = ObstacleField(env, place_obstacles(env.grid, args.obstacles, seed=0, keep_clear=env.end_points.reshape(N, 2),
-                                                   clearance=0.3), m=2)
     shield = ActionShield(env, args.shield_rate, args.shield_margin, u_max=1.0, stats=True, obstacles=field) if args.shield else None
     safe = torch.empty(E, N, 2, device=dev) if shield is not None else None
 
@@ -154,23 +177,26 @@ def main():
         else:
             env.step(storage.actions[t], into=(storage, t), execute=shield(storage.actions[t], out=safe))
     norm = ObsNormalizer(N, d_in, dev, clip=args.obs_clip) if args.obs_norm else None
-    see = (lambda z: z) if norm is None else norm           # what the networks read of an observation
+    augment = (lambda z: z) if seen_field is None else seen_field.observe
+    see = augment if norm is None else (lambda z: norm(augment(z)))            # what the networks read of an observation
     rnorm = RewardNormalizer(N, 0.99, dev, clip=args.reward_clip) if args.reward_norm else None
     # the reference's actor_lr argument is never read by train_NN; here the actor's lr is explicit
     if args.learner == "ppo":
         learner = PPOLearner(actor, critic, gamma=0.99, epochs=args.epochs, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                              lam=args.lam, time_limit=args.time_limit, ent_coef=args.ent_coef,
                              normalize_advantage=args.normalize_advantage, minibatches=args.minibatches, shuffle_seed=args.shuffle_seed,
-                             target_kl=args.target_kl, vf_clip=args.vf_clip, obs_norm=norm, share=args.share, reward_norm=rnorm)
+                             target_kl=args.target_kl, vf_clip=args.vf_clip, obs_norm=norm, share=args.share, reward_norm=rnorm,
+                             obstacles=seen_field, obstacle_weight=obstacle_weight)
     else:
         learner = SA2CLearner(actor, critic, gamma=0.99, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, lam=args.lam,
-                              time_limit=args.time_limit, ent_coef=args.ent_coef, obs_norm=norm, share=args.share, reward_norm=rnorm)
+                              time_limit=args.time_limit, ent_coef=args.ent_coef, obs_norm=norm, share=args.share, reward_norm=rnorm,
+                              obstacles=seen_field, obstacle_weight=obstacle_weight)
     if norm is not None:      # one warm-up window of statistics only: window 0 is not trained on the identity map
         storage.begin()
         for t in range(T):
-            actor.sample_action(env.z, env=env, act_out=storage.actions[t])
+            actor.sample_action(augment(env.z), env=env, act_out=storage.actions[t])
             step(t)
-        norm.update(storage.z_pre)
+        norm.update(augment(storage.z_pre))
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for ep in range(args.episodes):
         storage.begin()
@@ -214,6 +240,8 @@ def main():
             ok = tab["ep_len"] > 0
             free = (ok & (tab["ep_obstacle_hit_steps"] == 0)).sum().item() / max(int(ok.sum().item()), 1)
             ppo += f"  obstacle-free episodes {free:.2%} ({field.M} discs)"
+        if "obstacle_cost" in out:
+            ppo += f"  obstacle cost {float(out['obstacle_cost'].mean()):.4g} (weight {obstacle_weight:.3g})"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "
               f"actor loss {float(mean(out['actor_loss'])):+.3f}  grad norms {float(out['critic_grad_norm'].mean()):.1f} / "
               f"{float(mean(out['actor_grad_norm'])):.1f}{ppo}  update {start.elapsed_time(stop):.2f} ms")

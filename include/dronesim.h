@@ -833,7 +833,7 @@ int dronesim_shield_totals(const uint8_t *intervened, const float *correction, i
                            int64_t *nonfinite, double *correction_sum, float *correction_max, void *stream);
 
 /* Static obstacle discs (csrc/obstacles.hip, csrc/shield.hip; DESIGN.md has the guarantee and its conditions).  The step kernel,
- * the reward and the networks never read them: these entries work on stored observations, beside the step.
+ * never reads them: these entries work on stored observations, beside the step.
  *
  * Inputs: obstacles [M][3] float32 (x, y, r), one list shared by all envs, 0 <= M <= DRONESIM_MAX_OBSTACLES (may be NULL at
  * M = 0); xF [N][2] the goals; radius [N]; sense [N] the range of every agent.
@@ -869,7 +869,35 @@ int dronesim_shield_totals(const uint8_t *intervened, const float *correction, i
  * launches on `stream` (one without per-env tables): the backward column scan with the disc loop in its step, then one thread
  * per (env, table); no atomics: graph-capturable, bit-identical run to run.  E = 0 enqueues nothing.  EINVAL: NULL z / done (with
  * T > 0) / xF / radius / ep_len, T or E < 0, N outside 1..1024, k1 < 1, c not in {2, 5}, M outside 0..1024 (or NULL obstacles with M > 0), a
- * per-env table without its per-agent one.                                                                                       */
+ * per-env table without its per-agent one.
+ *
+ * Obstacle columns and obstacle cost -- what the networks and the reward see of the discs.  Both use the gap above, the ONE
+ * float32 expression, so they agree with the sense entry bit for bit.
+ * Columns: a record z[r][i] of d = k1 c floats becomes d + 3 m floats: floats [0, d) are the record's own bits, float
+ * d + 3 s + (0, 1, 2) is slot s of the sense entry's list, (p.x, p.y, o.r), an empty slot (0, 0, 0) -- the range, the ordering (gap
+ * ascending, then id ascending) and the NaN rule are the sense entry's own: the policy sees exactly the discs the shield constrains.
+ * Cost: the reference's collision term (drone_env.py:268-334: b log(d_i / d_ij) over the Delta-neighbourhood, 9.99e3 for a
+ * collision) with a disc in the neighbour's place.  Over ALL M discs in ascending id, accumulated in float32, with s = sense[i]:
+ * 9.99e3 where gap <= 0;  logf(s / gap) where 0 < gap <= s (the correctly rounded quotient);  0 otherwise (a NaN gap, or s <= 0
+ * with a positive gap, gives 0).  cost = fl32(weight sum); M = 0 gives 0.
+ * The shaped reward of transition t is fl32(reward[t] - cost(observation after step t)): z_final[t] where done[t] and z_final is
+ * given, the post-step observation z_post[t] otherwise.
+ *
+ * dronesim_obstacle_observe takes R rows of [N][k1 c] (a window ring of (T + 1) E rows, the truncated ends' M_t E rows or one
+ * step's E rows pass without a copy) and writes x_out [R][N][k1 c + 3 m] and, where cost_out is not NULL, cost_out [R][N].  One
+ * launch, one thread per record; the lists of a workgroup are parked in LDS and its 256 records leave as one contiguous run in
+ * lane order (16-byte stores where x_out is 16-byte aligned, dword stores otherwise; the same bits either way).
+ * dronesim_obstacle_reward is elementwise over (t, e, i) of z_post / z_final [T][E][N][k1 c], done [T][E], reward [T][E][N]: it
+ * writes reward_out [T][E][N] (reward_out == reward, in place, is allowed) and, where not NULL, cost_out [T][E][N]; z_final may be
+ * NULL.  One launch.  Both stage the list once per workgroup in LDS; no atomics, no workspace, no host synchronisation:
+ * graph-capturable, bit-identical run to run.  R = 0 / T E = 0 enqueues nothing.  EINVAL: a NULL pointer other than obstacles at
+ * M = 0, z_final and cost_out; R, T or E < 0, N outside 1..1024, k1 outside 1..DRONESIM_MAX_K + 1, c not in {2, 5}, M outside
+ * 0..1024, m outside 1..4, weight not finite or < 0.                                                                               */
+int dronesim_obstacle_observe(const float *z, const float *xF, const float *radius, const float *sense, const float *obstacles,
+                              int R, int N, int k1, int c, int M, int m, float *x_out, float *cost_out, float weight, void *stream);
+int dronesim_obstacle_reward(const float *z_post, const float *z_final, const uint8_t *done, const float *reward, const float *xF,
+                             const float *radius, const float *sense, const float *obstacles, int T, int E, int N, int k1, int c, int M,
+                             float weight, float *reward_out, float *cost_out, void *stream);
 int dronesim_obstacle_sense(const float *z, const float *xF, const float *radius, const float *sense, const float *obstacles,
                             int E, int N, int k1, int c, int M, int m, float *orow, int32_t *oid, float *gap_min, uint8_t *hit,
                             void *stream);

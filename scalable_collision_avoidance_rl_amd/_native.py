@@ -45,6 +45,7 @@ SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_roll
            "dronesim_rewnorm_workspace", "dronesim_rewnorm_update", "dronesim_rewnorm_apply",
            "dronesim_action_shield", "dronesim_shield_totals",
            "dronesim_obstacle_sense", "dronesim_action_shield_obstacles", "dronesim_episode_obstacle_safety",
+           "dronesim_obstacle_observe", "dronesim_obstacle_reward",
            "dronesim_last_error", "dronesim_error_string", "dronesim_version")
 
 
@@ -215,6 +216,9 @@ def lib():
     L.dronesim_action_shield_obstacles.argtypes = [vp] * 4 + [f32] * 4 + [i32] * 4 + [vp] * 3 + [vp, vp, i32, i32, f32, vp]
     L.dronesim_episode_obstacle_safety.argtypes = [vp] * 6 + [i32] * 6 + [vp] * 5 + [vp]
     L.dronesim_obstacle_sense.restype = L.dronesim_action_shield_obstacles.restype = L.dronesim_episode_obstacle_safety.restype = C.c_int
+    L.dronesim_obstacle_observe.argtypes = [vp] * 5 + [i32] * 6 + [vp, vp, f32, vp]
+    L.dronesim_obstacle_reward.argtypes = [vp] * 8 + [i32] * 6 + [f32, vp, vp, vp]
+    L.dronesim_obstacle_observe.restype = L.dronesim_obstacle_reward.restype = C.c_int
     L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
     PC = C.POINTER(DroneEpisodeCtl)
     L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]

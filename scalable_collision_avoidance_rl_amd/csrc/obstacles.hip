@@ -1,6 +1,8 @@
 // Static obstacle discs (include/dronesim.h states the rule): dronesim_obstacle_sense lists, per record (e, i), the m nearest of
 // the M discs within the agent's range from the agent's OWN observation -- the list the obstacle shield (shield.hip) turns into
-// half-planes --, dronesim_episode_obstacle_safety reduces a stored window to per-episode clearance and hit tables.
+// half-planes --, dronesim_episode_obstacle_safety reduces a stored window to per-episode clearance and hit tables,
+// dronesim_obstacle_observe appends that list to every record (the networks' obstacle columns) and dronesim_obstacle_reward takes
+// the obstacle cost of the observation after every stored step off its reward.
 //
 // Both need the agent's position, which its record holds: row 0 is x_i - xF_i, so x = z[0] + xF[i][0], y = z[1] + xF[i][1].  The
 // gap to disc o = (ox, oy, or):  p = o.xy - (x, y),  d = sqrtf(fmaf(p.y, p.y, p.x p.x)),  gap = (d - radius[i]) - or  (obstacle_gap
@@ -59,8 +61,39 @@ struct SenseArgs {
     unsigned long long records;
 };
 
+// Row 0 of a record, W floats wide (sense_load_width's rule; wave-uniform)
+__device__ __forceinline__ void load_row0(const float *rec, int W, float &zx, float &zy)
+{
+    if (W == 4) {                                              // k1 even, c = 2, 16-byte aligned: row 0 with row 1
+        const ob_f4 v = *reinterpret_cast<const ob_f4 *>(rec);
+        zx = v.x; zy = v.y;
+    } else if (W == 2) {
+        const ob_f2 v = *reinterpret_cast<const ob_f2 *>(rec);
+        zx = v.x; zy = v.y;
+    } else {
+        zx = rec[0]; zy = rec[1];
+    }
+}
+
 // MS list slots kept sorted by (gap, id) in registers: the discs come in ascending id, so a new one goes in front of the first
 // slot with a LARGER gap (or an empty one) and everything behind moves down one -- arrays indexed by unrolled counters only.
+template <int MS>
+__device__ __forceinline__ void sense_insert(float (&bg)[MS], float (&bx)[MS], float (&by)[MS], float (&br)[MS], int (&bi)[MS], bool in,
+                                             const ObstacleGap &g, float orad, int o)
+{
+    float cg = g.gap, cx = g.px, cy = g.py, cr = orad;
+    int ci = o;
+    bool moving = false;                                       // the carried entry has displaced a slot: every later slot moves down
+#pragma unroll
+    for (int s = 0; s < MS; ++s) {
+        moving = moving || (in && (cg < bg[s] || bi[s] < 0));
+        const float tg = bg[s], tx = bx[s], ty = by[s], tr = br[s];
+        const int ti = bi[s];
+        bg[s] = moving ? cg : tg; bx[s] = moving ? cx : tx; by[s] = moving ? cy : ty; br[s] = moving ? cr : tr; bi[s] = moving ? ci : ti;
+        cg = moving ? tg : cg; cx = moving ? tx : cx; cy = moving ? ty : cy; cr = moving ? tr : cr; ci = moving ? ti : ci;
+    }
+}
+
 template <int MS>
 __global__ void __launch_bounds__(256) obstacle_sense_kernel(const SenseArgs a)
 {
@@ -72,15 +105,7 @@ __global__ void __launch_bounds__(256) obstacle_sense_kernel(const SenseArgs a)
     const int i = (int)(r % (unsigned)a.N);
     const float *rec = a.z + r * (unsigned long long)a.stride;
     float zx, zy;
-    if (a.W == 4) {                                            // (wave-uniform) k1 even, c = 2, 16-byte aligned: row 0 with row 1
-        const ob_f4 v = *reinterpret_cast<const ob_f4 *>(rec);
-        zx = v.x; zy = v.y;
-    } else if (a.W == 2) {
-        const ob_f2 v = *reinterpret_cast<const ob_f2 *>(rec);
-        zx = v.x; zy = v.y;
-    } else {
-        zx = rec[0]; zy = rec[1];
-    }
+    load_row0(rec, a.W, zx, zy);
     const float x = zx + a.xF[2 * i], y = zy + a.xF[2 * i + 1];
     const float ri = a.radius[i], range = a.sense[i];
 
@@ -97,17 +122,7 @@ __global__ void __launch_bounds__(256) obstacle_sense_kernel(const SenseArgs a)
         gm = ob_nan_min(g.gap, gm);
         const bool in = g.gap <= range;                        // (a NaN gap is not in range)
         if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;  // most discs are out of every lane's range: the wave skips the insertion
-        float cg = g.gap, cx = g.px, cy = g.py, cr = orad;
-        int ci = o;
-        bool moving = false;                                   // the carried entry has displaced a slot: every later slot moves down
-#pragma unroll
-        for (int s = 0; s < MS; ++s) {
-            moving = moving || (in && (cg < bg[s] || bi[s] < 0));
-            const float tg = bg[s], tx = bx[s], ty = by[s], tr = br[s];
-            const int ti = bi[s];
-            bg[s] = moving ? cg : tg; bx[s] = moving ? cx : tx; by[s] = moving ? cy : ty; br[s] = moving ? cr : tr; bi[s] = moving ? ci : ti;
-            cg = moving ? tg : cg; cx = moving ? tx : cx; cy = moving ? ty : cy; cr = moving ? tr : cr; ci = moving ? ti : ci;
-        }
+        sense_insert<MS>(bg, bx, by, br, bi, in, g, orad, o);
     }
     if (!act) return;
     float *orow = a.orow + r * (unsigned long long)(3 * MS);
@@ -128,6 +143,150 @@ inline int sense_load_width(int k1, int c, uintptr_t z)
     if ((k1 % 2) == 0 && (z & 15u) == 0) return 4;
     return (z & 7u) == 0 ? 2 : 1;
 }
+
+// ---- dronesim_obstacle_observe, dronesim_obstacle_reward ---------------------------------------------------------------------------
+// One disc's term of the obstacle cost (include/dronesim.h): the reference's pair term b log(d_i / d_ij) with the disc in the
+// neighbour's place.  A NaN gap, a NaN range and a range <= 0 with a positive gap fail both comparisons: 0.
+constexpr float kObstacleHitCost = 9.99e3f;
+
+__device__ __forceinline__ float obstacle_cost_term(float gap, float range, bool near)
+{
+    return gap <= 0.0f ? kObstacleHitCost : (near ? logf(range / gap) : 0.0f);
+}
+
+struct ObserveArgs {
+    const float *z, *xF, *radius, *sense, *obstacles;
+    float *x_out, *cost;
+    float weight;
+    int N, stride, M, W, OW;                                   // W: row 0's load width; OW: 4 where x_out is 16-byte aligned, else 1
+    unsigned long long records;
+};
+
+// The sense kernel's scan with the record's augmented image as its output: [0, d) the record's own bits, then the MS list slots
+// (p.x, p.y, o.r).  The records of a workgroup are contiguous in z and in x_out, so the block leaves as ONE contiguous run of
+// 256 (d + 3 MS) floats: every thread parks its list in LDS (12 MS bytes), and after the barrier the workgroup walks the run in
+// lane order -- element g is float q = g mod (d + 3 MS) of record g / (d + 3 MS), from z (global, contiguous as well) where q < d and
+// from the parked lists otherwise -- with 16-byte stores where x_out allows it (a block starts at a multiple of 1024 (d + 3 MS)
+// bytes), dword stores otherwise: every store instruction of a wave covers whole lines.  No record passes through registers, so
+// d is a run-time value and nothing is indexed dynamically.  COST: the sum of obstacle_cost_term over ALL discs in ascending
+// id, times weight (its own rounding), one dword per thread.
+template <int MS, bool COST>
+__global__ void __launch_bounds__(256) obstacle_observe_kernel(const ObserveArgs a)
+{
+    __shared__ float s_obs[3 * kMaxObstacles];
+    __shared__ float s_list[256 * 3 * MS];
+    stage_obstacles(s_obs, a.obstacles, a.M);
+    const unsigned long long rb = (unsigned long long)blockIdx.x * 256u;
+    const unsigned long long r0 = rb + threadIdx.x;
+    const bool act = r0 < a.records;
+    const unsigned long long r = act ? r0 : a.records - 1;
+    const int i = (int)(r % (unsigned)a.N);
+    float zx, zy;
+    load_row0(a.z + r * (unsigned long long)a.stride, a.W, zx, zy);
+    const float x = zx + a.xF[2 * i], y = zy + a.xF[2 * i + 1];
+    const float ri = a.radius[i], range = a.sense[i];
+
+    const float inf = __builtin_inff();
+    float bg[MS], bx[MS], by[MS], br[MS];
+    int bi[MS];
+#pragma unroll
+    for (int s = 0; s < MS; ++s) { bg[s] = inf; bx[s] = by[s] = br[s] = 0.0f; bi[s] = -1; }
+    float sum = 0.0f;
+    const int M = a.M;
+    for (int o = 0; o < M; ++o) {
+        const float orad = s_obs[3 * o + 2];
+        const ObstacleGap g = obstacle_gap(x, y, ri, s_obs[3 * o], s_obs[3 * o + 1], orad);
+        const bool in = g.gap <= range;                        // (a NaN gap is not in range)
+        const bool any_in = __builtin_amdgcn_ballot_w64(in) != 0ull;
+        if (COST) {                                            // a hit adds its constant in range or not; the log runs with the insertion
+            if (any_in) sum += obstacle_cost_term(g.gap, range, in);
+            else sum += g.gap <= 0.0f ? kObstacleHitCost : 0.0f;
+        }
+        if (!any_in) continue;
+        sense_insert<MS>(bg, bx, by, br, bi, in, g, orad, o);
+    }
+    float *mine = s_list + 3 * MS * threadIdx.x;
+#pragma unroll
+    for (int s = 0; s < MS; ++s) { mine[3 * s] = bx[s]; mine[3 * s + 1] = by[s]; mine[3 * s + 2] = br[s]; }
+    if (COST && act) a.cost[r] = a.weight * sum;
+    __syncthreads();
+
+    const unsigned d = (unsigned)a.stride, w = d + 3u * MS;
+    const unsigned long long left = a.records - rb;
+    const unsigned total = (left < 256u ? (unsigned)left : 256u) * w;             // floats of this block's run (<= 256 * 57)
+    const float *zb = a.z + rb * d;
+    float *ob = a.x_out + rb * w;
+    if (a.OW == 4) {
+        for (unsigned g0 = 4u * threadIdx.x; g0 < total; g0 += 1024u) {
+            unsigned rec = g0 / w, q = g0 - rec * w;
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] = 0.0f;
+                if (g0 + j < total) v[j] = q < d ? zb[rec * d + q] : s_list[rec * (3u * MS) + (q - d)];
+                if (++q == w) { q = 0; ++rec; }
+            }
+            if (g0 + 4u <= total) {
+                ob_f4 o4; o4.x = v[0]; o4.y = v[1]; o4.z = v[2]; o4.w = v[3];
+                *reinterpret_cast<ob_f4 *>(ob + g0) = o4;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (g0 + j < total) ob[g0 + j] = v[j];
+            }
+        }
+    } else {
+        for (unsigned g0 = threadIdx.x; g0 < total; g0 += 256u) {
+            const unsigned rec = g0 / w, q = g0 - rec * w;
+            ob[g0] = q < d ? zb[rec * d + q] : s_list[rec * (3u * MS) + (q - d)];
+        }
+    }
+}
+
+struct RewardArgs {
+    const float *z_post, *z_final;
+    const uint8_t *done;
+    const float *reward, *xF, *radius, *sense, *obstacles;
+    float *reward_out, *cost;                                  // reward_out may be reward itself (one thread reads and writes an element)
+    float weight;
+    int N, stride, M, W;
+    unsigned long long records;                                // T E N
+};
+
+// Elementwise over (t, e, i): the cost of the observation after step t -- z_final's record where the step ended an episode and
+// z_final is given, the post-step ring slot's otherwise (RolloutStorage.next_z's substitution) -- off the reward.
+__global__ void __launch_bounds__(256) obstacle_reward_kernel(const RewardArgs a)
+{
+    __shared__ float s_obs[3 * kMaxObstacles];
+    stage_obstacles(s_obs, a.obstacles, a.M);
+    const unsigned long long r0 = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    const bool act = r0 < a.records;
+    const unsigned long long r = act ? r0 : a.records - 1;
+    const unsigned long long te = r / (unsigned)a.N;
+    const int i = (int)(r - te * (unsigned)a.N);
+    const float *src = (a.z_final && a.done[te] != 0) ? a.z_final : a.z_post;
+    float zx, zy;
+    load_row0(src + r * (unsigned long long)a.stride, a.W, zx, zy);
+    const float x = zx + a.xF[2 * i], y = zy + a.xF[2 * i + 1];
+    const float ri = a.radius[i], range = a.sense[i];
+    float sum = 0.0f;
+    const int M = a.M;
+    for (int o = 0; o < M; ++o) {
+        const float gap = obstacle_gap(x, y, ri, s_obs[3 * o], s_obs[3 * o + 1], s_obs[3 * o + 2]).gap;
+        const bool in = gap <= range;
+        if (__builtin_amdgcn_ballot_w64(in) != 0ull) sum += obstacle_cost_term(gap, range, in);
+        else sum += gap <= 0.0f ? kObstacleHitCost : 0.0f;
+    }
+    if (!act) return;
+    {
+#pragma clang fp contract(off)                                 // two roundings, as the rule states: the stored cost is the one subtracted
+        const float cost = a.weight * sum;
+        a.reward_out[r] = a.reward[r] - cost;
+        if (a.cost) a.cost[r] = cost;
+    }
+}
+
+inline bool obstacle_weight_ok(float weight) { return weight >= 0.0f && weight <= 3.402823466e38f; }   // (finite, not NaN, >= 0)
 
 // ---- dronesim_episode_obstacle_safety ---------------------------------------------------------------------------------------------
 // SafetyScan's scan (evaluate.hip) with the disc loop in its step: the same backward driver, the same restart at `done`, the same
@@ -262,6 +421,58 @@ int dronesim_obstacle_sense(const float *z, const float *xF, const float *radius
     else if (m == 2) hipLaunchKernelGGL(obstacle_sense_kernel<2>, grid, dim3(256), 0, s, a);
     else if (m == 3) hipLaunchKernelGGL(obstacle_sense_kernel<3>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(obstacle_sense_kernel<4>, grid, dim3(256), 0, s, a);
+    return dronesim_launched();
+}
+
+int dronesim_obstacle_observe(const float *z, const float *xF, const float *radius, const float *sense, const float *obstacles,
+                              int R, int N, int k1, int c, int M, int m, float *x_out, float *cost_out, float weight, void *stream)
+{
+    if (!z || !xF || !radius || !sense || !x_out) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: NULL z / xF / radius / sense / x_out");
+    if (R < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: R < 0, N outside 1..1024, k1 outside 1..9 or c not in {2, 5}");
+    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: M outside 0..1024, or NULL obstacles with M > 0");
+    if (m < 1 || m > kMaxSense) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: m outside 1..4");
+    if (!obstacle_weight_ok(weight)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: weight must be finite and >= 0");
+    if (R == 0) return DRONESIM_OK;
+    ObserveArgs a;
+    a.z = z; a.xF = xF; a.radius = radius; a.sense = sense; a.obstacles = obstacles; a.x_out = x_out; a.cost = cost_out; a.weight = weight;
+    a.N = N; a.stride = k1 * c; a.M = M; a.W = sense_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    a.OW = (reinterpret_cast<uintptr_t>(x_out) & 15u) == 0 ? 4 : 1;
+    a.records = (unsigned long long)R * (unsigned long long)N;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((a.records + 255) / 256));
+#define DRONESIM_OBSERVE(MS)                                                                                 \
+    do {                                                                                                     \
+        if (cost_out) hipLaunchKernelGGL((obstacle_observe_kernel<MS, true>), grid, dim3(256), 0, s, a);     \
+        else hipLaunchKernelGGL((obstacle_observe_kernel<MS, false>), grid, dim3(256), 0, s, a);             \
+    } while (0)
+    if (m == 1) DRONESIM_OBSERVE(1);
+    else if (m == 2) DRONESIM_OBSERVE(2);
+    else if (m == 3) DRONESIM_OBSERVE(3);
+    else DRONESIM_OBSERVE(4);
+#undef DRONESIM_OBSERVE
+    return dronesim_launched();
+}
+
+int dronesim_obstacle_reward(const float *z_post, const float *z_final, const uint8_t *done, const float *reward, const float *xF,
+                             const float *radius, const float *sense, const float *obstacles, int T, int E, int N, int k1, int c, int M,
+                             float weight, float *reward_out, float *cost_out, void *stream)
+{
+    if (!z_post || !done || !reward || !xF || !radius || !sense || !reward_out)
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: NULL z_post / done / reward / xF / radius / sense / reward_out");
+    if (T < 0 || E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
+        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: T or E < 0, N outside 1..1024, k1 outside 1..9 or c not in {2, 5}");
+    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: M outside 0..1024, or NULL obstacles with M > 0");
+    if (!obstacle_weight_ok(weight)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: weight must be finite and >= 0");
+    if (T == 0 || E == 0) return DRONESIM_OK;
+    RewardArgs a;
+    a.z_post = z_post; a.z_final = z_final; a.done = done; a.reward = reward; a.xF = xF; a.radius = radius; a.sense = sense;
+    a.obstacles = obstacles; a.reward_out = reward_out; a.cost = cost_out; a.weight = weight;
+    a.N = N; a.stride = k1 * c; a.M = M;
+    a.W = sense_load_width(k1, c, reinterpret_cast<uintptr_t>(z_post) | reinterpret_cast<uintptr_t>(z_final));
+    a.records = (unsigned long long)T * (unsigned long long)E * (unsigned long long)N;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(obstacle_reward_kernel, dim3((unsigned)((a.records + 255) / 256)), dim3(256), 0, s, a);
     return dronesim_launched();
 }
 

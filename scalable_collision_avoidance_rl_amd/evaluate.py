@@ -188,6 +188,9 @@ class Evaluator:
     per-episode obstacle tables (`obstacles.episode_obstacle_safety`: smallest gap to a disc, steps in touch with one), two
     launches more per round, and `safety_summary` gains ``obstacle_free_share``, ``arrived_clear_share``, ``min_obstacle_gap`` and
     ``mean_min_obstacle_gap``.  (Whether the discs are ENFORCED is the shield's business: ``ActionShield(env, ..., obstacles=field)``.)
+    ``obstacle_inputs=True`` (network actors, with ``obstacles=field``): actor and critic read ``field.observe(env.z)``, the record
+    plus the field's obstacle columns, ahead of ``obs_norm`` -- the networks of a learner with ``obstacles=field``; their ``d_in`` is
+    ``field.obs_width``.  This use needs no ``safety=True`` (without it no obstacle tables are made).
 
     A round is ``env.reset()``, ``T = max_time_steps`` steps into an owned `RolloutStorage`, then the two reductions.  Every env
     contributes exactly one episode per round -- its first one: a fresh episode always ends inside ``max_time_steps``
@@ -198,7 +201,8 @@ class Evaluator:
     Buffers are allocated by the first ``run`` (and again only when ``rounds`` changes); one round can be captured in a
     ``torch.cuda.graph`` after an eager warm-up call."""
 
-    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False, shield=None, obstacles=None):
+    def __init__(self, env, actor, critic=None, gamma=0.99, n_bins=32, obs_norm=None, safety=False, shield=None, obstacles=None,
+                 obstacle_inputs=False):
         from .drone_env import max_time_steps
         if not getattr(env, "batched", False):
             raise ValueError("Evaluator needs the batched (tensor) API of `drones`")
@@ -216,15 +220,24 @@ class Evaluator:
         else:
             if not getattr(actor, "sample_kind", 0):
                 raise ValueError("the actor needs a sampling head (softmax or Gaussian BatchedMLP)")
+            if obstacle_inputs:                             # the networks read the record plus the field's obstacle columns
+                if getattr(obstacles, "env", None) is not env:
+                    raise ValueError("obstacle_inputs=True needs obstacles=, an ObstacleField of this env")
+                width, source = obstacles.obs_width, "the env with the field's obstacle columns"
+            else:
+                width, source = env.local_state_space, "the env"
             for net, what in ((actor, "actor"), (critic, "critic")):
-                if net is not None and (net.n_agents != env.n_agents or net.d_in != env.local_state_space):
-                    raise ValueError(f"the {what} is built for {net.n_agents} agents x {net.d_in} inputs, the env has "
-                                     f"{env.n_agents} x {env.local_state_space}")
+                if net is not None and (net.n_agents != env.n_agents or net.d_in != width):
+                    raise ValueError(f"the {what} is built for {net.n_agents} agents x {net.d_in} inputs, {source} has "
+                                     f"{env.n_agents} x {width}")
             if critic is not None and critic.nout != 1:
                 raise ValueError("the critic must have one output")
             if obs_norm is not None:
                 obs_norm.check_networks(actor, critic)
+        if obstacle_inputs and self.controller is not None:
+            raise ValueError("the controllers read positions, not observations: they take no obstacle_inputs")
         self.actor, self.critic, self.obs_norm = actor, critic, obs_norm
+        self.input_field = obstacles if obstacle_inputs else None      # what feeds the networks `field.observe(env.z)`
         if shield is not None and getattr(shield, "env", None) is not env:
             raise ValueError("shield must be an ActionShield of this env")
         self.shield = shield
@@ -232,9 +245,9 @@ class Evaluator:
         if obstacles is not None:
             if getattr(obstacles, "env", None) is not env:
                 raise ValueError("obstacles must be an ObstacleField of this env")
-            if not self.safety:
+            if not self.safety and not obstacle_inputs:
                 raise ValueError("the obstacle tables are part of the safety tables: obstacles= needs safety=True")
-        self.obstacles = obstacles
+        self.obstacles = obstacles if self.safety else None             # (the field of the obstacle TABLES)
         self.obstacle_tables = None
         self.T = int(max_time_steps)
         self._rounds_run = 0
@@ -290,10 +303,11 @@ class Evaluator:
                 env.control(self.controller, out=st.actions[t])
                 env.step(st.actions[t], into=(st, t), execute=shield(st.actions[t], out=self._safe))
             return st
-        actor, critic, norm = self.actor, self.critic, self.obs_norm
+        actor, critic, norm, field = self.actor, self.critic, self.obs_norm, self.input_field
         st.begin()
         for t in range(self.T):                                                 # :69-94
-            z = env.z if norm is None else norm(env.z)                          # (the statistics are never updated here)
+            z = env.z if field is None else field.observe(env.z)                # raw -> obstacle columns -> normaliser
+            z = z if norm is None else norm(z)                                  # (the statistics are never updated here)
             if critic is not None:
                 critic.forward(z, out=st.values[t])
             actor.sample_action(z, env=env, act_out=st.actions[t])              # :78

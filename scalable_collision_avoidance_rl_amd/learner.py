@@ -35,6 +35,11 @@ N networks of a `BatchedMLP` are trained together by the HIP library (csrc/learn
   reward_norm= of both dronesim_rewnorm_update, dronesim_rewnorm_apply   a `RewardNormalizer` (reward_norm.py): the window is merged
                                        into the running discounted-return statistics, then the return scans read the rewards
                                        times ``1 / std(return)`` from a learner-owned buffer (default None)
+  obstacles= of both   dronesim_obstacle_observe, dronesim_obstacle_reward   an `ObstacleField` (obstacles.py): everything a network
+                                       reads is first given the field's obstacle columns (the networks' ``d_in`` is
+                                       ``field.obs_width``), ahead of ``obs_norm``, and ``obstacle_weight`` times the obstacle cost
+                                       of the observation after every step is taken off its reward, ahead of ``reward_norm``, both
+                                       into learner-owned buffers; ``train()`` also returns ``obstacle_cost [N]`` (default None)
   share= of BatchedAdam and both   dronesim_adam_step_shared, dronesim_kl_gate_shared, dronesim_mlp_tie   parameter sharing: a
                                        sharing map (`agent_groups`: None, ``"all"`` or a group id per agent) ties the networks of
                                        a group -- one set of weights, the gradient the mean of the members' per-agent gradients,
@@ -492,6 +497,8 @@ def _lambda_returns_ends(learner, storage, Vall, G, reward):
     _episode_ends(storage.done, storage.z_final, drone_env.DONE_RADIUS, M, learner.ends, learner.slot_t, learner.n_trunc,
                   learner.z_trunc)
     z_trunc = learner.z_trunc                                # (the kinds were decided on the RAW z_final: geometry)
+    if learner.obstacles is not None:
+        z_trunc = learner.obstacles.observe(z_trunc, out=learner._xo_trunc)
     if learner.obs_norm is not None:
         z_trunc = learner.obs_norm.norm(z_trunc, out=learner._xn_trunc)
     learner.critic.forward(z_trunc.view(M * E, N, -1), out=learner.V_trunc)
@@ -514,20 +521,70 @@ def _prepare_obs_norm(learner, storage):
     ring, and under ``time_limit="bootstrap"`` the terminal observations of the truncated ends."""
     import torch
     src = storage.z_pre if learner.lam is None else storage.z_all
-    learner._xn = torch.empty(tuple(src.shape), device=learner.critic.device)
+    dev, d_in = learner.critic.device, learner.critic.d_in   # (the networks' width: the storage's, plus the obstacle columns)
+    learner._xn = torch.empty(tuple(src.shape[:-1]) + (d_in,), device=dev)
     if learner.time_limit == "bootstrap":
-        learner._xn_trunc = torch.empty_like(learner.z_trunc)
+        learner._xn_trunc = torch.empty(tuple(learner.z_trunc.shape[:-1]) + (d_in,), device=dev)
+
+
+def _check_obstacle_inputs(obstacles, obstacle_weight, actor):
+    """``(field, weight)``: None and 0.0, or an `ObstacleField` whose ``obs_width`` is the networks' ``d_in`` and a finite weight
+    >= 0 of the obstacle cost."""
+    if obstacles is None:
+        if obstacle_weight != 0.0:
+            raise ValueError(f"obstacle_weight = {obstacle_weight!r} needs obstacles= (an ObstacleField)")
+        return None, 0.0
+    from .obstacles import check_weight
+    weight = check_weight(obstacle_weight)
+    width, N = getattr(obstacles, "obs_width", None), getattr(getattr(obstacles, "env", None), "n_agents", None)
+    if width is None or N is None:
+        raise ValueError(f"obstacles must be an ObstacleField, got {type(obstacles).__name__}")
+    if (actor.n_agents, actor.d_in) != (int(N), int(width)):
+        raise ValueError(f"with obstacles= the networks read the record plus the obstacle columns: {int(N)} agents x "
+                         f"field.obs_width = {int(width)} inputs, these read {actor.n_agents} x {actor.d_in}")
+    return obstacles, weight
+
+
+def _raw_width(learner):
+    """Floats per record of the storage this learner trains on: the networks' ``d_in``, less the obstacle columns."""
+    return learner.critic.d_in - (0 if learner.obstacles is None else 3 * learner.obstacles.m)
+
+
+def _prepare_obstacles(learner, storage, T, E, N):
+    """The learner's buffers of ``obstacles=`` (first call per shape): the augmented window, or with a ``lam`` the augmented ring,
+    under ``time_limit="bootstrap"`` the augmented truncated ends, the shaped reward, the weighted cost and its mean per agent."""
+    import torch
+    if getattr(storage, "env", None) is not learner.obstacles.env:
+        raise ValueError("with obstacles= the storage must be a RolloutStorage of the field's env")
+    dev, d_in = learner.critic.device, learner.critic.d_in
+    learner._xo = torch.empty((T if learner.lam is None else T + 1, E, N, d_in), device=dev)
+    if learner.time_limit == "bootstrap":
+        learner._xo_trunc = torch.empty(tuple(learner.z_trunc.shape[:-1]) + (d_in,), device=dev)
+    learner._rs = torch.empty(T, E, N, device=dev)
+    learner._oc = torch.empty(T, E, N, device=dev)
+    learner.obstacle_cost = torch.empty(N, device=dev)
 
 
 def _normalised(learner, storage, T):
-    """``(x, ring)``: what the networks read of this window -- the storage's own ``z_pre`` / ``z_all`` without an ``obs_norm``,
-    else their images under the normaliser's table as it stands (``x`` is the ring's first T slots)."""
-    if learner.obs_norm is None:
-        return storage.z_pre, (None if learner.lam is None else storage.z_all)
-    if learner.lam is None:
-        return learner.obs_norm.norm(storage.z_pre, out=learner._xn), None
-    ring = learner.obs_norm.norm(storage.z_all, out=learner._xn)
-    return ring[:T], ring
+    """``(x, ring)``: what the networks read of this window -- the storage's own ``z_pre`` / ``z_all`` without ``obstacles`` and
+    an ``obs_norm``; else first their images with the obstacle columns, then those under the normaliser's table as it stands
+    (``x`` is the ring's first T slots)."""
+    if learner.obstacles is None:
+        if learner.obs_norm is None:
+            return storage.z_pre, (None if learner.lam is None else storage.z_all)
+        if learner.lam is None:
+            return learner.obs_norm.norm(storage.z_pre, out=learner._xn), None
+        ring = learner.obs_norm.norm(storage.z_all, out=learner._xn)
+        return ring[:T], ring
+    seen = learner.obstacles.observe(storage.z_pre if learner.lam is None else storage.z_all, out=learner._xo)
+    if learner.obs_norm is not None:
+        seen = learner.obs_norm.norm(seen, out=learner._xn)
+    return (seen, None) if learner.lam is None else (seen[:T], seen)
+
+
+def _obs_norm_rows(learner, storage, T):
+    """What the statistics are fed after a call: the window's T E pre-step rows as the normaliser sees them."""
+    return storage.z_pre if learner.obstacles is None else learner._xo[:T]
 
 
 def _check_reward_norm(reward_norm, actor, share):
@@ -548,12 +605,18 @@ def _check_reward_norm(reward_norm, actor, share):
 def _normalised_reward(learner, storage):
     """What the return scans read: ``storage.reward`` itself without a ``reward_norm``; else the window is first merged into the
     running return statistics (unless ``update_reward_norm=False``) and then scaled into the learner's own ``_rn [T,E,N]`` --
-    ``storage.reward`` is never written."""
+    ``storage.reward`` is never written.  With ``obstacles`` the reward both of them see is the shaped one, in the learner's own
+    ``_rs [T,E,N]`` (`ObstacleField.shape_reward`); the weighted cost goes to ``_oc`` and its mean per agent to ``obstacle_cost``."""
+    reward = storage.reward
+    if learner.obstacles is not None:
+        import torch
+        reward = learner.obstacles.shape_reward(storage, learner.obstacle_weight, out=learner._rs, cost_out=learner._oc)
+        torch.mean(learner._oc.view(-1, learner._oc.shape[-1]), dim=0, out=learner.obstacle_cost)
     if learner.reward_norm is None:
-        return storage.reward
+        return reward
     if learner.update_reward_norm:
-        learner.reward_norm.update(storage.reward, storage.done)
-    return learner.reward_norm.norm(storage.reward, out=learner._rn)
+        learner.reward_norm.update(reward, storage.done)
+    return learner.reward_norm.norm(reward, out=learner._rn)
 
 
 MINIBATCH_ALIGN = 256               # every minibatch's block of a gathered buffer starts on this boundary (bytes)
@@ -662,11 +725,22 @@ class SA2CLearner:
     `Evaluator` and every logged statistic stay in raw units.  The critic's values (and G, and the advantage) are then in
     NORMALISED units.  ``train()`` also returns ``reward_scale [N]`` (float64, the scale this window was trained with).  A
     normaliser for another N raises ValueError, and so does, with ``share``, one whose statistics groups split a tied group
-    (``scope="team"`` always fits)."""
+    (``scope="team"`` always fits).
+
+    ``obstacles`` (default None: exactly the calls above, nothing more allocated) is an `ObstacleField` of the storage's env, for
+    obstacle-aware training; the networks' ``d_in`` must be ``field.obs_width`` (the record plus ``3 m`` obstacle columns), else
+    ValueError.  The order is raw -> obstacles -> normalisers.  ``train()`` first writes ``field.observe`` of ``z_pre`` (with a
+    ``lam``: of the ring) into a buffer of its own, ``_xo``, and THAT is what ``obs_norm`` and the networks read; under
+    ``time_limit="bootstrap"`` the end kinds are still decided on the RAW ``z_final`` and ``z_trunc`` is augmented (``_xo_trunc``)
+    before the normaliser and the critic.  ``field.shape_reward(storage, obstacle_weight)`` goes into ``_rs [T,E,N]`` (the
+    weighted cost into ``_oc``) and THAT is what ``reward_norm`` merges and scales and the return scans read; ``storage.reward``
+    is never written.  The statistics' update is fed the augmented ``z_pre``.  ``train()`` also returns ``obstacle_cost [N]``, the
+    window's mean weighted cost per agent, on the device.  ``obstacle_weight`` (finite, >= 0; 0 leaves the reward's bits) needs
+    ``obstacles``."""
 
     def __init__(self, actor, critic, gamma, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0, rows_per_chunk=None, lam=None,
                  time_limit="terminal", ent_coef=0.0, obs_norm=None, update_obs_norm=True, share=None, reward_norm=None,
-                 update_reward_norm=True):
+                 update_reward_norm=True, obstacles=None, obstacle_weight=0.0):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -682,6 +756,7 @@ class SA2CLearner:
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm, share=share)
         self.reward_norm = _check_reward_norm(reward_norm, actor, self.critic_opt.share)
         self.update_reward_norm = bool(update_reward_norm)
+        self.obstacles, self.obstacle_weight = _check_obstacle_inputs(obstacles, obstacle_weight, actor)
         self._shape = None
 
     def _prepare(self, storage):
@@ -693,7 +768,7 @@ class SA2CLearner:
             _prepare_ends(self, storage, T, E, N)
         if self._shape == (T, E, N):
             return
-        if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
+        if N != self.critic.n_agents or storage.z_pre.shape[-1] != _raw_width(self):
             raise ValueError("the storage's agents / observation width do not match the networks")
         if storage.actions is None:
             raise ValueError("the learner needs a storage with actions")
@@ -707,6 +782,8 @@ class SA2CLearner:
         self._actor_grad = GradientRunner(self.actor, T * E, self.rows_per_chunk)
         if self.ent_coef > 0:
             self._actor_grad._workspace("grad_ent")
+        if self.obstacles is not None:
+            _prepare_obstacles(self, storage, T, E, N)
         if self.obs_norm is not None:
             _prepare_obs_norm(self, storage)
         if self.reward_norm is not None:
@@ -753,13 +830,15 @@ class SA2CLearner:
     def _with_scale(self, out):
         if self.reward_norm is not None:
             out["reward_scale"] = self.reward_norm.scale
+        if self.obstacles is not None:
+            out["obstacle_cost"] = self.obstacle_cost
         return out
 
     def _update_obs_norm(self, storage):
         """``train()``'s last enqueued work: the window's T E pre-step rows into the statistics (ring slot T is the next window's
         slot 0 and is counted there)."""
         if self.obs_norm is not None and self.update_obs_norm:
-            self.obs_norm.update(storage.z_pre)
+            self.obs_norm.update(_obs_norm_rows(self, storage, self._shape[0]))
 
 
 class PPOLearner:
@@ -886,14 +965,18 @@ class PPOLearner:
     the window is merged into the running return statistics first, then scaled into the learner's ``_rn``, which step 1's scan
     reads in ``storage.reward``'s place (update first, then apply; ``storage.reward`` is never written).  G, the critic's values,
     the advantages and therefore ``vf_clip`` are then in NORMALISED units.  New output ``reward_scale [N]``.  With ``share`` the
-    statistics groups must keep tied agents together (ValueError otherwise)."""
+    statistics groups must keep tied agents together (ValueError otherwise).
+
+    ``obstacles`` / ``obstacle_weight`` as for `SA2CLearner` (default None: nothing above changes, nothing more allocated): the
+    window (or ring) and the truncated ends get the field's obstacle columns ahead of ``obs_norm``, the reward pays the weighted
+    obstacle cost ahead of ``reward_norm``; minibatches gather the augmented rows.  New output ``obstacle_cost [N]``."""
 
     BASELINES = ("once", "per_neighbour")
 
     def __init__(self, actor, critic, gamma, epochs=10, clip_eps=0.2, lr_actor=1e-3, lr_critic=1e-3, max_norm=10.0,
                  baseline="once", rows_per_chunk=None, lam=None, time_limit="terminal", ent_coef=0.0, normalize_advantage=False,
                  adv_eps=1e-8, minibatches=1, shuffle_seed=0, target_kl=None, vf_clip=None, obs_norm=None, update_obs_norm=True,
-                 share=None, reward_norm=None, update_reward_norm=True):
+                 share=None, reward_norm=None, update_reward_norm=True, obstacles=None, obstacle_weight=0.0):
         if critic.out_kind != 0 or critic.nout != 1:
             raise ValueError("the critic must be a BatchedMLP with out_kind 0 and one output")
         if actor.out_kind not in (1, 2):
@@ -924,6 +1007,7 @@ class PPOLearner:
         self.critic_opt = BatchedAdam(critic, lr=lr_critic, max_norm=max_norm, share=share)
         self.reward_norm = _check_reward_norm(reward_norm, actor, self.critic_opt.share)
         self.update_reward_norm = bool(update_reward_norm)
+        self.obstacles, self.obstacle_weight = _check_obstacle_inputs(obstacles, obstacle_weight, actor)
         self._shape = None
 
     def _prepare(self, storage):
@@ -937,7 +1021,7 @@ class PPOLearner:
             _prepare_ends(self, storage, T, E, N)
         if self._shape == (T, E, N):
             return
-        if N != self.critic.n_agents or storage.z_pre.shape[-1] != self.critic.d_in:
+        if N != self.critic.n_agents or storage.z_pre.shape[-1] != _raw_width(self):
             raise ValueError("the storage's agents / observation width do not match the networks")
         K = self.minibatches
         if (T * E) % K:
@@ -974,6 +1058,8 @@ class PPOLearner:
         if self.target_kl is not None:
             self.active = torch.ones(N, dtype=torch.int32, device=dev)
             self.actor_steps = torch.zeros(N, dtype=torch.int32, device=dev)
+        if self.obstacles is not None:
+            _prepare_obstacles(self, storage, T, E, N)
         if self.obs_norm is not None:
             _prepare_obs_norm(self, storage)
         if self.reward_norm is not None:
@@ -994,7 +1080,7 @@ class PPOLearner:
         import torch
         dev, M = self.critic.device, rows // K
         self.perm = torch.zeros(rows, dtype=torch.int32, device=dev)
-        d = storage.z_pre.shape[-1]
+        d = self.actor.d_in                                              # (the storage's width, plus the obstacle columns)
         shapes = ((N, d), (N, 2), (N,), (N,), (N,))                      # z_pre, actions, logp_old, adv, G
         if self.vf_clip is not None:
             shapes += ((N,),)                                            # and step 2's V, the clipped value loss's v_old
@@ -1126,7 +1212,9 @@ class PPOLearner:
             out = self._outputs()
         if self.obs_norm is not None and self.update_obs_norm:
             # the last enqueued work: the T E pre-step rows only (ring slot T is the next window's slot 0 and is counted there)
-            self.obs_norm.update(storage.z_pre)
+            self.obs_norm.update(_obs_norm_rows(self, storage, T))
         if self.reward_norm is not None:
             out["reward_scale"] = self.reward_norm.scale
+        if self.obstacles is not None:
+            out["obstacle_cost"] = self.obstacle_cost
         return out

@@ -2,9 +2,13 @@
 
 The reference draws ``n_obstacles`` discs ``[x, y, r]`` and only paints them (drone_env.py:155-169: "never read by dynamics or
 reward"), and so does `drones`.  This module makes them real in the layers that handle safety, beside the step -- the step kernel,
-the reward and the networks' input do not change:
+the does not change, and the reward and the networks' input change only where `observe` / `shape_reward` are asked for:
 
-  ObstacleField.sense            `dronesim_obstacle_sense` (csrc/obstacles.hip): per agent, the ``m`` nearest discs within its range,
+  ObstacleField.observe          `dronesim_obstacle_observe`: every record with its obstacle columns -- the list below as ``(p.x, p.y,
+                                 r)`` per slot -- the input of obstacle-aware networks (``obs_width`` floats per agent)
+  ObstacleField.shape_reward     `dronesim_obstacle_reward`: the obstacle cost of the observation after every stored step, taken
+                                 off its reward; ``SA2CLearner`` / ``PPOLearner(obstacles=field, obstacle_weight=w)`` use both
+  ObstacleField.sense           `dronesim_obstacle_sense` (csrc/obstacles.hip): per agent, the ``m`` nearest discs within its range,
                                  from its OWN observation (row 0 is ``x_i - xF_i``, so the record holds the position)
   ActionShield(obstacles=field)  one half-plane per listed disc in the projection (shield.py, csrc/shield.hip)
   ObstacleField.episode_safety   `dronesim_episode_obstacle_safety`: clearance and hit tables of every env's first episode from a
@@ -13,7 +17,9 @@ the reward and the networks' input do not change:
 
 The rule (include/dronesim.h states it for the kernels, tests/obstacle_ref.py in float64): ``x = z[0] + xF[i][0]``,
 ``y = z[1] + xF[i][1]``; to disc ``o``: ``p = o.xy - (x, y)``, ``d = |p|``, ``gap = d - radius[i] - o.r``.  A disc is in range where
-``gap <= sense[i]``; the list holds the ``m`` smallest gaps, ties to the lower id; ``gap_min`` / ``hit`` cover ALL discs.
+``gap <= sense[i]``; the list holds the ``m`` smallest gaps, ties to the lower id; ``gap_min`` / ``hit`` cover ALL discs.  The
+obstacle cost is the reference's collision term with a disc in the neighbour's place: over ALL discs ``9.99e3`` where ``gap <= 0``,
+``log(sense[i] / gap)`` where ``0 < gap <= sense[i]``, 0 otherwise, times a weight (tests/obstacle_obs_ref.py restates it).
 
 One list ``[M,3]`` serves all envs.  ``env.reset(renew_obstacles=True)`` (the reference's default) redraws ``env.obstacles``; a
 field follows only through ``field.set(env.obstacles)``.
@@ -56,6 +62,14 @@ def check_m(m):
     if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= MAX_SENSE:
         raise ValueError(f"m (list slots per agent) must be an integer in 1..{MAX_SENSE}, got {m!r}")
     return int(m)
+
+
+def check_weight(weight):
+    """The obstacle cost's weight as a float: a finite number >= 0 that float32 holds, else ValueError."""
+    import numbers
+    if isinstance(weight, bool) or not isinstance(weight, numbers.Real) or not 0.0 <= float(weight) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"the obstacle weight must be a finite number >= 0, got {weight!r}")
+    return float(weight)
 
 
 def place_obstacles(grid, n, seed=0, keep_clear=None, clearance=0.0, centres=None):
@@ -208,6 +222,8 @@ class ObstacleField:
         self._obs_view = self._obs[:self.M]
         self._sense = None if sense is None else torch.tensor(sense, dtype=torch.float32, device=env.device)
         self.orow = self.oid = self.gap_min = self.hit = None
+        self.cost = None                                       # `observe(cost=...)`'s plane of its last call
+        self._x, self._cost = {}, {}                           # `observe`'s owned buffers, per leading shape
         self.set(obs)
 
     @property
@@ -256,6 +272,103 @@ class ObstacleField:
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _native.check(rc, "dronesim_obstacle_sense")
         return self.orow, self.oid
+
+    @property
+    def obs_width(self):
+        """Floats per agent of `observe`'s output: the record's ``(k+1)c`` plus three per list slot."""
+        return (int(self.env.k_closest) + 1) * int(self.env.c) + 3 * self.m
+
+    def _geometry(self):
+        env = self.env
+        N, k1, c = int(env.n_agents), int(env.k_closest) + 1, int(env.c)
+        if not 1 <= N <= _MAX_AGENTS or not 1 <= k1 <= _MAX_K + 1 or c not in (2, 5):
+            raise ValueError(f"the obstacle entries need N in 1..{_MAX_AGENTS}, k + 1 in 1..{_MAX_K + 1} and c in (2, 5), got N = {N}, "
+                             f"k + 1 = {k1}, c = {c}")
+        return N, k1, c
+
+    def _env_tensors(self, dev):
+        import torch
+        env, rng = self.env, self.sense_range
+        N = int(env.n_agents)
+        for name, x, shape in (("xF", env._xF, (N, 2)), ("radius", env._radius, (N,)), ("sense", rng, (N,))):
+            _tensor_check(name, x, torch.float32, shape, dev)
+        return env._xF, env._radius, rng
+
+    def observe(self, z=None, out=None, cost=None):
+        """`dronesim_obstacle_observe`: the networks' input with the obstacle columns.  ``z [..., N, (k+1)c]`` (default ``env.z``;
+        the leading dims are rows: a `RolloutStorage` ring ``z_all``, the learner's ``z_trunc``, one step) gives
+        ``x [..., N, (k+1)c + 3m]``: the record's own bits, then slot ``s`` of `sense`'s list as ``(p.x, p.y, r)``, ``(0, 0, 0)`` where
+        it is empty.  Returns ``out`` (a contiguous float32 tensor of that shape), or an owned buffer that is reused for every later
+        input of this shape.  ``cost=weight`` (finite, >= 0) also fills the attribute ``cost [..., N]``, ``weight`` times the
+        obstacle cost of every record (include/dronesim.h has the rule).  One launch; capturable after an eager warm-up."""
+        import torch
+        from . import _native
+        N, k1, c = self._geometry()
+        d = k1 * c
+        z = self.env.z if z is None else z
+        weight = 0.0 if cost is None else check_weight(cost)
+        dev = torch.device(self.env.device)
+        if not torch.is_tensor(z) or z.dim() < 2 or tuple(z.shape[-2:]) != (N, d):
+            raise ValueError(f"z must be a [..., N, (k+1)c] = [..., {N}, {d}] tensor, got {tuple(getattr(z, 'shape', ()))}")
+        lead = tuple(int(n) for n in z.shape[:-2])
+        _tensor_check("z", z, torch.float32, lead + (N, d), dev)
+        if out is not None:
+            _tensor_check("out", out, torch.float32, lead + (N, self.obs_width), dev)
+        xF, radius, rng = self._env_tensors(dev)
+        lib = _native.lib()
+        if out is None:
+            out = self._x.get(lead)
+            if out is None:
+                out = self._x[lead] = torch.empty(lead + (N, self.obs_width), dtype=torch.float32, device=dev)
+        cost_out = None
+        if cost is not None:
+            cost_out = self._cost.get(lead)
+            if cost_out is None:
+                cost_out = self._cost[lead] = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+            self.cost = cost_out
+        R = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        with torch.cuda.device(dev):
+            rc = lib.dronesim_obstacle_observe(z.data_ptr(), xF.data_ptr(), radius.data_ptr(), rng.data_ptr(), self._obs.data_ptr(),
+                                               R, N, k1, c, self.M, self.m, out.data_ptr(),
+                                               None if cost_out is None else cost_out.data_ptr(), weight,
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_obstacle_observe")
+        return out
+
+    def shape_reward(self, storage, weight, out=None, cost_out=None):
+        """`dronesim_obstacle_reward` on a `RolloutStorage` of this env: ``reward[t] - weight * cost(observation after step t)``, the
+        observation being ``storage.z_final[t]`` where ``done[t]`` (auto_reset) and the post-step ring slot otherwise -- the
+        substitution of ``storage.next_z()``.  Returns ``out [T,E,N]`` (default: a new tensor; ``out=storage.reward`` shapes in
+        place -- ``storage.reward`` is never written otherwise); ``cost_out [T,E,N]`` receives the weighted cost."""
+        import torch
+        from . import _native
+        N, k1, c = self._geometry()
+        weight = check_weight(weight)
+        env = self.env
+        if getattr(storage, "env", None) is not env:
+            raise ValueError("storage must be a RolloutStorage of this field's env")
+        dev = torch.device(env.device)
+        T, E = (int(n) for n in storage.reward.shape[:2])
+        _tensor_check("storage.reward", storage.reward, torch.float32, (T, E, N), dev)
+        _tensor_check("storage.z", storage.z, torch.float32, (T, E, N, k1 * c), dev)
+        _tensor_check("storage.done", storage.done, torch.uint8, (T, E), dev)
+        if storage.z_final is not None:
+            _tensor_check("storage.z_final", storage.z_final, torch.float32, (T, E, N, k1 * c), dev)
+        for name, t in (("out", out), ("cost_out", cost_out)):
+            if t is not None:
+                _tensor_check(name, t, torch.float32, (T, E, N), dev)
+        xF, radius, rng = self._env_tensors(dev)
+        lib = _native.lib()
+        if out is None:
+            out = torch.empty(T, E, N, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.dronesim_obstacle_reward(storage.z.data_ptr(), None if storage.z_final is None else storage.z_final.data_ptr(),
+                                              storage.done.data_ptr(), storage.reward.data_ptr(), xF.data_ptr(), radius.data_ptr(),
+                                              rng.data_ptr(), self._obs.data_ptr(), T, E, N, k1, c, self.M, weight, out.data_ptr(),
+                                              None if cost_out is None else cost_out.data_ptr(),
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _native.check(rc, "dronesim_obstacle_reward")
+        return out
 
     def episode_safety(self, storage, out=None):
         """The obstacle tables of a `RolloutStorage` window of this env (`episode_obstacle_safety`): from its stored post-step

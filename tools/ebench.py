@@ -11,17 +11,22 @@
      `dronesim_control` and `dronesim_shield_totals` in the same session, and the control -> shield -> step(execute=) chain;
   5. `--obstacles` (alone): for M in {16, 64} discs, m = 2: the sense launch; sense + `dronesim_action_shield_obstacles` next to the
      plain `dronesim_action_shield` on the same observation; `dronesim_episode_obstacle_safety` next to `dronesim_episode_safety`
-     on the same window; and the control -> sense -> shield -> step(execute=) chain next to the plain chain.
+     on the same window; and the control -> sense -> shield -> step(execute=) chain next to the plain chain;
+  6. `--obstacle-obs` (alone): for M in {16, 64} discs, m = 2: `dronesim_obstacle_observe` on one step next to the sense launch and
+     on a T-step ring; `dronesim_obstacle_reward` on the window next to `dronesim_episode_obstacle_safety` on it; and
+     ``SA2CLearner.train`` with and without ``obstacles=`` on a 16-step window.
 
     python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
     python tools/ebench.py --shield [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/shield_ebench.jsonl]
     python tools/ebench.py --obstacles [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/obstacles_ebench.jsonl]
+    python tools/ebench.py --obstacle-obs [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/obstacle_obs_ebench.jsonl]
 Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -220,6 +225,77 @@ def obstacles(T, E, N, k, c, emit, counts=(16, 64), m=2):
         emit(dict(what="control -> sense -> shield -> step(execute=)", us=us, us_min=lo, yardstick_us=us_chain, ratio=us / us_chain, **rec))
 
 
+def obstacle_obs(T, E, N, k, c, emit, counts=(16, 64), m=2, train_T=16):
+    """Obstacle-aware training's two kernels next to their yardsticks, on `obstacles`' env state and discs: `observe` on one step
+    next to `dronesim_obstacle_sense`; `observe` on the T + 1 slots of a ring; `shape_reward` on the T-step window next to
+    `dronesim_episode_obstacle_safety` on it; and ``SA2CLearner.train`` on a ``train_T``-step window with and without the option
+    (the same hidden sizes; the option's networks read d + 3m inputs)."""
+    from scalable_collision_avoidance_rl_amd.learner import SA2CLearner
+    from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, episode_obstacle_safety, place_obstacles
+    from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
+    G = 28.0 if N == 64 else max(6.0, 0.45 * N)
+    dev, k1 = "cuda:0", k + 1
+    d = k1 * c
+    env = drones(N, 0, [G, G], "O", k_closest=k, deltas=np.ones(N), simplify_zstate=c == 2, n_envs=E, seed=0, auto_reset=True)
+    act = env.control("proportional")
+    for _ in range(20):
+        env.step(env.control("proportional", out=act))
+    base = dict(E=E, N=N, k=k, c=c, m=m)
+    # the window: the env's own positions jittered per slot, so that the lists are as full as on the env's observation
+    ring = env.z.unsqueeze(0).repeat(T + 1, 1, 1, 1)
+    ring[..., :2] += torch.randn(T + 1, E, N, 2, device=dev) * 0.3
+    done = torch.zeros(T, E, dtype=torch.uint8, device=dev); done[-1] = 1
+    reward = -torch.rand(T, E, N, device=dev)
+    window = SimpleNamespace(env=env, z=ring[1:], z_final=None, done=done, reward=reward)
+
+    def networks(d_in):
+        gp = torch.Generator().manual_seed(0)
+        rw = lambda *s: (torch.rand(*s, generator=gp) * 2 - 1) * 0.2
+        wa = [rw(N, d_in, 48), rw(N, 48), rw(N, 48, 48), rw(N, 48), rw(N, 48, 16), rw(N, 16)]
+        wc = [rw(N, d_in, 32), rw(N, 32), rw(N, 32, 32), rw(N, 32), rw(N, 32, 1), rw(N, 1)]
+        return BatchedMLP(*wa, 1, 1, device=dev, seed=7), BatchedMLP(*wc, 0, 0, device=dev)
+
+    st = RolloutStorage(env, train_T, actions=True)
+    actor, critic = networks(d)
+    st.begin()
+    for t in range(train_T):
+        actor.sample_action(env.z, env=env, act_out=st.actions[t])
+        env.step(st.actions[t], into=(st, t))
+    plain = SA2CLearner(actor, critic, 0.99)
+    us_train, lo_train = gtime(lambda: plain.train(st), calls=1, reps=5)
+    emit(dict(what="SA2CLearner.train (yardstick)", T=train_T, d_in=d, us=us_train, us_min=lo_train, **base))
+    for M in counts:
+        discs = place_obstacles([G, G], 2 * M, seed=M, keep_clear=env.end_points.reshape(N, 2), clearance=0.3)[:M]
+        assert discs.shape[0] == M
+        field = ObstacleField(env, discs, m=m)
+        rec = dict(base, M=M)
+        w = field.obs_width
+        us_sense, lo_sense = gtime(lambda: field.sense())
+        emit(dict(what="dronesim_obstacle_sense (yardstick)", us=us_sense, us_min=lo_sense, **rec))
+        us, lo = gtime(lambda: field.observe())
+        emit(dict(what="dronesim_obstacle_observe, one step", us=us, us_min=lo, yardstick_us=us_sense, ratio=us / us_sense,
+                  bytes_written=4 * w * E * N, write_tb_s=4 * w * E * N / 1e6 / us, slots_filled=float((field.oid >= 0).float().mean()), **rec))
+        us, lo = gtime(lambda: field.observe(cost=0.01))
+        emit(dict(what="dronesim_obstacle_observe with cost, one step", us=us, us_min=lo, yardstick_us=us_sense, ratio=us / us_sense, **rec))
+        x = torch.empty(T + 1, E, N, w, device=dev)
+        us, lo = gtime(lambda: field.observe(ring, out=x), calls=2)
+        emit(dict(what="dronesim_obstacle_observe, ring", T=T, us=us, us_min=lo, bytes_written=4 * w * (T + 1) * E * N,
+                  write_tb_s=4 * w * (T + 1) * E * N / 1e6 / us, gaps_per_ns=(T + 1) * E * N * M / 1e3 / us, **rec))
+        del x
+        out_o = episode_obstacle_safety(ring[1:], done, env._xF, env._radius, field.device_obstacles, c)
+        us_tab, lo_tab = gtime(lambda: episode_obstacle_safety(ring[1:], done, env._xF, env._radius, field.device_obstacles, c, out=out_o), calls=2)
+        emit(dict(what="dronesim_episode_obstacle_safety (yardstick)", T=T, us=us_tab, us_min=lo_tab, **rec))
+        shaped, cost = torch.empty_like(reward), torch.empty_like(reward)
+        us, lo = gtime(lambda: field.shape_reward(window, 0.01, out=shaped, cost_out=cost), calls=2)
+        emit(dict(what="dronesim_obstacle_reward", T=T, us=us, us_min=lo, yardstick_us=us_tab, ratio=us / us_tab,
+                  gaps_per_ns=T * E * N * M / 1e3 / us, paying_share=float((cost > 0).float().mean()), **rec))
+        actor_o, critic_o = networks(w)
+        learner = SA2CLearner(actor_o, critic_o, 0.99, obstacles=field, obstacle_weight=0.01)
+        us, lo = gtime(lambda: learner.train(st), calls=1, reps=5)
+        emit(dict(what="SA2CLearner.train(obstacles=field)", T=train_T, d_in=w, us=us, us_min=lo, yardstick_us=us_train,
+                  ratio=us / us_train, **rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=200)
@@ -231,6 +307,7 @@ def main():
     ap.add_argument("--skip-round", action="store_true")
     ap.add_argument("--shield", action="store_true", help="only the action shield next to the step launch")
     ap.add_argument("--obstacles", action="store_true", help="only the obstacle layer next to its yardsticks")
+    ap.add_argument("--obstacle-obs", action="store_true", help="only the obstacle columns and the obstacle cost next to their yardsticks")
     ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     a = ap.parse_args()
 
@@ -247,6 +324,9 @@ def main():
         return
     if a.obstacles:
         obstacles(a.T, a.envs, a.agents, a.k, a.c, emit)
+        return
+    if a.obstacle_obs:
+        obstacle_obs(a.T, a.envs, a.agents, a.k, a.c, emit)
         return
     done, us_eval = kernels(a.T, a.envs, a.agents, emit)
     safety(a.T, a.envs, a.agents, a.k, a.c, done, us_eval, emit)
