@@ -7,8 +7,10 @@ the memory and the stream.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
+import re
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # DRONESIM_LIB lets a developer A/B an alternative build of the SAME HIP library (no other backend exists)
@@ -17,37 +19,6 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dronesim.h")
 # the float64 verification variant (test infrastructure) is a library of its own: the product library exports the product only
 VERIFY_LIB_PATH = os.environ.get("DRONESIM_VERIFY_LIB") or os.path.join(_PKG, "libdronesim_verify.so")
 VERIFY_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dronesim_verify.h")
-VERIFY_SYMBOLS = ("dronesim_step_f64", "dronesim_observe_f64", "dronesim_verify_last_error")
-
-OK, EINVAL, EUNSUPPORTED, ELAUNCH = 0, -1, -2, -3
-CONTROL_PROPORTIONAL, CONTROL_GRADIENT = 0, 1
-MAX_K = 8
-MAX_AGENTS = 1024
-MAX_OBSTACLES = 1024                 # DRONESIM_MAX_OBSTACLES
-MAX_SENSE = 4                        # DRONESIM_MAX_SENSE
-
-# every symbol include/dronesim.h declares (tests check the .so exports all of them)
-STATS_SCRATCH_DOUBLES = 769          # DRONESIM_STATS_SCRATCH_DOUBLES (include/dronesim.h)
-EPISODE_REDUCE_DOUBLES = 8           # DRONESIM_EPISODE_REDUCE_DOUBLES
-SYMBOLS = ("dronesim_step", "dronesim_observe", "dronesim_reset", "dronesim_rollout", "dronesim_control", "dronesim_returns", "dronesim_advantage", "dronesim_episode_stats", "dronesim_mlp_forward", "dronesim_mlp_forward_bf16",
-           "dronesim_step_ex", "dronesim_step_call", "dronesim_rollout_ex", "dronesim_rollout_random", "dronesim_rollout_control", "dronesim_reset_ex", "dronesim_reset_observe", "dronesim_episode_reduce",
-           "dronesim_mlp_forward_bf16x3", "dronesim_mlp_forward_f16x2", "dronesim_mlp_bf16x3_stages", "dronesim_mlp_rt_blocks", "dronesim_mlp_rt16_blocks", "dronesim_mlp_forward_f16x2_rt",
-           "dronesim_mlp_grad_workspace", "dronesim_mlp_grad", "dronesim_adam_step",
-           "dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo",
-           "dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
-           "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent",
-           "dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
-           "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip",
-           "dronesim_adam_step_shared", "dronesim_kl_gate_shared", "dronesim_mlp_tie",
-           "dronesim_episode_eval", "dronesim_histogram_i32", "dronesim_episode_safety", "dronesim_lambda_returns", "dronesim_episode_ends", "dronesim_lambda_returns_ends",
-           "dronesim_row_permutation", "dronesim_gather_rows",
-           "dronesim_obsnorm_workspace", "dronesim_obsnorm_update", "dronesim_obsnorm_apply",
-           "dronesim_rewnorm_workspace", "dronesim_rewnorm_update", "dronesim_rewnorm_apply",
-           "dronesim_action_shield", "dronesim_shield_totals",
-           "dronesim_obstacle_sense", "dronesim_action_shield_obstacles", "dronesim_episode_obstacle_safety",
-           "dronesim_obstacle_observe", "dronesim_obstacle_reward",
-           "dronesim_last_error", "dronesim_error_string", "dronesim_version")
-
 
 class DroneParams(C.Structure):
     """Mirror of `struct DroneParams` (include/dronesim.h)."""
@@ -112,156 +83,156 @@ class DroneSimError(RuntimeError):
         self.code = code
 
 
-_lib = None
+# ---- the C ABI is stated once, in the headers: names, signatures and constants are read from them ------------------------------------
+Signature = collections.namedtuple("Signature", "restype argtypes stream")     # stream: the last parameter is `void *stream`
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+            "float": C.c_float, "double": C.c_double}
+# pointers that cross the ABI as a ctypes mirror; every other pointer is a raw address (c_void_p) -- DroneStepCall and
+# DroneEpisodeAcc among them: the step path passes those as plain integers
+_MIRRORS = {c.__name__: C.POINTER(c) for c in (DroneParams, DroneEpisodeCtl, DroneMlp, DroneMlpBf16, DroneParamsF64)}
+_MIRRORS["size_t"] = C.POINTER(C.c_size_t)
+_RESTYPES = {"int": C.c_int, "const char *": C.c_char_p}
+_DECLARATION = re.compile(r"([^;{}()]*?)\b(dronesim_\w+)\s*\(([^;{}]*)\)\s*;")
+# (a define whose value is an expression, such as DRONESIM_GATHER_MAX_ROW_BYTES (1 << 24), is not a constant of this table: it is
+# skipped here, and asking for one that is missing fails by name in _constant below)
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+DRONESIM_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", re.M)
+
+
+def _ctype(param, name):
+    """The ctypes class of one parameter `[const] type [*[const]]... [name]`; a type this table does not know is an error."""
+    words = param.replace("*", " * ").split()
+    base = [w for w in words[:words.index("*")] if w != "const"] if "*" in words else [w for w in words if w != "const"][:-1]
+    if len(base) != 1 or not re.fullmatch(r"[\w *]+", param):
+        raise ValueError(f"{name}: cannot read the parameter '{param.strip()}'")
+    if "*" in words:
+        return _MIRRORS.get(base[0], C.c_void_p) if words.count("*") == 1 else C.c_void_p
+    if base[0] not in _SCALARS:
+        raise ValueError(f"{name}: unknown parameter type '{base[0]}' in '{param.strip()}'")
+    return _SCALARS[base[0]]
+
+
+def parse_header(text):
+    """(constants, signatures) of a header's text: its integer `#define DRONESIM_*`s without the prefix, and a `Signature` per
+    declared `dronesim_*` function, in header order.  Never guesses: a declaration it cannot read raises with the entry's name."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2)) for m in _DEFINE.finditer(text)}
+    signatures = {}
+    for m in _DECLARATION.finditer(re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)):
+        ret, name, params = " ".join(m.group(1).replace("*", " * ").split()), m.group(2), " ".join(m.group(3).split())
+        if ret not in _RESTYPES:
+            raise ValueError(f"{name}: cannot read the declaration (return type '{ret}')")
+        params = [] if params == "void" else params.split(",")
+        signatures[name] = Signature(_RESTYPES[ret], [_ctype(p, name) for p in params],
+                                     bool(params) and params[-1].replace(" ", "") == "void*stream")
+    return constants, signatures
+
+
+def _read_header(path):
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not found: the bindings are read from the header that declares the C ABI")
+    with open(path) as f:
+        return parse_header(f.read())
+
+
+# The package needs the repository's include/ directory next to it: dronesim.h is read at import (names, signatures, constants).
+# dronesim_verify.h is test infrastructure: without it the package still imports, VERIFY_SYMBOLS is empty and verify_lib() raises.
+_CONSTANTS, SIGNATURES = _read_header(HEADER_PATH)
+VERIFY_SIGNATURES = _read_header(VERIFY_HEADER_PATH)[1] if os.path.exists(VERIFY_HEADER_PATH) else {}
+# every symbol the headers declare (tests check the libraries export all of them)
+SYMBOLS, VERIFY_SYMBOLS = tuple(SIGNATURES), tuple(VERIFY_SIGNATURES)
+
+
+def _constant(name):
+    if name not in _CONSTANTS:
+        raise ImportError(f"{HEADER_PATH}: no `#define DRONESIM_{name} <integer>` (an integer literal, bare or in parentheses)")
+    return _CONSTANTS[name]
+
+
+(OK, EINVAL, EUNSUPPORTED, ELAUNCH, CONTROL_PROPORTIONAL, CONTROL_GRADIENT, MAX_K, MAX_AGENTS, MAX_OBSTACLES, MAX_SENSE,
+ STATS_SCRATCH_DOUBLES, EPISODE_REDUCE_DOUBLES) = map(_constant, (
+     "OK", "EINVAL", "EUNSUPPORTED", "ELAUNCH", "CONTROL_PROPORTIONAL", "CONTROL_GRADIENT", "MAX_K", "MAX_AGENTS", "MAX_OBSTACLES",
+     "MAX_SENSE", "STATS_SCRATCH_DOUBLES", "EPISODE_REDUCE_DOUBLES"))
+
+
+def _load(path, signatures, hint):
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not found: the HIP extension is not built. {hint} There is no CPU fallback for this path.")
+    # torch first: the library's HIP calls must bind to the HIP runtime torch ships and initialises (the buffers and
+    # streams handed across the ABI live there); loaded on its own, the library would pull in the system's copy and
+    # see no context ("no ROCm-capable device is detected" at the first launch)
+    import torch  # noqa: F401
+    L = C.CDLL(path)
+    for name, sig in signatures.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = sig.restype, sig.argtypes
+    return L
+
+
+_lib = _vlib = None
 
 
 def lib():
     """Load libdronesim.so (built by __graft_entry__.build() / `make -C <pkg>/csrc`)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} not found: the HIP extension is not built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
-            "scalable_collision_avoidance_rl_amd/csrc`) with hipcc for gfx950. "
-            "There is no CPU fallback for this path.")
-    # torch first: the library's HIP calls must bind to the HIP runtime torch ships and initialises (the buffers and
-    # streams handed across the ABI live there); loaded on its own, the library would pull in the system's copy and
-    # see no context ("no ROCm-capable device is detected" at the first launch)
-    import torch  # noqa: F401
-    L = C.CDLL(LIB_PATH)
-    vp, i32, u64, i64, f32 = C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_float
-    P = C.POINTER(DroneParams)
-    L.dronesim_step.argtypes = [P] + [vp] * 10 + [i32, vp]
-    L.dronesim_observe.argtypes = [P] + [vp] * 8 + [i32, vp]
-    L.dronesim_rollout.argtypes = [P] + [vp] * 10 + [i32, i32, vp]
-    L.dronesim_control.argtypes = [P, i32, vp, vp, f32, i32, vp]
-    L.dronesim_control.restype = C.c_int
-    L.dronesim_episode_stats.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
-    L.dronesim_returns.argtypes = [vp, vp, f32, vp, i32, i32, i32, vp]
-    L.dronesim_advantage.argtypes = [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp]
-    L.dronesim_returns.restype = L.dronesim_advantage.restype = C.c_int
-    L.dronesim_lambda_returns.argtypes = [vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]
-    L.dronesim_lambda_returns.restype = C.c_int
-    L.dronesim_episode_ends.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
-    L.dronesim_lambda_returns_ends.argtypes = [vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, vp]
-    L.dronesim_episode_ends.restype = L.dronesim_lambda_returns_ends.restype = C.c_int
-    L.dronesim_mlp_forward.argtypes = [C.POINTER(DroneMlp), vp, vp, vp, vp, u64, u64, i64, vp, vp, i32, vp]
-    L.dronesim_mlp_forward.restype = C.c_int
-    L.dronesim_mlp_forward_bf16.argtypes = [C.POINTER(DroneMlpBf16), vp, vp, vp, vp, u64, u64, i64, vp, vp, i32, vp]
-    L.dronesim_mlp_forward_bf16.restype = C.c_int
-    L.dronesim_mlp_forward_bf16x3.argtypes = L.dronesim_mlp_forward_bf16.argtypes
-    L.dronesim_mlp_forward_bf16x3.restype = C.c_int
-    L.dronesim_mlp_forward_f16x2.argtypes = L.dronesim_mlp_forward_bf16.argtypes
-    L.dronesim_mlp_forward_f16x2.restype = C.c_int
-    L.dronesim_mlp_bf16x3_stages.argtypes = [C.c_int, C.c_int]
-    L.dronesim_mlp_rt_blocks.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.dronesim_mlp_rt16_blocks.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.dronesim_mlp_forward_f16x2_rt.argtypes = L.dronesim_mlp_forward_bf16.argtypes
-    L.dronesim_mlp_forward_f16x2_rt.restype = C.c_int
-    L.dronesim_mlp_bf16x3_stages.restype = C.c_int
-    PM = C.POINTER(DroneMlp)
-    L.dronesim_mlp_grad_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_mlp_grad.argtypes = [PM, vp, i32, f32, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    L.dronesim_adam_step.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp]
-    L.dronesim_mlp_grad_workspace.restype = L.dronesim_mlp_grad.restype = L.dronesim_adam_step.restype = C.c_int
-    L.dronesim_neighbour_advantage.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]
-    L.dronesim_mlp_grad_ppo_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_mlp_logp.argtypes = [PM, vp, i32, vp, vp, i32, vp, C.c_size_t, vp]
-    L.dronesim_mlp_grad_ppo.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    for name in ("dronesim_neighbour_advantage", "dronesim_mlp_grad_ppo_workspace", "dronesim_mlp_logp", "dronesim_mlp_grad_ppo"):
-        getattr(L, name).restype = C.c_int
-    L.dronesim_standardize_workspace.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_standardize.argtypes = [vp, vp, vp, i32, i32, f32, vp, C.c_size_t, vp]
-    L.dronesim_mlp_grad_ent_workspace.argtypes = L.dronesim_mlp_grad_ppo_ent_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_mlp_grad_ent.argtypes = [PM, vp, i32, f32, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    L.dronesim_mlp_grad_ppo_ent.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    for name in ("dronesim_standardize_workspace", "dronesim_standardize", "dronesim_mlp_grad_ent_workspace", "dronesim_mlp_grad_ent",
-                 "dronesim_mlp_grad_ppo_ent_workspace", "dronesim_mlp_grad_ppo_ent"):
-        getattr(L, name).restype = C.c_int
-    L.dronesim_mlp_grad_ppo_gated_workspace.argtypes = L.dronesim_mlp_grad_vclip_workspace.argtypes = [PM, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_mlp_grad_ppo_gated.argtypes = [PM, vp, i32, f32, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    L.dronesim_kl_gate.argtypes = [vp, f32, vp, vp, i32, i32, vp]
-    L.dronesim_adam_step_gated.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp]
-    L.dronesim_mlp_grad_vclip.argtypes = [PM, vp, i32, f32, vp, vp, f32, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    for name in ("dronesim_mlp_grad_ppo_gated_workspace", "dronesim_mlp_grad_ppo_gated", "dronesim_kl_gate", "dronesim_adam_step_gated",
-                 "dronesim_mlp_grad_vclip_workspace", "dronesim_mlp_grad_vclip"):
-        getattr(L, name).restype = C.c_int
-    # parameter sharing: the siblings' arguments, then active (or NULL) where it is new, group_ptr, members, n_groups, stream
-    L.dronesim_adam_step_shared.argtypes = [PM, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, i32, vp]
-    L.dronesim_kl_gate_shared.argtypes = [vp, f32, vp, vp, i32, i32, vp, vp, i32, vp]
-    L.dronesim_mlp_tie.argtypes = [PM, vp, vp, i32, vp]
-    L.dronesim_adam_step_shared.restype = L.dronesim_kl_gate_shared.restype = L.dronesim_mlp_tie.restype = C.c_int
-    L.dronesim_episode_eval.argtypes = [vp] * 5 + [f32] + [vp] * 8 + [i32, i32, i32, vp]
-    L.dronesim_histogram_i32.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    L.dronesim_episode_safety.argtypes = [vp] * 7 + [f32] + [i32] * 5 + [vp] * 7 + [vp]
-    L.dronesim_episode_eval.restype = L.dronesim_histogram_i32.restype = L.dronesim_episode_safety.restype = C.c_int
-    # (the four host arrays of dronesim_gather_rows are ctypes arrays: c_void_p / c_int64 times n_arrays)
-    L.dronesim_row_permutation.argtypes = [i32, u64, vp, vp, vp]
-    L.dronesim_gather_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.dronesim_row_permutation.restype = L.dronesim_gather_rows.restype = C.c_int
-    L.dronesim_obsnorm_workspace.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_obsnorm_update.argtypes = [vp, i32, i32, vp, vp, C.c_double, vp, C.c_size_t, vp]
-    L.dronesim_obsnorm_apply.argtypes = [vp, vp, i32, i32, vp, f32, vp]
-    L.dronesim_obsnorm_workspace.restype = L.dronesim_obsnorm_update.restype = L.dronesim_obsnorm_apply.restype = C.c_int
-    L.dronesim_rewnorm_workspace.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
-    L.dronesim_rewnorm_update.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, i32, vp, vp, vp, C.c_double, vp, C.c_size_t, vp]
-    L.dronesim_rewnorm_apply.argtypes = [vp, vp, i32, i32, i32, vp, f32, vp]
-    L.dronesim_rewnorm_workspace.restype = L.dronesim_rewnorm_update.restype = L.dronesim_rewnorm_apply.restype = C.c_int
-    L.dronesim_action_shield.argtypes = [vp] * 4 + [f32] * 4 + [i32] * 4 + [vp] * 4
-    L.dronesim_shield_totals.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    L.dronesim_action_shield.restype = L.dronesim_shield_totals.restype = C.c_int
-    L.dronesim_obstacle_sense.argtypes = [vp] * 5 + [i32] * 6 + [vp] * 4 + [vp]
-    L.dronesim_action_shield_obstacles.argtypes = [vp] * 4 + [f32] * 4 + [i32] * 4 + [vp] * 3 + [vp, vp, i32, i32, f32, vp]
-    L.dronesim_episode_obstacle_safety.argtypes = [vp] * 6 + [i32] * 6 + [vp] * 5 + [vp]
-    L.dronesim_obstacle_sense.restype = L.dronesim_action_shield_obstacles.restype = L.dronesim_episode_obstacle_safety.restype = C.c_int
-    L.dronesim_obstacle_observe.argtypes = [vp] * 5 + [i32] * 6 + [vp, vp, f32, vp]
-    L.dronesim_obstacle_reward.argtypes = [vp] * 8 + [i32] * 6 + [f32, vp, vp, vp]
-    L.dronesim_obstacle_observe.restype = L.dronesim_obstacle_reward.restype = C.c_int
-    L.dronesim_reset.argtypes = [P, i32, i32, f32, u64, i64] + [vp] * 6 + [i32, vp]
-    PC = C.POINTER(DroneEpisodeCtl)
-    L.dronesim_step_ex.argtypes = [P, PC] + [vp] * 10 + [i32, vp]
-    L.dronesim_step_call.argtypes = [vp, vp, vp]      # (plain integers: no per-call ctypes objects)
-    L.dronesim_step_call.restype = C.c_int
-    L.dronesim_rollout_ex.argtypes = [P, PC] + [vp] * 10 + [i32, i32, vp]
-    L.dronesim_rollout_random.argtypes = [P, PC] + [vp] * 10 + [i32, i32, vp]
-    L.dronesim_rollout_control.argtypes = [P, PC, i32, f32] + [vp] * 10 + [i32, i32, vp]
-    L.dronesim_reset_ex.argtypes = [P, PC] + [vp] * 5 + [i32, vp]
-    L.dronesim_reset_observe.argtypes = [P, PC] + [vp] * 7 + [i32, vp]
-    L.dronesim_episode_reduce.argtypes = [vp, i32, vp, vp]
-    for name in ("dronesim_step", "dronesim_observe", "dronesim_rollout", "dronesim_reset", "dronesim_step_ex",
-                 "dronesim_rollout_ex", "dronesim_rollout_random", "dronesim_rollout_control", "dronesim_reset_ex", "dronesim_reset_observe",
-                 "dronesim_episode_reduce", "dronesim_episode_stats", "dronesim_version"):
-        getattr(L, name).restype = C.c_int
-    L.dronesim_last_error.restype = C.c_char_p
-    L.dronesim_error_string.restype = C.c_char_p
-    L.dronesim_error_string.argtypes = [C.c_int]
-    _lib = L
-    return L
-
-
-_vlib = None
+    if _lib is None:
+        _lib = _load(LIB_PATH, SIGNATURES, "Run `python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
+                     "scalable_collision_avoidance_rl_amd/csrc`) with hipcc for gfx950.")
+    return _lib
 
 
 def verify_lib():
     """Load libdronesim_verify.so (include/dronesim_verify.h): the float64 verification variant, test infrastructure."""
     global _vlib
-    if _vlib is not None:
-        return _vlib
-    if not os.path.exists(VERIFY_LIB_PATH):
-        raise ImportError(f"{VERIFY_LIB_PATH} not found: run `make -C scalable_collision_avoidance_rl_amd/csrc` "
-                          "(hipcc, gfx950).  There is no CPU fallback.")
-    import torch  # noqa: F401  (same HIP runtime as the product library, see lib())
-    L = C.CDLL(VERIFY_LIB_PATH)
-    vp, i32 = C.c_void_p, C.c_int
-    P64 = C.POINTER(DroneParamsF64)
-    L.dronesim_step_f64.argtypes = [P64] + [vp] * 10 + [i32, vp]
-    L.dronesim_observe_f64.argtypes = [P64] + [vp] * 7 + [i32, vp]
-    L.dronesim_step_f64.restype = L.dronesim_observe_f64.restype = C.c_int
-    L.dronesim_verify_last_error.restype = C.c_char_p
-    _vlib = L
-    return L
+    if _vlib is None:
+        if not VERIFY_SIGNATURES:
+            _read_header(VERIFY_HEADER_PATH)            # (ImportError naming the missing header)
+        _vlib = _load(VERIFY_LIB_PATH, VERIFY_SIGNATURES, "Run `make -C scalable_collision_avoidance_rl_amd/csrc` (hipcc, gfx950).")
+    return _vlib
+
+
+def check_tensor(name, x, dtype, shape, device):
+    """ValueError unless `x` is what an entry point may read through a raw address: a contiguous tensor of this dtype and shape on
+    this device.  Nothing here touches a device."""
+    import torch
+    if not torch.is_tensor(x):
+        raise ValueError(f"{name} must be a tensor, got {type(x).__name__}")
+    if x.dtype != dtype or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {x.dtype} {tuple(x.shape)}"
+                         f"{'' if x.is_contiguous() else ' (not contiguous)'}")
+    if x.device != torch.device(device):
+        raise ValueError(f"{name} must live on the device {device}, got {x.device}")
+
+
+def call(name, *args, device=None):
+    """The one way a wrapper launches an entry point of libdronesim.so: a tensor goes as its data_ptr(), None as NULL, anything else
+    as it is; the call is made on `device` (default: that of the first tensor argument) and, where the header's last parameter is
+    `void *stream`, on that device's current stream; a non-zero return raises DroneSimError under the entry's name.
+    Two per-step hot paths keep marshalling of their own, tuned call by call: the step / reset / rollout launches of drone_env.py
+    (DroneStepCall: no per-call ctypes objects) and the policy forward of policies.py."""
+    import torch
+    Tensor, ptrs = torch.Tensor, []
+    for a in args:
+        if isinstance(a, Tensor):
+            if device is None:
+                device = a.device
+            a = a.data_ptr()
+        ptrs.append(a)
+    fn = getattr(lib(), name)
+    if SIGNATURES[name].stream:
+        if device is None:
+            raise ValueError(f"{name}: no tensor argument and no device= to launch on")
+        with torch.cuda.device(device):
+            rc = fn(*ptrs, torch.cuda.current_stream().cuda_stream)
+    else:       # the size and count queries are host code: no device, no stream, usable without a GPU
+        rc = fn(*ptrs)
+    check(rc, name)
+
+
+def workspace(name, *args):
+    """The byte count a `*_workspace` query writes through its last parameter."""
+    n = C.c_size_t(0)
+    call(name, *args, C.byref(n))                       # (no stream parameter: a pure host call)
+    return int(n.value)
 
 
 def check_verify(rc, where):

@@ -29,10 +29,19 @@ constexpr bool kPairParallelStep = false;
 #endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "dronesim.h"
 
 // records the thread-local error string returned by dronesim_last_error() and returns `code`
 __attribute__((visibility("hidden"))) int dronesim_fail(int code, const char *msg);
+
+// DRONESIM_EINVAL with the message "<where>: <what>" (where: the entry point's own name; dronesim_fail copies the string)
+inline int fail_at(const char *where, const char *what)
+{
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", where, what);
+    return dronesim_fail(DRONESIM_EINVAL, msg);
+}
 
 // the end of an entry point that has enqueued its kernels: DRONESIM_ELAUNCH with HIP's text if a launch was refused
 inline int dronesim_launched()

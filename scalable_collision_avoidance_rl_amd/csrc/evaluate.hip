@@ -10,8 +10,8 @@
 // seen gives its length.  reward, true_reward and V are read once, G is written once.  The per-env pieces (collisions, the mean
 // over agents in ascending agent order) are a second small launch: no float atomics anywhere, bit-identical run to run.
 // dronesim_episode_safety (below) reduces the same first episode from the stored observations: clearance, goal distance, arrival.
+#include "record_entry.hpp"
 #include "scan_common.hpp"
-#include "dronesim.h"
 
 namespace {
 
@@ -317,14 +317,6 @@ __global__ void __launch_bounds__(256) safety_env_kernel(const int32_t *__restri
     if (ep_arrived) ep_arrived[e] = outside ? 0 : 1;
 }
 
-// Host: the widest load both rows of every record allow (see above); `addresses`: the OR of the bases of z and z_final.
-inline int safety_load_width(int k1, int c, uintptr_t addresses)
-{
-    if (c != 2) return 1;
-    if ((k1 % 2) == 0 && (addresses & 15u) == 0) return 4;
-    return (addresses & 7u) == 0 ? 2 : 1;
-}
-
 }   // namespace
 
 extern "C" {
@@ -334,12 +326,13 @@ int dronesim_episode_eval(const float *reward, const float *true_reward, const i
                           double *agent_return, double *agent_true_return, double *ep_return, double *ep_true_return,
                           float *G, double *mean_adv, int T, int E, int N, void *stream)
 {
-    if (!reward || !true_reward || !done || !ep_len || T < 0 || E < 0 || N < 1)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_eval: bad argument");
-    if (ep_collisions && !n_coll) return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_eval: ep_collisions needs n_coll");
-    if (mean_adv && !V) return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_eval: mean_adv needs V");
+    const char *where = "dronesim_episode_eval";
+    if (!reward || !true_reward || !done || !ep_len) return fail_at(where, "NULL reward / true_reward / done / ep_len");
+    if (T < 0 || E < 0 || N < 1) return fail_at(where, "T or E < 0, or N < 1");
+    if (ep_collisions && !n_coll) return fail_at(where, "ep_collisions needs n_coll");
+    if (mean_adv && !V) return fail_at(where, "mean_adv needs V");
     if ((ep_return && !agent_return) || (ep_true_return && !agent_true_return))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_eval: ep_return / ep_true_return need agent_return / agent_true_return");
+        return fail_at(where, "ep_return / ep_true_return need agent_return / agent_true_return");
     if (E == 0) return DRONESIM_OK;
     const size_t cols = (size_t)E * N;
     EvalArgs a;
@@ -370,18 +363,19 @@ int dronesim_episode_safety(const float *z, const int32_t *nbr, const float *z_f
                             int32_t *ep_len, float *min_clearance, float *goal_dist_final, int32_t *arrive_step,
                             float *ep_min_clearance, float *ep_goal_dist_max, uint8_t *ep_arrived, void *stream)
 {
-    if (!z || !nbr || !done || !radius || !delta || !ep_len || T < 0 || E < 0 || N < 1 || N > 1024 || k1 < 2 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_safety: bad argument");
-    if (done_radius != done_radius) return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_safety: done_radius is NaN");
-    if ((z_final == nullptr) != (nbr_final == nullptr))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_safety: z_final and nbr_final go together");
+    const char *where = "dronesim_episode_safety";
+    if (!z || !nbr || !done || !radius || !delta || !ep_len) return fail_at(where, "NULL z / nbr / done / radius / delta / ep_len");
+    if (T < 0 || E < 0) return fail_at(where, "T or E < 0");
+    int rc = check_records(where, N, k1, 2, INT_MAX, c);
+    if (rc != DRONESIM_OK) return rc;
+    if (done_radius != done_radius) return fail_at(where, "done_radius is NaN");
+    if ((z_final == nullptr) != (nbr_final == nullptr)) return fail_at(where, "z_final and nbr_final go together");
     if ((ep_min_clearance && !min_clearance) || ((ep_goal_dist_max || ep_arrived) && !goal_dist_final))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_safety: ep_min_clearance needs min_clearance, ep_goal_dist_max / "
-                                              "ep_arrived need goal_dist_final");
+        return fail_at(where, "ep_min_clearance needs min_clearance, ep_goal_dist_max / ep_arrived need goal_dist_final");
     if (E == 0) return DRONESIM_OK;
     const size_t cols = (size_t)E * N;
     const SafetyOut o{ep_len, arrive_step, min_clearance, goal_dist_final};
-    const int W = safety_load_width(k1, c, reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(z_final));
+    const int W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(z_final));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((cols + 255) / 256));
     if (W == 4) {
@@ -394,7 +388,7 @@ int dronesim_episode_safety(const float *z, const int32_t *nbr, const float *z_f
         const SafetyScan<1> p{z, z_final, nbr, nbr_final, done, radius, delta, done_radius, N, k1, c};
         hipLaunchKernelGGL(episode_safety_kernel<1>, grid, dim3(256), 0, s, p, o, T, E);
     }
-    const int rc = dronesim_launched();
+    rc = dronesim_launched();
     if (rc != DRONESIM_OK || !(ep_min_clearance || ep_goal_dist_max || ep_arrived)) return rc;
     hipLaunchKernelGGL(safety_env_kernel, dim3((unsigned)((2 * (size_t)E + 255) / 256)), dim3(256), 0, s, ep_len, min_clearance,
                        goal_dist_final, done_radius, ep_min_clearance, ep_goal_dist_max, ep_arrived, E, N);
@@ -405,7 +399,7 @@ int dronesim_histogram_i32(const int32_t *values, const uint8_t *valid, int E, i
                            void *stream)
 {
     if (!values || !counts || E < 0 || n_bins < 1 || n_bins > (1 << 24))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_histogram_i32: bad argument");
+        return fail_at("dronesim_histogram_i32", "NULL values / counts, E < 0 or n_bins outside 1..2^24");
     hipLaunchKernelGGL(histogram_kernel, dim3(1), dim3(kHistThreads), 0, static_cast<hipStream_t>(stream), values, valid, E, n_bins,
                        reinterpret_cast<long long *>(counts), accumulate);
     return dronesim_launched();

@@ -942,13 +942,6 @@ int run_chain(const ChainJob &j)
     return dronesim_launched();
 }
 
-int fail_at(const char *where, const char *what)
-{
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", where, what);
-    return dronesim_fail(DRONESIM_EINVAL, msg);
-}
-
 int check_mlp(const DroneMlp *m, const char *where)
 {
     if (!m) return fail_at(where, "NULL DroneMlp");

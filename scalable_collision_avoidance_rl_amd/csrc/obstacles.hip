@@ -11,12 +11,12 @@
 // One thread per record, consecutive threads on consecutive records.  The disc loop is wave-uniform: the workgroup stages the list
 // once in LDS (12 bytes a disc, 12 KB at M = 1024) and every lane then reads the same LDS address, which broadcasts -- no lane
 // gathers from global memory.  A thread past the end stays (the staging has a barrier, the scan's flag fetch is a wave operation).
+#include "record_entry.hpp"
 #include "scan_common.hpp"
 
 namespace {
 
 constexpr int kMaxObstacles = DRONESIM_MAX_OBSTACLES;
-constexpr int kMaxSense = DRONESIM_MAX_SENSE;                   // list slots per record
 
 typedef float ob_f4 __attribute__((ext_vector_type(4)));
 typedef float ob_f2 __attribute__((ext_vector_type(2)));
@@ -57,11 +57,11 @@ struct SenseArgs {
     int32_t *oid;
     float *gap_min;
     uint8_t *hit;
-    int N, stride, M, W;                                       // stride: floats per record (k1 c); W: shield_load_width's rule
+    int N, stride, M, W;                                       // stride: floats per record (k1 c); W: record_load_width's rule
     unsigned long long records;
 };
 
-// Row 0 of a record, W floats wide (sense_load_width's rule; wave-uniform)
+// Row 0 of a record, W floats wide (record_load_width's rule; wave-uniform)
 __device__ __forceinline__ void load_row0(const float *rec, int W, float &zx, float &zy)
 {
     if (W == 4) {                                              // k1 even, c = 2, 16-byte aligned: row 0 with row 1
@@ -134,14 +134,6 @@ __global__ void __launch_bounds__(256) obstacle_sense_kernel(const SenseArgs a)
     }
     if (a.gap_min) a.gap_min[r] = gm;
     if (a.hit) a.hit[r] = gm <= 0.0f ? 1 : 0;
-}
-
-// Host: shield_load_width's rule (shield.hip) for row 0 of the records of z
-inline int sense_load_width(int k1, int c, uintptr_t z)
-{
-    if (c != 2) return 1;
-    if ((k1 % 2) == 0 && (z & 15u) == 0) return 4;
-    return (z & 7u) == 0 ? 2 : 1;
 }
 
 // ---- dronesim_obstacle_observe, dronesim_obstacle_reward ---------------------------------------------------------------------------
@@ -286,8 +278,6 @@ __global__ void __launch_bounds__(256) obstacle_reward_kernel(const RewardArgs a
     }
 }
 
-inline bool obstacle_weight_ok(float weight) { return weight >= 0.0f && weight <= 3.402823466e38f; }   // (finite, not NaN, >= 0)
-
 // ---- dronesim_episode_obstacle_safety ---------------------------------------------------------------------------------------------
 // SafetyScan's scan (evaluate.hip) with the disc loop in its step: the same backward driver, the same restart at `done`, the same
 // rare-path load of z_final.  A thread needs floats 0, 1 of record [t][e][i] only -- 8 bytes, so the staged load is 8 bytes wide
@@ -405,15 +395,16 @@ int dronesim_obstacle_sense(const float *z, const float *xF, const float *radius
                             int E, int N, int k1, int c, int M, int m, float *orow, int32_t *oid, float *gap_min, uint8_t *hit,
                             void *stream)
 {
-    if (!z || !xF || !radius || !sense || !orow || !oid) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: NULL z / xF / radius / sense / orow / oid");
-    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: E < 0, N outside 1..1024, k1 outside 1..9 or c not in {2, 5}");
-    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: M outside 0..1024, or NULL obstacles with M > 0");
-    if (m < 1 || m > kMaxSense) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_sense: m outside 1..4");
-    if (E == 0) return DRONESIM_OK;
+    const char *where = "dronesim_obstacle_sense";
+    if (!z || !xF || !radius || !sense || !orow || !oid) return fail_at(where, "NULL z / xF / radius / sense / orow / oid");
+    if (E < 0) return fail_at(where, "E < 0");
+    int rc = check_records(where, N, k1, 1, DRONESIM_MAX_K + 1, c);
+    if (rc == DRONESIM_OK) rc = check_discs(where, M, obstacles);
+    if (rc == DRONESIM_OK) rc = check_slots(where, m);
+    if (rc != DRONESIM_OK || E == 0) return rc;
     SenseArgs a;
     a.z = z; a.xF = xF; a.radius = radius; a.sense = sense; a.obstacles = obstacles; a.orow = orow; a.oid = oid; a.gap_min = gap_min; a.hit = hit;
-    a.N = N; a.stride = k1 * c; a.M = M; a.W = sense_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    a.N = N; a.stride = k1 * c; a.M = M; a.W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
     a.records = (unsigned long long)E * (unsigned long long)N;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.records + 255) / 256));
@@ -427,16 +418,17 @@ int dronesim_obstacle_sense(const float *z, const float *xF, const float *radius
 int dronesim_obstacle_observe(const float *z, const float *xF, const float *radius, const float *sense, const float *obstacles,
                               int R, int N, int k1, int c, int M, int m, float *x_out, float *cost_out, float weight, void *stream)
 {
-    if (!z || !xF || !radius || !sense || !x_out) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: NULL z / xF / radius / sense / x_out");
-    if (R < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: R < 0, N outside 1..1024, k1 outside 1..9 or c not in {2, 5}");
-    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: M outside 0..1024, or NULL obstacles with M > 0");
-    if (m < 1 || m > kMaxSense) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: m outside 1..4");
-    if (!obstacle_weight_ok(weight)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_observe: weight must be finite and >= 0");
-    if (R == 0) return DRONESIM_OK;
+    const char *where = "dronesim_obstacle_observe";
+    if (!z || !xF || !radius || !sense || !x_out) return fail_at(where, "NULL z / xF / radius / sense / x_out");
+    if (R < 0) return fail_at(where, "R < 0");
+    int rc = check_records(where, N, k1, 1, DRONESIM_MAX_K + 1, c);
+    if (rc == DRONESIM_OK) rc = check_discs(where, M, obstacles);
+    if (rc == DRONESIM_OK) rc = check_slots(where, m);
+    if (rc == DRONESIM_OK) rc = check_weight(where, weight);
+    if (rc != DRONESIM_OK || R == 0) return rc;
     ObserveArgs a;
     a.z = z; a.xF = xF; a.radius = radius; a.sense = sense; a.obstacles = obstacles; a.x_out = x_out; a.cost = cost_out; a.weight = weight;
-    a.N = N; a.stride = k1 * c; a.M = M; a.W = sense_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    a.N = N; a.stride = k1 * c; a.M = M; a.W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
     a.OW = (reinterpret_cast<uintptr_t>(x_out) & 15u) == 0 ? 4 : 1;
     a.records = (unsigned long long)R * (unsigned long long)N;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -458,18 +450,19 @@ int dronesim_obstacle_reward(const float *z_post, const float *z_final, const ui
                              const float *radius, const float *sense, const float *obstacles, int T, int E, int N, int k1, int c, int M,
                              float weight, float *reward_out, float *cost_out, void *stream)
 {
+    const char *where = "dronesim_obstacle_reward";
     if (!z_post || !done || !reward || !xF || !radius || !sense || !reward_out)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: NULL z_post / done / reward / xF / radius / sense / reward_out");
-    if (T < 0 || E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: T or E < 0, N outside 1..1024, k1 outside 1..9 or c not in {2, 5}");
-    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: M outside 0..1024, or NULL obstacles with M > 0");
-    if (!obstacle_weight_ok(weight)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_obstacle_reward: weight must be finite and >= 0");
-    if (T == 0 || E == 0) return DRONESIM_OK;
+        return fail_at(where, "NULL z_post / done / reward / xF / radius / sense / reward_out");
+    if (T < 0 || E < 0) return fail_at(where, "T or E < 0");
+    int rc = check_records(where, N, k1, 1, DRONESIM_MAX_K + 1, c);
+    if (rc == DRONESIM_OK) rc = check_discs(where, M, obstacles);
+    if (rc == DRONESIM_OK) rc = check_weight(where, weight);
+    if (rc != DRONESIM_OK || T == 0 || E == 0) return rc;
     RewardArgs a;
     a.z_post = z_post; a.z_final = z_final; a.done = done; a.reward = reward; a.xF = xF; a.radius = radius; a.sense = sense;
     a.obstacles = obstacles; a.reward_out = reward_out; a.cost = cost_out; a.weight = weight;
     a.N = N; a.stride = k1 * c; a.M = M;
-    a.W = sense_load_width(k1, c, reinterpret_cast<uintptr_t>(z_post) | reinterpret_cast<uintptr_t>(z_final));
+    a.W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z_post) | reinterpret_cast<uintptr_t>(z_final));
     a.records = (unsigned long long)T * (unsigned long long)E * (unsigned long long)N;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(obstacle_reward_kernel, dim3((unsigned)((a.records + 255) / 256)), dim3(256), 0, s, a);
@@ -481,27 +474,28 @@ int dronesim_episode_obstacle_safety(const float *z, const float *z_final, const
                                      float *min_obstacle_gap, int32_t *obstacle_hit_steps, float *ep_min_obstacle_gap,
                                      int32_t *ep_obstacle_hit_steps, void *stream)
 {
-    if (T < 0 || E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 1 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: T or E < 0, N outside 1..1024, k1 < 1 or c not in {2, 5}");
-    if (M < 0 || M > kMaxObstacles || (M > 0 && !obstacles))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: M outside 0..1024, or NULL obstacles with M > 0");
+    const char *where = "dronesim_episode_obstacle_safety";
+    if (T < 0 || E < 0) return fail_at(where, "T or E < 0");
+    int rc = check_records(where, N, k1, 1, INT_MAX, c);
+    if (rc == DRONESIM_OK) rc = check_discs(where, M, obstacles);
+    if (rc != DRONESIM_OK) return rc;
     if ((ep_min_obstacle_gap && !min_obstacle_gap) || (ep_obstacle_hit_steps && !obstacle_hit_steps))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: a per-env table needs the per-agent one it reduces");
+        return fail_at(where, "a per-env table needs the per-agent one it reduces");
     if (E == 0) return DRONESIM_OK;                            // (an empty window has no addresses: checked before the pointers)
-    if (!xF || !radius || !ep_len || (T > 0 && (!z || !done)))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_episode_obstacle_safety: NULL z / done / xF / radius / ep_len");
+    if (!xF || !radius || !ep_len || (T > 0 && (!z || !done))) return fail_at(where, "NULL z / done / xF / radius / ep_len");
     const size_t cols = (size_t)E * N;
-    const uintptr_t bases = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(z_final);
+    // a thread reads floats 0, 1 of a record: the scan has no 16-byte variant, a rule's 4 is served by the 8-byte one
+    const int W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(z_final));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((cols + 255) / 256));
-    if (c == 2 && (bases & 7u) == 0) {
+    if (W >= 2) {
         const ObstacleScan<2> p{z, z_final, done, xF, radius, nullptr, N, k1 * c, M};
         hipLaunchKernelGGL(episode_obstacle_kernel<2>, grid, dim3(256), 0, s, p, obstacles, ep_len, min_obstacle_gap, obstacle_hit_steps, T, E);
     } else {
         const ObstacleScan<1> p{z, z_final, done, xF, radius, nullptr, N, k1 * c, M};
         hipLaunchKernelGGL(episode_obstacle_kernel<1>, grid, dim3(256), 0, s, p, obstacles, ep_len, min_obstacle_gap, obstacle_hit_steps, T, E);
     }
-    const int rc = dronesim_launched();
+    rc = dronesim_launched();
     if (rc != DRONESIM_OK || !(ep_min_obstacle_gap || ep_obstacle_hit_steps)) return rc;
     hipLaunchKernelGGL(obstacle_env_kernel, dim3((unsigned)((2 * (size_t)E + 255) / 256)), dim3(256), 0, s, ep_len, min_obstacle_gap,
                        obstacle_hit_steps, ep_min_obstacle_gap, ep_obstacle_hit_steps, E, N);

@@ -22,7 +22,7 @@
 // obstacles.hip) behind the neighbour slots: the set-up and the solve are device functions templated on the capacity of the
 // constraint set (12 and 16), so both entries run ONE solver and the plain entry keeps its bits.
 // dronesim_shield_totals folds the per-call planes into per-agent running totals in a fixed order, without float atomics.
-#include "common.hpp"
+#include "record_entry.hpp"
 
 namespace {
 
@@ -249,14 +249,6 @@ __global__ void __launch_bounds__(256) action_shield_obstacles_kernel(const Shie
     shield_solve_store(a, r, ux, uy, kShieldBox + a.k1 - 1, ob.m, ax, ay, b);
 }
 
-// Host: episode_safety_kernel's width rule (evaluate.hip) for the records of z alone
-inline int shield_load_width(int k1, int c, uintptr_t z)
-{
-    if (c != 2) return 1;
-    if ((k1 % 2) == 0 && (z & 15u) == 0) return 4;
-    return (z & 7u) == 0 ? 2 : 1;
-}
-
 // Per-agent running totals of the planes [E][N].  A workgroup of 1024 lanes owns 4 adjacent agents: lane t holds agent t % 4 of
 // the tile and the envs t / 4, t / 4 + 256, ... in ascending order (a row of the tile is 4 bytes of `intervened` and 16 of
 // `correction`; narrow tiles, because one plane is small -- 1.3 MB at 64 agents x 4096 envs -- and the launch is bound by how many
@@ -318,6 +310,34 @@ __global__ void __launch_bounds__(kTotalsThreads) shield_totals_kernel(const uin
     }
 }
 
+// Host: the arguments of both shield entries, validated in ONE order and marshalled.  ob: nullptr for the plain entry; for the
+// obstacle entry its list as the caller gave it, rate_dt still holding obstacle_rate -- divided by dt here, behind the checks.  The
+// obstacle entry's own checks stand between the shared ones, so they are made here, where the order is stated once.
+int shield_args(const char *where, const float *z, const int32_t *nbr, const float *act, const float *radius, float rate, float margin,
+                float u_max, float dt, int E, int N, int k1, int c, float *act_out, uint8_t *intervened, float *correction,
+                ShieldObstacles *ob, ShieldArgs &a)
+{
+    if (!z || !nbr || !act || !radius || !act_out) return fail_at(where, "NULL z / nbr / act / radius / act_out");
+    if (ob && (!ob->orow || !ob->oid)) return fail_at(where, "NULL orow / oid");
+    if (E < 0) return fail_at(where, "E < 0");
+    int rc = check_records(where, N, k1, 2, DRONESIM_MAX_K + 1, c);
+    if (rc == DRONESIM_OK && ob) rc = check_slots(where, ob->m);
+    if (rc == DRONESIM_OK && ob) rc = check_discs(where, ob->M, nullptr, false);  // (the kernel reads the sensed rows, not the list)
+    if (rc != DRONESIM_OK) return rc;
+    if (!(rate > 0.0f && rate <= 0.5f)) return fail_at(where, "rate must be in (0, 0.5]");
+    if (ob && !(ob->rate_dt > 0.0f && ob->rate_dt <= 1.0f)) return fail_at(where, "obstacle_rate must be in (0, 1]");
+    if (!(margin >= 0.0f) || !(margin < __builtin_inff())) return fail_at(where, "margin must be finite and >= 0");
+    if (!(u_max > 0.0f)) return fail_at(where, "u_max must be > 0 (+inf: no box; not NaN)");
+    if (!(dt > 0.0f) || !(dt < __builtin_inff())) return fail_at(where, "dt must be finite and > 0");
+    a.z = z; a.nbr = nbr; a.act = act; a.radius = radius; a.act_out = act_out; a.intervened = intervened; a.correction = correction;
+    a.rate_dt = rate / dt; a.margin = margin; a.u_max = u_max;
+    a.N = N; a.k1 = k1; a.c = c;
+    a.act8 = ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(act_out)) & 7u) == 0 ? 1 : 0;
+    a.records = (unsigned long long)E * (unsigned long long)N;
+    if (ob) ob->rate_dt /= dt;
+    return DRONESIM_OK;
+}
+
 }   // namespace
 
 extern "C" {
@@ -326,21 +346,11 @@ int dronesim_action_shield(const float *z, const int32_t *nbr, const float *act,
                            float u_max, float dt, int E, int N, int k1, int c, float *act_out, uint8_t *intervened,
                            float *correction, void *stream)
 {
-    if (!z || !nbr || !act || !radius || !act_out) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield: NULL z / nbr / act / radius / act_out");
-    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 2 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield: E < 0, N outside 1..1024, k1 outside 2..9 or c not in {2, 5}");
-    if (!(rate > 0.0f && rate <= 0.5f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield: rate must be in (0, 0.5]");
-    if (!(margin >= 0.0f) || !(margin < __builtin_inff())) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield: margin must be finite and >= 0");
-    if (!(u_max > 0.0f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield: u_max must be > 0 (+inf: no box; not NaN)");
-    if (!(dt > 0.0f) || !(dt < __builtin_inff())) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield: dt must be finite and > 0");
-    if (E == 0) return DRONESIM_OK;
     ShieldArgs a;
-    a.z = z; a.nbr = nbr; a.act = act; a.radius = radius; a.act_out = act_out; a.intervened = intervened; a.correction = correction;
-    a.rate_dt = rate / dt; a.margin = margin; a.u_max = u_max;
-    a.N = N; a.k1 = k1; a.c = c;
-    a.act8 = ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(act_out)) & 7u) == 0 ? 1 : 0;
-    a.records = (unsigned long long)E * (unsigned long long)N;
-    const int W = shield_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    const int rc = shield_args("dronesim_action_shield", z, nbr, act, radius, rate, margin, u_max, dt, E, N, k1, c, act_out, intervened,
+                               correction, nullptr, a);
+    if (rc != DRONESIM_OK || E == 0) return rc;
+    const int W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.records + 255) / 256));
     if (W == 4) hipLaunchKernelGGL(action_shield_kernel<4>, grid, dim3(256), 0, s, a);
@@ -354,26 +364,12 @@ int dronesim_action_shield_obstacles(const float *z, const int32_t *nbr, const f
                                      float *correction, const float *orow, const int32_t *oid, int m, int M, float obstacle_rate,
                                      void *stream)
 {
-    if (!z || !nbr || !act || !radius || !act_out || !orow || !oid)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: NULL z / nbr / act / radius / act_out / orow / oid");
-    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS || k1 < 2 || k1 > DRONESIM_MAX_K + 1 || (c != 2 && c != 5))
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: E < 0, N outside 1..1024, k1 outside 2..9 or c not in {2, 5}");
-    if (m < 1 || m > DRONESIM_MAX_SENSE || M < 0 || M > DRONESIM_MAX_OBSTACLES)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: m outside 1..4 or M outside 0..1024");
-    if (!(rate > 0.0f && rate <= 0.5f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: rate must be in (0, 0.5]");
-    if (!(obstacle_rate > 0.0f && obstacle_rate <= 1.0f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: obstacle_rate must be in (0, 1]");
-    if (!(margin >= 0.0f) || !(margin < __builtin_inff())) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: margin must be finite and >= 0");
-    if (!(u_max > 0.0f)) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: u_max must be > 0 (+inf: no box; not NaN)");
-    if (!(dt > 0.0f) || !(dt < __builtin_inff())) return dronesim_fail(DRONESIM_EINVAL, "dronesim_action_shield_obstacles: dt must be finite and > 0");
-    if (E == 0) return DRONESIM_OK;
+    ShieldObstacles ob{orow, oid, obstacle_rate, m, M};
     ShieldArgs a;
-    a.z = z; a.nbr = nbr; a.act = act; a.radius = radius; a.act_out = act_out; a.intervened = intervened; a.correction = correction;
-    a.rate_dt = rate / dt; a.margin = margin; a.u_max = u_max;
-    a.N = N; a.k1 = k1; a.c = c;
-    a.act8 = ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(act_out)) & 7u) == 0 ? 1 : 0;
-    a.records = (unsigned long long)E * (unsigned long long)N;
-    const ShieldObstacles ob{orow, oid, obstacle_rate / dt, m, M};
-    const int W = shield_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
+    const int rc = shield_args("dronesim_action_shield_obstacles", z, nbr, act, radius, rate, margin, u_max, dt, E, N, k1, c, act_out,
+                               intervened, correction, &ob, a);
+    if (rc != DRONESIM_OK || E == 0) return rc;
+    const int W = record_load_width(k1, c, reinterpret_cast<uintptr_t>(z));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((a.records + 255) / 256));
     if (W == 4) hipLaunchKernelGGL(action_shield_obstacles_kernel<4>, grid, dim3(256), 0, s, a, ob);
@@ -385,9 +381,9 @@ int dronesim_action_shield_obstacles(const float *z, const int32_t *nbr, const f
 int dronesim_shield_totals(const uint8_t *intervened, const float *correction, int E, int N, int64_t *interventions,
                            int64_t *nonfinite, double *correction_sum, float *correction_max, void *stream)
 {
-    if (!intervened || !correction || !interventions || !nonfinite || !correction_sum || !correction_max)
-        return dronesim_fail(DRONESIM_EINVAL, "dronesim_shield_totals: NULL pointer");
-    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS) return dronesim_fail(DRONESIM_EINVAL, "dronesim_shield_totals: E < 0 or N outside 1..1024");
+    const char *where = "dronesim_shield_totals";
+    if (!intervened || !correction || !interventions || !nonfinite || !correction_sum || !correction_max) return fail_at(where, "NULL pointer");
+    if (E < 0 || N < 1 || N > DRONESIM_MAX_AGENTS) return fail_at(where, "E < 0 or N outside 1..1024");
     if (E == 0) return DRONESIM_OK;
     hipLaunchKernelGGL(shield_totals_kernel, dim3((unsigned)((N + kTotalsTile - 1) / kTotalsTile)), dim3(kTotalsThreads), 0,
                        static_cast<hipStream_t>(stream), intervened, correction, E, N, reinterpret_cast<long long *>(interventions),

@@ -91,15 +91,10 @@ def check_execute(execute, shape, device, batched=True):
     """``step(execute=)``'s argument: the ``[E,N,2]`` float32 tensor the launch integrates in place of ``actions``.  It is
     handed to the kernel as it is (no conversion, no copy), so anything else is a ValueError -- raised before any launch."""
     import torch
+    from ._native import check_tensor
     if not batched:
         raise ValueError("step(execute=...) needs the batched (tensor) API")
-    if not torch.is_tensor(execute):
-        raise ValueError(f"execute must be a tensor, got {type(execute).__name__}")
-    if execute.dtype != torch.float32 or tuple(execute.shape) != tuple(shape) or not execute.is_contiguous():
-        raise ValueError(f"execute must be a contiguous float32 tensor of shape {tuple(shape)}, got {execute.dtype} "
-                         f"{tuple(execute.shape)}{'' if execute.is_contiguous() else ' (not contiguous)'}")
-    if execute.device != torch.device(device):
-        raise ValueError(f"execute must live on the env's device {device}, got {execute.device}")
+    check_tensor("execute", execute, torch.float32, shape, device)
     return execute
 
 

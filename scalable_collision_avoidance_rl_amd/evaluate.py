@@ -13,7 +13,6 @@ histogram behind "runs with 0 collisions" (:148-156) and the running averages (:
 There is no CPU fallback: the tables come from the HIP library."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from collections import deque
 
@@ -34,7 +33,6 @@ def episode_eval(reward, true_reward, n_coll, done, V=None, gamma=0.99, out=None
     import torch
     from . import _native
     from .rollout_buffer import _prep
-    lib = _native.lib()
     reward = _prep(reward, torch.float32)
     T, E, N = reward.shape
     true_reward = _prep(true_reward, torch.float32, (T, E, N))
@@ -58,14 +56,9 @@ def episode_eval(reward, true_reward, n_coll, done, V=None, gamma=0.99, out=None
         dtype, shape = shapes[name]
         if not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
             raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-    ptr = lambda name: out[name].data_ptr() if name in out else None
-    with torch.cuda.device(dev):
-        rc = lib.dronesim_episode_eval(reward.data_ptr(), true_reward.data_ptr(), n_coll.data_ptr(), done.data_ptr(),
-                                       None if V is None else V.data_ptr(), float(gamma), out["ep_len"].data_ptr(),
-                                       ptr("ep_collisions"), ptr("agent_return"), ptr("agent_true_return"), ptr("ep_return"),
-                                       ptr("ep_true_return"), ptr("G"), ptr("mean_adv"), T, E, N,
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_episode_eval")
+    _native.call("dronesim_episode_eval", reward, true_reward, n_coll, done, V, float(gamma), out["ep_len"], out.get("ep_collisions"),
+                 out.get("agent_return"), out.get("agent_true_return"), out.get("ep_return"), out.get("ep_true_return"), out.get("G"),
+                 out.get("mean_adv"), T, E, N)
     return out
 
 
@@ -118,7 +111,6 @@ def episode_safety(z, nbr, done, radius, delta, z_final=None, nbr_final=None, do
     radius, delta = _prep(radius, torch.float32), _prep(delta, torch.float32)
     if z_final is not None:
         z_final, nbr_final = _prep(z_final, torch.float32), _prep(nbr_final, torch.int32)
-    lib = _native.lib()
     dev = z.device
     shapes = dict(ep_len=(torch.int32, (E,)), min_clearance=(torch.float32, (E, N)), goal_dist_final=(torch.float32, (E, N)),
                   arrive_step=(torch.int32, (E, N)), ep_min_clearance=(torch.float32, (E,)), ep_goal_dist_max=(torch.float32, (E,)),
@@ -129,14 +121,9 @@ def episode_safety(z, nbr, done, radius, delta, z_final=None, nbr_final=None, do
         dtype, shape = shapes[name]
         if not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
             raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-    ptr = lambda name: out[name].data_ptr() if name in out else None
-    with torch.cuda.device(dev):
-        rc = lib.dronesim_episode_safety(z.data_ptr(), nbr.data_ptr(), None if z_final is None else z_final.data_ptr(),
-                                         None if nbr_final is None else nbr_final.data_ptr(), done.data_ptr(), radius.data_ptr(),
-                                         delta.data_ptr(), float(done_radius), T, E, N, k1, c, out["ep_len"].data_ptr(),
-                                         ptr("min_clearance"), ptr("goal_dist_final"), ptr("arrive_step"), ptr("ep_min_clearance"),
-                                         ptr("ep_goal_dist_max"), ptr("ep_arrived"), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_episode_safety")
+    _native.call("dronesim_episode_safety", z, nbr, z_final, nbr_final, done, radius, delta, float(done_radius), T, E, N, k1, c,
+                 out["ep_len"], out.get("min_clearance"), out.get("goal_dist_final"), out.get("arrive_step"), out.get("ep_min_clearance"),
+                 out.get("ep_goal_dist_max"), out.get("ep_arrived"))
     return out
 
 
@@ -159,11 +146,7 @@ def histogram_i32(values, n_bins, valid=None, out=None, accumulate=False):
         out = torch.empty(int(n_bins) + 1, dtype=torch.int64, device=values.device)
     elif not (out.dtype == torch.int64 and out.numel() == int(n_bins) + 1 and out.is_contiguous() and out.device == values.device):
         raise ValueError("out must be a contiguous int64 [n_bins + 1] tensor on the values' device")
-    with torch.cuda.device(values.device):
-        rc = _native.lib().dronesim_histogram_i32(values.data_ptr(), None if valid is None else valid.data_ptr(), E, int(n_bins),
-                                                  out.data_ptr(), 1 if accumulate else 0,
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_histogram_i32")
+    _native.call("dronesim_histogram_i32", values, valid, E, int(n_bins), out, 1 if accumulate else 0)
     return out
 
 

@@ -109,10 +109,7 @@ def plain_struct(mlp):
 def grad_workspace_bytes(mlp, rows_per_chunk):
     """Bytes of device workspace `dronesim_mlp_grad` needs at ``rows_per_chunk`` rows per chunk."""
     from . import _native
-    n = C.c_size_t(0)
-    _native.check(_native.lib().dronesim_mlp_grad_workspace(C.byref(plain_struct(mlp)), int(rows_per_chunk), C.byref(n)),
-                  "dronesim_mlp_grad_workspace")
-    return int(n.value)
+    return _native.workspace("dronesim_mlp_grad_workspace", C.byref(plain_struct(mlp)), int(rows_per_chunk))
 
 
 WORKSPACE_BUDGET = 1 << 30          # bytes of gradient workspace per network that the default chunk size aims for
@@ -167,11 +164,10 @@ class GradientRunner:
         from . import _native
         bytes_attr, out_attr, _, lead = self._FORMS[form]
         if not hasattr(self, out_attr):
-            name, n = f"dronesim_mlp_{form}_workspace", C.c_size_t(0)
-            _native.check(getattr(_native.lib(), name)(C.byref(self._m), self.rc, C.byref(n)), name)
-            if int(n.value) > self.ws.numel() * 4:
-                self.ws = torch.empty((int(n.value) + 3) // 4, device=self.mlp.device)
-            setattr(self, bytes_attr, int(n.value))
+            n = _native.workspace(f"dronesim_mlp_{form}_workspace", C.byref(self._m), self.rc)
+            if n > self.ws.numel() * 4:
+                self.ws = torch.empty((n + 3) // 4, device=self.mlp.device)
+            setattr(self, bytes_attr, n)
             setattr(self, out_attr, torch.zeros(*lead, self.mlp.n_agents, device=self.mlp.device))
         return getattr(self, bytes_attr), getattr(self, out_attr)
 
@@ -183,19 +179,16 @@ class GradientRunner:
         import torch
         from . import _native
         loss = self.loss if loss_out is None else loss_out
-        ws_bytes, results = self.ws_bytes, () if form == "logp" else (self.grad.data_ptr(), loss.data_ptr())
+        ws_bytes, results = self.ws_bytes, () if form == "logp" else (self.grad, loss)
         if form in self._FORMS:
             ws_bytes, own = self._workspace(form)
             out = own if out is None else out
             if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != own.numel():
                 raise ValueError(f"{self._FORMS[form][2]} must be a contiguous float32 tensor {list(own.shape)}")
-            results += (out.data_ptr(),)
-        name, scale = "dronesim_mlp_" + form, () if form == "logp" else (float(row_scale),)
-        ptr = lambda t: t.data_ptr() if hasattr(t, "data_ptr") else t
-        with torch.cuda.device(self.mlp.device):
-            rc = getattr(_native.lib(), name)(C.byref(self._m), x.data_ptr(), self.rows, *scale, *map(ptr, head), *results, self.rc,
-                                              self.ws.data_ptr(), ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, name)
+            results += (out,)
+        scale = () if form == "logp" else (float(row_scale),)
+        _native.call("dronesim_mlp_" + form, C.byref(self._m), x, self.rows, *scale, *head, *results, self.rc, self.ws, ws_bytes,
+                     device=self.mlp.device)
         return (self.grad, loss) if out is None else (self.grad, loss, out)
 
     def run(self, x, row_scale, target=None, act=None, weight=None, loss_out=None):
@@ -372,30 +365,14 @@ class BatchedAdam:
         if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != self.mlp.n_agents
                                    or active.device != self.m1.device):
             raise ValueError(f"active must be a contiguous int32 tensor [{self.mlp.n_agents}] on {self.m1.device}")
+        shared = (C.byref(self._m), grad, self.m1, self.m2, self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.max_norm, norm)
         if self.share is not None:
-            with torch.cuda.device(self.mlp.device):
-                rc = _native.lib().dronesim_adam_step_shared(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
-                                                             self.steps.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                             self.max_norm, norm.data_ptr(),
-                                                             None if active is None else active.data_ptr(),
-                                                             self.share.group_ptr.data_ptr(), self.share.members.data_ptr(),
-                                                             self.share.n_groups, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _native.check(rc, "dronesim_adam_step_shared")
-            if refresh:
-                self.mlp.refresh_weights()
-            return norm
-        with torch.cuda.device(self.mlp.device):
-            if active is None:
-                rc = _native.lib().dronesim_adam_step(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
-                                                      self.steps.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                      self.max_norm, norm.data_ptr(),
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            else:
-                rc = _native.lib().dronesim_adam_step_gated(C.byref(self._m), grad.data_ptr(), self.m1.data_ptr(),
-                                                            self.m2.data_ptr(), self.steps.data_ptr(), self.lr, self.betas[0],
-                                                            self.betas[1], self.eps, self.max_norm, norm.data_ptr(),
-                                                            active.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_adam_step" if active is None else "dronesim_adam_step_gated")
+            _native.call("dronesim_adam_step_shared", *shared, active, self.share.group_ptr, self.share.members, self.share.n_groups,
+                         device=self.mlp.device)
+        elif active is None:
+            _native.call("dronesim_adam_step", *shared, device=self.mlp.device)
+        else:
+            _native.call("dronesim_adam_step_gated", *shared, active, device=self.mlp.device)
         if refresh:
             self.mlp.refresh_weights()
         return norm
@@ -442,14 +419,10 @@ def _ring(storage, T):
 def _lambda_returns(learner, storage, Vall, G, reward):
     """`dronesim_lambda_returns` of ``reward`` (the stored rewards, or their normalised image) with the values of all T+1 ring
     slots, into ``G``."""
-    import torch
     from . import _native
     T, E, N = learner._shape
-    with torch.cuda.device(learner.critic.device):
-        rc = _native.lib().dronesim_lambda_returns(reward.data_ptr(), storage.done.data_ptr(), Vall.data_ptr(),
-                                                   learner.gamma, learner.lam, G.data_ptr(), None, T, E, N,
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_lambda_returns")
+    _native.call("dronesim_lambda_returns", reward, storage.done, Vall, learner.gamma, learner.lam, G, None, T, E, N,
+                 device=learner.critic.device)
 
 
 TIME_LIMITS = ("terminal", "bootstrap")
@@ -489,7 +462,6 @@ def _prepare_ends(learner, storage, T, E, N):
 def _lambda_returns_ends(learner, storage, Vall, G, reward):
     """``time_limit="bootstrap"``: the kinds of the window's episode ends and the terminal observations of the truncated ones
     (`dronesim_episode_ends`), the PRE-update critic over those into ``V_trunc``, then `dronesim_lambda_returns_ends` into ``G``."""
-    import torch
     from . import _native, drone_env
     from .rollout_buffer import _episode_ends
     T, E, N = learner._shape
@@ -502,11 +474,8 @@ def _lambda_returns_ends(learner, storage, Vall, G, reward):
     if learner.obs_norm is not None:
         z_trunc = learner.obs_norm.norm(z_trunc, out=learner._xn_trunc)
     learner.critic.forward(z_trunc.view(M * E, N, -1), out=learner.V_trunc)
-    with torch.cuda.device(learner.critic.device):
-        rc = _native.lib().dronesim_lambda_returns_ends(reward.data_ptr(), learner.ends.data_ptr(), Vall.data_ptr(),
-                                                        learner.V_trunc.data_ptr(), M, learner.gamma, learner.lam, G.data_ptr(),
-                                                        None, T, E, N, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_lambda_returns_ends")
+    _native.call("dronesim_lambda_returns_ends", reward, learner.ends, Vall, learner.V_trunc, M, learner.gamma, learner.lam, G, None,
+                 T, E, N, device=learner.critic.device)
 
 
 def _check_obs_norm(obs_norm, actor, critic):
@@ -791,18 +760,13 @@ class SA2CLearner:
         self._shape = (T, E, N)
 
     def train(self, storage):
-        import torch
         from . import _native
         self._prepare(storage)
         T, E, N = self._shape
-        lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         x, ring = _normalised(self, storage, T)
         reward = _normalised_reward(self, storage)
         if self.lam is None:
-            with torch.cuda.device(self.critic.device):
-                rc = lib.dronesim_returns(reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
-                                          T, E, N, stream)
-            _native.check(rc, "dronesim_returns")
+            _native.call("dronesim_returns", reward, storage.done, self.gamma, self.G, T, E, N, device=self.critic.device)
         else:       # bootstrapped lambda-returns from the pre-update critic over all T+1 ring slots
             self.critic.forward(ring.view((T + 1) * E, N, -1), out=self.V_all)
             (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G, reward)
@@ -812,10 +776,8 @@ class SA2CLearner:
         # baseline from the post-update critic, advantage weights (:333-351)
         self.critic.forward(x.view(T * E, N, -1), out=self.V)
         nbr = storage.nbr_pre
-        with torch.cuda.device(self.critic.device):
-            rc = lib.dronesim_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(), storage.done.data_ptr(),
-                                        self.gamma, self.w.data_ptr(), T, E, N, int(nbr.shape[3]), stream)
-        _native.check(rc, "dronesim_advantage")
+        _native.call("dronesim_advantage", self.G, self.V, nbr, storage.done, self.gamma, self.w, T, E, N, int(nbr.shape[3]),
+                     device=self.critic.device)
         # actor (:327-357)
         if self.ent_coef > 0:
             ag, aloss, ent = self._actor_grad.run_ent(x, 1.0 / E, storage.actions, self.w, self.ent_coef / (T * E))
@@ -1050,9 +1012,7 @@ class PPOLearner:
             self._prepare_minibatches(storage, T * E, N, K)
         if self.normalize_advantage:
             from . import _native
-            n = C.c_size_t(0)
-            _native.check(_native.lib().dronesim_standardize_workspace(T * E, N, C.byref(n)), "dronesim_standardize_workspace")
-            self._std_ws_bytes = int(n.value)
+            self._std_ws_bytes = _native.workspace("dronesim_standardize_workspace", T * E, N)
             self._std_ws = torch.empty(self._std_ws_bytes // 8, dtype=torch.float64, device=dev)
             self.adv_stats = torch.zeros(2, N, device=dev)
         if self.target_kl is not None:
@@ -1097,9 +1057,8 @@ class PPOLearner:
         self._scalars = torch.zeros(4, self.epochs, K, N, device=dev)
         self._stats = torch.zeros(self.epochs, K, self._stat_rows, N, device=dev)
 
-    def _train_minibatches(self, storage, x, lib, stream):
+    def _train_minibatches(self, storage, x):
         """Step 3 with ``minibatches = K > 1``: per epoch a fresh device permutation, one gather, K critic-then-actor steps."""
-        import torch
         from . import _native
         T, E, N = self._shape
         K, rows = self.minibatches, T * E
@@ -1109,32 +1068,24 @@ class PPOLearner:
         n_arrays = len(arrays)
         src = (C.c_void_p * n_arrays)(*[t.data_ptr() for t in arrays])
         for ep in range(self.epochs):
-            with torch.cuda.device(self.critic.device):
-                rc = lib.dronesim_row_permutation(rows, self.shuffle_seed, self.critic_opt.steps.data_ptr(), self.perm.data_ptr(), stream)
-                _native.check(rc, "dronesim_row_permutation")
-                rc = lib.dronesim_gather_rows(self.perm.data_ptr(), rows, M, n_arrays, src, self._mb_dst, self._mb_row_bytes,
-                                              self._mb_block_bytes, stream)
-                _native.check(rc, "dronesim_gather_rows")
+            _native.call("dronesim_row_permutation", rows, self.shuffle_seed, self.critic_opt.steps, self.perm, device=self.critic.device)
+            _native.call("dronesim_gather_rows", self.perm, rows, M, n_arrays, src, self._mb_dst, self._mb_row_bytes, self._mb_block_bytes,
+                         device=self.critic.device)
             for b in range(K):
                 self._step(self._critic_mb, self._actor_mb, M, *(g.blocks[b] for g in self._mb), at=(ep, b),
-                           last=ep == self.epochs - 1 and b == K - 1, lib=lib, stream=stream)
+                           last=ep == self.epochs - 1 and b == K - 1)
         return self._outputs()
 
-    def _kl_gate(self, kl, reset, lib, stream):
-        import torch
+    def _kl_gate(self, kl, reset):
         from . import _native
         share = self.actor_opt.share
-        with torch.cuda.device(self.critic.device):
-            if share is None:
-                rc = lib.dronesim_kl_gate(None if kl is None else kl.data_ptr(), self.target_kl, self.active.data_ptr(),
-                                          self.actor_steps.data_ptr(), self.actor.n_agents, int(reset), stream)
-            else:       # the group's verdict, from the mean of its members' estimates, for all its members
-                rc = lib.dronesim_kl_gate_shared(None if kl is None else kl.data_ptr(), self.target_kl, self.active.data_ptr(),
-                                                 self.actor_steps.data_ptr(), self.actor.n_agents, int(reset),
-                                                 share.group_ptr.data_ptr(), share.members.data_ptr(), share.n_groups, stream)
-        _native.check(rc, "dronesim_kl_gate" if share is None else "dronesim_kl_gate_shared")
+        gate = (kl, self.target_kl, self.active, self.actor_steps, self.actor.n_agents, int(reset))
+        if share is None:
+            _native.call("dronesim_kl_gate", *gate, device=self.critic.device)
+        else:       # the group's verdict, from the mean of its members' estimates, for all its members
+            _native.call("dronesim_kl_gate_shared", *gate, share.group_ptr, share.members, share.n_groups, device=self.critic.device)
 
-    def _step(self, critic_grad, actor_grad, rows, x, act, logp_old, adv, G, V=None, *, at, last, lib, stream):
+    def _step(self, critic_grad, actor_grad, rows, x, act, logp_old, adv, G, V=None, *, at, last):
         """One critic step, then one actor step, on these ``rows`` rows (the window, or one minibatch's block of every gathered
         array; ``V`` only with ``vf_clip``), results into slot ``at`` of the per-step outputs.  ``last``: re-pack the forward
         images.  Under ``target_kl`` the actor step is the gated gradient, the gate on this step's KL estimate, the gated Adam
@@ -1148,7 +1099,7 @@ class PPOLearner:
         ppo, out = (x, 1.0 / rows, act, logp_old, adv, self.clip_eps), dict(loss_out=aloss, stats_out=self._stats[at])
         if self.target_kl is not None:
             ag, _, st = actor_grad.run_ppo_gated(*ppo, self.ent_coef / rows, active=self.active, **out)
-            self._kl_gate(st[5], False, lib, stream)
+            self._kl_gate(st[5], False)
             self.actor_opt.step(ag, norm_out=anorm, refresh=last, active=self.active)
             return
         ag = (actor_grad.run_ppo_ent(*ppo, self.ent_coef / rows, **out) if self._ent else actor_grad.run_ppo(*ppo, **out))[0]
@@ -1171,21 +1122,16 @@ class PPOLearner:
         return out
 
     def train(self, storage):
-        import torch
         from . import _native
         self._prepare(storage)
         T, E, N = self._shape
-        lib, stream = _native.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
         act, nbr = storage.actions, storage.nbr_pre
         x, ring = _normalised(self, storage, T)
         reward = _normalised_reward(self, storage)
         if self.target_kl is not None:
-            self._kl_gate(None, True, lib, stream)
+            self._kl_gate(None, True)
         if self.lam is None:
-            with torch.cuda.device(self.critic.device):
-                rc = lib.dronesim_returns(reward.data_ptr(), storage.done.data_ptr(), self.gamma, self.G.data_ptr(),
-                                          T, E, N, stream)
-            _native.check(rc, "dronesim_returns")
+            _native.call("dronesim_returns", reward, storage.done, self.gamma, self.G, T, E, N, device=self.critic.device)
         # the old policy's log-probabilities and the advantage from the pre-update critic, once per window (:484-501, :512-513)
         self._actor_grad.logp(x, act, self.logp_old)
         if self.lam is None:
@@ -1193,22 +1139,17 @@ class PPOLearner:
         else:       # the same forward over all T+1 ring slots; the bootstrapped lambda-returns of it
             self.critic.forward(ring.view((T + 1) * E, N, -1), out=self.V_all)
             (_lambda_returns if self.time_limit == "terminal" else _lambda_returns_ends)(self, storage, self.V_all, self.G, reward)
-        with torch.cuda.device(self.critic.device):
-            rc = lib.dronesim_neighbour_advantage(self.G.data_ptr(), self.V.data_ptr(), nbr.data_ptr(),
-                                                  int(self.baseline == "per_neighbour"), self.adv.data_ptr(), T, E, N,
-                                                  int(nbr.shape[3]), stream)
-        _native.check(rc, "dronesim_neighbour_advantage")
+        _native.call("dronesim_neighbour_advantage", self.G, self.V, nbr, int(self.baseline == "per_neighbour"), self.adv, T, E, N,
+                     int(nbr.shape[3]), device=self.critic.device)
         if self.normalize_advantage:
-            with torch.cuda.device(self.critic.device):
-                rc = lib.dronesim_standardize(self.adv.data_ptr(), self.adv.data_ptr(), self.adv_stats.data_ptr(), T * E, N,
-                                              self.adv_eps, self._std_ws.data_ptr(), self._std_ws_bytes, stream)
-            _native.check(rc, "dronesim_standardize")
+            _native.call("dronesim_standardize", self.adv, self.adv, self.adv_stats, T * E, N, self.adv_eps, self._std_ws,
+                         self._std_ws_bytes, device=self.critic.device)
         if self.minibatches > 1:
-            out = self._train_minibatches(storage, x, lib, stream)
+            out = self._train_minibatches(storage, x)
         else:
             for ep in range(self.epochs):
                 self._step(self._critic_grad, self._actor_grad, T * E, x, act, self.logp_old, self.adv, self.G, self.V, at=ep,
-                           last=ep == self.epochs - 1, lib=lib, stream=stream)
+                           last=ep == self.epochs - 1)
             out = self._outputs()
         if self.obs_norm is not None and self.update_obs_norm:
             # the last enqueued work: the T E pre-step rows only (ring slot T is the next window's slot 0 and is counted there)

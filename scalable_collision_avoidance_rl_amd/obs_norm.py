@@ -18,7 +18,6 @@ rollout window, ``train()`` and the update replay from one captured graph.  Impo
 library; `update` and `norm` need both (no CPU fallback).  A normaliser on the CPU only carries statistics (`state_dict`)."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 
@@ -82,24 +81,18 @@ class ObsNormalizer:
         import torch
         from . import _native
         if R not in self._ws_bytes:
-            n = C.c_size_t(0)
-            _native.check(_native.lib().dronesim_obsnorm_workspace(R, self.C, C.byref(n)), "dronesim_obsnorm_workspace")
-            self._ws_bytes[R] = int(n.value)
-            if self._ws is None or self._ws.numel() * 8 < int(n.value):
-                self._ws = torch.empty((int(n.value) + 7) // 8, dtype=torch.float64, device=self.device)
+            n = self._ws_bytes[R] = _native.workspace("dronesim_obsnorm_workspace", R, self.C)
+            if self._ws is None or self._ws.numel() * 8 < n:
+                self._ws = torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device)
         return self._ws, self._ws_bytes[R]
 
     def update(self, x):
         """Merge the finite values of ``x`` (``[T,E,N,d]``, ``[E,N,k+1,c]``, ... : leading dims are rows) into the statistics and
         rewrite the table."""
-        import torch
         from . import _native
         R = self._rows(x, "x")
         ws, ws_bytes = self._workspace(R)
-        with torch.cuda.device(self.device):
-            rc = _native.lib().dronesim_obsnorm_update(x.data_ptr(), R, self.C, self.state.data_ptr(), self.table.data_ptr(), self.eps,
-                                                       ws.data_ptr(), ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_obsnorm_update")
+        _native.call("dronesim_obsnorm_update", x, R, self.C, self.state, self.table, self.eps, ws, ws_bytes, device=self.device)
         return self
 
     def norm(self, x, out=None):
@@ -115,11 +108,7 @@ class ObsNormalizer:
         elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
                   and tuple(out.shape) == tuple(x.shape)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}")
-        with torch.cuda.device(self.device):
-            rc = _native.lib().dronesim_obsnorm_apply(x.data_ptr(), out.data_ptr(), R, self.C, self.table.data_ptr(),
-                                                      0.0 if self.clip is None else self.clip,
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_obsnorm_apply")
+        _native.call("dronesim_obsnorm_apply", x, out, R, self.C, self.table, 0.0 if self.clip is None else self.clip, device=self.device)
         return out
 
     __call__ = norm

@@ -27,11 +27,9 @@ field follows only through ``field.set(env.obstacles)``.
 There is no CPU fallback; importing this module needs neither a GPU nor the library."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from ._native import MAX_AGENTS as _MAX_AGENTS, MAX_K as _MAX_K, MAX_OBSTACLES, MAX_SENSE
+from ._native import MAX_AGENTS as _MAX_AGENTS, MAX_K as _MAX_K, MAX_OBSTACLES, MAX_SENSE, check_tensor as _tensor_check
 
 OBSTACLE_TABLES = ("min_obstacle_gap", "obstacle_hit_steps", "ep_min_obstacle_gap", "ep_obstacle_hit_steps")
 
@@ -109,17 +107,6 @@ def place_obstacles(grid, n, seed=0, keep_clear=None, clearance=0.0, centres=Non
     return obs
 
 
-def _tensor_check(name, x, dtype, shape, device):
-    import torch
-    if not torch.is_tensor(x):
-        raise ValueError(f"{name} must be a tensor, got {type(x).__name__}")
-    if x.dtype != dtype or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {x.dtype} {tuple(x.shape)}"
-                         f"{'' if x.is_contiguous() else ' (not contiguous)'}")
-    if x.device != device:
-        raise ValueError(f"{name} must live on the device {device}, got {x.device}")
-
-
 def _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final):
     """(T, E, N, d) of `episode_obstacle_safety`'s arguments, or ValueError -- shapes, dtypes and devices only."""
     import torch
@@ -168,17 +155,11 @@ def episode_obstacle_safety(z, done, xF, radius, obstacles, c, z_final=None, out
             _tensor_check(f"out[{name!r}]", t, shapes[name][0], shapes[name][1], dev)
         if "ep_len" not in out:
             raise ValueError("out needs ep_len")
-    lib = _native.lib()
     if out is None:
         out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, (dtype, shape) in shapes.items()}
-    ptr = lambda name: out[name].data_ptr() if name in out else None
-    with torch.cuda.device(dev):
-        rc = lib.dronesim_episode_obstacle_safety(z.data_ptr(), None if z_final is None else z_final.data_ptr(), done.data_ptr(),
-                                                  xF.data_ptr(), radius.data_ptr(), obstacles.data_ptr() if M else None, T, E, N, k1, c, M,
-                                                  out["ep_len"].data_ptr(), ptr("min_obstacle_gap"), ptr("obstacle_hit_steps"),
-                                                  ptr("ep_min_obstacle_gap"), ptr("ep_obstacle_hit_steps"),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_episode_obstacle_safety")
+    _native.call("dronesim_episode_obstacle_safety", z, z_final, done, xF, radius, obstacles if M else None, T, E, N, k1, c, M,
+                 out["ep_len"], out.get("min_obstacle_gap"), out.get("obstacle_hit_steps"), out.get("ep_min_obstacle_gap"),
+                 out.get("ep_obstacle_hit_steps"))
     return out
 
 
@@ -249,28 +230,20 @@ class ObstacleField:
         import torch
         from . import _native
         env = self.env
-        E, N, k1, c = int(env.n_envs), int(env.n_agents), int(env.k_closest) + 1, int(env.c)
+        E = int(env.n_envs)
+        N, k1, c = self._geometry()
         z = env.z if z is None else z
         dev = torch.device(env.device)
-        if not 1 <= N <= _MAX_AGENTS or not 1 <= k1 <= _MAX_K + 1 or c not in (2, 5):
-            raise ValueError(f"sensing needs N in 1..{_MAX_AGENTS}, k + 1 in 1..{_MAX_K + 1} and c in (2, 5), got N = {N}, k + 1 = {k1}, c = {c}")
         _tensor_check("z", z, torch.float32, (E, N, k1 * c), dev)
-        rng = self.sense_range
-        for name, x, shape in (("xF", env._xF, (N, 2)), ("radius", env._radius, (N,)), ("sense", rng, (N,))):
-            _tensor_check(name, x, torch.float32, shape, dev)
-        lib = _native.lib()
+        xF, radius, rng = self._env_tensors(dev)
         if self.orow is None:
             self.orow = torch.zeros(E, N, self.m, 3, dtype=torch.float32, device=dev)
             self.oid = torch.full((E, N, self.m), -1, dtype=torch.int32, device=dev)
         if gap_min and self.gap_min is None:
             self.gap_min = torch.zeros(E, N, dtype=torch.float32, device=dev)
             self.hit = torch.zeros(E, N, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.dronesim_obstacle_sense(z.data_ptr(), env._xF.data_ptr(), env._radius.data_ptr(), rng.data_ptr(),
-                                             self._obs.data_ptr(), E, N, k1, c, self.M, self.m, self.orow.data_ptr(), self.oid.data_ptr(),
-                                             self.gap_min.data_ptr() if gap_min else None, self.hit.data_ptr() if gap_min else None,
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_obstacle_sense")
+        _native.call("dronesim_obstacle_sense", z, xF, radius, rng, self._obs, E, N, k1, c, self.M, self.m, self.orow, self.oid,
+                     self.gap_min if gap_min else None, self.hit if gap_min else None)
         return self.orow, self.oid
 
     @property
@@ -315,7 +288,6 @@ class ObstacleField:
         if out is not None:
             _tensor_check("out", out, torch.float32, lead + (N, self.obs_width), dev)
         xF, radius, rng = self._env_tensors(dev)
-        lib = _native.lib()
         if out is None:
             out = self._x.get(lead)
             if out is None:
@@ -327,12 +299,7 @@ class ObstacleField:
                 cost_out = self._cost[lead] = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
             self.cost = cost_out
         R = int(np.prod(lead, dtype=np.int64)) if lead else 1
-        with torch.cuda.device(dev):
-            rc = lib.dronesim_obstacle_observe(z.data_ptr(), xF.data_ptr(), radius.data_ptr(), rng.data_ptr(), self._obs.data_ptr(),
-                                               R, N, k1, c, self.M, self.m, out.data_ptr(),
-                                               None if cost_out is None else cost_out.data_ptr(), weight,
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_obstacle_observe")
+        _native.call("dronesim_obstacle_observe", z, xF, radius, rng, self._obs, R, N, k1, c, self.M, self.m, out, cost_out, weight)
         return out
 
     def shape_reward(self, storage, weight, out=None, cost_out=None):
@@ -358,16 +325,10 @@ class ObstacleField:
             if t is not None:
                 _tensor_check(name, t, torch.float32, (T, E, N), dev)
         xF, radius, rng = self._env_tensors(dev)
-        lib = _native.lib()
         if out is None:
             out = torch.empty(T, E, N, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.dronesim_obstacle_reward(storage.z.data_ptr(), None if storage.z_final is None else storage.z_final.data_ptr(),
-                                              storage.done.data_ptr(), storage.reward.data_ptr(), xF.data_ptr(), radius.data_ptr(),
-                                              rng.data_ptr(), self._obs.data_ptr(), T, E, N, k1, c, self.M, weight, out.data_ptr(),
-                                              None if cost_out is None else cost_out.data_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_obstacle_reward")
+        _native.call("dronesim_obstacle_reward", storage.z, storage.z_final, storage.done, storage.reward, xF, radius, rng, self._obs,
+                     T, E, N, k1, c, self.M, weight, out, cost_out)
         return out
 
     def episode_safety(self, storage, out=None):

@@ -390,12 +390,9 @@ class BatchedMLP:
         group id per agent; None ties nothing); the leader of a group is its lowest-numbered member.  A `BatchedAdam` /
         learner built with the same ``share`` then keeps the members bit-identical.  Returns ``self``."""
         from .learner import SharingMap, plain_struct
-        torch = self._torch
         groups = SharingMap(share, self.n_agents, self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.dronesim_mlp_tie(C.byref(plain_struct(self)), groups.group_ptr.data_ptr(), groups.members.data_ptr(),
-                                            groups.n_groups, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        self._native.check(rc, "dronesim_mlp_tie")
+        self._native.call("dronesim_mlp_tie", C.byref(plain_struct(self)), groups.group_ptr, groups.members, groups.n_groups,
+                          device=self.device)
         self.refresh_weights()
         return self
 

@@ -26,7 +26,6 @@ so a rollout window and ``train()`` replay from one captured graph.  Importing t
 library; `update` and `norm` need both (no CPU fallback).  A normaliser on the CPU only carries statistics (`state_dict`)."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 from .obs_norm import _check_clip
@@ -112,11 +111,9 @@ class RewardNormalizer:
         import torch
         from . import _native
         if (T, E) not in self._ws_bytes:
-            n = C.c_size_t(0)
-            _native.check(_native.lib().dronesim_rewnorm_workspace(T, E, self.n_agents, C.byref(n)), "dronesim_rewnorm_workspace")
-            self._ws_bytes[(T, E)] = int(n.value)
-            if self._ws is None or self._ws.numel() * 8 < int(n.value):
-                self._ws = torch.empty((int(n.value) + 7) // 8, dtype=torch.float64, device=self.device)
+            n = self._ws_bytes[(T, E)] = _native.workspace("dronesim_rewnorm_workspace", T, E, self.n_agents)
+            if self._ws is None or self._ws.numel() * 8 < n:
+                self._ws = torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device)
         return self._ws, self._ws_bytes[(T, E)]
 
     def update(self, reward, done):
@@ -133,12 +130,8 @@ class RewardNormalizer:
         elif self.ret.shape[0] != E:
             raise ValueError(f"the carry is for {self.ret.shape[0]} envs, this window has {E} (a normaliser follows one set of envs)")
         ws, ws_bytes = self._workspace(T, E)
-        with torch.cuda.device(self.device):
-            rc = _native.lib().dronesim_rewnorm_update(reward.data_ptr(), done.data_ptr(), T, E, self.n_agents, self.gamma,
-                                                       self.group.data_ptr(), self.n_groups, self.ret.data_ptr(),
-                                                       self.state.data_ptr(), self.scale.data_ptr(), self.eps, ws.data_ptr(), ws_bytes,
-                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_rewnorm_update")
+        _native.call("dronesim_rewnorm_update", reward, done, T, E, self.n_agents, self.gamma, self.group, self.n_groups, self.ret,
+                     self.state, self.scale, self.eps, ws, ws_bytes, device=self.device)
         return self
 
     def norm(self, reward, out=None):
@@ -154,11 +147,8 @@ class RewardNormalizer:
         elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and out.device == reward.device
                   and tuple(out.shape) == tuple(reward.shape)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(reward.shape)} on {reward.device}")
-        with torch.cuda.device(self.device):
-            rc = _native.lib().dronesim_rewnorm_apply(reward.data_ptr(), out.data_ptr(), T, E, self.n_agents, self.scale.data_ptr(),
-                                                      0.0 if self.clip is None else self.clip,
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_rewnorm_apply")
+        _native.call("dronesim_rewnorm_apply", reward, out, T, E, self.n_agents, self.scale, 0.0 if self.clip is None else self.clip,
+                     device=self.device)
         return out
 
     __call__ = norm

@@ -19,7 +19,6 @@ The reductions run in the HIP library (dronesim_returns / dronesim_lambda_return
 dronesim_lambda_returns_ends / dronesim_advantage); there is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 # the reference's experience tuple (utils.py:241-242), field for field
@@ -216,15 +215,11 @@ def mc_returns(reward, gamma: float, done=None):
     marks steps that ended an episode (the scan restarts there)."""
     import torch
     from . import _native
-    lib = _native.lib()
     reward = _prep(reward, torch.float32)
     T, E, N = reward.shape
     d = None if done is None else _prep(done, torch.uint8, (T, E))
     G = torch.empty_like(reward)
-    with torch.cuda.device(reward.device):
-        rc = lib.dronesim_returns(reward.data_ptr(), None if d is None else d.data_ptr(), float(gamma),
-                                  G.data_ptr(), T, E, N, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_returns")
+    _native.call("dronesim_returns", reward, d, float(gamma), G, T, E, N)
     return G
 
 
@@ -238,14 +233,9 @@ def check_lam(lam):
 
 def _episode_ends(done, z_final, done_radius, M, ends, slot_t, n_trunc, z_trunc):
     """`dronesim_episode_ends` on checked, contiguous device tensors, into the caller's buffers."""
-    import torch
     from . import _native
     T, E, N, d = z_final.shape
-    with torch.cuda.device(done.device):
-        rc = _native.lib().dronesim_episode_ends(done.data_ptr(), z_final.data_ptr(), T, E, N, d, float(done_radius),
-                                                 ends.data_ptr(), slot_t.data_ptr(), n_trunc.data_ptr(), z_trunc.data_ptr(), M,
-                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_episode_ends")
+    _native.call("dronesim_episode_ends", done, z_final, T, E, N, d, float(done_radius), ends, slot_t, n_trunc, z_trunc, M)
 
 
 def episode_ends(done, z_final, done_radius, M):
@@ -293,7 +283,6 @@ def lambda_returns(reward, V, gamma: float, lam: float = 1.0, done=None, want_ad
         raise ValueError("ends and Vend go together: the kinds of the episode ends [T,E] and the values [M,E,N] of the "
                          "terminal observations of the truncated ones (episode_ends); got only one of them")
     from . import _native
-    lib = _native.lib()
     lam = check_lam(lam)
     if torch.is_tensor(reward) and torch.is_tensor(V) and (
             reward.dim() != 3 or tuple(V.shape) != (reward.shape[0] + 1,) + tuple(reward.shape[1:])):
@@ -312,20 +301,12 @@ def lambda_returns(reward, V, gamma: float, lam: float = 1.0, done=None, want_ad
         ends, Vend = _prep(ends, torch.uint8, (T, E)), _prep(Vend, torch.float32)
         G = torch.empty_like(reward)
         A = torch.empty_like(reward) if want_adv else None
-        with torch.cuda.device(reward.device):
-            rc = lib.dronesim_lambda_returns_ends(reward.data_ptr(), ends.data_ptr(), V.data_ptr(), Vend.data_ptr(), int(Vend.shape[0]),
-                                                  float(gamma), lam, G.data_ptr(), None if A is None else A.data_ptr(), T, E, N,
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _native.check(rc, "dronesim_lambda_returns_ends")
+        _native.call("dronesim_lambda_returns_ends", reward, ends, V, Vend, int(Vend.shape[0]), float(gamma), lam, G, A, T, E, N)
         return (G, A) if want_adv else G
     d = None if done is None else _prep(done, torch.uint8, (T, E))
     G = torch.empty_like(reward)
     A = torch.empty_like(reward) if want_adv else None
-    with torch.cuda.device(reward.device):
-        rc = lib.dronesim_lambda_returns(reward.data_ptr(), None if d is None else d.data_ptr(), V.data_ptr(), float(gamma), lam,
-                                         G.data_ptr(), None if A is None else A.data_ptr(), T, E, N,
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_lambda_returns")
+    _native.call("dronesim_lambda_returns", reward, d, V, float(gamma), lam, G, A, T, E, N)
     return (G, A) if want_adv else G
 
 
@@ -335,7 +316,6 @@ def neighbour_advantage(G, V, nbr_idx, gamma: float, done=None):
     before each step, i.e. ``rollout()['nbr_idx_pre']``)."""
     import torch
     from . import _native
-    lib = _native.lib()
     G = _prep(G, torch.float32)
     T, E, N = G.shape
     V = _prep(V, torch.float32, (T, E, N))
@@ -344,11 +324,7 @@ def neighbour_advantage(G, V, nbr_idx, gamma: float, done=None):
         raise ValueError(f"nbr_idx must be [T,E,N,k+1], got {tuple(nbr_idx.shape)}")
     d = None if done is None else _prep(done, torch.uint8, (T, E))
     w = torch.empty_like(G)
-    with torch.cuda.device(G.device):
-        rc = lib.dronesim_advantage(G.data_ptr(), V.data_ptr(), nbr_idx.data_ptr(), None if d is None else d.data_ptr(),
-                                    float(gamma), w.data_ptr(), T, E, N, int(nbr_idx.shape[3]),
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_advantage")
+    _native.call("dronesim_advantage", G, V, nbr_idx, d, float(gamma), w, T, E, N, int(nbr_idx.shape[3]))
     return w
 
 
@@ -359,7 +335,6 @@ def standardize(x, eps=1e-8, out=None, return_stats=False):
     ``y``, or ``(y, stats)`` with ``stats [2, N]`` = (mean, std) of the input when ``return_stats``."""
     import torch
     from . import _native
-    lib = _native.lib()
     x = _prep(x, torch.float32)
     if x.dim() < 1 or x.numel() == 0:
         raise ValueError(f"x must be a non-empty [..., N] tensor, got shape {tuple(x.shape)}")
@@ -372,12 +347,8 @@ def standardize(x, eps=1e-8, out=None, return_stats=False):
     elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
               and tuple(out.shape) == tuple(x.shape)):
         raise ValueError(f"out must be a contiguous float32 device tensor of shape {tuple(x.shape)}")
-    n = C.c_size_t(0)
-    _native.check(lib.dronesim_standardize_workspace(R, N, C.byref(n)), "dronesim_standardize_workspace")
-    ws = torch.empty(int(n.value) // 8, dtype=torch.float64, device=x.device)
+    ws_bytes = _native.workspace("dronesim_standardize_workspace", R, N)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device)
     stats = torch.empty(2, N, dtype=torch.float32, device=x.device) if return_stats else None
-    with torch.cuda.device(x.device):
-        rc = lib.dronesim_standardize(x.data_ptr(), out.data_ptr(), None if stats is None else stats.data_ptr(), R, N, float(eps),
-                                      ws.data_ptr(), int(n.value), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _native.check(rc, "dronesim_standardize")
+    _native.call("dronesim_standardize", x, out, stats, R, N, float(eps), ws, ws_bytes)
     return (out, stats) if return_stats else out

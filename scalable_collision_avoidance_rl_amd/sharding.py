@@ -9,7 +9,6 @@ per episode -- or per K steps -- makes the global figures available on every ran
 message is tens of bytes: latency-bound, kept off the per-step path."""
 from __future__ import annotations
 
-import ctypes as C
 
 from .drone_env import shard_range  # noqa: F401  (re-exported)
 
@@ -36,11 +35,7 @@ class EpisodeStats:
                 self._scratch = torch.zeros(_native.STATS_SCRATCH_DOUBLES, dtype=torch.float64, device=self.vec.device)
             r, tr = rewards.contiguous(), true_rewards.contiguous()
             nc = n_collisions.to(torch.int32).contiguous()
-            with torch.cuda.device(self.vec.device):
-                rc = _native.lib().dronesim_episode_stats(r.data_ptr(), tr.data_ptr(), nc.data_ptr(), E, N,
-                                                          self.vec.data_ptr(), self._scratch.data_ptr(),
-                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _native.check(rc, "dronesim_episode_stats")
+            _native.call("dronesim_episode_stats", r, tr, nc, E, N, self.vec, self._scratch, device=self.vec.device)
             return
         self.vec += torch.stack([rewards.sum(dtype=self.vec.dtype), true_rewards.sum(dtype=self.vec.dtype),
                                  n_collisions.sum(dtype=self.vec.dtype),

@@ -31,10 +31,9 @@ budget: ``obstacle_rate`` in (0, 1], default ``rate``.  For a listed disc the ga
 There is no CPU fallback; importing this module needs neither a GPU nor the library."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
-from ._native import MAX_AGENTS as _MAX_AGENTS, MAX_K as _MAX_K
+from ._native import MAX_AGENTS as _MAX_AGENTS, MAX_K as _MAX_K, check_tensor as _check_tensor
 
 
 def _number(name, x):
@@ -78,13 +77,7 @@ def _shield_shapes(actions, z, nbr, out, radius, E, N, k1, c, device):
     if out is not None:
         want += (("out", out, torch.float32, (E, N, 2)),)
     for name, x, dtype, shape in want:
-        if not torch.is_tensor(x):
-            raise ValueError(f"{name} must be a tensor, got {type(x).__name__}")
-        if x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}, got {x.dtype} {tuple(x.shape)}"
-                             f"{'' if x.is_contiguous() else ' (not contiguous)'}")
-        if x.device != device:
-            raise ValueError(f"{name} must live on the env's device {device}, got {x.device}")
+        _check_tensor(name, x, dtype, shape, device)
 
 
 class ActionShield:
@@ -142,7 +135,6 @@ class ActionShield:
         nbr = env.nbr_idx if nbr is None else nbr
         radius = env._radius
         _shield_shapes(actions, z, nbr, out, radius, E, N, k1, c, env.device)
-        lib = _native.lib()
         if self.intervened is None:
             self._alloc()
         if out is None:
@@ -150,25 +142,15 @@ class ActionShield:
         field = self.obstacles
         if field is not None:                               # the agent's obstacle list, from the observation it acts on
             orow, oid = field.sense(z)
-        with torch.cuda.device(env.device):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if field is None:
-                rc = lib.dronesim_action_shield(z.data_ptr(), nbr.data_ptr(), actions.data_ptr(), radius.data_ptr(), self.rate, self.margin,
-                                                self.u_max, dt, E, N, k1, c, out.data_ptr(), self.intervened.data_ptr(),
-                                                self.correction.data_ptr(), stream)
-                _native.check(rc, "dronesim_action_shield")
-            else:
-                rc = lib.dronesim_action_shield_obstacles(z.data_ptr(), nbr.data_ptr(), actions.data_ptr(), radius.data_ptr(), self.rate,
-                                                          self.margin, self.u_max, dt, E, N, k1, c, out.data_ptr(),
-                                                          self.intervened.data_ptr(), self.correction.data_ptr(), orow.data_ptr(),
-                                                          oid.data_ptr(), field.m, field.M, self.obstacle_rate, stream)
-                _native.check(rc, "dronesim_action_shield_obstacles")
-            if self.stats:
-                t = self._totals
-                rc = lib.dronesim_shield_totals(self.intervened.data_ptr(), self.correction.data_ptr(), E, N, t["interventions"].data_ptr(),
-                                                t["nonfinite"].data_ptr(), t["correction_sum"].data_ptr(), t["correction_max"].data_ptr(),
-                                                stream)
-                _native.check(rc, "dronesim_shield_totals")
+        shared = (z, nbr, actions, radius, self.rate, self.margin, self.u_max, dt, E, N, k1, c, out, self.intervened, self.correction)
+        if field is None:
+            _native.call("dronesim_action_shield", *shared)
+        else:
+            _native.call("dronesim_action_shield_obstacles", *shared, orow, oid, field.m, field.M, self.obstacle_rate)
+        if self.stats:
+            t = self._totals
+            _native.call("dronesim_shield_totals", self.intervened, self.correction, E, N, t["interventions"], t["nonfinite"],
+                         t["correction_sum"], t["correction_max"])
         self.calls += 1
         return out
 

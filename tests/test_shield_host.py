@@ -163,16 +163,15 @@ def test_evaluator_refuses_a_shield_of_another_env():
 def test_library_exports_the_shield_entry_points_with_the_declared_argtypes():
     lib = _native.lib()
     vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-    want = dict(dronesim_action_shield=[vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp],
-                dronesim_shield_totals=[vp, vp, i32, i32, vp, vp, vp, vp, vp])
+    want = ("dronesim_action_shield", "dronesim_shield_totals")
     assert set(want) == set(NEW_SYMBOLS)
     header = open(_native.HEADER_PATH).read()
     kinds = {"const float *": vp, "const int32_t *": vp, "const uint8_t *": vp, "float *": vp, "uint8_t *": vp, "int64_t *": vp,
              "double *": vp, "void *": vp, "float": f32, "int": i32}
-    for name, args in want.items():
+    for name in want:
         assert name in _native.SYMBOLS
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == args and fn.restype is C.c_int, name
+        assert fn.restype is C.c_int, name
         assert f"int {name}(" in header, name
         params = header.split(f"int {name}(")[1].split(");")[0].replace("\n", " ").split(",")
         declared = []
@@ -180,7 +179,7 @@ def test_library_exports_the_shield_entry_points_with_the_declared_argtypes():
             p = " ".join(p.split())
             t = p[:p.rindex("*") + 1] if "*" in p else p.rsplit(" ", 1)[0]
             declared.append(kinds[t])
-        assert declared == args, name
+        assert declared == list(fn.argtypes), name
     assert lib.dronesim_version() == 600
 
 

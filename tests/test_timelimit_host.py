@@ -120,11 +120,10 @@ def test_library_exports_the_entry_points_with_the_declared_argtypes():
     lib = _native.lib()
     vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
     header = open(_native.HEADER_PATH).read()
-    for name, argtypes in ((ENDS, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]),
-                           (SCAN, [vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, vp])):
+    for name in (ENDS, SCAN):
         assert name in _native.SYMBOLS
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is C.c_int
+        assert fn.restype is C.c_int
         assert f"int {name}(" in header
     # the header's parameter lists, type by type, against the argtypes
     kinds = {"const uint8_t *": vp, "const float *": vp, "uint8_t *": vp, "int32_t *": vp, "float *": vp, "void *": vp,
