@@ -11,6 +11,7 @@ each (E x rounds >= --episodes), every step of every env in one launch, and the 
     python examples/benchmark_agent.py ... --safety                        # closest approach, arrival and formation error per episode
     python examples/benchmark_agent.py ... --shield [--shield-rate X --shield-margin X]   # the same episodes again through an ActionShield
     python examples/benchmark_agent.py ... --obstacles 8 [--shield --safety]              # static discs that matter
+    python examples/benchmark_agent.py ... --obstacles 8 --per-env-obstacles               # a list of its own for every env
 
 ``--obs-norm FILE``: an `ObsNormalizer.state_dict()` saved with ``torch.save``; the actor and the critic then read the normalised
 observation (the reference's files carry no statistics, so there is none by default).
@@ -37,7 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import scalable_collision_avoidance_rl_amd.drone_env as drone_env          # was: import drone_env
 from scalable_collision_avoidance_rl_amd.evaluate import Evaluator, TrainedAgent    # was: from SAC_agents import *
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
-from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles
+from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles, place_obstacles_per_env
 from scalable_collision_avoidance_rl_amd.shield import ActionShield
 
 
@@ -57,12 +58,15 @@ def main():
     ap.add_argument("--shield-rate", type=float, default=0.25, help="share of a gap an agent may close per step, in (0, 0.5]")
     ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
     ap.add_argument("--obstacles", type=int, default=0, help="static discs off the goals, sensed, reported and (--shield) enforced")
+    ap.add_argument("--per-env-obstacles", action="store_true", help="every env gets --obstacles N discs of its own")
     ap.add_argument("--obstacle-rate", type=float, default=None, help="share of the gap to a disc an agent may close per step, in (0, 1]")
     ap.add_argument("--obstacle-inputs", action="store_true",
                     help="the saved networks were trained obstacle-aware: they read the record plus the field's obstacle columns")
     a = ap.parse_args()
     if a.obstacle_inputs and (not a.obstacles or a.controller):
         ap.error("--obstacle-inputs needs --obstacles N and saved networks (no --controller)")
+    if a.per_env_obstacles and not a.obstacles:
+        ap.error("--per-env-obstacles needs --obstacles N")
     a.safety = a.safety or a.obstacles > 0
 
     if a.controller:
@@ -83,14 +87,21 @@ def main():
 
     obs_norm = None
     field = None
-    if a.obstacles:
+    if a.per_env_obstacles:
+        discs, counts = place_obstacles_per_env(env.grid, a.obstacles, env.n_envs, seed=0, keep_clear=env.end_points.reshape(n_agents, 2),
+                                                clearance=0.3)
+        field = ObstacleField(env, discs, m=2, per_env=True, counts=counts)
+    elif a.obstacles:
         discs = place_obstacles(env.grid, a.obstacles, seed=0, keep_clear=env.end_points.reshape(n_agents, 2), clearance=0.3)
         field = ObstacleField(env, discs, m=2)
     if a.obs_norm:
         import torch
         width = field.obs_width if a.obstacle_inputs else env.local_state_space
         obs_norm = ObsNormalizer(n_agents, width, env.device).load_state_dict(torch.load(a.obs_norm))
-    if field is not None:
+    if field is not None and field.per_env:
+        print(f"Obstacles = a list per env: {int(counts.min())} .. {int(counts.max())} discs (of {a.obstacles} drawn per env; the rest "
+              f"covered a goal)")
+    elif field is not None:
         print(f"Obstacles = {field.M} discs (of {a.obstacles} drawn; the rest covered a goal), radius {discs[:, 2].min():.2f} .. "
               f"{discs[:, 2].max():.2f} m" if field.M else f"Obstacles = 0 (all {a.obstacles} drawn covered a goal)")
     ev = Evaluator(env, actor, critic, gamma=0.99, obs_norm=obs_norm, safety=a.safety, obstacles=field, obstacle_inputs=a.obstacle_inputs)

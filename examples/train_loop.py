@@ -8,7 +8,7 @@ actor loss + clip + Adam, for all N agents' networks at once in HIP.
                                   [--lam X] [--window T] [--time-limit {terminal,bootstrap}] [--ent-coef X]
                                   [--normalize-advantage] [--minibatches K] [--shuffle-seed S] [--target-kl X] [--vf-clip X]
                                   [--obs-norm] [--obs-clip X] [--share all] [--grid G] [--reward-norm] [--reward-clip X]
-                                  [--shield] [--shield-rate X] [--shield-margin X] [--obstacles N]
+                                  [--shield] [--shield-rate X] [--shield-margin X] [--obstacles N] [--per-env-obstacles]
 
 ``--learner ppo`` trains with `PPOLearner` instead -- the batched `SPPOAgents.train` (SAC_agents.py:410-573): the window is
 used for ``--epochs`` critic-and-actor steps with the clipped probability ratio (train_problem.py:43, ``M = 10``).
@@ -55,6 +55,9 @@ window's decisions the shield changed and the mean correction.  ``--obstacles N`
 reference's sizes off the goals (`place_obstacles`, an `ObstacleField`): the shield then also projects onto one half-plane per
 listed disc, and every episode line shows the share of the window's first episodes in which no agent touched a disc.  Without
 ``--obstacle-inputs`` the reward and the networks' input do not know the discs: the policy meets them as part of the environment.
+``--per-env-obstacles`` gives every env N discs of its own (`place_obstacles_per_env`, ``ObstacleField(per_env=True)``) and redraws
+them between windows with ``field.set(*place_obstacles_per_env(..., seed=window))``, as the reference's ``reset()`` redraws its
+discs: the networks' obstacle columns and the obstacle cost then describe as many maps as there are envs and windows.
 
 ``--obstacle-inputs`` makes the training obstacle-aware: the networks read `ObstacleField.observe` -- the record plus
 ``(p.x, p.y, r)`` of the two nearest discs in range, 12 inputs at k = 2 -- in the rollout (ahead of ``--obs-norm``) and in the
@@ -80,7 +83,7 @@ from scalable_collision_avoidance_rl_amd import drones
 from scalable_collision_avoidance_rl_amd.drone_env import dt
 from scalable_collision_avoidance_rl_amd.learner import PPOLearner, SA2CLearner
 from scalable_collision_avoidance_rl_amd.obs_norm import ObsNormalizer
-from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles
+from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, place_obstacles, place_obstacles_per_env
 from scalable_collision_avoidance_rl_amd.policies import BatchedMLP
 from scalable_collision_avoidance_rl_amd.reward_norm import RewardNormalizer
 from scalable_collision_avoidance_rl_amd.rollout_buffer import RolloutStorage
@@ -129,6 +132,8 @@ def main():
     ap.add_argument("--shield-margin", type=float, default=0.05, help="clearance [m] below which a gap may not shrink at all")
     ap.add_argument("--obstacles", type=int, default=0,
                     help="static discs off the goals, enforced by the shield (needs --shield or an --obstacle-weight > 0)")
+    ap.add_argument("--per-env-obstacles", action="store_true",
+                    help="every env gets discs of its own (--obstacles N each), redrawn between windows as the reference's reset() does")
     ap.add_argument("--obstacle-inputs", action="store_true",
                     help="obstacle-aware training: the networks read the record plus the nearest discs, the reward pays the obstacle cost")
     ap.add_argument("--obstacle-weight", type=float, default=None,
@@ -136,6 +141,8 @@ def main():
     args = ap.parse_args()
     if args.obstacle_inputs and not args.obstacles:
         ap.error("--obstacle-inputs needs --obstacles N")
+    if args.per_env_obstacles and not args.obstacles:
+        ap.error("--per-env-obstacles needs --obstacles N")
     if args.obstacle_weight is not None and not args.obstacle_inputs:
         ap.error("--obstacle-weight needs --obstacle-inputs (a cost the networks cannot see teaches nothing)")
     if args.obstacle_weight is not None and not 0.0 <= args.obstacle_weight < float("inf"):
@@ -153,7 +160,12 @@ def main():
     env = drones(N, 0, [args.grid, args.grid], "O", k_closest=2, deltas=np.ones(N), simplify_zstate=True, n_envs=E, batched=True,
                  device=dev, seed=1, auto_reset=True)
     field = None
-    if args.obstacles:
+    own_discs = lambda window: place_obstacles_per_env(env.grid, args.obstacles, E, seed=window,
+                                                       keep_clear=env.end_points.reshape(N, 2), clearance=0.3)
+    if args.per_env_obstacles:                               # a list per env: no policy can memorise one map
+        discs, counts = own_discs(0)
+        field = ObstacleField(env, discs, m=2, per_env=True, counts=counts)
+    elif args.obstacles:
         field = ObstacleField(env, place_obstacles(env.grid, args.obstacles, seed=0, keep_clear=env.end_points.reshape(N, 2),
                                                    clearance=0.3), m=2)
     seen_field = field if args.obstacle_inputs else None     # the field whose columns the networks read
@@ -199,6 +211,8 @@ def main():
         norm.update(augment(storage.z_pre))
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for ep in range(args.episodes):
+        if args.per_env_obstacles and ep:                    # other discs for every window, uploaded in place (inside a stored
+            field.set(*own_discs(ep))                        # window a list does not change: the tables and the cost read one)
         storage.begin()
         if shield is not None:
             shield.reset_totals()
@@ -239,7 +253,8 @@ def main():
             tab = field.episode_safety(storage)
             ok = tab["ep_len"] > 0
             free = (ok & (tab["ep_obstacle_hit_steps"] == 0)).sum().item() / max(int(ok.sum().item()), 1)
-            ppo += f"  obstacle-free episodes {free:.2%} ({field.M} discs)"
+            discs = f"{float(field.counts.mean()):.1f} discs per env, redrawn" if field.per_env else f"{field.M} discs"
+            ppo += f"  obstacle-free episodes {free:.2%} ({discs})"
         if "obstacle_cost" in out:
             ppo += f"  obstacle cost {float(out['obstacle_cost'].mean()):.4g} (weight {obstacle_weight:.3g})"
         print(f"episode {ep}: mean reward {float(storage.reward.mean()):+.4f}  critic loss {float(out['critic_loss'].mean()):.3f}  "

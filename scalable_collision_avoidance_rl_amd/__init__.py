@@ -10,7 +10,7 @@ from .drone_env import (DroneState, StepResult, clip_deltas, dim, drones, dt, fo
 from .evaluate import Evaluator, TrainedAgent
 from .learner import PPOLearner, SA2CLearner
 from .obs_norm import ObsNormalizer
-from .obstacles import ObstacleField, place_obstacles
+from .obstacles import ObstacleField, place_obstacles, place_obstacles_per_env
 from .reward_norm import RewardNormalizer
 from .rollout_buffer import episode_ends, lambda_returns
 from .shield import ActionShield
@@ -18,4 +18,4 @@ from .shield import ActionShield
 __all__ = ["drones", "DroneState", "StepResult", "dim", "dt", "max_time_steps", "formation_O",
            "clip_deltas", "lattice_divisions", "shard_range", "gradient_control", "proportional_control",
            "SA2CLearner", "PPOLearner", "Evaluator", "TrainedAgent", "lambda_returns", "episode_ends", "ObsNormalizer",
-           "RewardNormalizer", "ActionShield", "ObstacleField", "place_obstacles"]
+           "RewardNormalizer", "ActionShield", "ObstacleField", "place_obstacles", "place_obstacles_per_env"]

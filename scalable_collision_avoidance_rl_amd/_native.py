@@ -16,6 +16,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # DRONESIM_LIB lets a developer A/B an alternative build of the SAME HIP library (no other backend exists)
 LIB_PATH = os.environ.get("DRONESIM_LIB") or os.path.join(_PKG, "libdronesim.so")
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dronesim.h")
+# per-env obstacle sets: a product header of its own (libdronesim.so exports its symbols too)
+ENV_OBSTACLES_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dronesim_env_obstacles.h")
 # the float64 verification variant (test infrastructure) is a library of its own: the product library exports the product only
 VERIFY_LIB_PATH = os.environ.get("DRONESIM_VERIFY_LIB") or os.path.join(_PKG, "libdronesim_verify.so")
 VERIFY_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dronesim_verify.h")
@@ -134,24 +136,29 @@ def _read_header(path):
         return parse_header(f.read())
 
 
-# The package needs the repository's include/ directory next to it: dronesim.h is read at import (names, signatures, constants).
+# The package needs the repository's include/ directory next to it: dronesim.h and dronesim_env_obstacles.h are read at import
+# (names, signatures, constants).  SIGNATURES / SYMBOLS mean "what dronesim.h declares"; the per-env obstacle entries have a table
+# of their own, ENV_OBSTACLE_SIGNATURES / ENV_OBSTACLE_SYMBOLS, bound on the same library.
 # dronesim_verify.h is test infrastructure: without it the package still imports, VERIFY_SYMBOLS is empty and verify_lib() raises.
 _CONSTANTS, SIGNATURES = _read_header(HEADER_PATH)
+_ENV_OBSTACLE_CONSTANTS, ENV_OBSTACLE_SIGNATURES = _read_header(ENV_OBSTACLES_HEADER_PATH)
 VERIFY_SIGNATURES = _read_header(VERIFY_HEADER_PATH)[1] if os.path.exists(VERIFY_HEADER_PATH) else {}
 # every symbol the headers declare (tests check the libraries export all of them)
 SYMBOLS, VERIFY_SYMBOLS = tuple(SIGNATURES), tuple(VERIFY_SIGNATURES)
+ENV_OBSTACLE_SYMBOLS = tuple(ENV_OBSTACLE_SIGNATURES)
 
 
-def _constant(name):
-    if name not in _CONSTANTS:
-        raise ImportError(f"{HEADER_PATH}: no `#define DRONESIM_{name} <integer>` (an integer literal, bare or in parentheses)")
-    return _CONSTANTS[name]
+def _constant(name, constants=_CONSTANTS, path=HEADER_PATH):
+    if name not in constants:
+        raise ImportError(f"{path}: no `#define DRONESIM_{name} <integer>` (an integer literal, bare or in parentheses)")
+    return constants[name]
 
 
 (OK, EINVAL, EUNSUPPORTED, ELAUNCH, CONTROL_PROPORTIONAL, CONTROL_GRADIENT, MAX_K, MAX_AGENTS, MAX_OBSTACLES, MAX_SENSE,
  STATS_SCRATCH_DOUBLES, EPISODE_REDUCE_DOUBLES) = map(_constant, (
      "OK", "EINVAL", "EUNSUPPORTED", "ELAUNCH", "CONTROL_PROPORTIONAL", "CONTROL_GRADIENT", "MAX_K", "MAX_AGENTS", "MAX_OBSTACLES",
      "MAX_SENSE", "STATS_SCRATCH_DOUBLES", "EPISODE_REDUCE_DOUBLES"))
+MAX_ENV_OBSTACLES = _constant("MAX_ENV_OBSTACLES", _ENV_OBSTACLE_CONSTANTS, ENV_OBSTACLES_HEADER_PATH)
 
 
 def _load(path, signatures, hint):
@@ -175,7 +182,7 @@ def lib():
     """Load libdronesim.so (built by __graft_entry__.build() / `make -C <pkg>/csrc`)."""
     global _lib
     if _lib is None:
-        _lib = _load(LIB_PATH, SIGNATURES, "Run `python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
+        _lib = _load(LIB_PATH, {**SIGNATURES, **ENV_OBSTACLE_SIGNATURES}, "Run `python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                      "scalable_collision_avoidance_rl_amd/csrc`) with hipcc for gfx950.")
     return _lib
 
@@ -203,6 +210,14 @@ def check_tensor(name, x, dtype, shape, device):
         raise ValueError(f"{name} must live on the device {device}, got {x.device}")
 
 
+def signature(name):
+    """The `Signature` of a product entry point, from whichever product header declares it."""
+    sig = SIGNATURES.get(name) or ENV_OBSTACLE_SIGNATURES.get(name)
+    if sig is None:
+        raise KeyError(f"{name}: declared by neither {HEADER_PATH} nor {ENV_OBSTACLES_HEADER_PATH}")
+    return sig
+
+
 def call(name, *args, device=None):
     """The one way a wrapper launches an entry point of libdronesim.so: a tensor goes as its data_ptr(), None as NULL, anything else
     as it is; the call is made on `device` (default: that of the first tensor argument) and, where the header's last parameter is
@@ -218,7 +233,7 @@ def call(name, *args, device=None):
             a = a.data_ptr()
         ptrs.append(a)
     fn = getattr(lib(), name)
-    if SIGNATURES[name].stream:
+    if signature(name).stream:
         if device is None:
             raise ValueError(f"{name}: no tensor argument and no device= to launch on")
         with torch.cuda.device(device):

@@ -1,9 +1,10 @@
-// Host-side pieces shared by the entry points that read observation records z [..][N][k1][c] (shield.hip, obstacles.hip,
+// Host-side pieces shared by the entry points that read observation records z [..][N][k1][c] (shield.hip, obstacles.hip, env_obstacles.hip,
 // evaluate.hip): the load-width rule of their kernels and the checks of the arguments they have in common.  Every check returns
 // DRONESIM_OK or fails under the entry's own name (`where`), so an entry states only the order of its checks and its own ones.
 #pragma once
 #include <limits.h>
 #include "common.hpp"
+#include "dronesim_env_obstacles.h"
 
 // Floats per load of a record's rows: 4 (c = 2, k1 even, 16-byte aligned: two rows per load), 2 (c = 2, 8-byte aligned: one row per
 // load) or 1.  `addresses`: the OR of the bases of every array of records the kernel reads (z, and z_final where there is one).
@@ -32,6 +33,16 @@ inline int check_discs(const char *where, int M, const float *obstacles, bool re
     char what[96];
     if (reads_list) snprintf(what, sizeof what, "M outside 0..%d, or NULL obstacles with M > 0", DRONESIM_MAX_OBSTACLES);
     else snprintf(what, sizeof what, "M outside 0..%d", DRONESIM_MAX_OBSTACLES);
+    return fail_at(where, what);
+}
+
+// the per-env lists [E][M][3] (include/dronesim_env_obstacles.h): the row count M of every env, and the lists where M > 0; the
+// counts [E] may be NULL (every env holds M discs), their VALUES are device data and are clamped by the kernels
+inline int check_env_discs(const char *where, int M, const float *obstacles)
+{
+    if (M >= 0 && M <= DRONESIM_MAX_ENV_OBSTACLES && (M == 0 || obstacles)) return DRONESIM_OK;
+    char what[96];
+    snprintf(what, sizeof what, "M outside 0..%d, or NULL obstacles with M > 0", DRONESIM_MAX_ENV_OBSTACLES);
     return fail_at(where, what);
 }
 

@@ -14,6 +14,9 @@ the does not change, and the reward and the networks' input change only where `o
   ObstacleField.episode_safety   `dronesim_episode_obstacle_safety`: clearance and hit tables of every env's first episode from a
                                  stored window; ``Evaluator(..., safety=True, obstacles=field)`` reports them
   place_obstacles                host numpy: discs of the reference's sizes that leave given points (the goals) free
+  ObstacleField(per_env=True)    a disc list PER ENV, ``[E,M,3]`` with ``counts [E]``: the same four methods on the
+                                 `dronesim_env_obstacle_*` entries (csrc/env_obstacles.hip, include/dronesim_env_obstacles.h)
+  place_obstacles_per_env        `place_obstacles` per env, seeded ``[seed, e]``, zero-padded to one width
 
 The rule (include/dronesim.h states it for the kernels, tests/obstacle_ref.py in float64): ``x = z[0] + xF[i][0]``,
 ``y = z[1] + xF[i][1]``; to disc ``o``: ``p = o.xy - (x, y)``, ``d = |p|``, ``gap = d - radius[i] - o.r``.  A disc is in range where
@@ -21,15 +24,21 @@ The rule (include/dronesim.h states it for the kernels, tests/obstacle_ref.py in
 obstacle cost is the reference's collision term with a disc in the neighbour's place: over ALL discs ``9.99e3`` where ``gap <= 0``,
 ``log(sense[i] / gap)`` where ``0 < gap <= sense[i]``, 0 otherwise, times a weight (tests/obstacle_obs_ref.py restates it).
 
-One list ``[M,3]`` serves all envs.  ``env.reset(renew_obstacles=True)`` (the reference's default) redraws ``env.obstacles``; a
-field follows only through ``field.set(env.obstacles)``.
+Without ``per_env`` one list ``[M,3]`` serves all envs.  ``env.reset(renew_obstacles=True)`` (the reference's default) redraws
+``env.obstacles``; a field follows only through ``field.set(env.obstacles)``.  With ``per_env=True`` every env senses, avoids and
+pays for its OWN discs: ``obstacles [E,M,3]`` (``M <= 64``), env ``e`` holding rows ``0..counts[e]-1``, ids env-local; the rule is
+the same with env ``e``'s list in place of the shared one, and the outputs are bit-identical to the shared kernels run on that
+env's records with that env's list.  ``field.set(*place_obstacles_per_env(..., seed=window))`` between windows redraws them the way
+the reference's ``reset()`` does; inside a stored window a list does not change (the tables and the shaped reward read one list per
+env for the whole window).  The shield, the `Evaluator` and the learners work through the field and need nothing else.
 
 There is no CPU fallback; importing this module needs neither a GPU nor the library."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._native import MAX_AGENTS as _MAX_AGENTS, MAX_K as _MAX_K, MAX_OBSTACLES, MAX_SENSE, check_tensor as _tensor_check
+from ._native import (MAX_AGENTS as _MAX_AGENTS, MAX_ENV_OBSTACLES, MAX_K as _MAX_K, MAX_OBSTACLES, MAX_SENSE,
+                      check_tensor as _tensor_check)
 
 OBSTACLE_TABLES = ("min_obstacle_gap", "obstacle_hit_steps", "ep_min_obstacle_gap", "ep_obstacle_hit_steps")
 
@@ -54,6 +63,52 @@ def check_obstacles(obstacles, M=None):
     if M is not None and obs.shape[0] != M:
         raise ValueError(f"M is fixed at construction: this field holds {M} obstacles, got {obs.shape[0]}")
     return obs
+
+
+def check_env_obstacles(obstacles, counts=None, E=None, M=None):
+    """Per-env lists: ``obstacles`` as a float64 ``[E,M,3]`` array (x, y, r) and ``counts`` as an int64 ``[E]`` array (default: all
+    ``M``), or ValueError: wrong rank or shape, ``M > MAX_ENV_OBSTACLES``, non-finite entries or ``r < 0`` in ANY row (the rows
+    behind an env's count are padding, but they are uploaded), counts that are no integers in ``0..M``, or -- with ``E`` / ``M`` --
+    another env count / row count than those.  Nothing here touches a device."""
+    try:
+        obs = np.array(obstacles, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"per-env obstacles must be an [E,M,3] array of (x, y, r), got {type(obstacles).__name__}") from None
+    if obs.ndim != 3 or obs.shape[2] != 3:
+        raise ValueError(f"per-env obstacles must be an [E,M,3] array of (x, y, r), got shape {obs.shape}")
+    if E is not None and obs.shape[0] != E:
+        raise ValueError(f"per-env obstacles hold one list per env: E = {E}, got {obs.shape[0]} lists")
+    if obs.shape[1] > MAX_ENV_OBSTACLES:
+        raise ValueError(f"at most {MAX_ENV_OBSTACLES} obstacles per env, got M = {obs.shape[1]}")
+    if M is not None and obs.shape[1] != M:
+        raise ValueError(f"M is fixed at construction: this field holds {M} rows per env, got {obs.shape[1]}")
+    if not np.isfinite(obs).all():
+        raise ValueError("obstacles must be finite")
+    if (obs[:, :, 2] < 0).any():
+        raise ValueError("obstacle radii must be >= 0")
+    n_envs, rows = obs.shape[:2]
+    if counts is None:
+        return obs, np.full(n_envs, rows, np.int64)
+    try:
+        cnt = np.array(counts)
+    except (TypeError, ValueError):
+        raise ValueError(f"counts must be [E] integers, got {type(counts).__name__}") from None
+    if cnt.shape != (n_envs,) or cnt.dtype == np.bool_ or not np.issubdtype(cnt.dtype, np.integer):
+        raise ValueError(f"counts must be [E] = ({n_envs},) integers, got {cnt.dtype} {cnt.shape}")
+    if ((cnt < 0) | (cnt > rows)).any():
+        raise ValueError(f"counts must be in 0..M = 0..{rows}, got {int(cnt.min())}..{int(cnt.max())}")
+    return obs, cnt.astype(np.int64)
+
+
+def env_obstacle_plan(N, M, m=1):
+    """`dronesim_env_obstacle_plan`, a host query: how the per-env kernels reach their lists at ``N`` agents, ``M`` rows per env
+    and ``m`` slots -- ``dict(staged=bool, rows_per_block=int, lds_bytes=int)``: staged in LDS per workgroup or read directly, the
+    most rows (envs) a 256-record workgroup touches, and the most LDS a workgroup holds.  Needs the library, no GPU."""
+    import ctypes as C
+    from . import _native
+    staged, rows, lds = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _native.call("dronesim_env_obstacle_plan", int(N), int(M), int(m), C.byref(staged), C.byref(rows), C.byref(lds))
+    return dict(staged=bool(staged.value), rows_per_block=int(rows.value), lds_bytes=int(lds.value))
 
 
 def check_m(m):
@@ -107,7 +162,22 @@ def place_obstacles(grid, n, seed=0, keep_clear=None, clearance=0.0, centres=Non
     return obs
 
 
-def _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final):
+def place_obstacles_per_env(grid, n, E, seed=0, keep_clear=None, clearance=0.0):
+    """Host numpy: a list per env.  Env ``e``'s discs are exactly ``place_obstacles(grid, n, seed=[seed, e], keep_clear=...,
+    clearance=...)``, zero-padded to ``n`` rows.  Returns ``(obstacles [E,n,3] float64, counts [E] int64)`` -- what
+    ``ObstacleField(env, obstacles, per_env=True, counts=counts)`` and ``field.set(obstacles, counts)`` take."""
+    if isinstance(E, bool) or int(E) != E or E < 1:
+        raise ValueError(f"E must be an integer >= 1, got {E!r}")
+    if isinstance(seed, bool) or int(seed) != seed or seed < 0:
+        raise ValueError(f"seed must be an integer >= 0, got {seed!r}")
+    lists = [place_obstacles(grid, n, seed=[int(seed), e], keep_clear=keep_clear, clearance=clearance) for e in range(int(E))]
+    obs = np.zeros((int(E), int(n), 3))
+    for e, discs in enumerate(lists):
+        obs[e, :discs.shape[0]] = discs
+    return obs, np.array([discs.shape[0] for discs in lists], np.int64)
+
+
+def _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final, per_env=False):
     """(T, E, N, d) of `episode_obstacle_safety`'s arguments, or ValueError -- shapes, dtypes and devices only."""
     import torch
     if not all(torch.is_tensor(x) for x in (z, done, xF, radius, obstacles)) or z.dim() != 4:
@@ -122,7 +192,10 @@ def _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final):
     _tensor_check("done", done, torch.uint8, (T, E), dev)
     _tensor_check("xF", xF, torch.float32, (N, 2), dev)
     _tensor_check("radius", radius, torch.float32, (N,), dev)
-    if obstacles.dim() != 2 or obstacles.shape[1] != 3 or obstacles.shape[0] > MAX_OBSTACLES:
+    if per_env:
+        if obstacles.dim() != 3 or tuple(obstacles.shape[::2]) != (E, 3) or obstacles.shape[1] > MAX_ENV_OBSTACLES:
+            raise ValueError(f"per-env obstacles must be [E,M,3] = [{E},M,3] with M <= {MAX_ENV_OBSTACLES}, got {tuple(obstacles.shape)}")
+    elif obstacles.dim() != 2 or obstacles.shape[1] != 3 or obstacles.shape[0] > MAX_OBSTACLES:
         raise ValueError(f"obstacles must be [M,3] with M <= {MAX_OBSTACLES}, got {tuple(obstacles.shape)}")
     _tensor_check("obstacles", obstacles, torch.float32, tuple(obstacles.shape), dev)
     if z_final is not None:
@@ -145,7 +218,36 @@ def episode_obstacle_safety(z, done, xF, radius, obstacles, c, z_final=None, out
     T, E, N, d = _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final)
     if c not in (2, 5) or d % c:
         raise ValueError(f"c must be 2 or 5 and divide the record's {d} floats, got {c!r}")
-    k1, M, dev = d // c, int(obstacles.shape[0]), z.device
+    k1, M = d // c, int(obstacles.shape[0])
+    out = _safety_tables(out, E, N, z.device)
+    _native.call("dronesim_episode_obstacle_safety", z, z_final, done, xF, radius, obstacles if M else None, T, E, N, k1, c, M,
+                 out["ep_len"], out.get("min_obstacle_gap"), out.get("obstacle_hit_steps"), out.get("ep_min_obstacle_gap"),
+                 out.get("ep_obstacle_hit_steps"))
+    return out
+
+
+def episode_env_obstacle_safety(z, done, xF, radius, obstacles, counts, c, z_final=None, out=None):
+    """`dronesim_episode_env_obstacle_safety`: `episode_obstacle_safety` with a list per env -- ``obstacles [E,M,3]`` float32 and
+    ``counts [E]`` int32 on the device (``None``: every env holds ``M`` discs), env ``e`` reading its rows ``0..counts[e]-1`` for the
+    whole window.  The same five tables; an env without discs gets ``+inf`` and 0, as ``M = 0`` does there."""
+    import torch
+    from . import _native
+    T, E, N, d = _obstacle_safety_shapes(z, done, xF, radius, obstacles, z_final, per_env=True)
+    if c not in (2, 5) or d % c:
+        raise ValueError(f"c must be 2 or 5 and divide the record's {d} floats, got {c!r}")
+    if counts is not None:
+        _tensor_check("counts", counts, torch.int32, (E,), z.device)
+    k1, M = d // c, int(obstacles.shape[1])
+    out = _safety_tables(out, E, N, z.device)
+    _native.call("dronesim_episode_env_obstacle_safety", z, z_final, done, xF, radius, obstacles if M else None, counts, T, E, N,
+                 k1, c, M, out["ep_len"], out.get("min_obstacle_gap"), out.get("obstacle_hit_steps"),
+                 out.get("ep_min_obstacle_gap"), out.get("ep_obstacle_hit_steps"))
+    return out
+
+
+def _safety_tables(out, E, N, dev):
+    """`episode_obstacle_safety`'s ``out``, checked, or new tables."""
+    import torch
     shapes = dict(ep_len=(torch.int32, (E,)), min_obstacle_gap=(torch.float32, (E, N)), obstacle_hit_steps=(torch.int32, (E, N)),
                   ep_min_obstacle_gap=(torch.float32, (E,)), ep_obstacle_hit_steps=(torch.int32, (E,)))
     if out is not None:
@@ -157,9 +259,6 @@ def episode_obstacle_safety(z, done, xF, radius, obstacles, c, z_final=None, out
             raise ValueError("out needs ep_len")
     if out is None:
         out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, (dtype, shape) in shapes.items()}
-    _native.call("dronesim_episode_obstacle_safety", z, z_final, done, xF, radius, obstacles if M else None, T, E, N, k1, c, M,
-                 out["ep_len"], out.get("min_obstacle_gap"), out.get("obstacle_hit_steps"), out.get("ep_min_obstacle_gap"),
-                 out.get("ep_obstacle_hit_steps"))
     return out
 
 
@@ -182,13 +281,28 @@ class ObstacleField:
     ``s``-th nearest disc in range and ``oid [E,N,m]`` its id, empty slots ``(0, 0, 0)`` and -1.  With ``gap_min=True`` the
     attributes ``gap_min [E,N]`` (over ALL discs, ``+inf`` at ``M = 0``) and ``hit [E,N]`` uint8 are written too.  The buffers are
     allocated by the first call (the planes by the first call that asks for them) and reused: after an eager warm-up the calls
-    can be captured in a ``torch.cuda.graph``."""
+    can be captured in a ``torch.cuda.graph``.
 
-    def __init__(self, env, obstacles=None, m=2, sense=None):
+    ``per_env=True``: ``obstacles`` is ``[E,M,3]`` with ``E == env.n_envs`` and ``M <= 64``, one list per env, and ``counts [E]``
+    integers in ``0..M`` (default all ``M``) say how many rows of each env are discs (`check_env_obstacles`; without ``per_env`` a
+    3-D array is still refused).  ``M`` and ``E`` are fixed at construction; ``set(obstacles, counts=None)`` re-uploads discs and
+    counts IN PLACE.  `sense`, `observe`, `shape_reward` and `episode_safety` then run the per-env entries, with the same return
+    shapes, buffers and reuse; ids in ``oid`` are env-local.  `observe` needs leading dims that end in ``E`` (row ``q`` belongs to
+    env ``q % E``).  Attributes: ``per_env``, ``counts`` (int64 ``[E]``, None for a shared list), ``device_obstacles [E,M,3]``."""
+
+    def __init__(self, env, obstacles=None, m=2, sense=None, per_env=False, counts=None):
         if not getattr(env, "batched", False):
             raise ValueError("ObstacleField needs the batched (tensor) API of `drones`")
         self.m = check_m(m)
-        obs = check_obstacles(env.obstacles if obstacles is None else obstacles)
+        self.per_env = bool(per_env)
+        if self.per_env:
+            if obstacles is None:
+                raise ValueError("per_env=True needs obstacles [E,M,3] (the env draws one list)")
+            obs, cnt = check_env_obstacles(obstacles, counts, E=int(env.n_envs))
+        else:
+            if counts is not None:
+                raise ValueError("counts needs per_env=True")
+            obs, cnt = check_obstacles(env.obstacles if obstacles is None else obstacles), None
         N = int(env.n_agents)
         if sense is not None:
             sense = np.array(sense, np.float64)
@@ -196,16 +310,25 @@ class ObstacleField:
             if sense.shape != (N,) or np.isnan(sense).any():
                 raise ValueError(f"sense must be a number or [N] = ({N},) numbers, got shape {sense.shape}")
         import torch
-        self.env, self.M = env, int(obs.shape[0])
-        self.obstacles = obs
-        # (at least one row, so that the tensor has an address at M = 0; the kernels read M rows)
-        self._obs = torch.zeros(max(self.M, 1), 3, dtype=torch.float32, device=env.device)
-        self._obs_view = self._obs[:self.M]
+        self.env, self.M = env, int(obs.shape[-2])
+        self.obstacles, self.counts = obs, cnt
+        if self.per_env:                                       # [E,M,3] and the counts; at M = 0 the entries take NULL lists
+            self._obs = self._obs_view = torch.zeros(int(env.n_envs), self.M, 3, dtype=torch.float32, device=env.device)
+            self._counts = torch.zeros(int(env.n_envs), dtype=torch.int32, device=env.device)
+        else:
+            # (at least one row, so that the tensor has an address at M = 0; the kernels read M rows)
+            self._obs = torch.zeros(max(self.M, 1), 3, dtype=torch.float32, device=env.device)
+            self._obs_view = self._obs[:self.M]
         self._sense = None if sense is None else torch.tensor(sense, dtype=torch.float32, device=env.device)
         self.orow = self.oid = self.gap_min = self.hit = None
         self.cost = None                                       # `observe(cost=...)`'s plane of its last call
         self._x, self._cost = {}, {}                           # `observe`'s owned buffers, per leading shape
-        self.set(obs)
+        self.set(obs, cnt)
+
+    @property
+    def _lists(self):
+        """The per-env entries' ``obstacles`` argument: NULL at ``M = 0``."""
+        return self._obs if self.M else None
 
     @property
     def sense_range(self):
@@ -214,12 +337,22 @@ class ObstacleField:
 
     @property
     def device_obstacles(self):
-        """The discs as the kernels read them: float32 ``[M,3]`` on the env's device."""
+        """The discs as the kernels read them: float32 ``[M,3]`` (``[E,M,3]`` with ``per_env``) on the env's device."""
         return self._obs_view
 
-    def set(self, obstacles):
-        """Other discs, the same count: re-uploaded into the same device memory."""
+    def set(self, obstacles, counts=None):
+        """Other discs, the same count ``M`` (and, with ``per_env``, other ``counts``, default all ``M``): re-uploaded into the
+        same device memory."""
         import torch
+        if self.per_env:
+            obs, cnt = check_env_obstacles(obstacles, counts, E=int(self.env.n_envs), M=self.M)
+            self.obstacles, self.counts = obs, cnt
+            if self.M:
+                self._obs.copy_(torch.as_tensor(obs.astype(np.float32)))
+            self._counts.copy_(torch.as_tensor(cnt.astype(np.int32)))
+            return self
+        if counts is not None:
+            raise ValueError("counts needs per_env=True")
         obs = check_obstacles(obstacles, self.M)
         self.obstacles = obs
         if self.M:
@@ -242,8 +375,13 @@ class ObstacleField:
         if gap_min and self.gap_min is None:
             self.gap_min = torch.zeros(E, N, dtype=torch.float32, device=dev)
             self.hit = torch.zeros(E, N, dtype=torch.uint8, device=dev)
-        _native.call("dronesim_obstacle_sense", z, xF, radius, rng, self._obs, E, N, k1, c, self.M, self.m, self.orow, self.oid,
-                     self.gap_min if gap_min else None, self.hit if gap_min else None)
+        planes = (self.gap_min if gap_min else None, self.hit if gap_min else None)
+        if self.per_env:
+            _native.call("dronesim_env_obstacle_sense", z, xF, radius, rng, self._lists, self._counts, E, N, k1, c, self.M, self.m,
+                         self.orow, self.oid, *planes)
+        else:
+            _native.call("dronesim_obstacle_sense", z, xF, radius, rng, self._obs, E, N, k1, c, self.M, self.m, self.orow, self.oid,
+                         *planes)
         return self.orow, self.oid
 
     @property
@@ -284,6 +422,10 @@ class ObstacleField:
         if not torch.is_tensor(z) or z.dim() < 2 or tuple(z.shape[-2:]) != (N, d):
             raise ValueError(f"z must be a [..., N, (k+1)c] = [..., {N}, {d}] tensor, got {tuple(getattr(z, 'shape', ()))}")
         lead = tuple(int(n) for n in z.shape[:-2])
+        E = int(self.env.n_envs)
+        if self.per_env and (not lead or lead[-1] != E):
+            raise ValueError(f"with per-env obstacles the leading dims of z must end in E = {E} (row q belongs to env q % E), got "
+                             f"{tuple(z.shape)}")
         _tensor_check("z", z, torch.float32, lead + (N, d), dev)
         if out is not None:
             _tensor_check("out", out, torch.float32, lead + (N, self.obs_width), dev)
@@ -299,7 +441,11 @@ class ObstacleField:
                 cost_out = self._cost[lead] = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
             self.cost = cost_out
         R = int(np.prod(lead, dtype=np.int64)) if lead else 1
-        _native.call("dronesim_obstacle_observe", z, xF, radius, rng, self._obs, R, N, k1, c, self.M, self.m, out, cost_out, weight)
+        if self.per_env:
+            _native.call("dronesim_env_obstacle_observe", z, xF, radius, rng, self._lists, self._counts, R, E, N, k1, c, self.M,
+                         self.m, out, cost_out, weight)
+        else:
+            _native.call("dronesim_obstacle_observe", z, xF, radius, rng, self._obs, R, N, k1, c, self.M, self.m, out, cost_out, weight)
         return out
 
     def shape_reward(self, storage, weight, out=None, cost_out=None):
@@ -327,8 +473,14 @@ class ObstacleField:
         xF, radius, rng = self._env_tensors(dev)
         if out is None:
             out = torch.empty(T, E, N, dtype=torch.float32, device=dev)
-        _native.call("dronesim_obstacle_reward", storage.z, storage.z_final, storage.done, storage.reward, xF, radius, rng, self._obs,
-                     T, E, N, k1, c, self.M, weight, out, cost_out)
+        if self.per_env:
+            if E != int(env.n_envs):
+                raise ValueError(f"the storage holds {E} envs, the field {int(env.n_envs)} lists")
+            _native.call("dronesim_env_obstacle_reward", storage.z, storage.z_final, storage.done, storage.reward, xF, radius, rng,
+                         self._lists, self._counts, T, E, N, k1, c, self.M, weight, out, cost_out)
+        else:
+            _native.call("dronesim_obstacle_reward", storage.z, storage.z_final, storage.done, storage.reward, xF, radius, rng,
+                         self._obs, T, E, N, k1, c, self.M, weight, out, cost_out)
         return out
 
     def episode_safety(self, storage, out=None):
@@ -337,4 +489,7 @@ class ObstacleField:
         env = self.env
         if getattr(storage, "env", None) is not env:
             raise ValueError("storage must be a RolloutStorage of this field's env")
+        if self.per_env:
+            return episode_env_obstacle_safety(storage.z, storage.done, env._xF, env._radius, self._obs, self._counts, int(env.c),
+                                               storage.z_final, out=out)
         return episode_obstacle_safety(storage.z, storage.done, env._xF, env._radius, self._obs_view, int(env.c), storage.z_final, out=out)

@@ -14,11 +14,16 @@
      on the same window; and the control -> sense -> shield -> step(execute=) chain next to the plain chain;
   6. `--obstacle-obs` (alone): for M in {16, 64} discs, m = 2: `dronesim_obstacle_observe` on one step next to the sense launch and
      on a T-step ring; `dronesim_obstacle_reward` on the window next to `dronesim_episode_obstacle_safety` on it; and
-     ``SA2CLearner.train`` with and without ``obstacles=`` on a 16-step window.
+     ``SA2CLearner.train`` with and without ``obstacles=`` on a 16-step window;
+  7. `--obstacles --per-env` (alone): per-env obstacle sets (csrc/env_obstacles.hip) next to the shared-list kernels in the same
+     session, for M in {16, 64}, m = 2: sense, sense + obstacle shield, observe, reward, the tables and the control -> sense ->
+     shield -> step(execute=) chain, each with its per-env : shared ratio; then, at M = 64, the two small-N shapes on either side
+     of the staging rule (`dronesim_env_obstacle_plan` picks them): one takes the direct path, one the staged path.
 
     python tools/ebench.py [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/ebench.jsonl] [--skip-round] [--tag LABEL]
     python tools/ebench.py --shield [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/shield_ebench.jsonl]
     python tools/ebench.py --obstacles [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/obstacles_ebench.jsonl]
+    python tools/ebench.py --obstacles --per-env [--T 200] [--envs 4096] [--agents 64] [--out profiles/env_obstacles_ebench.jsonl]
     python tools/ebench.py --obstacle-obs [--T 200] [--envs 4096] [--agents 64] [--k 2] [--c 2] [--out profiles/obstacle_obs_ebench.jsonl]
 Prints one JSON line per measurement (appended to --out when given).  DRONESIM_LIB selects the build."""
 import argparse
@@ -296,6 +301,94 @@ def obstacle_obs(T, E, N, k, c, emit, counts=(16, 64), m=2, train_T=16):
                   ratio=us / us_train, **rec))
 
 
+def env_obstacles(T, E, N, k, c, emit, counts=(16, 64), m=2):
+    """Per-env obstacle sets next to the shared-list kernels, on `obstacles`' env state: for every M the shared rows first (the
+    yardstick, the rows of profiles/obstacles_ebench.jsonl), then the per-env rows with ``ratio`` = per-env : shared.  Env e's
+    list is `place_obstacles` seeded ``[M, e]``, M discs each.  Then the small-N pair of the staging rule at M = 64."""
+    from scalable_collision_avoidance_rl_amd.obstacles import ObstacleField, env_obstacle_plan, place_obstacles
+    from scalable_collision_avoidance_rl_amd.shield import ActionShield
+    G = 28.0 if N == 64 else max(6.0, 0.45 * N)
+    dev, k1 = "cuda:0", k + 1
+    env = drones(N, 0, [G, G], "O", k_closest=k, deltas=np.ones(N), simplify_zstate=c == 2, n_envs=E, seed=0, auto_reset=True)
+    act, safe = env.control("proportional"), torch.empty(E, N, 2, device=env.device)
+    for _ in range(20):
+        env.step(env.control("proportional", out=act))
+    base = dict(E=E, N=N, k=k, c=c, m=m)
+    z = torch.randn(T, E, N, k1 * c, device=dev) * 3.0
+    done = torch.zeros(T, E, dtype=torch.uint8, device=dev); done[-1] = 1
+    window = SimpleNamespace(env=env, z=z, z_final=None, done=done, reward=-torch.rand(T, E, N, device=dev))
+    shaped = torch.empty_like(window.reward)
+    goals = env.end_points.reshape(N, 2)
+
+    def rows(field, label, rec, yard):
+        """The six rows of one field; `yard`: the shared field's medians by row name (None: this IS the yardstick)."""
+        got = {}
+        sh = ActionShield(env, 0.25, 0.05, 1.0, obstacles=field)
+        tables = field.episode_safety(window)
+
+        def chain():
+            env.control("proportional", out=act)
+            env.step(act, execute=sh(act, out=safe))
+        for name, fn, calls in (("sense", lambda: field.sense(), 8), ("sense + obstacle shield", lambda: sh(act, out=safe), 8),
+                                ("observe", lambda: field.observe(), 8),
+                                ("reward", lambda: field.shape_reward(window, 0.01, out=shaped), 2),
+                                ("tables", lambda: field.episode_safety(window, out=tables), 2),
+                                ("control -> sense -> shield -> step(execute=)", chain, 8)):
+            us, lo = gtime(fn, calls=calls)
+            got[name] = us
+            line = dict(what=f"{label}: {name}", us=us, us_min=lo, **rec)
+            if name in ("reward", "tables"):
+                line["T"] = T
+            if yard is not None:
+                line.update(yardstick_us=yard[name], ratio=us / yard[name])
+            emit(line)
+        return got
+
+    for M in counts:
+        discs = place_obstacles([G, G], 2 * M, seed=M, keep_clear=goals, clearance=0.3)[:M]
+        assert discs.shape[0] == M
+        rec = dict(base, M=M)
+        yard = rows(ObstacleField(env, discs, m=m), "shared", rec, None)
+        def own_list(e):                                       # M discs off the goals, from as many draws as it takes
+            n = 2 * M
+            while True:
+                kept = place_obstacles([G, G], n, seed=[M, e], keep_clear=goals, clearance=0.3)
+                if kept.shape[0] >= M:
+                    return kept[:M]
+                n *= 2
+        per = np.stack([own_list(e) for e in range(E)])
+        assert per.shape == (E, M, 3)
+        plan = env_obstacle_plan(N, M, m)
+        rows(ObstacleField(env, per, m=m, per_env=True), "per-env", dict(rec, staged=plan["staged"], list_bytes=12 * M * E), yard)
+        del per
+    # the staging rule at small N: the largest N the rule sends to the direct path and the next one, which it stages, at the same
+    # M and about the same record count, on stand-in records (positions uniform over the discs' square)
+    M, records = 64, 1 << 20
+    n_direct = max(n for n in range(1, 65) if not env_obstacle_plan(n, M, m)["staged"])
+    n_staged = n_direct + 1
+    assert env_obstacle_plan(n_staged, M, m)["staged"]
+    for n in (n_direct, n_staged):
+        Es = records // n
+        plan = env_obstacle_plan(n, M, m)
+        g = torch.Generator(device=dev).manual_seed(n)
+        stand_in = SimpleNamespace(batched=True, n_envs=Es, n_agents=n, k_closest=k, c=2, device=torch.device(dev), z=None,
+                                   _xF=torch.zeros(n, 2, device=dev), _radius=torch.full((n,), 0.1, device=dev),
+                                   _delta=torch.ones(n, device=dev), obstacles=np.zeros((0, 3)))
+        lists = np.random.default_rng(n).uniform(0.0, 1.0, (Es, M, 3)) * np.array([G, G, 0.1 * G])
+        field = ObstacleField(stand_in, lists, m=m, per_env=True)
+        zs = torch.zeros(Es, n, k1 * 2, device=dev)
+        zs[..., :2] = torch.rand(Es, n, 2, device=dev, generator=g) * G
+        rec = dict(E=Es, N=n, k=k, c=2, m=m, M=M, staged=plan["staged"], rows_per_block=plan["rows_per_block"], list_bytes=12 * M * Es)
+        for name, fn in (("sense", lambda: field.sense(zs)), ("observe", lambda: field.observe(zs)),
+                         ("observe with cost", lambda: field.observe(zs, cost=0.01))):
+            us, lo = gtime(fn)
+            emit(dict(what=f"per-env, small N: {name}", us=us, us_min=lo, ns_per_record=1e3 * us / (Es * n), **rec))
+        shared = ObstacleField(stand_in, lists[0], m=m)
+        us, lo = gtime(lambda: shared.sense(zs))
+        emit(dict(what="shared, small N: sense (yardstick)", us=us, us_min=lo, ns_per_record=1e3 * us / (Es * n), **dict(rec, staged=None)))
+        del field, lists
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=200)
@@ -308,6 +401,7 @@ def main():
     ap.add_argument("--shield", action="store_true", help="only the action shield next to the step launch")
     ap.add_argument("--obstacles", action="store_true", help="only the obstacle layer next to its yardsticks")
     ap.add_argument("--obstacle-obs", action="store_true", help="only the obstacle columns and the obstacle cost next to their yardsticks")
+    ap.add_argument("--per-env", action="store_true", help="with --obstacles: the per-env obstacle sets next to the shared-list kernels")
     ap.add_argument("--tag", help="a free label copied into the JSON lines (e.g. which build was timed)")
     a = ap.parse_args()
 
@@ -321,6 +415,11 @@ def main():
                 f.write(line + "\n")
     if a.shield:
         shield(a.envs, a.agents, a.k, a.c, emit)
+        return
+    if a.per_env and not a.obstacles:
+        ap.error("--per-env goes with --obstacles")
+    if a.obstacles and a.per_env:
+        env_obstacles(a.T, a.envs, a.agents, a.k, a.c, emit)
         return
     if a.obstacles:
         obstacles(a.T, a.envs, a.agents, a.k, a.c, emit)
